@@ -11,6 +11,10 @@ forward pass with ESTIMATED bits; the real range-coded encode / decode (`VideoCo
 tools/time_codec.py and reported in DESIGN.md.  Inputs are resident in HBM before the timed region.  Ranks code
 independent GOPs (GOP sharding, no collective on the data path): weak scaling.
 
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds the legs that measure
+beyond it: rocprofv3 traffic passes, per-kernel and HBM rooflines, fp32 islands, the training step, the CPU oracle and
+the parity frame.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md §6 for every field).
 """
 import argparse
@@ -31,6 +35,8 @@ MFMA_F16_PEAK = 2.5e15             # dense fp16/bf16 MFMA peak, MI355X_MICROARCH
 HBM_PEAK = 8.0e12                  # HBM3E peak, MI355X_MICROARCH.md (~6.3e12 achievable)
 HP, WP = 1088, 1920
 PMC_FILE = "profiles/r02_conv3x3_64_64_1080p_pmc.txt"
+DUMP_LIMIT = 64_000_000            # bytes --dump-outputs may write
+PARAM_SAMPLE = 1 << 20             # --mode train: parameters dumped (of 28.2 M), a fixed seeded sample
 
 
 def self_launch(argv, n):
@@ -80,6 +86,34 @@ class GopRunner:
         if self.t == 6:
             self.t = 0
         return recon, bpp_res, bpp_mv
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: name -> tensor (or number) of the last timed step, written as d/<name>.npy in float32 / float64"""
+    import numpy as np
+    out = {}
+    for k, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach().cpu()
+            v = v if v.dtype == torch.float64 else v.float()
+        out[k] = np.asarray(v)
+    for k, v in out.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {k} is {v.dtype}, not float32 / float64")
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        raise ValueError(f"--dump-outputs: {total} bytes > {DUMP_LIMIT}")
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    print(f"[bench] wrote {len(out)} arrays ({total / 2**20:.1f} MiB) to {d}", file=sys.stderr, flush=True)
+
+
+def param_sample(model):
+    """PARAM_SAMPLE parameter values at fixed seeded positions of the concatenated parameter vector (module order)"""
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:PARAM_SAMPLE].sort().values
+    return flat[idx.to(flat.device)]
 
 
 def cpu_baseline(sample_hw=(HP, WP)):
@@ -386,7 +420,7 @@ def roofline_leg(runner):
 def train_measure(B, steps, warmup, rank, gpus, dev, dist, graph=False, scale_update="exact"):
     """BASELINE.json configs[2] (1 GPU) / [3] (N GPUs): one optimisation step (forward, backward incl. both entropy
     models, RCCL gradient mean over ranks, clipping, Adam, aux step, re-packing) on B 256x256 P-frame samples per rank
-    (weak scaling: the reference's batch 32 over 8 GPUs).  -> (seconds for `steps` steps, max over ranks; last log)"""
+    (weak scaling: the reference's batch 32 over 8 GPUs).  -> (seconds for `steps` steps, max over ranks; last log; model)"""
     from tdvc_amd.model import VideoCompressor
     from tdvc_amd.synth import fill_parameters, make_gop, ref_list
     from tdvc_amd.train import TrainStep
@@ -419,7 +453,7 @@ def train_measure(B, steps, warmup, rank, gpus, dev, dist, graph=False, scale_up
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.barrier()
         dt = float(t)
-    return dt, log
+    return dt, log, m
 
 
 def train_record(B, steps, warmup, gpus, dt, log):
@@ -441,10 +475,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", default="1088x1920", help="HxW of the CPU-oracle frame (default: the real 1088x1920 frame, about a minute)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes that measure roofline.traffic")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32-island, HBM-roofline and training legs of the N=1 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: rocprofv3 traffic passes, rooflines, fp32 islands, training step, "
+                         "CPU baseline and parity (the four options below trim them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-oracle frame and the parity record")
+    ap.add_argument("--cpu-sample", default="1088x1920", help="--full: HxW of the CPU-oracle frame (default: the real 1088x1920 frame, about a minute)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc child passes that measure roofline.traffic")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the fp32-island, HBM-roofline and training legs of the N=1 line")
     ap.add_argument("--mode", choices=("infer", "train"), default="infer",
                     help="infer (default, the headline metric) | train: BASELINE.json configs[2]/[3], one optimisation step per step")
     ap.add_argument("--scale-update", default="exact", choices=("exact", "lagged"),
@@ -452,6 +490,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="--mode train: replay the forward + backward as one captured HIP graph")
     ap.add_argument("--train-batch", type=int, default=4, help="samples per rank in --mode train (256x256 P-frames)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:       # no launcher: start the ranks ourselves, before any GPU call
         sys.exit(self_launch(sys.argv[1:], a.gpus))
@@ -461,7 +501,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != a.gpus:
         sys.exit(f"bench.py: --gpus {a.gpus} but the launcher started WORLD_SIZE={world} ranks")
-    if world == 1 and a.mode == "infer" and not a.no_extras and not a.no_pmc:
+    if world == 1 and a.mode == "infer" and a.full and not a.no_extras and not a.no_pmc:
         for kname in list(REP_LAUNCHES) + list(HBM_TOOLS):     # child processes: must run before this process initialises the GPU
             t_, src_ = measure_traffic(kname)
             LIVE_TRAFFIC[kname] = (t_, src_)
@@ -482,9 +522,11 @@ def main():
             dist.destroy_process_group()
 
     if a.mode == "train":
-        dt, log = train_measure(a.train_batch, a.steps, a.warmup, rank, a.gpus, dev, dist, a.graph, a.scale_update)
+        dt, log, tm = train_measure(a.train_batch, a.steps, a.warmup, rank, a.gpus, dev, dist, a.graph, a.scale_update)
         finish_dist()
         if rank == 0:
+            if a.dump_outputs:                 # the step's log and the parameters it updated (identical on every rank)
+                dump_outputs(a.dump_outputs, dict({k: float(log[k]) for k in log}, params_sample=param_sample(tm)))
             rec = train_record(a.train_batch, a.steps, a.warmup, a.gpus, dt, log)
             rec["ranks_seen"] = ranks_seen
             print(json.dumps(rec))
@@ -514,9 +556,10 @@ def main():
     finish_dist()                      # the other ranks are done: the legs below are rank 0's alone (no rank waits in a barrier)
     if rank != 0:
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"recon": recon, "bpp_res": bpp_res, "bpp_mv": bpp_mv})
 
     fps = a.gpus * a.steps / dt
-    roof = roofline_leg(runner)
     line = {
         "metric": "1080p P-frames/sec (encode + reconstruct, lambda=2048 config)", "value": round(fps, 3),
         "unit": "frames/s", "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
@@ -530,8 +573,11 @@ def main():
         "whole_path_frac_of_mfma_peak": round(FLOP_PER_PX * HP * WP * fps / a.gpus / MFMA_F16_PEAK, 4),
         "bpp_last": round(float(bpp_res + bpp_mv), 5),
         "ranks_seen": ranks_seen,
-        "roofline": roof,
     }
+    if not a.full:
+        print(json.dumps(line))
+        return
+    line["roofline"] = roofline_leg(runner)
     hip_par = None
     if a.gpus == 1 and not a.no_extras:
         line["roofline_hbm"] = hbm_rooflines(model)
@@ -557,7 +603,7 @@ def main():
         del model, runner
         torch.cuda.empty_cache()
         tsteps = 15
-        tdt, tlog = train_measure(4, tsteps, 3, 0, 1, dev, None)
+        tdt, tlog, _ = train_measure(4, tsteps, 3, 0, 1, dev, None)
         line["train_step"] = train_record(4, tsteps, 3, 1, tdt, tlog)
     print("[bench] gpu leg: " + json.dumps(line), file=sys.stderr, flush=True)
     if a.gpus == 1 and not a.no_cpu_baseline:

@@ -282,6 +282,30 @@ def test_bench_self_launch_forwards_arguments(monkeypatch):
     assert "WORLD_SIZE=4" in str(ex.value.code)
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: one DIR/<name>.npy per output, float32 (float64 kept), bit-equal to what the step returned;
+    the parameter sample of `--mode train` is the same positions on every call; more than 64 MB is refused, nothing written"""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    recon, bpp = torch.rand(1, 3, 64, 96), torch.tensor(0.25, dtype=torch.float16)
+    bench.dump_outputs(str(tmp_path / "d"), {"recon": recon, "bpp_res": bpp, "rd_loss": 1.5, "f64": torch.ones(2, dtype=torch.float64)})
+    assert sorted(os.listdir(tmp_path / "d")) == ["bpp_res.npy", "f64.npy", "rd_loss.npy", "recon.npy"]
+    r = np.load(tmp_path / "d" / "recon.npy")
+    assert r.dtype == np.float32 and np.array_equal(r, recon.numpy())
+    assert np.load(tmp_path / "d" / "bpp_res.npy").dtype == np.float32 and float(np.load(tmp_path / "d" / "bpp_res.npy")) == 0.25
+    assert np.load(tmp_path / "d" / "rd_loss.npy").dtype == np.float64 and np.load(tmp_path / "d" / "f64.npy").dtype == np.float64
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT // 4 + 1)})
+    assert not os.path.exists(tmp_path / "big")
+    m = torch.nn.Sequential(torch.nn.Linear(1500, 1000), torch.nn.Linear(1000, 10))
+    s = bench.param_sample(m)
+    assert s.shape == (bench.PARAM_SAMPLE,) and torch.equal(s, bench.param_sample(m))
+
+
 def test_tape_deferred_chains_run_behind_the_sweep():
     """`Tape.defer`: parameter-space chains that run as torch kernels (entropy-bottleneck softplus / tanh chain, GDN reparametrisation) are
     executed after the last backward node and after join() -- no MFMA kernel of the side stream is in flight then (torch's softplus kernels

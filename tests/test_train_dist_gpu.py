@@ -152,10 +152,10 @@ def test_bench_train_mode_under_one_rank_rccl_group(report):
     assert seen[0]["rank"] == 0 and seen[0]["rccl"] and (seen[0]["uuid"] or seen[0]["pci"])
 
 
-def test_bench_inference_mode_under_one_rank_rccl_group(report):
+def test_bench_inference_mode_under_one_rank_rccl_group(report, tmp_path):
     """the default (inference, GOP-sharded) mode of `bench.py` under a ONE-rank RCCL process group: what the driver's N > 1 scaling runs
     execute -- nccl init with the rank's device, GOP seeds per rank, barrier / max-over-ranks timing, `ranks_seen` -- minus the legs that
-    only rank 0 of a one-GPU run adds (`--no-extras --no-pmc --no-cpu-baseline`)"""
+    only rank 0 of a one-GPU run adds (`--no-extras --no-pmc --no-cpu-baseline`); `--dump-outputs` writes the last timed frame's outputs"""
     import json
     import subprocess
     import sys
@@ -163,9 +163,15 @@ def test_bench_inference_mode_under_one_rank_rccl_group(report):
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                TDVC_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-extras", "--no-pmc",
-                        "--no-cpu-baseline"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
     report(f"bench.py (inference) under a 1-rank nccl group: {line['value']} frames/s, {line['ms_per_step']} ms/frame; ranks_seen {line['ranks_seen']}")
     assert line["n_gpus"] == 1 and line["steps"] == 3 and line["value"] > 0 and line["scaling"] == "weak"
     assert len(line["ranks_seen"]) == 1 and line["ranks_seen"][0]["rccl"]
+    import numpy as np
+    assert sorted(os.listdir(tmp_path)) == ["bpp_mv.npy", "bpp_res.npy", "recon.npy"]
+    recon = np.load(tmp_path / "recon.npy")
+    assert recon.shape == (1, 3, 1088, 1920) and recon.dtype == np.float32 and np.isfinite(recon).all()
+    bpp = np.load(tmp_path / "bpp_res.npy").item() + np.load(tmp_path / "bpp_mv.npy").item()
+    assert abs(bpp - line["bpp_last"]) <= 1e-5
