@@ -686,7 +686,9 @@ def conv_wgrad(pc: PackedConv, g: FM, x: FM, dw: torch.Tensor, scale=1.0, square
         e1.record()
         PROFILE.append(dict(kernel="conv_wgrad", shape=f"{o['kh']}x{o['kw']} s{o['stride']} {x.C}->{pc.cout} @{x.N}x{x.H}x{x.W}", e0=e0, e1=e1,
                             flops=2.0 * x.N * Ho * Wo * pc.cout * x.C * len(taps), flops_real=2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(taps),
-                            bytes=0.0))
+                            bytes=0.0,
+                            # geometry class (kh, kw, stride, cin, cout, shuffle, square_x, masked): the op-level test coverage guard
+                            geo=(o["kh"], o["kw"], o["stride"], pc.cin_real, pc.cout, bool(pc.shuffle), bool(square_x), "wgrad_taps" in o)))
 
 
 def _bias_index(pc: PackedConv, device):
