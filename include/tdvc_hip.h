@@ -506,6 +506,27 @@ int tdvc_ssim_level(const float* x, const float* y, int N, int C, int H, int W, 
                     float c1, float c2, float* ssim_out, float* cs_out, float* work, int64_t work_floats, void* stream);
 int tdvc_avgpool2_pad_f32(const float* x, int64_t planes, int H, int W, float* out, void* stream);
 
+/* ---------------------------------------------------------------- MS-SSIM as a training distortion: the backward half
+ * tdvc_ssim_level_backward: dx = scale * d(sum_n g_ssim[n] * S[n] + g_cs[n] * CS[n]) / dx, where S[n] / CS[n] are the RAW
+ * per-image means tdvc_ssim_level writes (before (v + 1) / 2) and y is held constant (both maps are symmetric in x and y:
+ * swap the operands for the gradient with respect to y).  g_ssim / g_cs are DEVICE arrays of N floats and are never read
+ * on the host; `win` is a HOST array as in tdvc_ssim_level.  g_pool, when not NULL, is the gradient of the next (coarser)
+ * level, [N][C][(H + 2*(H%2) - 2) / 2 + 1][(W + 2*(W%2) - 2) / 2 + 1]: the backward of tdvc_avgpool2_pad_f32,
+ * 0.25 * g_pool[(iy + H%2) / 2][(ix + W%2) / 2], is added (unscaled) in the same store, so the backward of the whole
+ * pyramid is one launch per level, coarse to fine.  dx ([N][C][H][W]) is overwritten.  A gather with a fixed summation
+ * order and no atomics: bit-reproducible.  All fp32.
+ * tdvc_msssim_level_grads: the scalar tail (ms_ssim_torch.py:183-188) and its gradient.  cs: DEVICE [levels][N] cs means
+ * and ssim_last: DEVICE [N] ssim means of the last level, both AFTER (v + 1) / 2; weights: HOST array of `levels`
+ * (<= TDVC_MSSSIM_MAX_LEVELS) floats; grad_out: DEVICE [N] upstream gradient of the MS-SSIM value, NULL = ones.  Writes
+ * ms_out[N] = prod_{l < levels-1} cs_l^w_l * ssim^w_last and g_ssim / g_cs ([levels][N] each): the gradients with respect
+ * to the RAW means of every level, ready for tdvc_ssim_level_backward (only the last level's g_ssim is non-zero). */
+#define TDVC_MSSSIM_MAX_LEVELS 8
+int tdvc_ssim_level_backward(const float* x, const float* y, int N, int C, int H, int W, const float* win, int win_size,
+                             float c1, float c2, const float* g_ssim, const float* g_cs, float scale, const float* g_pool,
+                             float* dx, void* stream);
+int tdvc_msssim_level_grads(const float* cs, const float* ssim_last, const float* weights, int levels, int N, const float* grad_out,
+                            float* ms_out, float* g_ssim, float* g_cs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,148 @@ __global__ void avgpool2_pad_kernel(const float* x, long planes, int H, int W, i
   out[i] = 0.25f * s;
 }
 
+// ---------------------------------------------------------------------------------------------------- backward of one level
+// d(g_ssim[n] * mean ssim_map + g_cs[n] * mean cs_map) / dX, Y constant (the maps are symmetric: dY = the same kernel with the
+// operands swapped).  A gather: one workgroup per 32x16 tile of dX.  With R = win - 1 it loads X, Y on the tile + 2R apron,
+// recomputes the five filtered statistics on the tile + R apron (every map position whose window covers a tile pixel), turns
+// them into the three partial-derivative maps
+//   P_mu = a cs (2 mu2 - 2 mu1 l) / B1 + k (2 mu1 cs - 2 mu2) / B2,   P_xx = -k cs / B2,   P_xy = 2 k / B2       (k = a l + b)
+// (zero outside the valid map) and filters those back with the transposed window:
+//   dX(q) = scale * sum_p w(q - p) [P_mu(p) + 2 X(q) P_xx(p) + Y(q) P_xy(p)]  +  0.25 g_pool((q + pad) / 2)
+// the last term being the backward of the padded 2x2 average pooling towards the next (coarser) level.  No atomics, fixed
+// summation order.  LDS at win = 11: X, Y 2 x 36x52, horizontal statistics 5 x 36x42 (re-used by the 3 x 16x42 vertically
+// back-filtered maps), P maps 3 x 26x42: 57.3 KB, two workgroups per CU.
+struct SsimLevelBwd {
+  const float *x, *y, *g_ssim, *g_cs, *g_pool;
+  float* dx;
+  int N, C, H, W, win;
+  float taps[MS_MAXWIN];
+  float c1, c2, scale, inv_m;
+  int tiles_x, Hp, Wp;
+};
+
+__global__ __launch_bounds__(256) void ssim_level_backward_kernel(const SsimLevelBwd p) {
+  extern __shared__ float sm[];
+  const int R = p.win - 1;
+  const int IW = MS_TW + 2 * R, IH = MS_TH + 2 * R, PW = MS_TW + R, PH = MS_TH + R;
+  float* tx = sm;                         // [IH][IW] X tile, origin (qy0 - R, qx0 - R)
+  float* ty = tx + IH * IW;               // [IH][IW] Y tile
+  float* hz = ty + IH * IW;               // [5][IH][PW] horizontally filtered X, Y, XX, YY, XY; later [3][MS_TH][PW] (vt)
+  float* pm = hz + 5 * IH * PW;           // [3][PH][PW] P_mu, P_xx, P_xy, origin (qy0 - R, qx0 - R) in map coordinates
+  float* vt = hz;
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x, c = blockIdx.y, n = blockIdx.z;
+  const int tcol = tile % p.tiles_x, trow = tile / p.tiles_x;
+  const int Hv = p.H - R, Wv = p.W - R;
+  const int qy0 = trow * MS_TH, qx0 = tcol * MS_TW;
+  const long plane = ((long)n * p.C + c) * p.H * p.W;
+  const float* xp = p.x + plane;
+  const float* yp = p.y + plane;
+  for (int i = tid; i < IH * IW; i += 256) {
+    const int r = i / IW, q = i - r * IW;
+    const int iy = qy0 - R + r, ix = qx0 - R + q;
+    const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+    tx[i] = ok ? xp[(long)iy * p.W + ix] : 0.f;
+    ty[i] = ok ? yp[(long)iy * p.W + ix] : 0.f;
+  }
+  __syncthreads();
+  const int HS = IH * PW;
+  for (int i = tid; i < HS; i += 256) {
+    const int r = i / PW, q = i - r * PW;
+    float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
+    for (int k = 0; k < p.win; ++k) {
+      const float w = p.taps[k], u = tx[r * IW + q + k], v = ty[r * IW + q + k];
+      a += w * u; b += w * v; aa += w * (u * u); bb += w * (v * v); ab += w * (u * v);
+    }
+    hz[i] = a; hz[HS + i] = b; hz[2 * HS + i] = aa; hz[3 * HS + i] = bb; hz[4 * HS + i] = ab;
+  }
+  __syncthreads();
+  const float ga = p.g_ssim[n] * p.inv_m, gb = p.g_cs[n] * p.inv_m;
+  const int PS = PH * PW;
+  for (int i = tid; i < PS; i += 256) {
+    const int r = i / PW, q = i - r * PW;
+    const int py = qy0 - R + r, px = qx0 - R + q;
+    float pmu = 0.f, pxx = 0.f, pxy = 0.f;
+    if (py >= 0 && py < Hv && px >= 0 && px < Wv) {
+      float mu1 = 0.f, mu2 = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
+      for (int k = 0; k < p.win; ++k) {
+        const float w = p.taps[k];
+        const int o = (r + k) * PW + q;
+        mu1 += w * hz[o]; mu2 += w * hz[HS + o]; xx += w * hz[2 * HS + o]; yy += w * hz[3 * HS + o]; xy += w * hz[4 * HS + o];
+      }
+      const float mu1s = mu1 * mu1, mu2s = mu2 * mu2, mu12 = mu1 * mu2;
+      const float s1 = xx - mu1s, s2 = yy - mu2s, s12 = xy - mu12;
+      const float rb1 = 1.f / (mu1s + mu2s + p.c1), rb2 = 1.f / (s1 + s2 + p.c2);
+      const float l = (2.f * mu12 + p.c1) * rb1, cs = (2.f * s12 + p.c2) * rb2;
+      const float k = ga * l + gb;
+      pmu = ga * cs * (2.f * mu2 - 2.f * mu1 * l) * rb1 + k * (2.f * mu1 * cs - 2.f * mu2) * rb2;
+      pxx = -k * cs * rb2;
+      pxy = 2.f * k * rb2;
+    }
+    pm[i] = pmu; pm[PS + i] = pxx; pm[2 * PS + i] = pxy;
+  }
+  __syncthreads();                        // every read of hz is done: vt may overwrite it
+  const int VS = MS_TH * PW;
+  for (int i = tid; i < VS; i += 256) {
+    const int r = i / PW, q = i - r * PW;
+    float a = 0.f, b = 0.f, d = 0.f;
+    for (int k = 0; k < p.win; ++k) {     // map row qy - k  ->  local row r + R - k
+      const float w = p.taps[k];
+      const int o = (r + R - k) * PW + q;
+      a += w * pm[o]; b += w * pm[PS + o]; d += w * pm[2 * PS + o];
+    }
+    vt[i] = a; vt[VS + i] = b; vt[2 * VS + i] = d;
+  }
+  __syncthreads();
+  const int ph = p.H & 1, pw = p.W & 1;
+  for (int i = tid; i < MS_TH * MS_TW; i += 256) {
+    const int r = i / MS_TW, q = i - r * MS_TW;
+    const int qy = qy0 + r, qx = qx0 + q;
+    if (qy >= p.H || qx >= p.W) continue;
+    float a = 0.f, b = 0.f, d = 0.f;
+    for (int k = 0; k < p.win; ++k) {     // map column qx - k  ->  local column q + R - k
+      const float w = p.taps[k];
+      const int o = r * PW + q + R - k;
+      a += w * vt[o]; b += w * vt[VS + o]; d += w * vt[2 * VS + o];
+    }
+    const int t = (r + R) * IW + q + R;
+    float g = p.scale * (a + 2.f * tx[t] * b + ty[t] * d);
+    if (p.g_pool) {
+      const long pp = ((long)n * p.C + c) * p.Hp * p.Wp;
+      g += 0.25f * p.g_pool[pp + (long)((qy + ph) >> 1) * p.Wp + ((qx + pw) >> 1)];
+    }
+    p.dx[plane + (long)qy * p.W + qx] = g;
+  }
+}
+
+// The scalar tail of MS-SSIM and its gradient (ms_ssim_torch.py:183-188), one thread per image:
+//   ms[n] = prod_{l < L-1} cs_l^w_l * ssim^w_{L-1}      (the reference multiplies the ssim factor into every one of the L-1 terms)
+// and, for an upstream gradient go[n] of ms[n], the gradients of the loss with respect to every level's RAW means (the
+// inputs here are the means after (v + 1) / 2, hence the 1/2):  g_cs[l][n] = go w_l ms / (2 cs_l) for l < L-1,
+// g_ssim[L-1][n] = go (L-1) w_{L-1} ms / (2 ssim); every other entry is zero.
+struct MsssimGrads {
+  const float *cs, *ssim, *grad_out;
+  float *ms, *g_ssim, *g_cs;
+  int L, N;
+  float w[TDVC_MSSSIM_MAX_LEVELS];
+};
+
+__global__ __launch_bounds__(256) void msssim_level_grads_kernel(const MsssimGrads p) {
+  for (int n = threadIdx.x; n < p.N; n += 256) {
+    const int last = p.L - 1;
+    const float s = p.ssim[n], ps = powf(s, p.w[last]);
+    float ms = 1.f;
+    for (int l = 0; l < last; ++l) ms *= powf(p.cs[(long)l * p.N + n], p.w[l]) * ps;
+    const float go = p.grad_out ? p.grad_out[n] : 1.f;
+    for (int l = 0; l < p.L; ++l) {
+      p.g_ssim[(long)l * p.N + n] = 0.f;
+      p.g_cs[(long)l * p.N + n] = l < last ? go * (0.5f * p.w[l] * ms / p.cs[(long)l * p.N + n]) : 0.f;
+    }
+    p.g_ssim[(long)last * p.N + n] = go * (0.5f * (float)last * p.w[last] * ms / s);
+    p.ms[n] = ms;
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t tdvc_ssim_level_work_floats(int N, int C, int H, int W, int win) {
@@ -162,4 +304,45 @@ extern "C" int tdvc_avgpool2_pad_f32(const float* x, int64_t planes, int H, int 
   hipLaunchKernelGGL(avgpool2_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, (long)planes,
                      H, W, ph, pw, Ho, Wo, out);
   return tdvc_launch_status("tdvc_avgpool2_pad_f32");
+}
+
+extern "C" int tdvc_ssim_level_backward(const float* x, const float* y, int N, int C, int H, int W, const float* win, int win_size,
+                                        float c1, float c2, const float* g_ssim, const float* g_cs, float scale, const float* g_pool,
+                                        float* dx, void* stream) {
+  TDVC_CHECK(x && y && win && g_ssim && g_cs && dx, "tdvc_ssim_level_backward: null pointer");
+  TDVC_CHECK(N > 0 && C > 0 && win_size >= 1 && win_size <= MS_MAXWIN && (win_size & 1) == 1 && H >= win_size && W >= win_size,
+             "tdvc_ssim_level_backward: bad geometry (N %d C %d H %d W %d window %d: odd window <= %d, image >= window)", N, C, H, W, win_size, MS_MAXWIN);
+  TDVC_CHECK(N <= 65535 && C <= 65535, "tdvc_ssim_level_backward: too many images / channels for one launch");
+  SsimLevelBwd p;
+  p.x = x; p.y = y; p.g_ssim = g_ssim; p.g_cs = g_cs; p.g_pool = g_pool; p.dx = dx;
+  p.N = N; p.C = C; p.H = H; p.W = W; p.win = win_size;
+  for (int k = 0; k < MS_MAXWIN; ++k) p.taps[k] = k < win_size ? win[k] : 0.f;        // `win` is HOST memory (the 1-D kernel)
+  p.c1 = c1; p.c2 = c2; p.scale = scale;
+  p.inv_m = (float)(1.0 / ((double)C * (H - win_size + 1) * (W - win_size + 1)));
+  p.tiles_x = (W + MS_TW - 1) / MS_TW;
+  const int tiles_y = (H + MS_TH - 1) / MS_TH;
+  p.Hp = (H + 2 * (H % 2) - 2) / 2 + 1; p.Wp = (W + 2 * (W % 2) - 2) / 2 + 1;
+  const int R = win_size - 1, IW = MS_TW + 2 * R, IH = MS_TH + 2 * R, PW = MS_TW + R, PH = MS_TH + R;
+  const size_t lds = sizeof(float) * ((size_t)2 * IH * IW + (size_t)5 * IH * PW + (size_t)3 * PH * PW);
+  static TdvcPerDeviceFlag attr;
+  if (!attr.flag()) {
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&ssim_level_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (err != hipSuccess) { tdvc_set_error("tdvc_ssim_level_backward: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
+    attr.flag() = true;
+  }
+  TDVC_CHECK(lds <= 96 * 1024, "tdvc_ssim_level_backward: LDS plan %zu bytes too large", lds);
+  hipLaunchKernelGGL(ssim_level_backward_kernel, dim3(p.tiles_x * tiles_y, C, N), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);
+  return tdvc_launch_status("tdvc_ssim_level_backward");
+}
+
+extern "C" int tdvc_msssim_level_grads(const float* cs, const float* ssim_last, const float* weights, int levels, int N, const float* grad_out,
+                                       float* ms_out, float* g_ssim, float* g_cs, void* stream) {
+  TDVC_CHECK(cs && ssim_last && weights && ms_out && g_ssim && g_cs, "tdvc_msssim_level_grads: null pointer");
+  TDVC_CHECK(levels >= 1 && levels <= TDVC_MSSSIM_MAX_LEVELS && N > 0, "tdvc_msssim_level_grads: bad geometry (levels %d of at most %d, N %d)", levels,
+             TDVC_MSSSIM_MAX_LEVELS, N);
+  MsssimGrads p;
+  p.cs = cs; p.ssim = ssim_last; p.grad_out = grad_out; p.ms = ms_out; p.g_ssim = g_ssim; p.g_cs = g_cs; p.L = levels; p.N = N;
+  for (int l = 0; l < TDVC_MSSSIM_MAX_LEVELS; ++l) p.w[l] = l < levels ? weights[l] : 0.f;      // `weights` is HOST memory
+  hipLaunchKernelGGL(msssim_level_grads_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+  return tdvc_launch_status("tdvc_msssim_level_grads");
 }

@@ -10,6 +10,7 @@ optimizer / clip / aux-optimizer order (`tools/train.py:136-152`), checkpoint na
 by rank and the gradients averaged over RCCL (`train.GradBuckets`).
 
   python -m tdvc_amd.tools.train --iters 20 --batch 4 --size 256
+  python -m tdvc_amd.tools.train --distortion ms-ssim --train-lambda 8     # rd_loss = lambda * (1 - MS-SSIM) + bpp (tools/train.py:133,139)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m tdvc_amd.tools.train --batch 4
 """
 from __future__ import annotations
@@ -37,7 +38,7 @@ def septuplet_samples(frames: torch.Tensor):
     return out
 
 
-def main():
+def make_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=4, help="samples per rank")
@@ -53,7 +54,13 @@ def main():
     ap.add_argument("--vimeo", default="", help="Vimeo-septuplet root (<dir>/<clip>/im1..7.png): tdvc_amd.data.DataSet with the "
                                                 "reference's sample rule and augmentation (train.py:78-80); default: synthetic septuplets")
     ap.add_argument("--num-workers", type=int, default=4)
-    a = ap.parse_args()
+    ap.add_argument("--distortion", choices=("mse", "ms-ssim"), default="mse",
+                    help="what lambda multiplies: MSE (tools/train.py:136-140) or 1 - MS-SSIM (the commented line :133,139; --size >= 176)")
+    return ap
+
+
+def main():
+    a = make_parser().parse_args()
 
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dist = None
@@ -71,7 +78,9 @@ def main():
     else:
         fill_parameters(net)
     net = net.to(dev)
-    step = TrainStep(net, train_lambda=a.train_lambda, lr=a.lr, loss_scale=a.loss_scale)
+    step = TrainStep(net, train_lambda=a.train_lambda, lr=a.lr, loss_scale=a.loss_scale, distortion=a.distortion)
+    if rank == 0:
+        print(json.dumps({"distortion": a.distortion, "train_lambda": a.train_lambda, "batch": a.batch, "size": a.size, "world": world}), flush=True)
 
     pool, cursor = [], 0
     t0 = time.time()
@@ -113,7 +122,8 @@ def main():
         log = step(x, refs)
         if rank == 0:
             psnr = 10.0 * torch.log10(torch.tensor(1.0 / max(log["mse"], 1e-12))).item()
-            print(json.dumps({"iter": it + 1, "rd_loss": round(log["rd_loss"], 4), "psnr": round(psnr, 3),
+            extra = {"ms_ssim": round(1.0 - log["distortion"], 5)} if a.distortion == "ms-ssim" else {}
+            print(json.dumps({"iter": it + 1, "rd_loss": round(log["rd_loss"], 4), "psnr": round(psnr, 3), **extra,
                               "bpp": round(log["bpp_res"] + log["bpp_mv"], 4), "aux": round(log["aux_loss"], 2),
                               "grad_norm": round(log["grad_norm"], 3), "s_per_iter": round((time.time() - t0) / (it + 1), 3)}), flush=True)
             if a.save_dir and ((it + 1) % a.latest_every == 0 or (it + 1) % a.save_every == 0 or it + 1 == a.iters):

@@ -136,13 +136,16 @@ class StepLog(Mapping):
     """What one TrainStep call reports: rd_loss, mse, bpp_res, bpp_mv, aux_loss, grad_norm, loss_scale (after this step's
     update), skipped.  The step itself never waits for the GPU: the seven scalars travel to pinned host memory behind the
     step's kernels and the first read of any key waits for that copy (the reference reads its losses every 10th iteration,
-    tools/train.py:159-163; GradScaler.step's own host read of found_inf has gone into the fused Adam kernel)."""
+    tools/train.py:159-163; GradScaler.step's own host read of found_inf has gone into the fused Adam kernel).
+    A step with a distortion other than MSE sends an eighth scalar, the distortion D that rd_loss was computed from; its log has
+    the extra key "distortion" (on that instance only: KEYS is what every log has)."""
     KEYS = ("rd_loss", "mse", "bpp_res", "bpp_mv", "aux_loss", "grad_norm", "loss_scale", "skipped")
 
     def __init__(self, owner, vals):
         self._owner, self._d, self._scale_after = owner, None, None
+        self._keys = self.KEYS + (("distortion",) if vals.numel() == 8 else ())
         if vals.is_cuda:
-            self._host = torch.empty(7, dtype=torch.float32, pin_memory=True)
+            self._host = torch.empty(vals.numel(), dtype=torch.float32, pin_memory=True)
             self._host.copy_(vals, non_blocking=True)
             self._ev = torch.cuda.Event()
             self._ev.record()
@@ -165,6 +168,8 @@ class StepLog(Mapping):
             skipped = v[6] != 0.0
             self._d = dict(rd_loss=v[0], mse=v[1], bpp_res=v[2], bpp_mv=v[3], aux_loss=v[4],
                            grad_norm=float("nan") if skipped else v[5], loss_scale=self._scale_after, skipped=skipped)
+            if len(v) == 8:
+                self._d["distortion"] = v[7]
             self._owner = None
         return self._d
 
@@ -172,20 +177,49 @@ class StepLog(Mapping):
         return self._vals()[k]
 
     def __iter__(self):
-        return iter(self.KEYS)
+        return iter(self._keys)
 
     def __len__(self):
-        return len(self.KEYS)
+        return len(self._keys)
 
     def __repr__(self):
         return f"StepLog({self._vals()!r})"
 
 
+def _seed_mse(recon, target, diff, lam, loss_scale):
+    """d(lambda * MSE) / d recon, scaled, in one rounding per element; the MSE itself is reduced by the caller (see _forward_backward)"""
+    return None, diff * (2.0 * lam * loss_scale / diff.numel())
+
+
+def _seed_from(fn):
+    """the seed of a distortion `fn(recon_fp32, target_fp32) -> (D, dD / d recon)`: its gradient times lambda * loss_scale, in fp32"""
+    def seed(recon, target, diff, lam, loss_scale):
+        D, g = fn(recon, target)
+        if g.shape != recon.shape or g.dtype != torch.float32:
+            raise ValueError(f"distortion: the gradient must be fp32 of recon's shape {tuple(recon.shape)}, got {g.dtype} {tuple(g.shape)}")
+        return D.reshape(()).float(), g * (lam * loss_scale)
+    return seed
+
+
+def msssim_distortion(recon, target):
+    """D = 1 - mean_n ms_ssim(recon, target, data_range=1.0) and dD / d recon (main/model/ms_ssim_torch.py's ms_ssim, the one the
+    reference evaluates with): HIP forward and backward of `tdvc_amd.metrics`, no host synchronisation"""
+    from . import metrics
+    n = recon.shape[0]
+    ms, g = metrics.ms_ssim_value_and_grad(recon, target, data_range=1.0, grad_out=torch.full((n,), -1.0 / n, dtype=torch.float32, device=recon.device))
+    return 1.0 - ms.mean(), g
+
+
 class TrainStep:
     def __init__(self, model, train_lambda: float = 2048.0, lr: float = 1e-4, loss_scale: float = 1024.0, clip: float = 2.0,
                  dynamic_scale: bool = True, growth_interval: int = 2000, graph: bool = False, graph_warmup: int = 2,
-                 side_stream: bool = True, scale_update: str = "exact", freeze_gc: bool = True):
-        """freeze_gc: after the second step (model, packed weights, descriptor caches and pools exist by then; bench.py's three warm-up steps
+                 side_stream: bool = True, scale_update: str = "exact", freeze_gc: bool = True, distortion="mse"):
+        """distortion: what lambda multiplies in rd_loss.  "mse" (the reference's active line, tools/train.py:136-140); "ms-ssim":
+        rd_loss = lambda * (1 - mean_n ms_ssim(recon, input, data_range=1.0)) + bpp_res + bpp_mv, the reference's commented line
+        (:133,139), images of at least 176 pixels a side; or a callable fn(recon_fp32, target_fp32) -> (D, dD_drecon) with D a
+        0-dim device tensor and dD_drecon fp32 of recon's shape.  All three seed the backward sweep the same way: the gradient times
+        lambda * loss_scale goes into the tape's gradient of recon.  Other than with "mse" the log carries D as "distortion".
+        freeze_gc: after the second step (model, packed weights, descriptor caches and pools exist by then; bench.py's three warm-up steps
         include the collection) everything alive
         moves to the garbage collector's permanent generation (gc.freeze): a step allocates ~50 k short-lived containers (tape
         closures, descriptors), which triggers full collections, and each of those walked the whole heap of the process --
@@ -197,9 +231,20 @@ class TrainStep:
         still skipped exactly, by the flag on the device).  With dynamic_scale=False nothing ever waits.
         graph=True: after `graph_warmup` eager steps (they build every lazily packed form) the forward + backward of
         one step is captured into a HIP graph and replayed: ~2300 launches leave the Python interpreter's critical
-        path.  Input shapes are then fixed; a loss-scale change re-captures."""
+        path (never fewer than two eager steps, see below).  Input shapes are then fixed; a loss-scale change re-captures."""
+        if distortion == "mse":
+            self._seed = _seed_mse
+        elif distortion == "ms-ssim":
+            self._seed = _seed_from(msssim_distortion)
+        elif callable(distortion):
+            self._seed = _seed_from(distortion)
+        else:
+            raise ValueError(f'distortion must be "mse", "ms-ssim" or a callable, not {distortion!r}')
+        self.distortion = distortion
         self.model = model
-        self.use_graph, self.graph_warmup, self._eager_steps = bool(graph), int(graph_warmup), 0
+        # at least two eager steps: the gradient buckets are re-laid after the first one (GradBuckets.reorder), and only the second builds
+        # the device pointer tables of the coders on the final layout -- a host-to-device copy, which a capture does not allow
+        self.use_graph, self.graph_warmup, self._eager_steps = bool(graph), max(int(graph_warmup), 2), 0
         self._graph = None
         self._ready, self._n_nodes = None, None      # gradient-completion order, learnt on step 0
         # weight-gradient kernels run on a side stream next to the dgrad chain (autograd.Tape.off_path)
@@ -243,13 +288,15 @@ class TrainStep:
                 # later steps: all-reduce finished buckets under the rest of the sweep (same tape shape as the logged step)
                 tape.on_node_done = lambda k: self._node_done(tape, k)
             recon, bpp_res, bpp_mv, _, _ = self.model(input_image, refer_frames, True)
-            diff = recon - input_image.float()
+            target = input_image.float()
+            diff = recon - target
             if pool is not None:
                 # last step's re-zeroing of the mirrors (5 GB of fills on the side stream) has the optimizer, the re-packing and this
                 # forward to finish under: nothing before this line writes a mirror
                 torch.cuda.current_stream().wait_stream(self._side)
-            # d(lambda * MSE)/d recon, scaled; the rate terms are seeded through tape.rate_grad
-            tape.grad_tensor(recon).copy_(diff * (2.0 * self.lam * self.loss_scale / diff.numel()))
+            # d(lambda * distortion)/d recon, scaled; the rate terms are seeded through tape.rate_grad
+            D, seed = self._seed(recon, target, diff, self.lam, self.loss_scale)
+            tape.grad_tensor(recon).copy_(seed)
             tape.rate_grad = 1.0 / float(B * H * W)
             tape.backward()
         if pool is not None:
@@ -261,18 +308,24 @@ class TrainStep:
         # MSE itself is reduced by the caller, outside a captured graph: torch's multi-block reduction zeroes its
         # semaphores with a memset node, and on this ROCm build the first replay after other work on the stream returned
         # partial sums (tools/graph_reduce_repro.py); the gradients never depended on that scalar
-        return diff, bpp_res.mean(), bpp_mv.mean()
+        return diff, bpp_res.mean(), bpp_mv.mean(), D
 
     def _capture(self, input_image, refer_frames):
         self._static_in = (input_image.clone(), refer_frames.clone())
         self._graph = torch.cuda.CUDAGraph()
         self._graph_scale = self.loss_scale
+        if self.distortion == "ms-ssim":
+            from . import metrics
+            metrics._weights_on(metrics._WEIGHTS, input_image.device)      # the level weights reach the device before the capture, not in it
         torch.cuda.synchronize()
         with torch.cuda.graph(self._graph):
             self._static_out = self._forward_backward(*self._static_in, capturing=True)
 
     def __call__(self, input_image: torch.Tensor, refer_frames: torch.Tensor) -> dict:
         model = self.model
+        if self.distortion == "ms-ssim":
+            from . import metrics
+            metrics._check_pyramid(input_image.shape[-2], input_image.shape[-1], len(metrics._WEIGHTS), 11)      # ValueError before any launch
         self._calls += 1
         if self._calls == 3 and self.freeze_gc:
             gc.collect()
@@ -290,9 +343,9 @@ class TrainStep:
             self._static_in[0].copy_(input_image)
             self._static_in[1].copy_(refer_frames)
             self._graph.replay()
-            diff, bpp_res, bpp_mv = self._static_out
+            diff, bpp_res, bpp_mv, D = self._static_out
         else:
-            diff, bpp_res, bpp_mv = self._forward_backward(input_image, refer_frames)
+            diff, bpp_res, bpp_mv, D = self._forward_backward(input_image, refer_frames)
             self._eager_steps += 1
         mse = (diff * diff).mean()
         self.buckets.all_reduce_mean()
@@ -323,7 +376,10 @@ class TrainStep:
             aux.backward()
         self.aux_optimizer.step()
         refresh_packed(model)
-        vals = torch.stack([self.lam * mse + bpp_res + bpp_mv, mse, bpp_res, bpp_mv, aux.detach().float(), gnorm, found])
+        if D is None:
+            vals = torch.stack([self.lam * mse + bpp_res + bpp_mv, mse, bpp_res, bpp_mv, aux.detach().float(), gnorm, found])
+        else:
+            vals = torch.stack([self.lam * D + bpp_res + bpp_mv, mse, bpp_res, bpp_mv, aux.detach().float(), gnorm, found, D])
         log = StepLog(self, vals)
         self._pending.append(log)
         if not vals.is_cuda:
