@@ -120,6 +120,11 @@ int tdvc_conv2d(const tdvc_conv_desc* d, void* stream);
 /* Rows per image of tdvc_conv_desc::chan_sum this conv would write, 0 when its kernel has no fused channel sum (the caller then
  * runs tdvc_channel_sum over y), < 0 on a malformed descriptor.  `chan_sum` itself is ignored here. */
 int tdvc_conv_chan_sum_rows(const tdvc_conv_desc* d);
+/* ABI 5.  Name of the kernel tdvc_conv2d would dispatch this descriptor to -- what tdvc_last_conv_kernel() reports after the
+ * launch -- or NULL with tdvc_last_error() set when tdvc_conv2d would reject it.  Same validation and selection, no launch:
+ * never touches the device (the pointers are only checked for alignment), the launch-parity state or tdvc_last_conv_kernel();
+ * `chan_sum` is ignored.  The string belongs to the calling thread and is valid until its next call. */
+const char* tdvc_conv_select(const tdvc_conv_desc* d);
 /* The fp32 islands: main/model/pnet.py:33-49,57-73 run both coders with autocast OFF (and enabled_amp=False runs the
  * whole model fp32).  Same descriptor with an fp32 input fmap (C %% 8 == 0) and `w` = the fp32 packing below; fp32
  * accumulation on v_mfma_f32_32x32x2_f32; aux / residual / output fmaps fp32 or fp16.  tdvc_conv2d forwards here

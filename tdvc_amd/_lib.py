@@ -59,6 +59,7 @@ _i, _f, _i64 = C.c_int, C.c_float, C.c_int64
 SIGNATURES = {
     "tdvc_abi_version": (_i, []),
     "tdvc_conv_chan_sum_rows": (_i, [C.POINTER(ConvDesc)]),
+    "tdvc_conv_select": (C.c_char_p, [C.POINTER(ConvDesc)]),
     "tdvc_last_error": (C.c_char_p, []),
     "tdvc_last_conv_kernel": (C.c_char_p, []),
     "tdvc_prepare_device": (_i, []),

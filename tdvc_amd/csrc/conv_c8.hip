@@ -120,16 +120,9 @@ __global__ __launch_bounds__(NTHR_C8, 4) void conv_c8_kernel(const ConvParams p,
 
 }  // namespace
 
-static bool g_c8_enabled = true;
-// tests and A/B benchmarks switch the kernel off to send the same layers to the direct kernel (conv_mfma<1,2,1>)
-extern "C" void tdvc_debug_enable_conv_c8(int enable) { g_c8_enabled = enable != 0; }
-
 bool conv_c8_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_C8") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  if (off || !g_c8_enabled) return false;
-  bool taps33 = d->ntaps == 9 && d->kh == 3 && d->kw == 3 && d->pad == 1;
-  for (int t = 0; taps33 && t < 9; ++t) taps33 = d->tap_dy[t] == t / 3 && d->tap_dx[t] == t % 3;
-  return taps33 && d->ck == 8 && d->stride == 1 && d->cout == 64 && d->x.C == 8 && !d->s2d && !d->square_input && (long)Ho * Wo >= 8192 &&
+  return convk::taps_dense(d, 3, 3, 1) && d->ck == 8 && d->stride == 1 && d->cout == 64 && d->x.C == 8 && !d->s2d && !d->square_input &&
+         (long)Ho * Wo >= convk::LARGE_MAP_PIXELS &&
          convk::conv_is_lean(p) && !p.res.p && !p.res2.p && p.y.C >= 64 && (long)d->x.N * Ho * ((Wo + 31) / 32) < (1L << 30);
 }
 

@@ -22,6 +22,53 @@ struct ConvParams {
   int8_t tap_dy[TDVC_MAX_TAPS], tap_dx[TDVC_MAX_TAPS];
 };
 
+// ---- host side: what the kernels' eligibility predicates and launchers share (the dispatch table is in conv_dispatch.hip) ------
+// Kernel switches.  conv_on(id) is 0 when TDVC_CONV_V1 or the switch's own TDVC_CONV_NO_* variable is set, else what the
+// tdvc_debug_enable_* setter last stored: 1 by default; for conv_row a mask of its four geometries (15 by default).
+enum ConvSwitch { SW_NONE = -1, SW_V2, SW_V3, SW_V5, SW_V7, SW_V9, SW_V10, SW_V11, SW_ROW, SW_C8, SW_N16, SW_GDN128, SW_COUNT };
+int conv_on(int id);
+long conv_v9_work_limit();      // pixels x output channels above which a v3-eligible layer stays on v3 (tdvc_debug_set_conv_v9_work_limit)
+
+// Output pixels per image from which the streaming kernels (v5, v7, v10, v11, conv_row, conv_c8, conv_n16, gdn128) take a layer;
+// at or below this many pixels over the whole batch the split-K kernel (v9) does.  ops.SMALL_MAP_PIXELS mirrors it.
+constexpr long LARGE_MAP_PIXELS = 8192;
+
+// the window is kh x kw with every tap present, in raster order (the streaming kernels derive (dy, dx) from the tap index)
+inline bool taps_dense(const tdvc_conv_desc* d, int kh, int kw, int pad) {
+  if (d->ntaps != kh * kw || d->kh != kh || d->kw != kw || d->pad != pad) return false;
+  for (int t = 0; t < d->ntaps; ++t)
+    if (d->tap_dy[t] != t / kw || d->tap_dx[t] != t % kw) return false;
+  return true;
+}
+
+// Counted waits (v7, v11) assume that EVERY wave issued its epilogue stores.  A wave covers `wave_ch` consecutive packed output
+// channels (sub-pixel store: inside one sub-pixel) and stores as soon as its first 8-channel chunk is inside the view y.C, so
+// the view must reach into the last wave's channels; a narrower view would leave whole waves without stores.
+inline bool all_waves_store(const tdvc_conv_desc* d, int wave_ch) {
+  const int ych = d->out_mode == TDVC_OUT_SHUFFLE2 ? d->cout >> 2 : (d->cout + wave_ch - 1) / wave_ch * wave_ch;
+  return d->y.C > ych - wave_ch;
+}
+
+// workgroups along x of a persistent launch: `slots` workgroups shared by the (cout block, image) pairs, at most one per tile
+inline int persistent_grid_x(int slots, int cout_blocks, int N, int ntiles) {
+  const int gx = slots / (cout_blocks * N);
+  return gx < 1 ? 1 : (gx > ntiles ? ntiles : gx);
+}
+
+// Raises the dynamic-LDS limit of Kern to `lds_limit` once per device, then launches it.
+template <auto Kern, typename... Args>
+int launch_big_lds(const char* what, int lds_limit, dim3 grid, dim3 block, int lds, hipStream_t st, Args... args) {
+  static TdvcPerDeviceFlag raised;          // one per Kern
+  bool& done = raised.flag();
+  if (!done) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+    if (err != hipSuccess) { tdvc_set_error("%s: hipFuncSetAttribute failed: %s", what, hipGetErrorString(err)); return (int)err; }
+    done = true;
+  }
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  return tdvc_launch_status(what);
+}
+
 
 // Epilogue for 4 consecutive output channels co..co+3 of output pixel (oy, ox) of image n:
 // bias -> GDN -> fp16 rounding (DCN quirk) -> activation -> residual(s) -> store (NHWC fp16 / fp32,

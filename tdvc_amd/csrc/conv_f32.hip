@@ -218,8 +218,8 @@ extern "C" int tdvc_pack_conv_weights_indexed_f32(const float* w, const int32_t*
   return tdvc_launch_status("tdvc_pack_conv_weights_indexed_f32");
 }
 
-// tdvc_conv2d forwards here when the input fmap is fp32 (`d->w` then points at the fp32 packing).
-extern "C" int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream) {
+// what tdvc_conv2d_f32 accepts (also asked by tdvc_conv_select) -> TDVC_OK and the output map
+int conv_f32_validate(const tdvc_conv_desc* d, int& Ho, int& Wo) {
   TDVC_CHECK(d, "tdvc_conv2d_f32: null descriptor");
   TDVC_CHECK(fmap_ok32(d->x) && (d->x.C % 8) == 0 && (d->x.sp % 4) == 0 && (d->x.sn % 4) == 0 && aligned16(d->x.p),
              "tdvc_conv2d_f32: input must be an fp32 fmap with C %% 8 == 0, 16-byte aligned pixels");
@@ -232,8 +232,8 @@ extern "C" int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream) {
   for (int t = 0; t < d->ntaps; ++t)
     TDVC_CHECK(d->tap_dy[t] >= 0 && d->tap_dy[t] < d->kh && d->tap_dx[t] >= 0 && d->tap_dx[t] < d->kw,
                "tdvc_conv2d_f32: tap %d out of the %dx%d window", t, d->kh, d->kw);
-  const int Ho = (d->x.H + 2 * d->pad - d->kh) / d->stride + 1;
-  const int Wo = (d->x.W + 2 * d->pad - d->kw) / d->stride + 1;
+  Ho = (d->x.H + 2 * d->pad - d->kh) / d->stride + 1;
+  Wo = (d->x.W + 2 * d->pad - d->kw) / d->stride + 1;
   TDVC_CHECK(Ho > 0 && Wo > 0, "tdvc_conv2d_f32: empty output");
   TDVC_CHECK((long)Ho * Wo * 4 * d->x.N < 2147483647L && (long)d->x.H * d->x.W < 2147483647L, "tdvc_conv2d_f32: image too large (pixel indices are 32-bit)");
   const int shuf = d->out_mode == TDVC_OUT_SHUFFLE2;
@@ -258,6 +258,13 @@ extern "C" int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream) {
     TDVC_CHECK((d->res2.dtype == TDVC_F32 ? fmap_ok32(d->res2) : fmap_ok16(d->res2)) && d->res2.N == d->x.N &&
                    d->res2.H == (shuf ? 2 * Ho : Ho) && d->res2.W == (shuf ? 2 * Wo : Wo), "tdvc_conv2d_f32: bad second residual fmap");
   if (d->bias) TDVC_CHECK(aligned16(d->bias), "tdvc_conv2d_f32: bias unaligned");
+  return TDVC_OK;
+}
+
+// tdvc_conv2d forwards here when the input fmap is fp32 (`d->w` then points at the fp32 packing).
+extern "C" int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream) {
+  int Ho, Wo;
+  if (const int rc = conv_f32_validate(d, Ho, Wo)) return rc;
 
   ConvParams p;
   memset(&p, 0, sizeof(p));

@@ -125,33 +125,21 @@ __global__ __launch_bounds__(GD_NTHR, 2) void gdn128_kernel(const ConvParams p, 
 
 }  // namespace
 
-static bool g_gdn128_enabled = true;
-// tests and A/B benchmarks switch the kernel off to send the same layers to conv_mfma_v5 (1x1 conv + GDN epilogue)
-extern "C" void tdvc_debug_enable_gdn128(int enable) { g_gdn128_enabled = enable != 0; }
-
 bool gdn128_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_GDN128") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  if (off || !g_gdn128_enabled) return false;
   // the GDN call of ops.conv: 1x1 / stride 1 / pad 0 over x^2, multiplicand aux == x itself, fp16 NHWC output, optional fp16
   // residual of the output geometry, no activation
   return d->kh == 1 && d->kw == 1 && d->ntaps == 1 && d->stride == 1 && d->pad == 0 && d->ck == 32 && d->square_input && d->gdn != TDVC_GDN_NONE &&
          d->x.C == 128 && d->cout == 128 && !d->s2d && d->out_mode == TDVC_OUT_NHWC && d->y.dtype == TDVC_F16 && d->y.C >= 128 && d->bias &&
          d->act == TDVC_ACT_NONE && !d->round_before_act && !d->res2.p && d->aux.p == d->x.p && d->aux.sp == d->x.sp && d->aux.sn == d->x.sn &&
          d->aux.dtype == TDVC_F16 && (!d->res.p || (d->res.dtype == TDVC_F16 && d->res.C >= 128)) &&
-         (long)Ho * Wo >= 8192 && (long)d->x.N * Ho * Wo < (1L << 31) - 64;
+         (long)Ho * Wo >= convk::LARGE_MAP_PIXELS && (long)d->x.N * Ho * Wo < (1L << 31) - 64;
 }
 
 int launch_gdn128(const ConvParams& p, int N, hipStream_t st) {
   const long total = (long)N * p.Ho * p.Wo;
   long blocks = ((total + 31) / 32 + GD_NW - 1) / GD_NW;
   if (blocks > 512) blocks = 512;                    // two workgroups per CU
-  auto go = [&](auto kern) -> int {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, GD_LDS);
-    if (err != hipSuccess) { tdvc_set_error("gdn128: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(GD_NTHR), GD_LDS, st, p, (unsigned)total, (unsigned)((long)p.Ho * p.Wo));
-    return 0;
-  };
-  const int rc = p.res.p ? go(&gdn128_kernel<true>) : go(&gdn128_kernel<false>);
-  if (rc) return rc;
-  return tdvc_launch_status("tdvc_conv2d(gdn128)");
+  const auto go = p.res.p ? convk::launch_big_lds<&gdn128_kernel<true>, ConvParams, unsigned, unsigned>
+                          : convk::launch_big_lds<&gdn128_kernel<false>, ConvParams, unsigned, unsigned>;
+  return go("tdvc_conv2d(gdn128)", GD_LDS, dim3((unsigned)blocks), dim3(GD_NTHR), GD_LDS, st, p, (unsigned)total, (unsigned)((long)p.Ho * p.Wo));
 }

@@ -18,29 +18,6 @@
 #include "conv_common.h"
 
 using convk::ConvParams;
-int launch_conv_v2(const ConvParams& p, int ntiles, int cout_blocks, int N, hipStream_t st);
-bool conv_v2_eligible(const tdvc_conv_desc* d, int Ho, int Wo);
-int launch_conv_v3(const ConvParams& p, int cout_blocks, int N, hipStream_t st);
-bool conv_v3_eligible(const tdvc_conv_desc* d, int Ho, int Wo);
-int launch_conv_v5(const ConvParams& p, int cout_blocks, int N, hipStream_t st);
-bool conv_v5_eligible(const tdvc_conv_desc* d, int Ho, int Wo);
-int conv_v5_chan_sum_rows(int Ho, int Wo, int cout_blocks, int N);
-int launch_conv_v7(const ConvParams& p, int cout_blocks, int N, hipStream_t st);
-bool conv_v7_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo);
-int launch_conv_v11(const ConvParams& p, int cout_blocks, int N, hipStream_t st);
-bool conv_v11_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo);
-int launch_conv_row(int geo, const ConvParams& p, int N, hipStream_t st);
-int conv_row_geometry(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo);
-int launch_conv_v10(const ConvParams& p, int cout_blocks, int N, hipStream_t st);
-bool conv_v10_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo);
-int launch_conv_v9(const ConvParams& p, int ck8, int cout_tiles32, int N, hipStream_t st);
-bool conv_v9_eligible(const tdvc_conv_desc* d, int Ho, int Wo, bool v3_ok);
-bool conv_c8_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo);
-int launch_conv_c8(const ConvParams& p, int N, hipStream_t st);
-bool conv_n16_eligible(const tdvc_conv_desc* d, int Ho, int Wo);
-int launch_conv_n16(const ConvParams& p, int N, hipStream_t st);
-bool gdn128_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo);
-int launch_gdn128(const ConvParams& p, int N, hipStream_t st);
 
 namespace {
 
@@ -275,164 +252,19 @@ extern "C" int tdvc_pack_conv_weights(const float* w, int cout, int cin_real, in
   return TDVC_OK;
 }
 
-static thread_local char g_last_kernel[48] = "";
+// the direct kernel as the dispatch table's last entry (conv_dispatch.hip)
+int conv_direct_lds_bytes(const tdvc_conv_desc* d) { return lds_bytes(d->ck, d->kh, d->kw, d->stride); }
+int conv_cout_tiles(int cout) { return cout_tiles(cout); }
 
-// Tile-walk direction.  The 256 MB Infinity Cache sits in front of HBM and every layer streams a map slightly larger
-// than it (64 channels x 1088 x 1920 fp16 = 267 MB): when layer l+1 reads, in the same raster order, what layer l just
-// wrote, the head of the map has already been pushed out by its tail and nothing hits.  Consecutive launches therefore
-// walk the tile raster in OPPOSITE directions: the consumer starts on the producer's most recently written tiles (and on
-// the tail of the residual the producer read), which are still resident.  Launch parity is per host thread (one stream
-// of launches per rank); any order is correct, the alternation only decides what hits.
-static thread_local unsigned g_walk_parity = 0;
-static int g_walk_mode = -1;      // -1: read TDVC_CONV_WALK once (0 = always forward, 1 = alternate [default])
-extern "C" void tdvc_debug_set_conv_walk(int mode) { g_walk_mode = mode; }
-static int next_walk_reverse() {
-  if (g_walk_mode < 0) { const char* e = getenv("TDVC_CONV_WALK"); g_walk_mode = e ? atoi(e) : 1; }
-  return g_walk_mode == 1 ? (int)(g_walk_parity++ & 1u) : 0;
-}
-
-// query_rows: validate and dispatch as tdvc_conv2d would, but return the rows of tdvc_conv_desc::chan_sum instead of launching
-static int conv2d_impl(const tdvc_conv_desc* d, void* stream, bool query_rows) {
-  TDVC_CHECK(d, "tdvc_conv2d: null descriptor");
-  if (d->x.dtype == TDVC_F32) {           // fp32 islands (pnet.py:33,57): fp32 activations + fp32 packing -> conv_f32.hip
-    if (query_rows) return 0;
-    TDVC_CHECK(!d->chan_sum, "tdvc_conv2d: chan_sum is not available on the fp32 path (tdvc_conv_chan_sum_rows() == 0)");
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "conv_f32");
-    return tdvc_conv2d_f32(d, stream);
-  }
-  TDVC_CHECK(fmap_ok16(d->x), "tdvc_conv2d: input must be an fp16 fmap with C,sp %% 8 == 0 and 16-byte aligned");
-  TDVC_CHECK(d->w && aligned16(d->w), "tdvc_conv2d: weights null/unaligned");
-  TDVC_CHECK(d->stride == 1 || d->stride == 2, "tdvc_conv2d: stride %d unsupported", d->stride);
-  TDVC_CHECK(d->ntaps >= 1 && d->ntaps <= TDVC_MAX_TAPS && d->kh >= 1 && d->kh <= 7 && d->kw >= 1 && d->kw <= 7,
-             "tdvc_conv2d: bad kernel %dx%d ntaps=%d", d->kh, d->kw, d->ntaps);
-  TDVC_CHECK(d->ck == 8 || d->ck == 16 || d->ck == 32 || d->ck == 64, "tdvc_conv2d: bad ck %d", d->ck);
-  TDVC_CHECK(d->cout >= 1, "tdvc_conv2d: cout");
-  for (int t = 0; t < d->ntaps; ++t)
-    TDVC_CHECK(d->tap_dy[t] >= 0 && d->tap_dy[t] < d->kh && d->tap_dx[t] >= 0 && d->tap_dx[t] < d->kw,
-               "tdvc_conv2d: tap %d out of the %dx%d window", t, d->kh, d->kw);
-  int Ho = (d->x.H + 2 * d->pad - d->kh) / d->stride + 1;
-  int Wo = (d->x.W + 2 * d->pad - d->kw) / d->stride + 1;
-  if (d->s2d) {
-    TDVC_CHECK(d->kh == 2 && d->kw == 2 && d->stride == 1 && d->pad == 1 && d->ntaps == 4 && d->ck == 32 && !d->square_input && !d->gdn,
-               "tdvc_conv2d: s2d expects the virtual 2x2 / stride 1 / pad 1 conv packed with ck=32");
-    TDVC_CHECK((d->x.H % 2) == 0 && (d->x.W % 2) == 0 && (d->x.C % 32) == 0 && d->cout >= 64,
-               "tdvc_conv2d: s2d needs even H, W, C %% 32 == 0 and cout >= 64 (got %dx%dx%d, cout %d)", d->x.H, d->x.W, d->x.C, d->cout);
-    Ho = d->x.H / 2;
-    Wo = d->x.W / 2;
-  }
-  TDVC_CHECK(Ho > 0 && Wo > 0, "tdvc_conv2d: empty output");
-  TDVC_CHECK((long)Ho * Wo * 4 < 2147483647L && (long)d->x.H * d->x.W < 2147483647L, "tdvc_conv2d: image too large (pixel indices are 32-bit)");
-  const int lds = lds_bytes(d->ck, d->kh, d->kw, d->stride);
-
-  const int shuf = d->out_mode == TDVC_OUT_SHUFFLE2;
-  if (d->out_mode == TDVC_OUT_NCHW_F32) {
-    TDVC_CHECK(d->y.p && d->y.N == d->x.N, "tdvc_conv2d: NCHW output null / batch mismatch");
-  } else {
-    TDVC_CHECK(d->y.dtype == TDVC_F32 ? fmap_ok32(d->y) : fmap_ok16(d->y), "tdvc_conv2d: bad output fmap");
-    TDVC_CHECK(d->y.N == d->x.N && d->y.H == (shuf ? 2 * Ho : Ho) && d->y.W == (shuf ? 2 * Wo : Wo),
-               "tdvc_conv2d: output geometry %dx%d does not match conv result %dx%d%s", d->y.H, d->y.W, Ho, Wo,
-               shuf ? " (x2 shuffle)" : "");
-    if (shuf) TDVC_CHECK((d->cout % 128) == 0, "tdvc_conv2d: SHUFFLE2 needs cout %% 128 == 0");
-    if (d->y.dtype == TDVC_F16) TDVC_CHECK((d->y.C % 8) == 0, "tdvc_conv2d: fp16 output C %% 8");
-  }
-  if (d->gdn) {
-    TDVC_CHECK(fmap_ok16(d->aux) && d->aux.H == Ho && d->aux.W == Wo && d->aux.N == d->x.N && d->aux.C >= d->cout &&
-                   !shuf && (d->cout % 64) == 0,
-               "tdvc_conv2d: GDN aux fmap mismatch");
-  }
-  if (d->res.p) {
-    TDVC_CHECK(d->res.dtype == TDVC_F32 ? fmap_ok32(d->res) : fmap_ok16(d->res), "tdvc_conv2d: bad residual fmap");
-    TDVC_CHECK(d->res.N == d->x.N && d->res.H == (shuf ? 2 * Ho : Ho) && d->res.W == (shuf ? 2 * Wo : Wo),
-               "tdvc_conv2d: residual geometry mismatch");
-  }
-  if (d->res2.p) {
-    TDVC_CHECK(fmap_ok16(d->res2) && d->res2.N == d->x.N && d->res2.H == (shuf ? 2 * Ho : Ho) && d->res2.W == (shuf ? 2 * Wo : Wo),
-               "tdvc_conv2d: bad second residual fmap");
-  }
-  if (d->bias) TDVC_CHECK(aligned16(d->bias), "tdvc_conv2d: bias unaligned");
-
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = reinterpret_cast<const half_t*>(d->x.p); p.x_sn = d->x.sn; p.x_sp = d->x.sp;
-  p.H = d->x.H; p.W = d->x.W; p.Cin = d->x.C;
-  p.w = reinterpret_cast<const half_t*>(d->w); p.bias = d->bias;
-  p.y = to_dev(d->y); p.Ho = Ho; p.Wo = Wo; p.cout = d->cout;
-  p.aux = d->gdn ? to_dev(d->aux) : null_fmap();
-  p.res = d->res.p ? to_dev(d->res) : null_fmap();
-  p.res2 = d->res2.p ? to_dev(d->res2) : null_fmap();
-  p.ntaps = d->ntaps; p.kh = d->kh; p.kw = d->kw; p.pad = d->pad;
-  p.in_stride = d->stride;
-  const int ck8 = d->ck / 8;
-  p.s2d = d->s2d; p.Corig = d->x.C;
-  p.bcast_T = d->bcast_T; p.bcast_slope = d->bcast_slope;
-  p.nchunks = d->s2d ? (4 * d->x.C) / d->ck : (d->x.C + d->ck - 1) / d->ck;
-  p.steps = (d->ntaps * ck8 + 1) / 2;
-  p.square = d->square_input; p.gdn = d->gdn; p.act = d->act; p.slope = d->slope;
-  p.round16 = d->round_before_act; p.out_mode = d->out_mode;
-  memcpy(p.tap_dy, d->tap_dy, sizeof(p.tap_dy));
-  memcpy(p.tap_dx, d->tap_dx, sizeof(p.tap_dx));
-  const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + TH - 1) / TH;
-  p.tiles_x = tiles_x;
-  p.reverse = query_rows ? 0 : next_walk_reverse();
-  p.csum = nullptr;
-  const int tiles = cout_tiles(d->cout);
-  const int mt = tiles == 1 ? 1 : 2;
-  if (mt == 2 && convk::conv_is_simple(p)) {
-    p.simple = convk::conv_is_lean(p) ? 2 : 1;       // 2: the lean packed-fp16 form of the transposed epilogue (conv_common.h)
-    p.slope = convk::conv_simple_slope(p);
-  }
-  {
-    // fused channel sums (tdvc_conv_desc::chan_sum): the lean epilogue of conv_mfma_v5 with one block of 64 output channels
-    const bool csum_ok = !d->bcast_T && !d->s2d && tiles == 2 && p.simple == 2 && !conv_v9_eligible(d, Ho, Wo, conv_v3_eligible(d, Ho, Wo)) &&
-                         !gdn128_eligible(d, p, Ho, Wo) && conv_v5_eligible(d, Ho, Wo);
-    if (query_rows) return csum_ok ? conv_v5_chan_sum_rows(Ho, Wo, 1, d->x.N) : 0;
-    TDVC_CHECK(!d->chan_sum || (csum_ok && (reinterpret_cast<uintptr_t>(d->chan_sum) & 15) == 0),
-               "tdvc_conv2d: chan_sum on a conv whose kernel has no fused channel sum (tdvc_conv_chan_sum_rows() == 0) or unaligned");
-    p.csum = d->chan_sum;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  auto chose = [](const char* name) { snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", name); };
-  if (d->bcast_T) {          // temporal 1x1 conv + broadcast add + LeakyReLU over the slices at y: one kernel takes it (conv_mfma_v5)
-    TDVC_CHECK(d->bcast_T == 4 && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->cout == 64 && d->y.C == 64 && d->y.sp >= 4 * 64 &&
-                   d->y.dtype == TDVC_F16 && d->out_mode == TDVC_OUT_NHWC && d->act == TDVC_ACT_NONE && !d->gdn && !d->res.p && !d->res2.p &&
-                   !d->square_input && !d->round_before_act && d->bias && d->bcast_slope >= 0.f && d->bcast_slope <= 1.f && conv_v5_eligible(d, Ho, Wo) &&
-                   convk::conv_is_lean(p),
-               "tdvc_conv2d: bcast_T needs a plain 1x1 / stride 1 conv to 64 channels of >= 8192 pixels, y a 64-channel window of a buffer with >= 4 slices, bcast_T == 4");
-    p.simple = 2;
-    p.slope = 1.f;
-    chose("conv_mfma_v5(bcast)");
-    return launch_conv_v5(p, 1, d->x.N, st);
-  }
-  if (d->s2d) {
-    if (const int geo = conv_row_geometry(d, p, Ho, Wo); geo >= 0) { chose("conv_row(s2d)"); return launch_conv_row(geo, p, d->x.N, st); }
-    TDVC_CHECK(conv_v3_eligible(d, Ho, Wo), "tdvc_conv2d: s2d conv not eligible for the stage-pipelined kernel");
-    chose("conv_mfma_v3(s2d)");
-    return launch_conv_v3(p, tiles / 2, d->x.N, st);
-  }
-  if (conv_v9_eligible(d, Ho, Wo, conv_v3_eligible(d, Ho, Wo))) { chose("conv_mfma_v9"); return launch_conv_v9(p, ck8, tiles, d->x.N, st); }
-  if (gdn128_eligible(d, p, Ho, Wo)) { chose("gdn128"); return launch_gdn128(p, d->x.N, st); }
-  if (conv_v5_eligible(d, Ho, Wo)) { chose("conv_mfma_v5"); return launch_conv_v5(p, tiles / 2, d->x.N, st); }
-  if (conv_c8_eligible(d, p, Ho, Wo)) { chose("conv_c8"); return launch_conv_c8(p, d->x.N, st); }
-  if (conv_n16_eligible(d, Ho, Wo)) { chose("conv_n16"); return launch_conv_n16(p, d->x.N, st); }
-  if (const int geo = conv_row_geometry(d, p, Ho, Wo); geo >= 0) { chose("conv_row"); return launch_conv_row(geo, p, d->x.N, st); }
-  if (conv_v10_eligible(d, p, Ho, Wo)) { chose("conv_mfma_v10"); return launch_conv_v10(p, tiles / 2, d->x.N, st); }
-  if (conv_v7_eligible(d, p, Ho, Wo)) { chose("conv_mfma_v7"); return launch_conv_v7(p, tiles / 2, d->x.N, st); }
-  if (conv_v11_eligible(d, p, Ho, Wo)) { chose("conv_mfma_v11"); return launch_conv_v11(p, tiles / 2, d->x.N, st); }
-  if (conv_v3_eligible(d, Ho, Wo)) { chose("conv_mfma_v3"); return launch_conv_v3(p, tiles / 2, d->x.N, st); }
-  if (conv_v2_eligible(d, Ho, Wo)) { chose("conv_mfma_v2"); return launch_conv_v2(p, 0, tiles / 2, d->x.N, st); }
-  TDVC_CHECK(lds <= 64 * 1024, "tdvc_conv2d: LDS plan %d bytes too large for the direct kernel (use tdvc_conv_plan)", lds);
-  dim3 grid(tiles_x * tiles_y, tiles / mt, d->x.N);
-  snprintf(g_last_kernel, sizeof(g_last_kernel), "conv_mfma<%d,%d,%d>", ck8, mt, d->stride);
+int launch_conv_direct(const ConvParams& p, int ck8, int stride, int N, hipStream_t st) {
+  const int tiles = cout_tiles(p.cout), mt = tiles == 1 ? 1 : 2;
+  const int lds = lds_bytes(ck8 * 8, p.kh, p.kw, stride);
+  const dim3 grid(p.tiles_x * ((p.Ho + TH - 1) / TH), tiles / mt, N);
   const size_t lds_v1 = (p.simple && lds < 256 + 4 * 32 * 144) ? 256 + 4 * 32 * 144 : lds;
   switch (ck8) {
-    case 1: return launch_m<1>(p, mt, d->stride, grid, lds_v1, st);
-    case 2: return launch_m<2>(p, mt, d->stride, grid, lds_v1, st);
-    case 4: return launch_m<4>(p, mt, d->stride, grid, lds_v1, st);
-    default: return launch_m<8>(p, mt, d->stride, grid, lds_v1, st);
+    case 1: return launch_m<1>(p, mt, stride, grid, lds_v1, st);
+    case 2: return launch_m<2>(p, mt, stride, grid, lds_v1, st);
+    case 4: return launch_m<4>(p, mt, stride, grid, lds_v1, st);
+    default: return launch_m<8>(p, mt, stride, grid, lds_v1, st);
   }
 }
-
-extern "C" int tdvc_conv2d(const tdvc_conv_desc* d, void* stream) { return conv2d_impl(d, stream, false); }
-extern "C" int tdvc_conv_chan_sum_rows(const tdvc_conv_desc* d) { return conv2d_impl(d, nullptr, true); }
-
-extern "C" const char* tdvc_last_conv_kernel(void) { return g_last_kernel; }

@@ -365,17 +365,9 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
 
 extern "C" void tdvc_debug_set_stamp_buffer_v10(void* buf, int cap_blocks) { g_stamp10 = (long long*)buf; g_stamp10_cap = cap_blocks; }
 
-static bool g_v10_enabled = true;
-// tests and A/B benchmarks switch the kernel off to send the same layers to conv_mfma_v7
-extern "C" void tdvc_debug_enable_conv_v10(int enable) { g_v10_enabled = enable != 0; }
-
 bool conv_v10_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_V10") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  if (off || !g_v10_enabled) return false;
-  bool taps33 = d->ntaps == 9 && d->kh == 3 && d->kw == 3 && d->pad == 1;
-  for (int t = 0; taps33 && t < 9; ++t) taps33 = d->tap_dy[t] == t / 3 && d->tap_dx[t] == t % 3;
-  return taps33 && d->ck == 32 && d->stride == 1 && d->cout >= 64 && d->x.C == 64 && !d->s2d &&
-         !d->square_input && (long)Ho * Wo >= 8192 && convk::conv_is_lean(p);
+  return convk::taps_dense(d, 3, 3, 1) && d->ck == 32 && d->stride == 1 && d->cout >= 64 && d->x.C == 64 && !d->s2d &&
+         !d->square_input && (long)Ho * Wo >= convk::LARGE_MAP_PIXELS && convk::conv_is_lean(p);
 }
 
 int launch_conv_v10(const ConvParams& p, int cout_blocks, int N, hipStream_t st) {
@@ -388,21 +380,12 @@ int launch_conv_v10(const ConvParams& p, int cout_blocks, int N, hipStream_t st)
   e.ntiles = q.tiles_x * tiles_y;
   e.zeros = reinterpret_cast<const half_t*>(zeros);
   q.slope = convk::conv_simple_slope(p);
-  int gx = 256 / (cout_blocks * N);
-  if (gx < 1) gx = 1;
-  if (gx > e.ntiles) gx = e.ntiles;
-  dim3 grid(gx, cout_blocks, N);
-  auto go = [&](auto kern, bool stamp) -> int {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("conv v10: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    hipLaunchKernelGGL(kern, grid, dim3(NTHR10), LDS10, st, q, e, stamp ? g_stamp10 : (long long*)nullptr, stamp ? g_stamp10_cap : 0);
-    return 0;
-  };
+  dim3 grid(convk::persistent_grid_x(256, cout_blocks, N, e.ntiles), cout_blocks, N);
   const int nres = (p.res.p ? 1 : 0) + (p.res2.p ? 1 : 0);
   if (nres == 1 && !p.res.p) { q.res = q.res2; q.res2 = null_fmap(); }        // a single residual is always `res`
-  int rc;
-  if (g_stamp10) rc = nres == 0 ? go(&conv_mfma_v10_kernel<0, true>, true) : nres == 1 ? go(&conv_mfma_v10_kernel<1, true>, true) : go(&conv_mfma_v10_kernel<2, true>, true);
-  else rc = nres == 0 ? go(&conv_mfma_v10_kernel<0, false>, false) : nres == 1 ? go(&conv_mfma_v10_kernel<1, false>, false) : go(&conv_mfma_v10_kernel<2, false>, false);
-  if (rc) return rc;
-  return tdvc_launch_status("tdvc_conv2d(v10)");
+#define V10_GO(NRES, STAMP) convk::launch_big_lds<&conv_mfma_v10_kernel<NRES, STAMP>, ConvParams, V10Extra, long long*, int>
+  const auto go = g_stamp10 ? (nres == 0 ? V10_GO(0, true) : nres == 1 ? V10_GO(1, true) : V10_GO(2, true))
+                            : (nres == 0 ? V10_GO(0, false) : nres == 1 ? V10_GO(1, false) : V10_GO(2, false));
+#undef V10_GO
+  return go("tdvc_conv2d(v10)", 160 * 1024, grid, dim3(NTHR10), LDS10, st, q, e, g_stamp10, g_stamp10 ? g_stamp10_cap : 0);
 }

@@ -328,24 +328,14 @@ __global__ __launch_bounds__(NTHR11, 1) void conv_mfma_v11_kernel(const ConvPara
 extern "C" void tdvc_debug_set_stamp_buffer_v11(void* buf, int cap_blocks) { g_stamp11 = (long long*)buf; g_stamp11_cap = cap_blocks; }
 extern "C" void tdvc_debug_set_v11_experiment(int mode) { g_v11_experiment = mode; }
 
-static bool g_v11_enabled = true;
-// tests and A/B benchmarks switch the kernel off to send the same layers to conv_mfma_v3
-extern "C" void tdvc_debug_enable_conv_v11(int enable) { g_v11_enabled = enable != 0; }
-
 bool conv_v11_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_V11") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
   static const int min_cin = getenv("TDVC_V11_MIN_CIN") ? atoi(getenv("TDVC_V11_MIN_CIN")) : 128;
-  if (off || !g_v11_enabled) return false;
-  bool taps33 = d->ntaps == 9 && d->kh == 3 && d->kw == 3 && d->pad == 1;
-  for (int t = 0; taps33 && t < 9; ++t) taps33 = d->tap_dy[t] == t / 3 && d->tap_dx[t] == t % 3;
   // The counted `vmcnt(8)` at the top of a stage assumes that EVERY wave issued its 8 epilogue stores: a narrower output view
   // (y.C at or below cout - 32, or cout / 4 - 32 for the sub-pixel store) would leave whole waves without stores and their
   // weight DMA pieces in flight across the barrier -- such launches go to the stage-pipelined kernel instead.
-  // A wave covers 32 consecutive packed rows (cout % 64 == 0 here; sub-pixel store: inside one sub-pixel, cq % 32 == 0): it
-  // stores as soon as its first 8-channel chunk is inside the view.
-  const bool all_waves_store = d->y.C > (p.out_mode == TDVC_OUT_SHUFFLE2 ? (d->cout >> 2) : d->cout) - 32;
-  return taps33 && all_waves_store && d->ck == 32 && d->stride == 1 && d->cout >= 64 && (d->cout % 64) == 0 && (d->x.C % 32) == 0 && d->x.C >= min_cin && !d->s2d &&
-         !d->square_input && (long)Ho * Wo >= 8192 &&
+  // A wave covers 32 consecutive packed rows (cout % 64 == 0 here; sub-pixel store: inside one sub-pixel, cq % 32 == 0).
+  return convk::taps_dense(d, 3, 3, 1) && convk::all_waves_store(d, 32) && d->ck == 32 && d->stride == 1 && d->cout >= 64 && (d->cout % 64) == 0 &&
+         (d->x.C % 32) == 0 && d->x.C >= min_cin && !d->s2d && !d->square_input && (long)Ho * Wo >= convk::LARGE_MAP_PIXELS &&
          (convk::conv_is_lean(p) || (convk::conv_is_simple(p) && !p.gdn && p.out_mode == TDVC_OUT_SHUFFLE2 && ((d->cout >> 2) % 32) == 0));
 }
 
@@ -360,20 +350,8 @@ int launch_conv_v11(const ConvParams& p, int cout_blocks, int N, hipStream_t st)
   e.zeros = reinterpret_cast<const half_t*>(zeros);
   e.experiment = g_v11_experiment;
   q.slope = convk::conv_simple_slope(p);
-  int gx = 256 / (cout_blocks * N);
-  if (gx < 1) gx = 1;
-  if (gx > e.ntiles) gx = e.ntiles;
-  dim3 grid(gx, cout_blocks, N);
-  static TdvcPerDeviceFlag attr_flags;
-  bool& attr_done = attr_flags.flag();
-  if (!attr_done) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v11_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v11_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("conv v11: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    attr_done = true;
-  }
-  if (g_stamp11) hipLaunchKernelGGL(conv_mfma_v11_kernel<true>, grid, dim3(NTHR11), LDS11, st, q, e, g_stamp11, g_stamp11_cap);
-  else hipLaunchKernelGGL(conv_mfma_v11_kernel<false>, grid, dim3(NTHR11), LDS11, st, q, e, (long long*)nullptr, 0);
-  return tdvc_launch_status("tdvc_conv2d(v11)");
+  dim3 grid(convk::persistent_grid_x(256, cout_blocks, N, e.ntiles), cout_blocks, N);
+  const auto go = g_stamp11 ? convk::launch_big_lds<&conv_mfma_v11_kernel<true>, ConvParams, V11Extra, long long*, int>
+                            : convk::launch_big_lds<&conv_mfma_v11_kernel<false>, ConvParams, V11Extra, long long*, int>;
+  return go("tdvc_conv2d(v11)", 160 * 1024, grid, dim3(NTHR11), LDS11, st, q, e, g_stamp11, g_stamp11 ? g_stamp11_cap : 0);
 }

@@ -161,13 +161,11 @@ inline int v2_lds_bytes(int kh, int kw) { return 256 + 2 * WSLICE + (TH2 + kh - 
 extern "C" void tdvc_debug_set_stamp_buffer(void* buf, int cap_blocks) { g_stamp_buf = (long long*)buf; g_stamp_cap = cap_blocks; }
 
 bool conv_v2_eligible(const tdvc_conv_desc* d, int Ho, int Wo) {
-  static const bool force_v1 = getenv("TDVC_CONV_V1") != nullptr;
-  if (force_v1) return false;
   return d->ck == 32 && d->stride == 1 && d->ntaps >= 2 && d->cout >= 64 && d->x.C >= 32 && !d->square_input &&
          v2_lds_bytes(d->kh, d->kw) <= 80 * 1024 && (long)Ho * Wo >= 2048;
 }
 
-int launch_conv_v2(const ConvParams& p, int ntiles_unused, int cout_blocks, int N, hipStream_t st) {
+int launch_conv_v2(const ConvParams& p, int cout_blocks, int N, hipStream_t st) {
   ConvParams q = p;
   q.tiles_x = (p.Wo + TW2 - 1) / TW2;
   const int tiles_y = (p.Ho + TH2 - 1) / TH2;
@@ -176,25 +174,10 @@ int launch_conv_v2(const ConvParams& p, int ntiles_unused, int cout_blocks, int 
   const bool simple = convk::conv_is_simple(p);
   if (simple) q.slope = convk::conv_simple_slope(p);
   dim3 grid(q.tiles_x * tiles_y, cout_blocks, N);
-  hipError_t err = hipSuccess;
-  static TdvcPerDeviceFlag attr_flags;
-  bool& attr_done = attr_flags.flag();
-  if (!attr_done) {
-    err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v2_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("conv v2: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    attr_done = true;
-  }
-  const bool lean = simple && convk::conv_is_lean(p);
-  if (g_stamp_buf && simple) {
-    static bool a2 = false;
-    if (!a2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v2_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); a2 = true; }
-    hipLaunchKernelGGL((conv_mfma_v2_kernel<1, true>), grid, dim3(256), lds, st, q, g_stamp_buf, g_stamp_cap);
-  } else if (lean) hipLaunchKernelGGL((conv_mfma_v2_kernel<2>), grid, dim3(256), lds, st, q, (long long*)nullptr, 0);
-  else if (simple) hipLaunchKernelGGL((conv_mfma_v2_kernel<1>), grid, dim3(256), lds, st, q, (long long*)nullptr, 0);
-  else hipLaunchKernelGGL((conv_mfma_v2_kernel<0>), grid, dim3(256), lds, st, q, (long long*)nullptr, 0);
-  return tdvc_launch_status("tdvc_conv2d(v2)");
+  const bool stamp = g_stamp_buf && simple;
+  const auto go = stamp ? convk::launch_big_lds<&conv_mfma_v2_kernel<1, true>, ConvParams, long long*, int>
+                  : simple ? (convk::conv_is_lean(p) ? convk::launch_big_lds<&conv_mfma_v2_kernel<2>, ConvParams, long long*, int>
+                                                     : convk::launch_big_lds<&conv_mfma_v2_kernel<1>, ConvParams, long long*, int>)
+                           : convk::launch_big_lds<&conv_mfma_v2_kernel<0>, ConvParams, long long*, int>;
+  return go("tdvc_conv2d(v2)", 80 * 1024, grid, dim3(256), lds, st, q, stamp ? g_stamp_buf : nullptr, stamp ? g_stamp_cap : 0);
 }

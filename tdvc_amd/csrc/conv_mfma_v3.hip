@@ -209,8 +209,6 @@ inline int v3_lds_bytes(int kh, int kw, int ntaps) { return 512 + v3_tile_bytes(
 extern "C" void tdvc_debug_set_stamp_buffer_v3(void* buf, int cap_blocks) { g_stamp3 = (long long*)buf; g_stamp3_cap = cap_blocks; }
 
 bool conv_v3_eligible(const tdvc_conv_desc* d, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_V3") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  if (off) return false;
   const long minpix = 256;        // below: a handful of tiles, the direct kernel's shorter prologue wins
   return d->ck == 32 && d->stride == 1 && d->ntaps >= 2 && d->ntaps <= WLOADS && d->kh <= 3 && d->kw <= 3 && d->cout >= 64 &&
          d->x.C >= 32 && !d->square_input && ((long)Ho * Wo * d->x.N >= minpix || d->s2d);
@@ -227,28 +225,11 @@ int launch_conv_v3(const ConvParams& p, int cout_blocks, int N, hipStream_t st) 
   const bool simple = convk::conv_is_simple(p);
   if (simple) q.slope = convk::conv_simple_slope(p);
   // persistent grid: two workgroups per CU over all (cout block, image) pairs
-  int gx = 512 / (cout_blocks * N);
-  if (gx < 1) gx = 1;
-  if (gx > e.ntiles) gx = e.ntiles;
-  dim3 grid(gx, cout_blocks, N);
-  static TdvcPerDeviceFlag attr_flags;
-  bool& attr_done = attr_flags.flag();
-  if (!attr_done) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v3_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("conv v3: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    attr_done = true;
-  }
-  const bool lean = simple && convk::conv_is_lean(p);
-  if (g_stamp3 && simple) {
-    static bool a2 = false;
-    if (!a2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v3_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); a2 = true; }
-    hipLaunchKernelGGL((conv_mfma_v3_kernel<1, true>), grid, dim3(256), lds, st, q, e, g_stamp3, g_stamp3_cap);
-  } else if (lean) hipLaunchKernelGGL((conv_mfma_v3_kernel<2>), grid, dim3(256), lds, st, q, e, (long long*)nullptr, 0);
-  else if (simple) hipLaunchKernelGGL((conv_mfma_v3_kernel<1>), grid, dim3(256), lds, st, q, e, (long long*)nullptr, 0);
-  else hipLaunchKernelGGL((conv_mfma_v3_kernel<0>), grid, dim3(256), lds, st, q, e, (long long*)nullptr, 0);
-  return tdvc_launch_status("tdvc_conv2d(v3)");
+  dim3 grid(convk::persistent_grid_x(512, cout_blocks, N, e.ntiles), cout_blocks, N);
+  const bool stamp = g_stamp3 && simple;
+  const auto go = stamp ? convk::launch_big_lds<&conv_mfma_v3_kernel<1, true>, ConvParams, V3Extra, long long*, int>
+                  : simple ? (convk::conv_is_lean(p) ? convk::launch_big_lds<&conv_mfma_v3_kernel<2>, ConvParams, V3Extra, long long*, int>
+                                                     : convk::launch_big_lds<&conv_mfma_v3_kernel<1>, ConvParams, V3Extra, long long*, int>)
+                           : convk::launch_big_lds<&conv_mfma_v3_kernel<0>, ConvParams, V3Extra, long long*, int>;
+  return go("tdvc_conv2d(v3)", 80 * 1024, grid, dim3(256), lds, st, q, e, stamp ? g_stamp3 : nullptr, stamp ? g_stamp3_cap : 0);
 }

@@ -215,46 +215,26 @@ inline int v5_tl(int kh, int kw) { return ((WR + kh - 1) * (TW5 + kw - 1) * 4 + 
 
 template <int TL>
 int launch_tl(const ConvParams& q, const V5Extra& e, int mode, dim3 grid, int lds, hipStream_t st) {
-  static TdvcPerDeviceFlag attr_flags;
-  bool& attr_done = attr_flags.flag();
-  if (!attr_done) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v5_kernel<1, TL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v5_kernel<2, TL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v5_kernel<0, TL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err == hipSuccess)
-      err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_v5_kernel<4, TL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("conv v5: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    attr_done = true;
-  }
-  if (mode == 4) hipLaunchKernelGGL((conv_mfma_v5_kernel<4, TL>), grid, dim3(NTHR5), lds, st, q, e);
-  else if (mode == 2) hipLaunchKernelGGL((conv_mfma_v5_kernel<2, TL>), grid, dim3(NTHR5), lds, st, q, e);
-  else if (mode == 1) hipLaunchKernelGGL((conv_mfma_v5_kernel<1, TL>), grid, dim3(NTHR5), lds, st, q, e);
-  else hipLaunchKernelGGL((conv_mfma_v5_kernel<0, TL>), grid, dim3(NTHR5), lds, st, q, e);
-  return tdvc_launch_status("tdvc_conv2d(v5)");
+  const auto go = mode == 4 ? convk::launch_big_lds<&conv_mfma_v5_kernel<4, TL>, ConvParams, V5Extra>
+                  : mode == 2 ? convk::launch_big_lds<&conv_mfma_v5_kernel<2, TL>, ConvParams, V5Extra>
+                  : mode == 1 ? convk::launch_big_lds<&conv_mfma_v5_kernel<1, TL>, ConvParams, V5Extra>
+                              : convk::launch_big_lds<&conv_mfma_v5_kernel<0, TL>, ConvParams, V5Extra>;
+  return go("tdvc_conv2d(v5)", 160 * 1024, grid, dim3(NTHR5), lds, st, q, e);
 }
 
 }  // namespace
 
 bool conv_v5_eligible(const tdvc_conv_desc* d, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_V5") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  if (off) return false;
   const int nchunks = (d->x.C + CK5 - 1) / CK5;
   const int tl = v5_tl(d->kh, d->kw);
   const bool stride_ok = d->stride == 1 || (d->stride == 2 && d->kh == 1 && d->kw == 1 && d->pad == 0);   // ResidualBlockWithStride skips
   return d->ck == 32 && stride_ok && d->ntaps >= 1 && d->ntaps <= 9 && d->kh <= 3 && d->kw <= 3 && d->cout >= 64 &&
-         d->x.C >= 32 && !d->s2d && ((long)Ho * Wo >= 8192 || d->stride == 2) && tl == 4 &&     // stride 2: the only ck = 32 kernel that takes it
-
+         d->x.C >= 32 && !d->s2d && ((long)Ho * Wo >= convk::LARGE_MAP_PIXELS || d->stride == 2) && tl == 4 &&     // stride 2: the only ck = 32 kernel that takes it
          v5_lds_bytes(d->kh, d->kw, d->ntaps, nchunks) <= 160 * 1024;
 }
 
 // workgroups along x for a launch over `nbtiles` tiles (also the row count of tdvc_conv_desc::chan_sum: 8 waves per workgroup)
-static int v5_grid_x(int nbtiles, int cout_blocks, int N) {
-  int gx = 256 / (cout_blocks * N);
-  if (gx < 1) gx = 1;
-  return gx > nbtiles ? nbtiles : gx;
-}
+static int v5_grid_x(int nbtiles, int cout_blocks, int N) { return convk::persistent_grid_x(256, cout_blocks, N, nbtiles); }
 int conv_v5_chan_sum_rows(int Ho, int Wo, int cout_blocks, int N) {
   const int nbtiles = ((Wo + TW5 - 1) / TW5) * ((Ho + WR * NWAVE - 1) / (WR * NWAVE));
   return v5_grid_x(nbtiles, cout_blocks, N) * NWAVE;

@@ -235,15 +235,10 @@ __global__ __launch_bounds__(NTHR7, 1) void conv_mfma_v7_kernel(const ConvParams
 extern "C" void tdvc_debug_set_stamp_buffer_v7(void* buf, int cap_blocks) { g_stamp7 = (long long*)buf; g_stamp7_cap = cap_blocks; }
 
 bool conv_v7_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_V7") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  if (off) return false;
-  bool taps33 = d->ntaps == 9 && d->kh == 3 && d->kw == 3 && d->pad == 1;
-  for (int t = 0; taps33 && t < 9; ++t) taps33 = d->tap_dy[t] == t / 3 && d->tap_dx[t] == t % 3;
-  // the counted vmcnt(8) of a full tile assumes every wave stored (see conv_v11_eligible); here a wave covers the 64 packed
-  // rows of its cout block (sub-pixel store: inside one sub-pixel, cq % 64 == 0 by conv_is_simple)
-  const bool all_waves_store = d->y.C > (p.out_mode == TDVC_OUT_SHUFFLE2 ? (d->cout >> 2) - 64 : ((d->cout + 63) / 64 - 1) * 64);
-  return taps33 && all_waves_store && d->ck == 32 && d->stride == 1 && d->cout >= 64 && (d->x.C == 32 || d->x.C == 64) && !d->s2d &&
-         !d->square_input && (long)Ho * Wo >= 8192 && convk::conv_is_simple(p);
+  // the counted vmcnt(8) of a full tile assumes every wave stored; a wave covers the 64 packed rows of its cout block (sub-pixel
+  // store: inside one sub-pixel, cq % 64 == 0 by conv_is_simple)
+  return convk::taps_dense(d, 3, 3, 1) && convk::all_waves_store(d, 64) && d->ck == 32 && d->stride == 1 && d->cout >= 64 &&
+         (d->x.C == 32 || d->x.C == 64) && !d->s2d && !d->square_input && (long)Ho * Wo >= convk::LARGE_MAP_PIXELS && convk::conv_is_simple(p);
 }
 
 int launch_conv_v7(const ConvParams& p, int cout_blocks, int N, hipStream_t st) {
@@ -256,17 +251,8 @@ int launch_conv_v7(const ConvParams& p, int cout_blocks, int N, hipStream_t st) 
   e.ntiles = q.tiles_x * tiles_y;
   e.zeros = reinterpret_cast<const half_t*>(zeros);
   q.slope = convk::conv_simple_slope(p);
-  int gx = 256 / (cout_blocks * N);
-  if (gx < 1) gx = 1;
-  if (gx > e.ntiles) gx = e.ntiles;
-  dim3 grid(gx, cout_blocks, N);
-  auto go = [&](auto kern, bool stamp) -> int {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("conv v7: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    hipLaunchKernelGGL(kern, grid, dim3(NTHR7), LDS7, st, q, e, stamp ? g_stamp7 : (long long*)nullptr, stamp ? g_stamp7_cap : 0);
-    return 0;
-  };
-  const int rc = g_stamp7 ? go(&conv_mfma_v7_kernel<true>, true) : go(&conv_mfma_v7_kernel<false>, false);
-  if (rc) return rc;
-  return tdvc_launch_status("tdvc_conv2d(v7)");
+  dim3 grid(convk::persistent_grid_x(256, cout_blocks, N, e.ntiles), cout_blocks, N);
+  const auto go = g_stamp7 ? convk::launch_big_lds<&conv_mfma_v7_kernel<true>, ConvParams, V7Extra, long long*, int>
+                           : convk::launch_big_lds<&conv_mfma_v7_kernel<false>, ConvParams, V7Extra, long long*, int>;
+  return go("tdvc_conv2d(v7)", 160 * 1024, grid, dim3(NTHR7), LDS7, st, q, e, g_stamp7, g_stamp7 ? g_stamp7_cap : 0);
 }

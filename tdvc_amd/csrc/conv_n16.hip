@@ -156,19 +156,13 @@ inline int n16_lds(int cin, int kh, int kw, int ntaps, int ncb) {
 
 }  // namespace
 
-static bool g_n16_enabled = true;
-// tests and A/B benchmarks switch the kernel off to send the same layers to the direct kernel
-extern "C" void tdvc_debug_enable_conv_n16(int enable) { g_n16_enabled = enable != 0; }
-
 bool conv_n16_eligible(const tdvc_conv_desc* d, int Ho, int Wo) {
-  static const bool off = getenv("TDVC_CONV_NO_N16") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  if (off || !g_n16_enabled) return false;
   const int cin = d->x.C;
   const bool cin_ok = cin == 8 || cin == 16 || cin == 32 || cin == 64;
   // a single channel chunk (ck == cin): the packed blob's k order is then the flattened (tap, channel) order this kernel walks
-  bool dense = d->ntaps == d->kh * d->kw;                        // the kernel derives (dy, dx) from the tap index
-  for (int t = 0; dense && t < d->ntaps; ++t) dense = d->tap_dy[t] == t / d->kw && d->tap_dx[t] == t % d->kw;
-  return cin_ok && dense && d->ck == cin && d->stride == 1 && d->cout <= 32 && !d->s2d && !d->square_input && !d->gdn && (long)Ho * Wo >= 8192 &&
+  const bool dense = convk::taps_dense(d, d->kh, d->kw, d->pad);          // any window, any padding
+  return cin_ok && dense && d->ck == cin && d->stride == 1 && d->cout <= 32 && !d->s2d && !d->square_input && !d->gdn &&
+         (long)Ho * Wo >= convk::LARGE_MAP_PIXELS &&
          n16_lds(cin, d->kh, d->kw, d->ntaps, d->cout <= 16 ? 1 : 2) <= 150 * 1024;
 }
 
@@ -184,13 +178,6 @@ int launch_conv_n16(const ConvParams& p, int N, hipStream_t st) {
   const int lds = n16_lds(p.Cin, p.kh, p.kw, p.ntaps, ncb);
   const int per_cu = lds <= 78 * 1024 ? 2 : 1;     // 16 or 8 waves per CU
   int grid = e.ntiles < 256 * per_cu ? e.ntiles : 256 * per_cu;
-  auto go = [&](auto kern) -> int {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("conv n16: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(N16_NTHR), lds, st, p, e);
-    return 0;
-  };
-  const int rc = ncb == 1 ? go(&conv_n16_kernel<1>) : go(&conv_n16_kernel<2>);
-  if (rc) return rc;
-  return tdvc_launch_status("tdvc_conv2d(n16)");
+  const auto go = ncb == 1 ? convk::launch_big_lds<&conv_n16_kernel<1>, ConvParams, N16Extra> : convk::launch_big_lds<&conv_n16_kernel<2>, ConvParams, N16Extra>;
+  return go("tdvc_conv2d(n16)", 160 * 1024, dim3(grid), dim3(N16_NTHR), lds, st, p, e);
 }

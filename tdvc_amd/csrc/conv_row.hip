@@ -477,35 +477,24 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
 
 }  // namespace
 
-static int g_row_enabled = 15;
-// tests and A/B benchmarks: bit 0 = the Cin = 128 -> 128 k layers (off: conv_mfma_v11 takes them), bit 1 = Cin = 64 (off: conv_mfma_v10),
-// bit 2 = Cin = 128 -> 64 (2k + 1) (off: conv_mfma_v11), bit 3 = the space-to-depth form of the stride-2 convs (off: conv_mfma_v3)
-extern "C" void tdvc_debug_enable_conv_row(int enable) { g_row_enabled = enable; }
-
-static bool row_off() {
-  static const bool off = getenv("TDVC_CONV_NO_ROW") != nullptr || getenv("TDVC_CONV_V1") != nullptr;
-  return off || !g_row_enabled;
-}
-
-// -> geometry id, or -1
+// -> geometry id, or -1.  The switch is a mask (tdvc_debug_enable_conv_row): bit 0 = the Cin = 128 -> 128 k layers (off: conv_mfma_v11
+// takes them), bit 1 = Cin = 64 (off: conv_mfma_v10), bit 2 = Cin = 128 -> 64 (2k + 1) (off: conv_mfma_v11), bit 3 = the
+// space-to-depth form of the stride-2 convs (off: conv_mfma_v3)
 int conv_row_geometry(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int Wo) {
-  if (row_off() || d->ck != 32 || d->square_input || !d->bias || (long)Ho * Wo < 8192 || Ho < 16 || (d->res.p && d->res2.p)) return -1;
+  const int on = convk::conv_on(convk::SW_ROW);
+  if (d->ck != 32 || d->square_input || !d->bias || (long)Ho * Wo < convk::LARGE_MAP_PIXELS || Ho < 16 || (d->res.p && d->res2.p)) return -1;
   const bool shuf = p.out_mode == TDVC_OUT_SHUFFLE2;
   const int ych = shuf ? (d->cout >> 2) : d->cout;       // channels of an output pixel
   if (d->y.C < ych || (d->res.p && d->res.C < ych) || (d->res2.p && d->res2.C < ych)) return -1;
   if (d->s2d) {                                  // the virtual 2x2 / stride 1 / pad 1 conv over the space-to-depth view of a 3x3 stride-2 conv
-    const bool ok = (g_row_enabled & 8) && d->x.C == 64 && (d->cout % 128) == 0 && convk::conv_is_lean(p) && d->kh == 2 && d->kw == 2 && d->ntaps == 4 &&
-                    d->tap_dy[0] == 0 && d->tap_dx[0] == 0 && d->tap_dy[1] == 0 && d->tap_dx[1] == 1 && d->tap_dy[2] == 1 && d->tap_dx[2] == 0 &&
-                    d->tap_dy[3] == 1 && d->tap_dx[3] == 1;
+    const bool ok = (on & 8) && d->x.C == 64 && (d->cout % 128) == 0 && convk::conv_is_lean(p) && convk::taps_dense(d, 2, 2, 1);
     return ok ? GEO_S2D64 : -1;
   }
-  bool taps33 = d->ntaps == 9 && d->kh == 3 && d->kw == 3 && d->pad == 1 && d->stride == 1;
-  for (int t = 0; taps33 && t < 9; ++t) taps33 = d->tap_dy[t] == t / 3 && d->tap_dx[t] == t % 3;
-  if (!taps33) return -1;
+  if (!convk::taps_dense(d, 3, 3, 1) || d->stride != 1) return -1;
   const bool lean = convk::conv_is_lean(p);
-  if (d->x.C == 128 && (d->cout % 128) == 0 && (g_row_enabled & 1) && (lean || (convk::conv_is_simple(p) && !p.gdn && shuf && (ych % 8) == 0))) return GEO_C128;
-  if (d->x.C == 128 && (d->cout % 64) == 0 && (g_row_enabled & 4) && lean) return GEO_C128W;
-  if (d->x.C == 64 && (d->cout % 64) == 0 && (g_row_enabled & 2) && lean) return GEO_C64;
+  if (d->x.C == 128 && (d->cout % 128) == 0 && (on & 1) && (lean || (convk::conv_is_simple(p) && !p.gdn && shuf && (ych % 8) == 0))) return GEO_C128;
+  if (d->x.C == 128 && (d->cout % 64) == 0 && (on & 4) && lean) return GEO_C128W;
+  if (d->x.C == 64 && (d->cout % 64) == 0 && (on & 2) && lean) return GEO_C64;
   return -1;
 }
 
@@ -540,22 +529,17 @@ static int launch_conv_row_t(const ConvParams& p, int N, hipStream_t st) {
   }
   const bool has1 = q.res != nullptr;
   const int act = q.slope == 1.f ? 0 : (q.slope == 0.f ? 1 : 2);
-  auto go = [&](auto kern) -> int {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (err != hipSuccess) { tdvc_set_error("conv_row: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(RW_NTHR), G::LDS, st, q);
-    return 0;
-  };
   const int nres = has1 ? 1 : 0;
   int rc = TDVC_EINVAL;
-#define RW_CASE(A, R, S) if (act == A && nres == R && shuf == S) rc = go(&conv_row_kernel<GID, A, R, S>);
+#define RW_CASE(A, R, S) \
+  if (act == A && nres == R && shuf == S) \
+    rc = convk::launch_big_lds<&conv_row_kernel<GID, A, R, S>>("tdvc_conv2d(conv_row)", G::LDS, dim3(grid), dim3(RW_NTHR), G::LDS, st, q);
   RW_CASE(0, 0, false) RW_CASE(0, 1, false) RW_CASE(1, 0, false) RW_CASE(1, 1, false) RW_CASE(2, 0, false) RW_CASE(2, 1, false)
   if constexpr (GID == GEO_C128) {
     RW_CASE(0, 0, true) RW_CASE(0, 1, true) RW_CASE(1, 0, true) RW_CASE(1, 1, true) RW_CASE(2, 0, true) RW_CASE(2, 1, true)
   }
 #undef RW_CASE
-  if (rc) return rc;
-  return tdvc_launch_status("tdvc_conv2d(conv_row)");
+  return rc;
 }
 
 int launch_conv_row(int geo, const ConvParams& p, int N, hipStream_t st) {

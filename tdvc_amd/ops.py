@@ -368,7 +368,7 @@ def pack_conv(weight: torch.Tensor, bias: torch.Tensor | None, stride=1, pad=0, 
     return pc
 
 
-SMALL_MAP_PIXELS = 8192      # conv_mfma_v9's range (csrc/conv_mfma_v9.hip)
+SMALL_MAP_PIXELS = 8192      # conv_mfma_v9's range: LARGE_MAP_PIXELS of csrc/conv_common.h
 
 
 def _plain_form(pc: PackedConv) -> PackedConv:

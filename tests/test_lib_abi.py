@@ -27,7 +27,7 @@ def test_every_declared_symbol_is_exported_and_bound():
         assert hasattr(lib, s), f"{s} declared in include/tdvc_hip.h but not exported"
         assert s in L.SIGNATURES, f"{s} has no ctypes signature in tdvc_amd/_lib.py"
     assert set(L.SIGNATURES) == set(syms)
-    assert lib.tdvc_abi_version() >= 1
+    assert lib.tdvc_abi_version() >= 5          # 5: tdvc_conv_select
 
 
 def test_struct_sizes_match_header_layout():
