@@ -308,7 +308,13 @@ def record_conv(tape: Tape, x: FM, pc, y, act, slope, res, res2, gdn, aux, squar
             held |= tape.add_identity(res, g)
         if res2 is not None and tape.needs_grad(res2):
             held |= tape.add_identity(res2, g)
-        if g.f32:                                 # fp32 outputs (flow, latents): the MFMA backward kernels take fp16
+        if x.f32:                                 # the layer ran in fp32 (fp32 coders): its backward does too -- conv_f32 on the
+            if nchw_out is not None:              # dgrad packing, conv_wgrad_f32; an fp16 gradient (x_hat is stored fp16) is cast up
+                raise NotImplementedError("autograd: planar output of an fp32 conv")
+            if not g.f32:
+                g = ops.copy_cast(g, FM.empty(g.N, g.H, g.W, g.C, dtype=torch.float32, device=g.t.device))
+                held = False
+        elif g.f32:                               # fp32 outputs (flow, latents): the MFMA backward kernels take fp16
             g = ops.copy_cast(g, FM.empty(g.N, g.H, g.W, ops.pad8(g.C), device=g.t.device))
             held = False
         fresh = (lambda: FM.empty(g.N, g.H, g.W, g.C, dtype=g.t.dtype, device=g.t.device)) if held else (lambda: None)
@@ -361,6 +367,15 @@ def record_se_gate(tape: Tape, x: FM, p, partial, nblocks, gate):
         dmean = ops.se_gate_backward(p, partial, nblocks, x.H * x.W, gate, dgate, tape.inv_scale, grads)
         if tape.needs_grad(x):
             ops.bcast_channel_add(tape.grad(x), dmean, 1.0 / (x.H * x.W))
+
+    tape.add(bwd)
+
+
+def record_cast(tape: Tape, x: FM, out: FM):
+    """out = float(x): grad(x) += round(grad(out))"""
+    def bwd():
+        if tape.needs_grad(x):
+            accumulate(tape.grad(x), tape.grad(out))
 
     tape.add(bwd)
 
@@ -440,7 +455,7 @@ def record_gdn(tape: Tape, x: FM, pc, y: FM, res, gdn):
         n32 = ops.conv(x, pc, square=True, out_dtype=torch.float32)
         dx = tape.grad(x)
         dn = ops.gdn_backward(g, x, n32, gdn == ops.GDN_INV, dx)
-        t = ops.conv_dgrad(pc, dn, FM.empty(x.N, x.H, x.W, x.C, device=x.t.device), accumulate=False)
+        t = ops.conv_dgrad(pc, dn, FM.empty(x.N, x.H, x.W, x.C, dtype=x.t.dtype, device=x.t.device), accumulate=False)
         ops.mul2_accumulate(dx, x, t)
         dgamma, dbeta = tape.zeros_like(pc.wsrc), tape.zeros_like(pc.bsrc)
         ops.conv_wgrad(pc, dn, x, dgamma.view(-1), scale=tape.inv_scale, square_x=True, db=dbeta)

@@ -948,7 +948,7 @@ extern "C" int tdvc_match_gather_backward(const tdvc_fmap* fin, const tdvc_fmap*
 }
 
 extern "C" int tdvc_gdn_backward(const tdvc_fmap* g, const tdvc_fmap* x, const tdvc_fmap* n32, int inverse, const tdvc_fmap* dn, const tdvc_fmap* dx, void* stream) {
-  TDVC_CHECK(g && x && n32 && dn && dx && fmap_any(*g) && fmap_ok16(*x) && fmap_ok32(*n32) && fmap_ok16(*dn) && fmap_ok16(*dx) && same_geom(*g, *x) &&
+  TDVC_CHECK(g && x && n32 && dn && dx && fmap_any(*g) && fmap_any(*x) && fmap_ok32(*n32) && fmap_any(*dn) && fmap_any(*dx) && same_geom(*g, *x) &&
                  same_geom(*g, *n32) && same_geom(*g, *dn) && same_geom(*g, *dx) && (g->C % 8) == 0 && x->C >= g->C && n32->C >= g->C && dn->C >= g->C &&
                  dx->C >= g->C, "tdvc_gdn_backward: bad arguments");
   const long total = (long)g->N * g->H * g->W * (g->C / 8);
@@ -957,7 +957,8 @@ extern "C" int tdvc_gdn_backward(const tdvc_fmap* g, const tdvc_fmap* x, const t
 }
 
 extern "C" int tdvc_mul2_accumulate(const tdvc_fmap* dx, const tdvc_fmap* x, const tdvc_fmap* t, void* stream) {
-  TDVC_CHECK(dx && x && t && fmap_ok16(*dx) && fmap_ok16(*x) && fmap_ok16(*t) && same_geom(*dx, *x) && same_geom(*dx, *t) && x->C >= dx->C && t->C >= dx->C,
+  // the kernel moves 8 channels per thread: fp16 maps have C % 8 == 0 by construction (fmap_ok16), fp32 maps are held to it here
+  TDVC_CHECK(dx && x && t && fmap_any(*dx) && fmap_any(*x) && fmap_any(*t) && (dx->C % 8) == 0 && same_geom(*dx, *x) && same_geom(*dx, *t) && x->C >= dx->C && t->C >= dx->C,
              "tdvc_mul2_accumulate: bad arguments");
   const long total = (long)dx->N * dx->H * dx->W * (dx->C / 8);
   hipLaunchKernelGGL(mul2_accumulate_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), to_dev(*x), to_dev(*t));

@@ -334,6 +334,162 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
   }
 }
 
+// The fp32 form (fp32 coders in training): dY and X are fp32 maps, the contraction runs on
+// v_mfma_f32_32x32x2_f32.  K = 2 PIXELS per instruction: lane (r, hh) supplies dY[pixel hh][co r] and X[pixel hh + tap][ci r],
+// so lanes 0..31 read 32 consecutive channels of one channel-innermost pixel -- both operands are coalesced 128-byte reads
+// in the order the MFMA wants them, no transpose and therefore no LDS staging: they come through L1 as in conv_f32.hip (the
+// four waves of a workgroup read the same dY values, the taps of a wave overlapping X windows).  The fp32 matrix pipe takes
+// 64 cycles per MFMA, a k-step of 6 MFMAs has 384 cycles to hide its 5 dword loads per lane.
+// Same decomposition as conv_wgrad_kernel: one workgroup owns a (64 co x 32 ci x <= 12 taps) block of dW, wave w the taps
+// w, w + 4, w + 8, and walks the worker's 8 x 32 pixel blocks; same grid, same workspace [P][ntaps][co][ci] (+ bwork), same
+// second stage.  Loads are unconditional at clamped addresses and zeroed by an opaque bit mask where they are consumed
+// (conv_f32.hip: a select next to the load made hipcc sink the loads behind branches; 0 * Inf of a multiplier is NaN).
+// U k-steps (2 U pixels of one output row) are fetched at a time, one group ahead of the MFMAs that consume them.
+template <int U>
+__global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const WgradParams p) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int T = p.co_tiles * p.ci_tiles * p.ngroups;                // grid mapping of conv_wgrad_kernel
+  const int jx = (int)blockIdx.x >> 3;
+  const int worker = ((int)blockIdx.x & 7) + 8 * (jx / T), nworkers = p.nworkers;
+  if (worker >= nworkers) return;
+  const int item = jx % T, tile = item % (p.co_tiles * p.ci_tiles), zgroup = item / (p.co_tiles * p.ci_tiles);
+  const int cit = tile % p.ci_tiles, cot = tile / p.ci_tiles;
+  const int tap0 = zgroup * WG_MAXT, ntaps_g = min(WG_MAXT, p.ntaps_all - tap0);
+  const int co0 = cot * WG_CO, ci0 = cit * WG_CI;
+  if (wave >= ntaps_g) return;                                      // a wave without a tap (wave-uniform; the kernel has no barrier)
+
+  int tdy[3], tdx[3];
+  bool tv[3];
+#pragma unroll
+  for (int ai = 0; ai < 3; ++ai) {
+    const int t = wave + 4 * ai;
+    tv[ai] = t < ntaps_g;                                           // an absent tap reads tap 0's window and skips its MFMAs
+    const int tt = tap0 + (tv[ai] ? t : 0);
+    tdy[ai] = p.tap_dy[tt] - p.pad;
+    tdx[ai] = p.tap_dx[tt] - p.pad;
+  }
+  // channels of this lane: padding lanes (beyond the map's channels) read channel 0 and are masked to zero
+  int gch[2];
+  unsigned gcm[2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const int c = co0 + m * 32 + r;
+    gch[m] = c < p.g.C ? c : 0;
+    gcm[m] = c < p.g.C ? 0xFFFFFFFFu : 0u;
+  }
+  const int xch = ci0 + r < p.x.C ? ci0 + r : 0;
+  const unsigned xcm = ci0 + r < p.x.C ? 0xFFFFFFFFu : 0u;
+  const float* gp = reinterpret_cast<const float*>(p.g.p);
+  const float* xp = reinterpret_cast<const float*>(p.x.p);
+
+  f32x16 acc[3][2];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[a][m][i] = 0.f;
+  // bias gradient: wave 0 of input-channel tile 0 / tap group 0 sums the dY values it feeds to the MFMAs
+  const bool do_bias = p.bwork != nullptr && cit == 0 && zgroup == 0 && wave == 0;
+  float bs[2] = {0.f, 0.f};
+
+  const int per_img = p.blocks_x * p.blocks_y;
+  for (int blk = worker; blk < p.nblocks; blk += nworkers) {
+    const int n = blk / per_img;
+    const int rem = blk - n * per_img;
+    const int by = rem / p.blocks_x, bx = rem - by * p.blocks_x;
+    const int oy0 = by * WG_TH, ox0 = bx * WG_TW;
+    const int rows = min(WG_TH, p.Ho - oy0), cols = min(WG_TW, p.Wo - ox0);      // the part of the block inside the map
+    const int ngrp = (cols + 2 * U - 1) / (2 * U), nit = rows * ngrp;
+    const float* gb = gp + (long)n * p.g.sn;
+    const float* xb = xp + (long)n * p.x.sn;
+
+    float ga[2][U][2], xa[2][U][3];
+    unsigned bits[2];
+    // group `it`: U k-steps of output row it / ngrp; bit 4u = pixel valid, bit 4u + 1 + ai = tap ai's input pixel inside the image
+    auto fetch = [&](int it, float (&gf)[U][2], float (&xf)[U][3], unsigned& bt) {
+      const int itc = min(it, nit - 1);
+      const int row = itc / ngrp, grp = itc - row * ngrp;
+      const int oy = oy0 + row;
+      unsigned b = 0;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ox = ox0 + (grp * U + u) * 2 + hh;
+        const bool pv = (int)(it < nit) & (int)(ox < p.Wo);
+        const int oxc = min(ox, p.Wo - 1);
+        const float* gq = gb + (oy * p.Wo + oxc) * p.g.sp;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) gf[u][m] = gq[gch[m]];
+        b |= (pv ? 1u : 0u) << (4 * u);
+#pragma unroll
+        for (int ai = 0; ai < 3; ++ai) {
+          const int iy = oy * p.stride + tdy[ai], ix = oxc * p.stride + tdx[ai];
+          const bool ok = (int)pv & (int)(iy >= 0) & (int)(iy < p.x.H) & (int)(ix >= 0) & (int)(ix < p.x.W);
+          const int iyc = min(max(iy, 0), p.x.H - 1), ixc = min(max(ix, 0), p.x.W - 1);
+          xf[u][ai] = xb[(iyc * p.x.W + ixc) * p.x.sp + xch];
+          b |= (ok ? 1u : 0u) << (4 * u + 1 + ai);
+        }
+      }
+      asm volatile("" : "+v"(b));
+      bt = b;
+    };
+    auto mfmas = [&](float (&gf)[U][2], float (&xf)[U][3], unsigned bt) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        float a[2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          a[m] = __uint_as_float(__float_as_uint(gf[u][m]) & (0u - ((bt >> (4 * u)) & 1u)) & gcm[m]);
+          if (do_bias) bs[m] += a[m];
+        }
+#pragma unroll
+        for (int ai = 0; ai < 3; ++ai) {
+          float b = __uint_as_float(__float_as_uint(xf[u][ai]) & (0u - ((bt >> (4 * u + 1 + ai)) & 1u)) & xcm);
+          if (p.square_x) b *= b;
+          if (tv[ai]) {                                               // wave-uniform
+#pragma unroll
+            for (int m = 0; m < 2; ++m) acc[ai][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b, acc[ai][m], 0, 0, 0);
+          }
+        }
+      }
+    };
+    fetch(0, ga[0], xa[0], bits[0]);
+    for (int it = 0; it < nit; it += 2) {
+      fetch(it + 1, ga[1], xa[1], bits[1]);             // past the end: clamped addresses, all bits clear -> exact zeros
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas(ga[0], xa[0], bits[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      fetch(it + 2, ga[0], xa[0], bits[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas(ga[1], xa[1], bits[1]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  const int CIW = p.ci_tiles * WG_CI, COW = p.co_tiles * WG_CO;
+  if (do_bias) {                                                     // the two pixel halves of the wave, in a fixed order
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const float t = bs[m] + __shfl_xor(bs[m], 32);
+      if (hh == 0) p.bwork[(long)worker * COW + co0 + m * 32 + r] = t;
+    }
+  }
+  float* wk = p.work + (long)worker * p.ntaps_all * COW * CIW;
+#pragma unroll
+  for (int ai = 0; ai < 3; ++ai) {
+    const int t = wave + 4 * ai;
+    if (t < ntaps_g) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int row = (i & 3) + 8 * (i >> 2) + 4 * hh;
+          wk[((long)(tap0 + t) * COW + (co0 + m * 32 + row)) * CIW + (ci0 + r)] = acc[ai][m][i];
+        }
+    }
+  }
+}
+
 // dW[row_off[co] + chan_off[ci] + tap_off[t]] += scale * sum over workers (fixed order); the tables are the layer's
 // forward packing tables (convpack.forward_tables), so PixelShuffle row order, concatenation channel order,
 // zero-padded channels and Conv3d holders scatter to the right parameter element
@@ -458,7 +614,12 @@ extern "C" int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, 
                                         float* work, int64_t work_floats, tdvc_wgrad_reduce_job* job, void* stream) {
   TDVC_CHECK(job, "tdvc_conv_wgrad_partials: null job");
   TDVC_CHECK(g && x && dw && work && tap_dy && tap_dx && row_off && chan_off && tap_off, "tdvc_conv_wgrad: null pointer");
-  TDVC_CHECK(fmap_ok16(*g) && fmap_ok16(*x) && g->N == x->N, "tdvc_conv_wgrad: fmaps must be fp16 with matching batch");
+  // both maps fp16: the transposing-read kernel; both fp32: conv_wgrad_f32_kernel (same workspace, same second stage)
+  TDVC_CHECK(g->dtype == x->dtype, "tdvc_conv_wgrad: dY is %s, X is %s: both fmaps must be fp16 or both fp32", g->dtype == TDVC_F32 ? "fp32" : "fp16",
+             x->dtype == TDVC_F32 ? "fp32" : "fp16");
+  const bool f32 = g->dtype == TDVC_F32;
+  TDVC_CHECK((f32 ? fmap_ok32(*g) && fmap_ok32(*x) : fmap_ok16(*g) && fmap_ok16(*x)) && g->N == x->N,
+             "tdvc_conv_wgrad: fmaps must be valid %s maps with matching batch", f32 ? "fp32" : "fp16");
   TDVC_CHECK(stride == 1 || stride == 2, "tdvc_conv_wgrad: stride %d", stride);
   TDVC_CHECK(ntaps >= 1 && ntaps <= TDVC_MAX_TAPS && kh >= 1 && kh <= 7 && kw >= 1 && kw <= 7, "tdvc_conv_wgrad: bad window");
   TDVC_CHECK(cout >= 1 && cout <= g->C, "tdvc_conv_wgrad: cout %d > dY channels %d", cout, g->C);
@@ -479,8 +640,6 @@ extern "C" int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, 
   p.blocks_x = (Wo + WG_TW - 1) / WG_TW; p.blocks_y = (Ho + WG_TH - 1) / WG_TH;
   p.nblocks = x->N * p.blocks_x * p.blocks_y;
   p.tih = (WG_TH - 1) * stride + kh; p.tiw = (WG_TW - 1) * stride + kw;
-  const size_t lds = (size_t)WG_TH * WG_TW * PSG + (size_t)p.tih * p.tiw * PSX;
-  TDVC_CHECK(lds <= 160 * 1024, "tdvc_conv_wgrad: LDS plan %zu bytes too large", lds);
   p.work = work;
   p.square_x = square_x;
   const int groups = (ntaps + WG_MAXT - 1) / WG_MAXT;
@@ -488,17 +647,24 @@ extern "C" int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, 
   p.nworkers = workers; p.ngroups = groups;
   p.bwork = db ? work + (long)workers * p.co_tiles * WG_CO * p.ci_tiles * WG_CI * ntaps : nullptr;
   p.stamps = (g_wg_stamp && (long)p.co_tiles * p.ci_tiles * workers * groups <= g_wg_stamp_cap) ? g_wg_stamp : nullptr;
-  const int xl = (p.tih * p.tiw * (WG_CI / 8) + 255) / 256;
-  TDVC_CHECK(xl <= 18, "tdvc_conv_wgrad: X tile of %dx%d pixels needs %d pieces per thread (max 18)", p.tih, p.tiw, xl);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  auto go = [&](auto kern) -> int {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (err != hipSuccess) { tdvc_set_error("tdvc_conv_wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((workers + 7) / 8) * p.co_tiles * p.ci_tiles * groups)), dim3(256), lds, st, p);
-    return 0;
-  };
-  const int rc = xl <= 6 ? go(&conv_wgrad_kernel<6>) : (xl <= 9 ? go(&conv_wgrad_kernel<9>) : go(&conv_wgrad_kernel<18>));
-  if (rc) return rc;
+  const dim3 grid((unsigned)(8 * ((workers + 7) / 8) * p.co_tiles * p.ci_tiles * groups));
+  if (f32) {                         // operands straight from global memory in MFMA order: no LDS plan, no per-thread tile pieces
+    hipLaunchKernelGGL(conv_wgrad_f32_kernel<4>, grid, dim3(256), 0, st, p);
+  } else {
+    const size_t lds = (size_t)WG_TH * WG_TW * PSG + (size_t)p.tih * p.tiw * PSX;
+    TDVC_CHECK(lds <= 160 * 1024, "tdvc_conv_wgrad: LDS plan %zu bytes too large", lds);
+    const int xl = (p.tih * p.tiw * (WG_CI / 8) + 255) / 256;
+    TDVC_CHECK(xl <= 18, "tdvc_conv_wgrad: X tile of %dx%d pixels needs %d pieces per thread (max 18)", p.tih, p.tiw, xl);
+    auto go = [&](auto kern) -> int {
+      hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (err != hipSuccess) { tdvc_set_error("tdvc_conv_wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
+      return 0;
+    };
+    const int rc = xl <= 6 ? go(&conv_wgrad_kernel<6>) : (xl <= 9 ? go(&conv_wgrad_kernel<9>) : go(&conv_wgrad_kernel<18>));
+    if (rc) return rc;
+  }
   const long total = (long)cout * cin * ntaps;
   const int wblocks = (int)((total + 63) / 64), bblocks = db ? (cout + 63) / 64 : 0;
   job->work = work; job->bwork = p.bwork;

@@ -479,16 +479,16 @@ class Cheng2020Anchor(nn.Module, PackCache):
     # -- forward (`main/model/pnet.py:34,58`) ------------------------------------------------
     def _as_f32(self, x: FM) -> FM:
         """`estmv.float()` / `input_residual.float()` of pnet.py:34,58: the fp32 island's input"""
-        return x if x.f32 else ops.copy_cast(x, FM.empty(x.N, x.H, x.W, x.C, dtype=torch.float32, device=x.t.device))
+        return x if x.f32 else ops.cast_f32(x)
 
     def run(self, x: FM, training: bool, out: FM | None = None, res: FM | None = None, trace=None, noise=None, f32=False):
         """x: (B,H,W,64) fp16.  Returns (x_hat FM [+res], bits tensor (2,) float64 = [y, z]).
         `f32`: run the coder as the reference's fp32 island (pnet.py:33-49: autocast off, `estmv.float()`): fp32
-        activations and weights on the fp32 MFMA form of every conv; inference only."""
+        activations and weights on the fp32 MFMA form of every conv.  With `training` under the tape the whole island is
+        differentiated in fp32 as well (fp32 gradient mirrors, conv_f32 data gradients, conv_wgrad_f32 weight gradients); only its
+        entry cast and its fp16 reconstruction touch fp16 maps."""
         dev = x.t.device
         if f32:
-            if training:
-                raise RuntimeError("the fp32-island mode has no backward: train with the default (fp16-in / fp32-accumulate) coders")
             x = self._as_f32(x)
         adt = torch.float32 if f32 else torch.float16          # activation dtype inside the coder
         y32, y16 = self.run_g_a(x)

@@ -36,6 +36,10 @@ class VideoCompressor(nn.Module):
         # `enable_amp: True` (cfg/predict.yaml) keeps fp32 coders; here that value selects the fp16-in coders, so the reference-faithful
         # setting is coder_fp32 = True (tools/predict: yaml key `coder_fp32: true` or --coder-fp32), independent of `enabled_amp`
         self.coder_fp32 = False
+        # training with fp32 coders (what the reference's tools/train.py optimises): a .train() forward keeps both coders in fp32 and the
+        # tape differentiates them in fp32 (conv_f32 dgrad, conv_wgrad_f32).  Set by TrainStep(coder_fp32=True).  Unset, a .train()
+        # forward runs the fp16-in / fp32-accumulate coders whatever `enabled_amp` / `coder_fp32` say (with a warning)
+        self.train_coder_fp32 = False
         # symbol order of the y streams encode() writes and decode() expects: "raster" (compressai's, what the reference's
         # decoder reads) or "wavefront" (an extension: the decoder takes an anti-diagonal per step instead of a position)
         self.stream_order = "raster"
@@ -69,7 +73,9 @@ class VideoCompressor(nn.Module):
         if not (input_image.is_cuda and refer_frames.is_cuda):
             raise RuntimeError("tdvc_amd.VideoCompressor runs on a HIP device only (no CPU fallback)")
         f32 = (not enabled_amp) or self.coder_fp32
-        if f32 and self.training:
+        if self.training and self.train_coder_fp32:
+            f32 = True
+        elif f32 and self.training:
             if not self.__dict__.get("_warned_fp32_train"):
                 import warnings
                 warnings.warn("tdvc_amd: the fp32-island coders are an inference / coding mode; training runs the default "

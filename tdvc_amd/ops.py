@@ -133,6 +133,9 @@ def from_nchw(x: torch.Tensor, Cpad: int | None = None, dtype=torch.float16, out
 
 
 # ----------------------------------------------------------------------------- conv
+FORMS_CREATED = 0            # PackedConv objects built so far (train.refresh_packed: has a form appeared since the PackBatch was built?)
+
+
 @dataclass
 class PackedConv:
     w: torch.Tensor          # device uint8 blob (fragment-ordered fp16)
@@ -160,17 +163,29 @@ class PackedConv:
     param_b: torch.Tensor | None = None
     owner: object | None = None            # module that maps this layer's weight gradient to its own parameters (GDN)
     w32: torch.Tensor | None = None        # fp32 twin of `w` for the fp32 islands (conv_f32.hip), packed on first use
+    w32_buf: torch.Tensor | None = None    # the buffer of a twin that a re-pack of `w` made stale: the next packed_f32() fills it again
+
+    def __post_init__(self):
+        global FORMS_CREATED
+        FORMS_CREATED += 1                 # a layer or a derived form (dgrad, plain, column) is new: PackBatch tables are incomplete
 
     def packed_f32(self) -> torch.Tensor:
-        """the same fragment order as `w`, as floats (tdvc_pack_conv_weights_indexed_f32)"""
+        """the same fragment order as `w`, as floats (tdvc_pack_conv_weights_indexed_f32).  Packed on first use and again on the first
+        use after a re-pack of `w` (stale_f32()): into the same buffer, so training with fp32 coders allocates nothing per step"""
         if self.w32 is None:
-            self.w32 = _pack_from_tables_f32(self.wsrc, self.tables)
+            self.w32, self.w32_buf = _pack_from_tables_f32(self.wsrc, self.tables, self.w32_buf), None
         return self.w32
+
+    def stale_f32(self):
+        """`w` was re-packed from updated parameters: the fp32 twin (if one was ever built) follows on its next use.  No launch here: a
+        default-mode training step never pays for twins it does not use"""
+        if self.w32 is not None:
+            self.w32_buf, self.w32 = self.w32, None
 
     def repack(self):
         """re-pack from the (updated) fp32 parameters: one kernel launch, plus the bias gather"""
         _pack_from_tables(self.wsrc, self.tables, self.w)
-        self.w32 = None
+        self.stale_f32()
         if self.bsrc is not None:
             b = self.bsrc.detach().float()
             self.bias[:self.cout] = b[torch.from_numpy(convpack.shuffle_perm(self.cout)).to(b.device)] if self.shuffle else b
@@ -220,13 +235,14 @@ def _pack_from_tables(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Te
     return dst
 
 
-def _pack_from_tables_f32(wsrc: torch.Tensor, tb: convpack.PackTables) -> torch.Tensor:
+def _pack_from_tables_f32(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None = None) -> torch.Tensor:
     lib = L.lib()
     nbytes = lib.tdvc_conv_packed_bytes(tb.cout, tb.cin, len(tb.taps), tb.ck)
     assert nbytes > 0
     w = wsrc.detach()
     assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
-    dst = torch.empty(nbytes // 2, dtype=torch.float32, device=w.device)      # 8 floats where the fp16 blob has 8 halves
+    if dst is None or dst.numel() != nbytes // 2 or dst.device != w.device:
+        dst = torch.empty(nbytes // 2, dtype=torch.float32, device=w.device)      # 8 floats where the fp16 blob has 8 halves
     L.check(lib.tdvc_pack_conv_weights_indexed_f32(w.data_ptr(), tb.row_off.data_ptr(), tb.chan_off.data_ptr(), tb.tap_off.data_ptr(),
                                                    tb.row_mask.data_ptr(), tb.chan_mask.data_ptr(), tb.tap_mask.data_ptr(),
                                                    tb.cout, tb.cin, len(tb.taps), tb.ck, dst.data_ptr(), _stream()), "pack_conv_weights_indexed_f32")
@@ -257,7 +273,8 @@ class PackBatch:
             walk(pc.dgrad)
             walk(pc.__dict__.get("_colpc"))
             walk(pc.__dict__.get("_plain"))
-        for pc in pcs:
+        self.forms = FORMS_CREATED                 # forms built after this walk (a layer's first dgrad, the plain form of an s2d layer the
+        for pc in pcs:                             # first time it sees a small or an fp32 map) are not members: refresh_packed rebuilds
             walk(pc)
         self._build()
 
@@ -310,7 +327,7 @@ class PackBatch:
         L.check(L.lib().tdvc_pack_conv_weights_batch(self.jobs.data_ptr(), self.starts.data_ptr(), len(self.pcs), self.total_blocks, _stream()),
                 "pack_conv_weights_batch")
         for pc in self.pcs:
-            pc.w32 = None                # fp32 twins (fp32 islands, inference only) are rebuilt from the parameters on next use
+            pc.stale_f32()               # fp32 twins (fp32 islands, fp32-coder training) are re-packed from the parameters on next use
 
 
 def _pick_ck(cin, cout, kh, kw, stride, pad):
@@ -459,8 +476,6 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
             part = torch.empty((x.N, rows, pc.cout), dtype=torch.float32, device=x.t.device)
             d.chan_sum = part.data_ptr()
             chan_sum.append((part, rows))
-    if x.f32 and TAPE is not None and not _IN_BACKWARD:
-        raise L.TdvcHipError("conv: the fp32 form has no backward (the fp32 islands are an inference / coding mode)")
     if bcast_T and TAPE is not None and not _IN_BACKWARD:
         raise L.TdvcHipError("conv: bcast_T is an inference-only fusion (under the tape use conv + bcast_add_act)")
     if PROFILE is not None:
@@ -684,7 +699,7 @@ def conv_wgrad(pc: PackedConv, g: FM, x: FM, dw: torch.Tensor, scale=1.0, square
                                 work.data_ptr(), nwork, _stream()), "conv_wgrad")
     if PROFILE is not None:
         e1.record()
-        PROFILE.append(dict(kernel="conv_wgrad", shape=f"{o['kh']}x{o['kw']} s{o['stride']} {x.C}->{pc.cout} @{x.N}x{x.H}x{x.W}", e0=e0, e1=e1,
+        PROFILE.append(dict(kernel="conv_wgrad_f32" if x.f32 else "conv_wgrad", shape=f"{o['kh']}x{o['kw']} s{o['stride']} {x.C}->{pc.cout} @{x.N}x{x.H}x{x.W}", e0=e0, e1=e1,
                             flops=2.0 * x.N * Ho * Wo * pc.cout * x.C * len(taps), flops_real=2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(taps),
                             bytes=0.0,
                             # geometry class (kh, kw, stride, cin, cout, shuffle, square_x, masked): the op-level test coverage guard
@@ -711,8 +726,8 @@ def conv_bgrad(pc: PackedConv, g: FM, db: torch.Tensor, scale=1.0) -> None:
 
 
 def gdn_backward(g: FM, x: FM, n32: FM, inverse: bool, dx: FM) -> FM:
-    """-> dn (fp16); dx += g * n^(-+1/2)"""
-    dn = FM.empty(g.N, g.H, g.W, g.C, device=g.t.device)
+    """-> dn (x's dtype); dx += g * n^(-+1/2)"""
+    dn = FM.empty(g.N, g.H, g.W, g.C, dtype=x.t.dtype, device=g.t.device)
     d1, d2, d3, d4, d5 = g.desc(), x.desc(), n32.desc(), dn.desc(), dx.desc()
     L.check(L.lib().tdvc_gdn_backward(C.byref(d1), C.byref(d2), C.byref(d3), int(inverse), C.byref(d4), C.byref(d5), _stream()), "gdn_backward")
     return dn
@@ -727,6 +742,14 @@ def copy_cast(src: FM, dst: FM) -> FM:
     ds, dd = src.desc(), dst.desc()
     L.check(L.lib().tdvc_copy_cast(C.byref(ds), C.byref(dd), _stream()), "copy_cast")
     return dst
+
+
+def cast_f32(x: FM) -> FM:
+    """a recorded fp16 -> fp32 copy: the entry of an fp32 island (`estmv.float()`, pnet.py:34,58); its backward rounds the island's
+    fp32 input gradient into the fp16 mirror"""
+    out = copy_cast(x, FM.empty(x.N, x.H, x.W, x.C, dtype=torch.float32, device=x.t.device))
+    _rec("cast", x, out)
+    return out
 
 
 def clamp01_backward(g: FM, y: FM) -> FM:

@@ -11,6 +11,7 @@ by rank and the gradients averaged over RCCL (`train.GradBuckets`).
 
   python -m tdvc_amd.tools.train --iters 20 --batch 4 --size 256
   python -m tdvc_amd.tools.train --distortion ms-ssim --train-lambda 8     # rd_loss = lambda * (1 - MS-SSIM) + bpp (tools/train.py:133,139)
+  python -m tdvc_amd.tools.train --coder-fp32                              # both coders optimised in fp32 (pnet.py:33,57)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m tdvc_amd.tools.train --batch 4
 """
 from __future__ import annotations
@@ -56,6 +57,8 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num-workers", type=int, default=4)
     ap.add_argument("--distortion", choices=("mse", "ms-ssim"), default="mse",
                     help="what lambda multiplies: MSE (tools/train.py:136-140) or 1 - MS-SSIM (the commented line :133,139; --size >= 176)")
+    ap.add_argument("--coder-fp32", action="store_true",
+                    help="optimise mvCoder / resCoder in fp32, as the reference does (main/model/pnet.py:33,57): TrainStep(coder_fp32=True)")
     return ap
 
 
@@ -78,9 +81,9 @@ def main():
     else:
         fill_parameters(net)
     net = net.to(dev)
-    step = TrainStep(net, train_lambda=a.train_lambda, lr=a.lr, loss_scale=a.loss_scale, distortion=a.distortion)
+    step = TrainStep(net, train_lambda=a.train_lambda, lr=a.lr, loss_scale=a.loss_scale, distortion=a.distortion, coder_fp32=a.coder_fp32)
     if rank == 0:
-        print(json.dumps({"distortion": a.distortion, "train_lambda": a.train_lambda, "batch": a.batch, "size": a.size, "world": world}), flush=True)
+        print(json.dumps({"distortion": a.distortion, "coder_fp32": a.coder_fp32, "train_lambda": a.train_lambda, "batch": a.batch, "size": a.size, "world": world}), flush=True)
 
     pool, cursor = [], 0
     t0 = time.time()

@@ -45,7 +45,10 @@ def refresh_packed(model: torch.nn.Module) -> None:
         for key in [k for k, v in pk.items() if isinstance(v, ops.PackedConvPair)]:
             del pk[key]                              # inference-only fused form (Res_Block): rebuilt from the live weights on next use
     batch = model.__dict__.get("_pack_batch")
-    if batch is None or [id(pc) for pc in batch.roots] != [id(pc) for pc in pcs]:
+    # rebuilt when a layer or a derived form is new: a mode or size change mid-training (fp32 coders after default steps, a smaller crop)
+    # creates dgrad / plain forms after the first step, and a form outside the batch would keep the weights -- and the fp32 twin -- it was
+    # built with
+    if batch is None or batch.forms != ops.FORMS_CREATED or [id(pc) for pc in batch.roots] != [id(pc) for pc in pcs]:
         batch = ops.PackBatch(pcs)                   # one launch for every conv layer (forward, dgrad and column forms)
         batch.roots = pcs
         model.__dict__["_pack_batch"] = batch
@@ -213,12 +216,15 @@ def msssim_distortion(recon, target):
 class TrainStep:
     def __init__(self, model, train_lambda: float = 2048.0, lr: float = 1e-4, loss_scale: float = 1024.0, clip: float = 2.0,
                  dynamic_scale: bool = True, growth_interval: int = 2000, graph: bool = False, graph_warmup: int = 2,
-                 side_stream: bool = True, scale_update: str = "exact", freeze_gc: bool = True, distortion="mse"):
+                 side_stream: bool = True, scale_update: str = "exact", freeze_gc: bool = True, distortion="mse", coder_fp32: bool = False):
         """distortion: what lambda multiplies in rd_loss.  "mse" (the reference's active line, tools/train.py:136-140); "ms-ssim":
         rd_loss = lambda * (1 - mean_n ms_ssim(recon, input, data_range=1.0)) + bpp_res + bpp_mv, the reference's commented line
         (:133,139), images of at least 176 pixels a side; or a callable fn(recon_fp32, target_fp32) -> (D, dD_drecon) with D a
         0-dim device tensor and dD_drecon fp32 of recon's shape.  All three seed the backward sweep the same way: the gradient times
         lambda * loss_scale goes into the tape's gradient of recon.  Other than with "mse" the log carries D as "distortion".
+        coder_fp32: optimise mvCoder / resCoder as the reference does, outside autocast (main/model/pnet.py:33,57): fp32 activations,
+        fp32 weights and fp32 gradients through both coders, on the fp32 matrix pipe (conv_f32, conv_wgrad_f32).  The flag is written to
+        `model.train_coder_fp32`; loss scaling, clipping, Adam and the gradient buckets do not change.  Not available with graph=True.
         freeze_gc: after the second step (model, packed weights, descriptor caches and pools exist by then; bench.py's three warm-up steps
         include the collection) everything alive
         moves to the garbage collector's permanent generation (gc.freeze): a step allocates ~50 k short-lived containers (tape
@@ -242,6 +248,12 @@ class TrainStep:
             raise ValueError(f'distortion must be "mse", "ms-ssim" or a callable, not {distortion!r}')
         self.distortion = distortion
         self.model = model
+        self.coder_fp32 = bool(coder_fp32)
+        if self.coder_fp32 and graph:
+            # the fp32 weight twins are re-packed lazily, on first use after an optimizer step (an allocation-free launch, but one whose
+            # place in the stream a captured graph would freeze together with the pre-step weights of the eager warm-up)
+            raise ValueError("TrainStep: coder_fp32=True is not supported with graph=True (the fp32-coder step runs eagerly)")
+        model.train_coder_fp32 = self.coder_fp32
         # at least two eager steps: the gradient buckets are re-laid after the first one (GradBuckets.reorder), and only the second builds
         # the device pointer tables of the coders on the final layout -- a host-to-device copy, which a capture does not allow
         self.use_graph, self.graph_warmup, self._eager_steps = bool(graph), max(int(graph_warmup), 2), 0
