@@ -288,6 +288,20 @@ int tdvc_rans_decoder_decode(void* handle, const int32_t* indexes, int64_t n, co
                              int32_t* symbols_out);
 void tdvc_rans_decoder_destroy(void* handle);
 
+/* Lane-split y stream (an extension like the wavefront order; the reference's decoder cannot read it): the symbols of one
+ * image, given as [npos][M] in wavefront order, are split over L independent sub-streams ("lanes"), symbol c of a position
+ * going to lane c % L.  Container: 4 bytes {'L', 1, L, 0}, L little-endian uint16 sub-stream lengths in 32-bit words, then
+ * the L sub-streams, lane l's being exactly what tdvc_rans_encode emits for lane l's symbols in that order.  L must divide
+ * M; the host entry points take 1 <= L <= 255, the device decoder (tdvc_ar_decode_lanes_step) 64 or 128.
+ * encode: -> bytes written or < 0 (a lane of more than 65 535 words included).  decode: the reference decoder, over the
+ * decode routine the device kernel uses (csrc/rans_lane.h); validates the header and the length table against nbytes. */
+int64_t tdvc_rans_encode_lanes(const int32_t* symbols, const int32_t* indexes, int64_t npos, int M, int L,
+                               const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
+                               const int32_t* offsets, uint8_t* out, int64_t cap);
+int tdvc_rans_decode_lanes(const uint8_t* data, int64_t nbytes, const int32_t* indexes, int64_t npos, int M,
+                           const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
+                           const int32_t* offsets, int32_t* symbols_out);
+
 /* compressai `_CXX.pmf_to_quantized_cdf` (used by EntropyModel._pmf_to_cdf inside update(),
  * main/model/pnet.py:47,71): pmf[n] -> quantised cdf[n+1] at `precision` bits, every bin >= 1. Host code. */
 int tdvc_pmf_to_quantized_cdf(const float* pmf, int n, int precision, int32_t* cdf_out);
@@ -337,6 +351,34 @@ int tdvc_ar_wavefront(const uint8_t* data, int64_t nbytes, const int32_t* cdfs, 
                       const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
                       const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
                       const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
+/* Device decoder of a lane-split stream (tdvc_rans_encode_lanes).  stream_dev: the whole container in DEVICE memory
+ * (4-byte aligned, nbytes long); state_dev: device buffer of tdvc_ar_lanes_state_bytes(L) bytes holding the L lane states
+ * and one sticky error word (its last uint32), which is the only error channel: a damaged stream is flagged, every read
+ * stays inside the payload.  The tables of tdvc_rans_decode in DEVICE memory, packed: cdf16_dev holds every table's entries end
+ * to end as uint16 (the last entry of a table, 1 << 16, wraps to 0 and is implied), n16 entries in all (16-byte aligned, padded
+ * to a multiple of 8); table t = cdf_sizes_dev[t] entries from cdf_starts_dev[t]; offsets_dev[t]; ncdfs >= ntable tables.  The
+ * kernel keeps the first 27 648 entries in LDS (compressai's 64 Gaussian tables have 27 256).
+ * tdvc_ar_lanes_init: lane states from the container's length table (and error word = 0).
+ * tdvc_ar_decode_lanes_step: one step of npos positions: one workgroup of L threads, thread l decoding the symbols (k, c),
+ * c % L == l, in stream order; does what tdvc_ar_indexes + the range decoder + tdvc_ar_quantize do: indexes / symbols at the
+ * compact rows cbase + k of [..][M] arrays, y_hat(h, w, c) = q + mean in y_hat's dtype.  Lane states carry over in state_dev. */
+int64_t tdvc_ar_lanes_state_bytes(int L);
+int tdvc_ar_lanes_init(const uint8_t* stream_dev, int64_t nbytes, int L, uint32_t* state_dev, void* stream);
+int tdvc_ar_decode_lanes_step(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
+                              const uint8_t* stream_dev, int64_t nbytes, int L, const uint16_t* cdf16_dev, int32_t n16,
+                              const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs,
+                              uint32_t* state_dev,
+                              const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream);
+/* tdvc_ar_wavefront's decoder direction for a lane-split stream: `data` (HOST memory) is validated and uploaded once into
+ * stream_dev (>= nbytes of stream_cap bytes), then per step gather -> convs -> tdvc_ar_decode_lanes_step with no
+ * synchronisation; after the last step the error word is read back with the call's only stream wait, TDVC_EINVAL if it is
+ * set.  Allocates nothing.  sym_dev / idx_dev are [H*W][M] in wavefront order. */
+int tdvc_ar_wavefront_lanes(const uint8_t* data, int64_t nbytes, uint8_t* stream_dev, int64_t stream_cap, uint32_t* state_dev,
+                            const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
+                            const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
+                            const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
+                            const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
+                            const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
 /* q[n][h][w][c] = round(z - median[c]) as int32 in the fmap's own order (factorised-prior symbols). */
 int tdvc_round_symbols(const tdvc_fmap* z, const float* median, int32_t* out, void* stream);
 

@@ -99,6 +99,11 @@ SIGNATURES = {
     "tdvc_dcn_columns": (_i, [_FM, _FM, _i, _FM, _P]),
     "tdvc_ar_decode_serial": (_i, [_P, _i64, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
     "tdvc_ar_wavefront": (_i, [_P, _i64, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
+    "tdvc_ar_lanes_state_bytes": (_i64, [_i]),
+    "tdvc_ar_lanes_init": (_i, [_P, _i64, _i, _P, _P]),
+    "tdvc_ar_decode_lanes_step": (_i, [_FM, _P, _i, _P, _i, _P, _i64, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _FM, _P, _P, _i64, _P]),
+    "tdvc_ar_wavefront_lanes": (_i, [_P, _i64, _P, _i64, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i,
+                                     _P, _i, _P, _P, _P]),
     "tdvc_ssim_level_work_floats": (_i64, [_i] * 5),
     "tdvc_ssim_level": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _f, _f, _P, _P, _P, _i64, _P]),
     "tdvc_avgpool2_pad_f32": (_i, [_P, _i64, _i, _i, _P, _P]),
@@ -142,6 +147,8 @@ SIGNATURES = {
     "tdvc_quantize": (_i, [_FM, _FM, _FM, _P]),
     "tdvc_rans_encode": (_i64, [_P, _P, _i64, _P, C.c_int32, _P, _P, _P, _i64]),
     "tdvc_rans_decode": (_i, [_P, _i64, _P, _i64, _P, C.c_int32, _P, _P, _P]),
+    "tdvc_rans_encode_lanes": (_i64, [_P, _P, _i64, _i, _i, _P, C.c_int32, _P, _P, _P, _i64]),
+    "tdvc_rans_decode_lanes": (_i, [_P, _i64, _P, _i64, _i, _P, C.c_int32, _P, _P, _P]),
     "tdvc_rans_decoder_create": (_P, [_P, _i64]),
     "tdvc_rans_decoder_decode": (_i, [_P, _P, _i64, _P, C.c_int32, _P, _P, _P]),
     "tdvc_rans_decoder_destroy": (None, [_P]),

@@ -3,6 +3,7 @@
 // The dense math in between (context conv as a 12*M -> 2M 1x1 conv, entropy_parameters) runs on the
 // MFMA conv kernel.  All integer / index outputs are exact; nothing here uses atomics.
 #include "common.h"
+#include "rans_lane.h"
 
 namespace {
 
@@ -82,6 +83,137 @@ __global__ void round_symbols_kernel(FMap z, const float* median, int32_t* out) 
   const long pix = t % npix;
   const int n = (int)(t / npix);
   out[i] = (int)rintf(reinterpret_cast<const float*>(z.p)[(long)n * z.sn + pix * z.sp + c] - median[c]);
+}
+
+// ---- lane-split y streams (rans_lane.h): the range decoder of one anti-diagonal on the device, one thread per lane.
+// Lane state lives in a device buffer between the steps' launches: uint32 [L][4] = {x low, x high, next word, end word}
+// per lane, then one sticky `bad` word (the only error channel: nothing here faults on a damaged stream, it flags it).
+constexpr int kLaneStateWords = 4;
+
+__device__ __forceinline__ void lane_store(const TdvcLane& st, uint32_t* state, int lane, int L) {
+  uint32_t* s = state + lane * kLaneStateWords;
+  s[0] = (uint32_t)st.x; s[1] = (uint32_t)(st.x >> 32); s[2] = st.pos; s[3] = st.end;
+  if (st.bad) state[L * kLaneStateWords] = 1;                  // every writer stores the same value
+}
+
+// one workgroup of L threads; data: the whole container on the device, nwords: 32-bit words of its payload
+__global__ void ar_lanes_init_kernel(const uint8_t* data, uint32_t nwords, uint32_t* state) {
+  const int L = (int)blockDim.x, lane = (int)threadIdx.x;
+  const uint8_t* tab = data + kLanesHeaderBytes;
+  uint32_t begin = 0;
+  for (int j = 0; j < lane; ++j) begin += (uint32_t)tab[2 * j] | ((uint32_t)tab[2 * j + 1] << 8);
+  const uint32_t len = (uint32_t)tab[2 * lane] | ((uint32_t)tab[2 * lane + 1] << 8);
+  TdvcLane st;
+  tdvc_lane_init(st, data + tdvc_lanes_payload_offset(L), begin, len, nwords);
+  if (lane == 0) state[L * kLaneStateWords] = 0;
+  __syncthreads();
+  lane_store(st, state, lane, L);
+}
+
+// The CDF tables as the kernel reads them: every table's entries packed end to end as uint16 (table t at cdf16[starts[t]],
+// sizes[t] entries; the last entry of a table is 1 << 16, which does not fit and is implied), n16 <= kLdsCdf entries in all.
+// They are copied into LDS at the start of a launch -- the 64 tables of compressai's scale table have 27 256 entries -- so
+// that the bin search's dependent probes are LDS reads; a larger table set is refused by tdvc_ar_decode_lanes_step.
+constexpr int kLdsCdf = 27648;                                  // 54 KB
+constexpr int kChunkSyms = 6144;                                // symbols between two barriers: 48 positions of 128 channels
+constexpr int kLanesLds = kLdsCdf * 2 + kChunkSyms * 4 + 64 * 4 * 4 + kChunkSyms;      // cdf | q | starts, sizes, offsets, scale table | ci
+typedef __attribute__((address_space(3))) const uint16_t* lds_u16_ptr;
+struct CdfDev {
+  lds_u16_ptr lds;
+  int start, size;
+  __device__ __forceinline__ uint32_t operator()(int32_t i) const { return i == size - 1 ? 65536u : lds[start + i]; }
+  __device__ __forceinline__ uint32_t inner(int32_t i) const { return lds[start + i]; }
+};
+
+// scale_index() over a copy of the scale table in LDS whose entries from ntable - 1 on are -inf (they never count): the same
+// 63 comparisons, fetched as 16 independent 16-byte LDS reads instead of 63 dependent ones
+__device__ __forceinline__ int scale_index_lds(float s, const float* tab64, int ntable) {
+  s = fmaxf(s, 0.11f);
+  int cnt = 0;
+#pragma unroll
+  for (int j = 0; j < 64; j += 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(tab64 + j);
+    cnt += (s <= t[0] ? 1 : 0) + (s <= t[1] ? 1 : 0) + (s <= t[2] ? 1 : 0) + (s <= t[3] ? 1 : 0);
+  }
+  return ntable - 1 - cnt;
+}
+
+// What ar_indexes_kernel + the host range decoder + ar_quantize_kernel do for one step of a wavefront-ordered stream, in three
+// phases per chunk of positions.  A (all threads, coalesced): scale -> CDF index of every symbol, into LDS and `idx`.  B: lane
+// `threadIdx.x` decodes its symbols (k, c), c % L == lane, in stream order (k, then c) -- the serial part; it touches LDS only,
+// apart from the lane's own renormalisation words, so no wait of the state update covers another memory operation.  C (all
+// threads, coalesced): sym at the compact row cbase + k and y_hat(h, w, c) = q + mean.  T: y_hat's element type.
+template <typename T>
+__global__ void __launch_bounds__(128) ar_decode_lanes_kernel(FMap gp, const int32_t* __restrict__ pos, int npos, const float* __restrict__ table,
+                                                              int ntable, const uint8_t* __restrict__ payload, uint32_t nwords,
+                                                              const uint16_t* __restrict__ cdf16, int n16, const int32_t* __restrict__ cdf_starts,
+                                                              const int32_t* __restrict__ cdf_sizes, const int32_t* __restrict__ offsets,
+                                                              uint32_t* state, FMap yh, int32_t* __restrict__ sym, int32_t* __restrict__ idx, long cbase) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  uint16_t* s_cdf = reinterpret_cast<uint16_t*>(s_raw);
+  int32_t* s_q = reinterpret_cast<int32_t*>(s_raw + kLdsCdf * 2);
+  int32_t* s_start = s_q + kChunkSyms;
+  int32_t* s_size = s_start + 64;
+  int32_t* s_off = s_size + 64;
+  float* s_table = reinterpret_cast<float*>(s_off + 64);
+  uint8_t* s_ci = reinterpret_cast<uint8_t*>(s_table + 64);
+  const int L = (int)blockDim.x, lane = (int)threadIdx.x, M = yh.C;
+  if (lane < 64) s_table[lane] = lane < ntable - 1 ? table[lane] : -INFINITY;       // ntable <= 64 <= L
+  if (lane < ntable) {
+    const int start = cdf_starts[lane], size = cdf_sizes[lane];
+    const bool ok = start >= 0 && size >= 0 && start <= n16 && size <= n16 - start;
+    s_start[lane] = ok ? start : 0;
+    s_size[lane] = ok ? size : 0;                              // a table outside the array has no entries: the decode flags it
+    s_off[lane] = offsets[lane];
+  }
+  const int nchunk = n16 / 8;                                  // 16-byte chunks, 1 <= nchunk <= kLdsCdf / 8
+  for (int c0 = lane; c0 < nchunk; c0 += L * 8) {              // eight loads in flight per thread, no branch between them:
+    int ix[8];                                                 // an index past the end is clamped, which re-copies the last
+    uint4 v[8];                                                // chunk onto itself
+#pragma unroll
+    for (int u = 0; u < 8; ++u) ix[u] = min(c0 + u * L, nchunk - 1);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = reinterpret_cast<const uint4*>(cdf16)[ix[u]];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) reinterpret_cast<uint4*>(s_cdf)[ix[u]] = v[u];
+  }
+  TdvcLane st;
+  {
+    const uint32_t* s = state + lane * kLaneStateWords;
+    st.x = (uint64_t)s[0] | ((uint64_t)s[1] << 32);
+    st.end = s[3] < nwords ? s[3] : nwords;                    // whatever the buffer holds, no read leaves the payload
+    st.pos = s[2] < st.end ? s[2] : st.end;
+    st.bad = 0;
+  }
+  __syncthreads();
+  const int per = M / L, kc = kChunkSyms / M;                  // positions per chunk (M <= kChunkSyms)
+  for (int k0 = 0; k0 < npos; k0 += kc) {
+    const int nk = npos - k0 < kc ? npos - k0 : kc, ne = nk * M;
+    for (int e = lane; e < ne; e += L) {                       // A
+      const int k = k0 + e / M, c = e % M;
+      const int ci = scale_index_lds((reinterpret_cast<const float*>(gp.p) + (long)k * gp.sp)[c], s_table, ntable);
+      s_ci[e] = (uint8_t)ci;
+      idx[(cbase + k) * M + c] = ci;
+    }
+    __syncthreads();
+    for (int k = 0; k < nk; ++k)                               // B
+      for (int j = 0; j < per; ++j) {
+        const int e = k * M + lane + j * L, ci = s_ci[e];
+        const int size = s_size[ci];
+        const CdfDev cdf{(lds_u16_ptr)s_cdf, s_start[ci], size};
+        s_q[e] = tdvc_lane_decode(st, payload, cdf, size) + s_off[ci];
+      }
+    __syncthreads();
+    for (int e = lane; e < ne; e += L) {                       // C
+      const int k = k0 + e / M, c = e % M;
+      const int h = pos[2 * k], w = pos[2 * k + 1], q = s_q[e];
+      const float mean = (reinterpret_cast<const float*>(gp.p) + (long)k * gp.sp)[M + c];
+      reinterpret_cast<T*>(yh.p)[((long)h * yh.W + w) * yh.sp + c] = (T)((float)q + mean);
+      sym[(cbase + k) * M + c] = q;
+    }
+    __syncthreads();                                           // s_ci / s_q are free for the next chunk
+  }
+  lane_store(st, state, lane, L);
 }
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -245,6 +377,120 @@ extern "C" int tdvc_ar_wavefront(const uint8_t* data, int64_t nbytes, const int3
     (void)hipStreamSynchronize(st);
     (void)hipHostFree(host);
     tdvc_rans_decoder_destroy(dec);
+  }
+  return rc;
+}
+
+// ---- lane-split y streams: the decoder's loop with the range decoder on the device
+namespace {
+struct LanesArgs {                                             // what every launch of the lane kernels needs, validated once
+  const uint8_t* stream_dev; uint32_t nwords; int L;
+};
+int lanes_args(const char* who, const uint8_t* stream_dev, int64_t nbytes, int L, int M, uint32_t* state_dev, LanesArgs* a) {
+  TDVC_CHECK(stream_dev && state_dev, "%s: null stream / state buffer", who);
+  TDVC_CHECK((L == 64 || L == 128) && M >= L && M % L == 0, "%s: the device decoder takes 64 or 128 lanes that divide the channel count (L = %d, M = %d)", who, L, M);
+  const int64_t off = tdvc_lanes_payload_offset(L);
+  TDVC_CHECK(nbytes >= off && (nbytes - off) % 4 == 0 && (nbytes - off) / 4 <= (int64_t)L * kLanesMaxWords, "%s: bad stream size %lld", who, (long long)nbytes);
+  TDVC_CHECK((((uintptr_t)stream_dev) & 3) == 0 && (((uintptr_t)state_dev) & 3) == 0, "%s: the stream / state buffers must be 4-byte aligned", who);
+  a->stream_dev = stream_dev; a->nwords = (uint32_t)((nbytes - off) / 4); a->L = L;
+  return TDVC_OK;
+}
+}  // namespace
+
+extern "C" int64_t tdvc_ar_lanes_state_bytes(int L) { return L >= 1 ? (int64_t)sizeof(uint32_t) * ((int64_t)L * kLaneStateWords + 1) : TDVC_EINVAL; }
+
+extern "C" int tdvc_ar_lanes_init(const uint8_t* stream_dev, int64_t nbytes, int L, uint32_t* state_dev, void* stream) {
+  LanesArgs a;
+  if (int rc = lanes_args("tdvc_ar_lanes_init", stream_dev, nbytes, L, L, state_dev, &a)) return rc;
+  hipLaunchKernelGGL(ar_lanes_init_kernel, dim3(1), dim3(L), 0, ST(stream), a.stream_dev, a.nwords, state_dev);
+  return tdvc_launch_status("tdvc_ar_lanes_init");
+}
+
+extern "C" int tdvc_ar_decode_lanes_step(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
+                                         const uint8_t* stream_dev, int64_t nbytes, int L, const uint16_t* cdf16_dev, int32_t n16,
+                                         const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs,
+                                         uint32_t* state_dev,
+                                         const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream) {
+  TDVC_CHECK(gp && pos && scale_table && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && symbols && indexes && npos >= 1 && cbase >= 0,
+             "tdvc_ar_decode_lanes_step: null / empty");
+  TDVC_CHECK(ntable >= 2 && ntable <= 64 && ncdfs >= ntable, "tdvc_ar_decode_lanes_step: 2..64 scale-table entries, one CDF per entry expected");
+  TDVC_CHECK(n16 >= 8 && n16 % 8 == 0 && aligned16(cdf16_dev), "tdvc_ar_decode_lanes_step: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
+  TDVC_CHECK(n16 <= kLdsCdf, "tdvc_ar_decode_lanes_step: %d packed CDF entries, the kernel's LDS holds %d", n16, kLdsCdf);
+  TDVC_CHECK(fmap_ok32(*gp) && (y_hat->dtype == TDVC_F32 ? fmap_ok32(*y_hat) : fmap_ok16(*y_hat)) && y_hat->N == 1 && gp->C >= 2 * y_hat->C && gp->W >= npos,
+             "tdvc_ar_decode_lanes_step: bad gp / y_hat");
+  LanesArgs a;
+  if (int rc = lanes_args("tdvc_ar_decode_lanes_step", stream_dev, nbytes, L, y_hat->C, state_dev, &a)) return rc;
+  const uint8_t* payload = a.stream_dev + tdvc_lanes_payload_offset(L);
+  TDVC_CHECK(y_hat->C <= kChunkSyms, "tdvc_ar_decode_lanes_step: more than %d channels", kChunkSyms);
+  static TdvcPerDeviceFlag attr;
+  if (!attr.flag()) {
+    for (const void* k : {reinterpret_cast<const void*>(&ar_decode_lanes_kernel<float>), reinterpret_cast<const void*>(&ar_decode_lanes_kernel<half_t>)}) {
+      const hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLanesLds);
+      if (err != hipSuccess) { tdvc_set_error("tdvc_ar_decode_lanes_step: cannot reserve %d bytes of LDS: %s", kLanesLds, hipGetErrorString(err)); return (int)err; }
+    }
+    attr.flag() = true;
+  }
+  if (y_hat->dtype == TDVC_F32)
+    hipLaunchKernelGGL(ar_decode_lanes_kernel<float>, dim3(1), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, payload, a.nwords,
+                       cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
+  else
+    hipLaunchKernelGGL(ar_decode_lanes_kernel<half_t>, dim3(1), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, payload, a.nwords,
+                       cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
+  return tdvc_launch_status("tdvc_ar_decode_lanes_step");
+}
+
+// The decoder's loop over anti-diagonals for a lane-split stream: one upload of the string, then per step gather -> convs ->
+// ar_decode_lanes_kernel, the encoder's enqueue count and like it no synchronisation until the image is done; then the sticky
+// `bad` word comes back with the one stream wait of the call.  Nothing is allocated here.
+extern "C" int tdvc_ar_wavefront_lanes(const uint8_t* data, int64_t nbytes, uint8_t* stream_dev, int64_t stream_cap, uint32_t* state_dev,
+                                       const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
+                                       const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
+                                       const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
+                                       const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
+                                       const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream) {
+  TDVC_CHECK(data && stream_dev && state_dev && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && params && x1 && pc && convs && gp && pos_dev &&
+             step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront_lanes: null argument");
+  TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && nsteps >= 1 && M >= 1 && M <= 4096 && W >= 1 && M == y_hat->C, "tdvc_ar_wavefront_lanes: bad sizes");
+  int L = 0;
+  if (const char* why = tdvc_lanes_check(data, nbytes, M, &L)) { tdvc_set_error("tdvc_ar_wavefront_lanes: %s", why); return TDVC_EINVAL; }
+  TDVC_CHECK(nbytes <= stream_cap, "tdvc_ar_wavefront_lanes: the device stream buffer holds %lld bytes, the string has %lld", (long long)stream_cap, (long long)nbytes);
+  long total = 0;
+  for (int s = 0; s < nsteps; ++s) {
+    TDVC_CHECK(step_sizes[s] >= 1 && step_sizes[s] <= x1->W && step_sizes[s] <= pc->W && step_sizes[s] <= gp->W, "tdvc_ar_wavefront_lanes: a step exceeds the staging buffers");
+    total += step_sizes[s];
+  }
+  TDVC_CHECK(total == (long)y_hat->H * y_hat->W, "tdvc_ar_wavefront_lanes: the steps must cover every position once");
+  hipStream_t st = ST(stream);
+  tdvc_conv_desc d[8];
+  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
+  hipError_t err = hipMemcpyAsync(stream_dev, data, (size_t)nbytes, hipMemcpyHostToDevice, st);
+  if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes: upload failed: %s", hipGetErrorString(err)); return (int)err; }
+  int rc = tdvc_ar_lanes_init(stream_dev, nbytes, L, state_dev, stream);
+  long o = 0;
+  for (int s = 0; s < nsteps && rc == TDVC_OK; ++s) {
+    const int n = step_sizes[s];
+    const int32_t* pos = pos_dev + 2 * o;
+    rc = tdvc_ar_gather(y_hat, params, pos, n, x1, pc, stream);
+    for (int c = 0; c < nconvs && rc == TDVC_OK; ++c) {
+      d[c].x.W = n;
+      d[c].y.W = n;
+      rc = tdvc_conv2d(&d[c], stream);
+    }
+    if (rc == TDVC_OK)
+      rc = tdvc_ar_decode_lanes_step(gp, pos, n, scale_table, ntable, stream_dev, nbytes, L, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, ncdfs,
+                                     state_dev, y_hat, sym_dev, idx_dev, o, stream);
+    o += n;
+  }
+  uint32_t bad = 0;
+  if (rc == TDVC_OK) {
+    err = hipMemcpyAsync(&bad, state_dev + (long)L * kLaneStateWords, sizeof(bad), hipMemcpyDeviceToHost, st);
+    if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes: reading the error word failed: %s", hipGetErrorString(err)); rc = (int)err; }
+  }
+  err = hipStreamSynchronize(st);                             // also: `data` and `bad` are the caller's / this frame's memory
+  if (rc == TDVC_OK && err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes: stream wait failed: %s", hipGetErrorString(err)); rc = (int)err; }
+  if (rc == TDVC_OK && bad) {
+    tdvc_set_error("tdvc_ar_wavefront_lanes: corrupt or exhausted lane-split stream (a lane ran out of words or met an impossible code)");
+    rc = TDVC_EINVAL;
   }
   return rc;
 }

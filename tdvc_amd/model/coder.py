@@ -145,7 +145,7 @@ def subpel_conv3x3(cin, cout, r=1):
 
 
 LR = dict(act=ACT_LRELU, slope=0.01)
-STREAM_ORDERS = ("raster", "wavefront")
+STREAM_ORDERS = ("raster", "wavefront", "lanes")
 
 # host range coding off the critical path (compress(defer=True), VideoCompressor.encode): the coder library releases the GIL
 _RANS_POOL = None
@@ -632,7 +632,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
         return c
 
     @torch.no_grad()
-    def compress(self, x: FM, f32=False, order="raster", defer=False):
+    def compress(self, x: FM, f32=False, order="raster", defer=False, lanes=64):
         """-> {"strings": [y_strings, z_strings], "shape": (h, w)} like compressai's compress()
         (`f32`: the fp32-island mode, see run()).
 
@@ -644,9 +644,14 @@ class Cheng2020Anchor(nn.Module, PackCache):
         `order`: symbol order of the y stream.  "raster" is compressai's (h, w, c) order: the stream the reference writes, decoded
         position by position.  "wavefront" emits the same symbols anti-diagonal by anti-diagonal (the order the encoder computes
         them in, wavefront_steps()), which lets decompress() decode a whole diagonal per step: an extension, not readable by the
-        reference's decoder."""
+        reference's decoder.  "lanes" is the wavefront sequence split over `lanes` (64 or 128) independent rANS sub-streams, channel
+        c in lane c % lanes (ops.rans_encode_lanes: a 4-byte header, a length table, the sub-streams), which lets decompress() run
+        the range decoder on the GPU, one thread per lane, with no host round trip inside the loop; it costs about 8 bytes per
+        lane and, like "wavefront", the reference's decoder cannot read it.  The GPU side of all three orders is the same."""
         if order not in STREAM_ORDERS:
             raise ValueError(f"order must be one of {STREAM_ORDERS}, got {order!r}")
+        if order == "lanes" and (lanes not in ops.LANE_COUNTS or self.M % lanes):
+            raise ValueError(f"lanes must be one of {ops.LANE_COUNTS} and divide M = {self.M}, got {lanes!r}")
         dev = x.t.device
         ebt, gct, table = self._coder_tables()
         M = self.M
@@ -676,7 +681,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
             ops.ar_wavefront(None, None, y32.batch(b, 1), y_hat, params.batch(b, 1), chain["x1"], chain["pc"], chain["descs"], chain["gp"],
                              flat, sizes, M, W, table, idx, sym)
             hs, hi = st["host"][b]
-            if order == "wavefront":
+            if order != "raster":
                 hs.copy_(sym[fl[:, 0], fl[:, 1]], non_blocking=True)
                 hi.copy_(idx[fl[:, 0], fl[:, 1]], non_blocking=True)
             else:
@@ -687,6 +692,8 @@ class Cheng2020Anchor(nn.Module, PackCache):
 
             def job(ev=ev, hs=hs, hi=hi):
                 ev.synchronize()
+                if order == "lanes":
+                    return ops.rans_encode_lanes(hs.numpy(), hi.numpy(), gct, lanes)
                 return ops.rans_encode(hs.numpy(), hi.numpy(), gct)
             y_jobs.append(_rans_pool().submit(job) if defer else job())
             dbg.append({"y_hat": y_hat, "symbols": sym, "indexes": idx})
@@ -697,7 +704,8 @@ class Cheng2020Anchor(nn.Module, PackCache):
     @torch.no_grad()
     def decompress(self, strings, shape, synth=True, f32=False, order="raster"):
         """strings as returned by compress(); "raster": serial position-by-position context decoding (the stream order of
-        compressai's bitstream); "wavefront": one anti-diagonal per step (W + 3(H-1) steps instead of H*W).
+        compressai's bitstream); "wavefront": one anti-diagonal per step (W + 3(H-1) steps instead of H*W), the range decoder on
+        the host; "lanes": the same steps with the range decoder on the GPU (the lane count is read from the string's header).
         -> {"x_hat": FM, "y_hat": FM}.  `f32` and `order` must match the encoder's."""
         if order not in STREAM_ORDERS:
             raise ValueError(f"order must be one of {STREAM_ORDERS}, got {order!r}")
@@ -718,9 +726,9 @@ class Cheng2020Anchor(nn.Module, PackCache):
         y_hat_all = FM.zeros(B, H, W, M, dtype=adt, device=dev)
         sym = torch.zeros((H, W, M), dtype=torch.int32, device=dev)
         idx = torch.zeros((H, W, M), dtype=torch.int32, device=dev)
-        if order == "wavefront":
+        if order != "raster":
             for b in range(B):
-                self._decode_wavefront(strings[0][b], gct, table, y_hat_all.batch(b, 1), params.batch(b, 1))
+                self._decode_wavefront(strings[0][b], gct, table, y_hat_all.batch(b, 1), params.batch(b, 1), lanes=order == "lanes")
             return {"x_hat": self.run_g_s(y_hat_all) if synth else None, "y_hat": y_hat_all}
         # the per-position chain over one-position staging buffers; the loop itself runs natively
         # (tdvc_ar_decode_serial: Python drove it at ~230 us per position)
@@ -754,8 +762,9 @@ class Cheng2020Anchor(nn.Module, PackCache):
         e = self.entropy_parameters
         return [self._ctx_1x1(), pk_conv(self, "ep0", e[0]), pk_conv(self, "ep2", e[2]), pk_conv(self, "ep4", e[4])]
 
-    def _decode_wavefront(self, data, gct, table, y_hat, params):
-        """one image of a wavefront-ordered y stream (tdvc_ar_wavefront, decoder direction)"""
+    def _decode_wavefront(self, data, gct, table, y_hat, params, lanes=False):
+        """one image of a wavefront-ordered y stream (tdvc_ar_wavefront, decoder direction), or with `lanes` of a lane-split one
+        (tdvc_ar_wavefront_lanes: the string goes to the device once, the range decoder runs there)"""
         dev, M = y_hat.t.device, self.M
         H, W = y_hat.H, y_hat.W
         steps = self.wavefront_steps(H, W)
@@ -763,8 +772,16 @@ class Cheng2020Anchor(nn.Module, PackCache):
         chain = self._ar_chain(H, y_hat.t.dtype, dev)
         sym = torch.zeros((H * W, M), dtype=torch.int32, device=dev)          # wavefront order
         idx = torch.zeros((H * W, M), dtype=torch.int32, device=dev)
-        ops.ar_wavefront(data, gct, None, y_hat, params, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat,
-                         np.array([len(st) for st in steps], dtype=np.int32), M, W, table, idx, sym)
+        sizes = np.array([len(st) for st in steps], dtype=np.int32)
+        if lanes:
+            nl = ops.lanes_of(data)
+            if nl not in ops.LANE_COUNTS or M % nl:
+                raise ValueError(f"the y stream declares {nl} lanes; the decoder takes {ops.LANE_COUNTS} dividing M = {M}")
+            stream_dev = torch.empty((len(data) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+            ops.ar_wavefront_lanes(data, gct, stream_dev, ops.ar_lanes_state(nl, dev), y_hat, params, chain["x1"], chain["pc"], chain["descs"],
+                                   chain["gp"], flat, sizes, M, W, table, idx, sym)
+            return
+        ops.ar_wavefront(data, gct, None, y_hat, params, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, M, W, table, idx, sym)
 
 def _g_a(N):
     return nn.Sequential(

@@ -41,8 +41,11 @@ class VideoCompressor(nn.Module):
         # forward runs the fp16-in / fp32-accumulate coders whatever `enabled_amp` / `coder_fp32` say (with a warning)
         self.train_coder_fp32 = False
         # symbol order of the y streams encode() writes and decode() expects: "raster" (compressai's, what the reference's
-        # decoder reads) or "wavefront" (an extension: the decoder takes an anti-diagonal per step instead of a position)
+        # decoder reads), "wavefront" (an extension: the decoder takes an anti-diagonal per step instead of a position) or "lanes"
+        # (a second extension: the wavefront sequence split over `stream_lanes` = 64 or 128 rANS sub-streams, which the decoder's
+        # GPU kernel reads, one thread per lane, with no host round trip inside the loop; decode() reads the count from the stream)
         self.stream_order = "raster"
+        self.stream_lanes = 64
         self.mvCoder = MVCoder(N=128)
         self.resCoder = ResCoder(N=128)
         self.extra_fea = FeaExtra(2)
@@ -179,13 +182,13 @@ class VideoCompressor(nn.Module):
         self.mvCoder.update()
         self.resCoder.update()
         f32 = self.coder_fp32
-        mv = self.mvCoder.compress(estmv, f32=f32, order=self.stream_order, defer=True)       # range coding on worker threads
+        mv = self.mvCoder.compress(estmv, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes)       # range coding on worker threads
         cat = lambda dbg: FM(torch.cat([d["y_hat"].t for d in dbg], 0))
         out = {}
 
         def res_y_hat(pred):
             resid = ops.scale_act_res(f_cur, FM.empty(B, H, W, 64, device=dev), res=pred, res_sign=-1.0)
-            out["res"] = self.resCoder.compress(resid, f32=f32, order=self.stream_order, defer=True)
+            out["res"] = self.resCoder.compress(resid, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes)
             return cat(out["res"]["_debug"])
         recon = self._reconstruct(cat(mv["_debug"]), res_y_hat, feats, refs8, iframe8)
         rs = out["res"]

@@ -1107,6 +1107,24 @@ class CdfTables:
         self.sizes = np.ascontiguousarray(lengths.detach().cpu().numpy().reshape(-1), dtype=np.int32)
         self.offsets = np.ascontiguousarray(offsets.detach().cpu().numpy().reshape(-1), dtype=np.int32)
         self.stride = self.cdf.shape[1]
+        self._dev = {}
+
+    def device(self, dev):
+        """device copies for the on-device range decoder (tdvc_ar_decode_lanes_step), made once per device: every table's
+        entries end to end as uint16 (a table's last entry, 1 << 16, wraps to 0: the kernel implies it), padded to a
+        multiple of 8; per table its start in that array, its size, its offset -> (cdf16, starts, sizes, offsets)"""
+        dev = torch.device(dev)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        key = str(dev)
+        if key not in self._dev:
+            starts = np.concatenate([[0], np.cumsum(self.sizes[:-1])]).astype(np.int32)
+            n16 = (int(self.sizes.sum()) + 7) // 8 * 8
+            packed = np.zeros(n16, dtype=np.uint16)
+            for t, (o, n) in enumerate(zip(starts, self.sizes)):
+                packed[o:o + n] = self.cdf[t, :n].astype(np.uint16)
+            self._dev[key] = (torch.from_numpy(packed.view(np.int16)).to(dev),) + tuple(torch.from_numpy(a).to(dev) for a in (starts, self.sizes, self.offsets))
+        return self._dev[key]
 
 
 def rans_encode(symbols: np.ndarray, indexes: np.ndarray, t: CdfTables) -> bytes:
@@ -1168,6 +1186,90 @@ def ar_wavefront(data: bytes | None, t: CdfTables | None, y: FM | None, y_hat: F
                                       t.offsets.ctypes.data if t else None, C.byref(dy) if dy is not None else None, C.byref(dyh), C.byref(dp),
                                       C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W,
                                       scale_table.data_ptr(), scale_table.numel(), idx.data_ptr(), sym.data_ptr(), _stream()), "ar_wavefront")
+
+
+LANE_COUNTS = (64, 128)          # what the device decoder of a lane-split stream takes
+
+
+def rans_encode_lanes(symbols: np.ndarray, indexes: np.ndarray, t: CdfTables, lanes: int = 64) -> bytes:
+    """symbols / indexes [npos][M] in wavefront order -> the lane-split container (`tdvc_rans_encode_lanes`): header, length
+    table, `lanes` sub-streams; channel c of every position goes to lane c % lanes"""
+    s = np.ascontiguousarray(symbols, dtype=np.int32)
+    i = np.ascontiguousarray(indexes, dtype=np.int32)
+    if s.ndim != 2 or s.shape != i.shape:
+        raise ValueError("rans_encode_lanes: symbols and indexes must both be [npos][M]")
+    out = np.empty(8 * s.size + 16 * int(lanes) + 64, dtype=np.uint8)          # a symbol: at most 16 + 4 + 32 bits
+    n = L.lib().tdvc_rans_encode_lanes(s.ctypes.data, i.ctypes.data, s.shape[0], s.shape[1], int(lanes), t.cdf.ctypes.data, t.stride,
+                                       t.sizes.ctypes.data, t.offsets.ctypes.data, out.ctypes.data, out.size)
+    if n < 0:
+        msg = L.lib().tdvc_last_error().decode("utf-8", "replace")
+        raise ValueError(f"rans_encode_lanes: {msg}")
+    return out[:n].tobytes()
+
+
+def rans_decode_lanes(data: bytes, indexes: np.ndarray, t: CdfTables) -> np.ndarray:
+    """the host reference decoder of a lane-split container (`tdvc_rans_decode_lanes`); indexes [npos][M] -> symbols [npos][M]"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    i = np.ascontiguousarray(indexes, dtype=np.int32)
+    if i.ndim != 2:
+        raise ValueError("rans_decode_lanes: indexes must be [npos][M]")
+    out = np.empty(i.shape, dtype=np.int32)
+    L.check(L.lib().tdvc_rans_decode_lanes(buf.ctypes.data if buf.size else None, buf.size, i.ctypes.data, i.shape[0], i.shape[1], t.cdf.ctypes.data,
+                                           t.stride, t.sizes.ctypes.data, t.offsets.ctypes.data, out.ctypes.data), "rans_decode_lanes")
+    return out
+
+
+def lanes_of(data: bytes) -> int:
+    """the lane count a lane-split container declares"""
+    if len(data) < 4 or data[0:2] != b"L\x01" or data[3] != 0:
+        raise ValueError("not a lane-split y stream (order=\"lanes\")")
+    return data[2]
+
+
+def ar_lanes_state(lanes: int, device) -> torch.Tensor:
+    """device buffer of the lane states + the sticky error word (its last element) for `ar_decode_lanes_step`"""
+    return torch.zeros(int(L.lib().tdvc_ar_lanes_state_bytes(int(lanes))) // 4, dtype=torch.int32, device=device)
+
+
+def ar_lanes_init(stream_dev: torch.Tensor, nbytes: int, lanes: int, state: torch.Tensor) -> None:
+    """lane states from the length table of the container in `stream_dev` (uint8, device)"""
+    assert stream_dev.dtype == torch.uint8 and stream_dev.numel() >= nbytes and state.numel() * 4 >= L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
+    L.check(L.lib().tdvc_ar_lanes_init(stream_dev.data_ptr(), nbytes, int(lanes), state.data_ptr(), _stream()), "ar_lanes_init")
+
+
+def ar_decode_lanes_step(gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, stream_dev: torch.Tensor, nbytes: int, lanes: int,
+                         t: CdfTables, state: torch.Tensor, y_hat: FM, symbols: torch.Tensor, indexes: torch.Tensor, cbase: int) -> None:
+    """one step of the on-device decoder of a lane-split stream (`tdvc_ar_decode_lanes_step`): the range decoder, the CDF
+    indexes and the quantiser's write-back of `npos` positions; symbols / indexes rows cbase .. cbase + npos of [..][M]"""
+    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
+    assert stream_dev.dtype == torch.uint8 and stream_dev.numel() >= nbytes and state.numel() * 4 >= L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
+    assert symbols.numel() >= (cbase + npos) * y_hat.C and indexes.numel() >= (cbase + npos) * y_hat.C and pos.numel() >= 2 * npos
+    dg, dh = gp.desc(), y_hat.desc()
+    L.check(L.lib().tdvc_ar_decode_lanes_step(C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(), stream_dev.data_ptr(), nbytes,
+                                              int(lanes), cdf16.data_ptr(), cdf16.numel(), starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(),
+                                              sizes.numel(), state.data_ptr(), C.byref(dh), symbols.data_ptr(), indexes.data_ptr(), cbase, _stream()),
+            "ar_decode_lanes_step")
+
+
+def ar_wavefront_lanes(data: bytes, t: CdfTables, stream_dev: torch.Tensor, state: torch.Tensor, y_hat: FM, params: FM, x1: FM, pc: FM,
+                       descs: list, gp: FM, pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor,
+                       idx: torch.Tensor, sym: torch.Tensor) -> None:
+    """the decoder's context loop of one image for a lane-split stream (`tdvc_ar_wavefront_lanes`): the string is uploaded once
+    into `stream_dev`, every step's range decoding runs on the device, one stream wait at the end"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    lanes = lanes_of(data)
+    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
+    assert stream_dev.dtype == torch.uint8 and state.numel() * 4 >= L.lib().tdvc_ar_lanes_state_bytes(lanes)
+    assert sym.numel() >= y_hat.H * y_hat.W * M and idx.numel() >= y_hat.H * y_hat.W * M
+    arr = (L.ConvDesc * len(descs))(*descs)
+    ss = np.ascontiguousarray(step_sizes, dtype=np.int32)
+    dyh, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
+    L.check(L.lib().tdvc_ar_wavefront_lanes(buf.ctypes.data, buf.size, stream_dev.data_ptr(), stream_dev.numel(), state.data_ptr(),
+                                            cdf16.data_ptr(), cdf16.numel(), starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), C.byref(dyh),
+                                            C.byref(dp),
+                                            C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W,
+                                            scale_table.data_ptr(), scale_table.numel(), idx.data_ptr(), sym.data_ptr(), _stream()),
+            "ar_wavefront_lanes")
 
 
 def ar_gather(y_hat: FM, params: FM, pos: torch.Tensor, npos: int, x1: FM, pc: FM):

@@ -35,6 +35,9 @@ def _msssim(rc: torch.Tensor, xc: torch.Tensor) -> float:
     return float(metrics.ms_ssim(rc.float(), xc.float(), data_range=1.0))
 
 
+STREAM_ORDER_FLAGS = {"raster": 0, "wavefront": 1, "lanes": 2}        # first shape word of the y records
+
+
 def code_gop(net, frames: torch.Tensor, enable_amp: bool = True, bitstream_dir: str | None = None, tag: str = ""):
     """frames: (T,3,h,w) on the GPU, frame 0 = I-frame reconstruction. Returns per-P-frame stats.
     With `bitstream_dir` every frame is really coded (`VideoCompressor.encode`), written as a container file in the
@@ -54,8 +57,8 @@ def code_gop(net, frames: torch.Tensor, enable_amp: bool = True, bitstream_dir: 
             t_e = time.time() - t_e
             flat = [s[0] for s in enc["strings"]]
             # first shape word: the reference writes the batch index (always 0); the y records of a wavefront-ordered
-            # stream carry 1 there so that a reader cannot mistake them for compressai's raster order
-            wf = int(net.stream_order == "wavefront")
+            # stream carry 1 there, those of a lane-split stream 2, so that a reader cannot mistake them for compressai's raster order
+            wf = STREAM_ORDER_FLAGS[net.stream_order]
             shp = [(wf if i % 2 == 0 else 0, 128, *enc["shapes"][i // 2]) for i in range(4)]
             path = os.path.join(bitstream_dir, f"{tag}frame{t:03d}.bin")
             with open(path, "wb") as f:
@@ -98,8 +101,10 @@ def main():
     ap.add_argument("--val-dataset", default="UVG", choices=("UVG", "MCL-JCV", "HEVC"), help="with --dataset-root (predict.py:154-166)")
     ap.add_argument("--cls", default="B", help="HEVC class A..E")
     ap.add_argument("--train-lambda", type=int, default=2048, help="selects the BPG QP of the I-frames (dataset.py:25-36)")
-    ap.add_argument("--stream-order", default="raster", choices=("raster", "wavefront"),
-                    help="with --bitstream-dir: y-symbol order (raster = the reference's; wavefront = diagonal-parallel decoding)")
+    ap.add_argument("--stream-order", default="raster", choices=("raster", "wavefront", "lanes"),
+                    help="with --bitstream-dir: y-symbol order (raster = the reference's; wavefront = diagonal-parallel decoding; "
+                         "lanes = wavefront order split over rANS sub-streams, range decoder on the GPU)")
+    ap.add_argument("--stream-lanes", type=int, default=64, choices=(64, 128), help="with --stream-order lanes: sub-streams per y string")
     ap.add_argument("--coder-fp32", action="store_true", help="both coders as fp32 islands (the reference's precision), also with enable_amp: True")
     a = ap.parse_args()
     opt = {"model": "pnet", "pretrain": a.pretrain, "val_dataset": "synthetic", "class": "-", "enable_amp": True}
@@ -123,6 +128,7 @@ def main():
     # otherwise selects this build's fp16-in / fp32-accumulate coders
     net.coder_fp32 = bool(opt.get("coder_fp32", False)) or a.coder_fp32
     net.stream_order = a.stream_order
+    net.stream_lanes = a.stream_lanes
     t0 = time.time()
     stats = []
     dataset = None
@@ -154,7 +160,8 @@ def main():
                "psnr": sum(s["psnr"] for s in allstats) / n, "msssim": sum(s["msssim"] for s in allstats) / n, "seconds": time.time() - t0, "cfg": opt}
         timed = [s for s in allstats if "encode_s" in s]
         if timed:
-            res.update(stream_order=a.stream_order, encode_s_per_frame=sum(s["encode_s"] for s in timed) / len(timed),
+            res.update(stream_order=a.stream_order, **({"stream_lanes": a.stream_lanes} if a.stream_order == "lanes" else {}),
+                       bytes=[s["bytes"] for s in timed], encode_s_per_frame=sum(s["encode_s"] for s in timed) / len(timed),
                        decode_s_per_frame=sum(s["decode_s"] for s in timed) / len(timed),
                        encode_s=[round(s["encode_s"], 4) for s in timed], decode_s=[round(s["decode_s"], 4) for s in timed])
         print(json.dumps(res))
