@@ -100,6 +100,21 @@ int tdvc_prepare_device(void);
  * ...; "" before the first call).  Diagnostic for profiles and benchmarks; never NULL. */
 const char* tdvc_last_conv_kernel(void);
 
+/* ---------------------------------------------------------------- launch predicate (ABI 7)
+ * Device-side skipping of work whose inputs did not change, with no host synchronisation: `flag` is one int of device memory,
+ * written on the stream by an earlier launch (tdvc_frame_changed).  While a predicate is set on the calling thread (NULL clears
+ * it), the launches of the PREDICATED kernels -- conv_c8, conv_pair, conv_row (tdvc_conv2d / tdvc_conv_pair dispatching to them)
+ * and both kernels of tdvc_avgpool_k -- carry the pointer: every workgroup reads *flag once at its top, before any barrier,
+ * LDS-DMA or store, and returns when it is 0, leaving its outputs as they were.  Every other kernel launched under a
+ * predicate runs in full (correct, only not shortened).  tdvc_last_launch_predicated(): 1 when the last launching entry point
+ * on this thread passed the predicate into its kernel(s), else 0. */
+int tdvc_set_predicate(const int* flag);
+int tdvc_last_launch_predicated(void);
+/* flag[0] = (cur != cache), compared exactly as 16-byte integer words (NaN payloads and signed zeros count); when they differ
+ * `cache` becomes a copy of `cur`, else its bytes are not touched.  fp16 maps of one geometry (N, H, W, C), each with its own
+ * pixel / batch strides.  Three enqueued steps: flag = 0, compare, conditional copy. */
+int tdvc_frame_changed(const tdvc_fmap* cur, tdvc_fmap* cache, int* flag, void* stream);
+
 /* ---------------------------------------------------------------- conv transforms
  * Replaces every torch.nn.Conv2d / Conv3d(1,3,3) / Conv3d(3,1,1) / compressai
  * conv3x3 / subpel_conv3x3 / MaskedConv2d / GDN 1x1 call on the path:

@@ -18,6 +18,16 @@ void tdvc_set_error(const char* fmt, ...);
 // per-device scratch (lib.cpp): >= 4 KB of zeros nobody writes, >= 16 KB dump page nobody reads; 0 or a HIP error code
 int tdvc_scratch_pages(const void** zeros, void** dump);
 
+// launch predicate (lib.cpp): the thread's flag pointer or null, for the launchers of the kernels that test it; every launch is
+// closed by tdvc_note_launch() (from tdvc_launch_status), which is what tdvc_last_launch_predicated() reports
+const int* tdvc_launch_predicate();
+void tdvc_note_launch();
+// top of a predicated kernel: one wave-uniform load, before any barrier, LDS-DMA or store
+#define TDVC_PREDICATE_RETURN(pred)                       \
+  do {                                                    \
+    if ((pred) != nullptr && *(pred) == 0) return;        \
+  } while (0)
+
 #define TDVC_CHECK(cond, ...)            \
   do {                                   \
     if (!(cond)) {                       \
@@ -27,6 +37,7 @@ int tdvc_scratch_pages(const void** zeros, void** dump);
   } while (0)
 
 static inline int tdvc_launch_status(const char* what) {
+  tdvc_note_launch();
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     tdvc_set_error("%s: launch failed: %s", what, hipGetErrorString(e));

@@ -25,6 +25,7 @@ constexpr int EW_C8 = 32 * 144;                      // one transposed output ro
 constexpr int LDS_C8 = 256 + NW_C8 * EW_C8;          // bias + 4 wave-private regions
 
 __global__ __launch_bounds__(NTHR_C8, 4) void conv_c8_kernel(const ConvParams p, int tiles_x, int total_tiles) {
+  TDVC_PREDICATE_RETURN(p.pred);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* bias_s = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -129,6 +130,7 @@ bool conv_c8_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int 
 int launch_conv_c8(const ConvParams& p, int N, hipStream_t st) {
   ConvParams q = p;
   q.slope = convk::conv_simple_slope(p);
+  q.pred = tdvc_launch_predicate();
   const int tiles_x = (p.Wo + 31) / 32;
   const long total = (long)N * p.Ho * tiles_x;
   int grid = (int)((total + NW_C8 - 1) / NW_C8);

@@ -20,6 +20,7 @@ struct ConvParams {
   int bcast_T; float bcast_slope;   // conv_mfma_v5 only: y[:, t] = lrelu(y[:, t] + conv) over bcast_T slices (tdvc_conv_desc::bcast_T)
   float* csum;                      // conv_mfma_v5 only: partial channel sums of the stored values (tdvc_conv_desc::chan_sum), or null
   int8_t tap_dy[TDVC_MAX_TAPS], tap_dx[TDVC_MAX_TAPS];
+  const int* pred;                  // conv_c8 only: launch predicate (tdvc_set_predicate), or null.  Last: no other field moves
 };
 
 // ---- host side: what the kernels' eligibility predicates and launchers share (the dispatch table is in conv_dispatch.hip) ------

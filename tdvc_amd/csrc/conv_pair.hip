@@ -119,6 +119,7 @@ struct PairParams {
   int strips, segs, seg_rows, jobs;
   float slope1, slope2;     // max(v, v * slope): 1 = none, 0 = ReLU, else LeakyReLU
   int experiment;           // timing diagnostics (tdvc_debug_set_pair_experiment): 1 no DMA after the prologue, 2 stores to the dump line, 4 no barrier
+  const int* pred;          // launch predicate (tdvc_set_predicate) or null: the kernel returns at once when *pred == 0
 };
 
 // swizzle term of pixel q of a ring row (see the LDS image note at the top)
@@ -155,6 +156,7 @@ template <int XRING> __device__ __forceinline__ int pair_slot(int kk) {
 // A1 / A2: activation after conv1 / conv2: 0 none, 1 ReLU, 2 max(v, v * slope) (LeakyReLU; slope 1 = none)
 template <int NCB, int A1, int A2, bool ADDX, bool RES2, bool STAMP = false>
 __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, long long* stamps = nullptr, int stamp_cap = 0) {
+  TDVC_PREDICATE_RETURN(p.pred);
   using G = PairGeo<NCB>;
   constexpr int PW = G::PW, ROWB = G::ROWB, TROWB = G::TROWB, SROW = G::SROW, XRING = G::XRING, PF = G::PF, X0 = G::X0, T0 = G::T0, S0 = G::S0;
   constexpr int NF = 6 * NCB;                  // B fragments of a row
@@ -595,6 +597,7 @@ extern "C" int tdvc_conv_pair(const tdvc_conv_pair_desc* d, void* stream) {
   p.segs = (p.H + p.seg_rows - 1) / p.seg_rows;
   p.jobs = (int)(base * p.segs);
   const int grid = p.jobs < 256 ? p.jobs : 256;
+  p.pred = tdvc_launch_predicate();
   auto go = [&](auto kern, int lds) -> int {
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (err != hipSuccess) { tdvc_set_error("tdvc_conv_pair: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }

@@ -98,6 +98,7 @@ struct RowParams {
   int strips;               // SW-column strips per image row
   float slope;              // max(v, v * slope): 1 = none, 0 = ReLU
   int reverse;
+  const int* pred;          // launch predicate (tdvc_set_predicate) or null: the kernel returns at once when *pred == 0
 };
 
 template <int PXB> __device__ __forceinline__ int rw_f(int q) {                                          // ring-row swizzle term
@@ -163,6 +164,7 @@ template <int GID> constexpr int rw_first_group_of_row0() {        // the first 
 // with two stays on conv_mfma_v11 / v10); SHUF: PixelShuffle(2) store
 template <int GID, int ACT, int NRES, bool SHUF>
 __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p) {
+  TDVC_PREDICATE_RETURN(p.pred);
   using G = RowDerived<GID>;
   constexpr int NKC = G::NKC, KH = G::KH, KW = G::KW, SW = G::SW, CO = G::CO, PXB = G::PXB, XRING = G::XRING, PF = G::PF, NP = G::NP;
   constexpr int NG = rw_ngroups<GID>(), G0 = rw_first_group_of_row0<GID>();
@@ -530,6 +532,7 @@ static int launch_conv_row_t(const ConvParams& p, int N, hipStream_t st) {
   const bool has1 = q.res != nullptr;
   const int act = q.slope == 1.f ? 0 : (q.slope == 0.f ? 1 : 2);
   const int nres = has1 ? 1 : 0;
+  q.pred = tdvc_launch_predicate();
   int rc = TDVC_EINVAL;
 #define RW_CASE(A, R, S) \
   if (act == A && nres == R && shuf == S) \

@@ -16,8 +16,29 @@ void tdvc_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int tdvc_abi_version(void) { return 6; }   // 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
+extern "C" int tdvc_abi_version(void) { return 7; }   // 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
 extern "C" const char* tdvc_last_error(void) { return g_err; }
+
+// ---- launch predicate (tdvc_set_predicate): a device flag the predicated kernels (conv_c8, conv_pair, conv_row, avgpool_k) read at
+// their top; a launcher of one of them takes it with tdvc_launch_predicate() right before its launch, and tdvc_launch_status() -- the
+// tail of EVERY launching entry point -- closes the launch with tdvc_note_launch(): the query then says whether that launch carried it.
+static thread_local const int* g_pred = nullptr;
+static thread_local int g_pred_taken = 0, g_pred_last = 0;
+
+extern "C" int tdvc_set_predicate(const int* flag) {
+  if (reinterpret_cast<uintptr_t>(flag) & 3) { tdvc_set_error("tdvc_set_predicate: flag must be 4-byte aligned"); return TDVC_EINVAL; }
+  g_pred = flag;
+  return TDVC_OK;
+}
+extern "C" int tdvc_last_launch_predicated(void) { return g_pred_last; }
+const int* tdvc_launch_predicate() {
+  g_pred_taken = g_pred != nullptr;
+  return g_pred;
+}
+void tdvc_note_launch() {
+  g_pred_last = g_pred_taken;
+  g_pred_taken = 0;
+}
 
 // ---- per-device scratch: a page of zeros nobody writes (DMA source of out-of-image halo pixels) and a dump page nobody
 // reads (store target of lanes outside a strip).  One allocation per device, created under a mutex on the first launch that

@@ -430,8 +430,9 @@ __global__ void resize_bilinear_kernel(FMap x, FMap y, const float* chscale) {
 // Stage 2: one thread per (cell, channel): strips summed in order, / area.  (The FeatureFix pooling at 1080p is
 // 136 x 136 pixels per cell and only 8 x 14 cells: one block per cell left 144 of 256 CUs idle and ran 0.8 TB/s.)
 constexpr int POOL_ROWS = 8;
-__global__ __launch_bounds__(256) void avgpool_k_strip_kernel(FMap x, int scale, float* work, int wp, int nsplit) {
+__global__ __launch_bounds__(256) void avgpool_k_strip_kernel(FMap x, int scale, float* work, int wp, int nsplit, const int* pred) {
   __shared__ float red[256][9];
+  TDVC_PREDICATE_RETURN(pred);
   const int chunks = x.C / 8;
   const int lanes = 256 / chunks;
   const int tid = threadIdx.x;
@@ -475,7 +476,8 @@ __global__ __launch_bounds__(256) void avgpool_k_strip_kernel(FMap x, int scale,
   }
 }
 
-__global__ void avgpool_k_final_kernel(const float* work, float* pooled, long total, int C_, int nsplit, float area) {
+__global__ void avgpool_k_final_kernel(const float* work, float* pooled, long total, int C_, int nsplit, float area, const int* pred) {
+  TDVC_PREDICATE_RETURN(pred);
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const long cell = i / C_;
@@ -483,6 +485,33 @@ __global__ void avgpool_k_final_kernel(const float* work, float* pooled, long to
   float s = 0.f;
   for (int k = 0; k < nsplit; ++k) s += work[(cell * nsplit + k) * C_ + c];
   pooled[i] = s / area;
+}
+
+// ------------------------------------------------------------------ frame compare (tdvc_frame_changed)
+// 16-byte word i of an fp16 map: image n, pixel, 8-channel chunk -- each map through its own strides (the I-frame is a strided batch
+// view of the reference stack)
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4* frame_word(const FMap& f, long i) {
+  const int c8 = f.C / 8;
+  const long per_img = (long)f.H * f.W * c8;
+  const long n = i / per_img, rem = i - n * per_img;
+  const long pix = rem / c8;
+  const int ck = (int)(rem - pix * c8);
+  return reinterpret_cast<u32x4*>(reinterpret_cast<half_t*>(f.p) + n * f.sn + pix * f.sp + ck * 8);
+}
+// flag[0] = 1 when any word differs; integer compare: NaN payloads and the sign of zero count.  Many threads may store the 1.
+__global__ __launch_bounds__(EW_BLOCK) void frame_compare_kernel(FMap cur, FMap cache, long words, int* flag) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= words) return;
+  const u32x4 a = *frame_word(cur, i), b = *frame_word(cache, i);
+  if (((a[0] ^ b[0]) | (a[1] ^ b[1]) | (a[2] ^ b[2]) | (a[3] ^ b[3])) != 0u) flag[0] = 1;
+}
+// cache = cur when the compare said "changed"
+__global__ __launch_bounds__(EW_BLOCK) void frame_refresh_kernel(FMap cur, FMap cache, long words, const int* flag) {
+  if (flag[0] == 0) return;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= words) return;
+  *frame_word(cache, i) = *frame_word(cur, i);
 }
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {
@@ -806,10 +835,22 @@ extern "C" int tdvc_avgpool_k(const tdvc_fmap* x, int scale, float* pooled, int 
              "tdvc_avgpool_k: bad arguments");
   const int nsplit = (scale + POOL_ROWS - 1) / POOL_ROWS;
   TDVC_CHECK(work_floats >= tdvc_avgpool_k_work_floats(x->N, hp, wp, x->C, scale), "tdvc_avgpool_k: workspace too small (tdvc_avgpool_k_work_floats)");
-  hipLaunchKernelGGL(avgpool_k_strip_kernel, dim3(hp * wp * nsplit, x->N), dim3(256), 0, ST(stream), to_dev(*x), scale, work, wp, nsplit);
+  const int* pred = tdvc_launch_predicate();         // both kernels carry it: a skipped strip pass leaves `work` stale, and `pooled` with it
+  hipLaunchKernelGGL(avgpool_k_strip_kernel, dim3(hp * wp * nsplit, x->N), dim3(256), 0, ST(stream), to_dev(*x), scale, work, wp, nsplit, pred);
   const long total = (long)x->N * hp * wp * x->C;
-  hipLaunchKernelGGL(avgpool_k_final_kernel, grid1d(total), dim3(256), 0, ST(stream), work, pooled, total, x->C, nsplit, (float)scale * (float)scale);
+  hipLaunchKernelGGL(avgpool_k_final_kernel, grid1d(total), dim3(256), 0, ST(stream), work, pooled, total, x->C, nsplit, (float)scale * (float)scale, pred);
   return tdvc_launch_status("tdvc_avgpool_k");
+}
+
+extern "C" int tdvc_frame_changed(const tdvc_fmap* cur, tdvc_fmap* cache, int* flag, void* stream) {
+  TDVC_CHECK(cur && cache && flag && fmap_ok16(*cur) && fmap_ok16(*cache) && same_geom(*cur, *cache) && cur->C == cache->C &&
+             (reinterpret_cast<uintptr_t>(flag) & 3) == 0, "tdvc_frame_changed: fp16 maps of one geometry and a 4-byte aligned flag");
+  const hipError_t err = hipMemsetAsync(flag, 0, sizeof(int), ST(stream));
+  if (err != hipSuccess) { tdvc_set_error("tdvc_frame_changed: hipMemsetAsync failed: %s", hipGetErrorString(err)); return (int)err; }
+  const long words = (long)cur->N * cur->H * cur->W * (cur->C / 8);
+  hipLaunchKernelGGL(frame_compare_kernel, grid1d(words), dim3(EW_BLOCK), 0, ST(stream), to_dev(*cur), to_dev(*cache), words, flag);
+  hipLaunchKernelGGL(frame_refresh_kernel, grid1d(words), dim3(EW_BLOCK), 0, ST(stream), to_dev(*cur), to_dev(*cache), words, flag);
+  return tdvc_launch_status("tdvc_frame_changed");
 }
 
 extern "C" int tdvc_patch_match(const float* pin, const float* pref, int N, int hp, int wp, int C, int32_t* idx, void* stream) {

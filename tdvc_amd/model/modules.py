@@ -394,6 +394,21 @@ class FeatureExtract(nn.Module, PackCache):
         return ops.conv(t, pk_conv(self, "last", self.conv_last), out=out, res=x1)
 
 
+FEATUREFIX_REUSE = True         # A/B switch: FeatureFix keeps the I-frame's feature maps across the P-frames of a GOP (device-predicated)
+
+
+class IFrameReuse:
+    """FeatureFix's state for one (device, stream, B, H, W, scale): what `FeatureExtract_ref` + `avgpool_k` make of the I-frame, and the
+    frame they were made from.  `usable` is None until the first call has shown whether every launch of the chain carries the predicate
+    (False: the buffers are dropped and the chain runs in full, unpredicated, on every call).  `log`: the last call's per-kernel answers."""
+
+    __slots__ = ("key", "y", "iframe", "pref", "flag", "usable", "log")
+
+    def __init__(self, key):
+        self.key, self.usable, self.log = key, None, []
+        self.y = self.iframe = self.pref = self.flag = None
+
+
 class FeatureFix(nn.Module, PackCache):
     """`main/model/pnet.py:187-263`: reference-based in-loop filter"""
 
@@ -418,10 +433,18 @@ class FeatureFix(nn.Module, PackCache):
         dev = x.t.device
         lr = dict(act=ACT_LRELU, slope=0.1)
         fin = self.FeatureExtract_input.run(x)
-        y = FM.empty(B, H, W, 128, device=dev)            # [o | fref]
-        fref = self.FeatureExtract_ref.run(iframe8, out=y.ch(64, 64))
         scale = 8 if training else int(H / 8)
-        pin, pref = ops.avgpool_k(fin, scale), ops.avgpool_k(fref, scale)
+        # fref and its pooled map depend on the I-frame and the weights only: slot 0 of the reference list is the GOP's I-frame for every
+        # P-frame of the GOP (tools/predict.py).  Training, the tape, the per-kernel profile (a table of real work) and traced calls (they
+        # hand out `fref`) compute them afresh
+        if FEATUREFIX_REUSE and not training and ops.TAPE is None and ops.PROFILE is None and trace is None and not iframe8.f32:
+            y, pref = self._iframe_features(iframe8, scale)
+            fref = y.ch(64, 64)
+        else:
+            y = FM.empty(B, H, W, 128, device=dev)            # [o | fref]
+            fref = self.FeatureExtract_ref.run(iframe8, out=y.ch(64, 64))
+            pref = ops.avgpool_k(fref, scale)
+        pin = ops.avgpool_k(fin, scale)
         idx = ops.patch_match(pin, pref)
         cat = FM.empty(B, H, W, 128, device=dev)          # [fin*cor | out*cor]
         ops.match_gather(fin, fref, idx, scale, cat)
@@ -435,3 +458,54 @@ class FeatureFix(nn.Module, PackCache):
         if trace is not None:
             trace.update(ff_idx=idx, ff_fin=fin, ff_fref=fref)
         return rgb
+
+    def reuse_state(self) -> IFrameReuse | None:
+        return self.__dict__.get("_packed", {}).get("iframe_reuse")
+
+    def _iframe_features(self, iframe8: FM, scale: int):
+        """-> (y, pref): the (B,H,W,128) buffer whose upper half is FeatureExtract_ref(I-frame), and its pooled map.  Both persist
+        in the state; from the second call on a device-side compare of the I-frame with the cached one (`ops.frame_changed`) sets a flag
+        and the chain's six kernels are launched under it: they return at once when the frame is the cached one.  No host wait, no
+        dependence on tensor identity, and bit-identical results (the compare is exact).  The state lives in the packed-weight
+        cache: `clear_packed()` (load_state_dict, .to()) and `train.refresh_packed` drop it with the weights it was computed from."""
+        B, H, W = iframe8.N, iframe8.H, iframe8.W
+        dev = iframe8.t.device
+        key = (dev.index, ops._stream().value, B, H, W, scale)
+        cache = self.__dict__.setdefault("_packed", {})
+        st = cache.get("iframe_reuse")
+        if st is None or st.key != key:
+            st = cache["iframe_reuse"] = IFrameReuse(key)
+
+        def chain(y, pref):
+            fref = self.FeatureExtract_ref.run(iframe8, out=y.ch(64, 64))
+            ops.avgpool_k(fref, scale, out=pref)
+
+        def fresh():
+            return (FM.empty(B, H, W, 128, device=dev),
+                    torch.empty((B, H // scale, W // scale, 64), dtype=torch.float32, device=dev))
+
+        if st.usable is False:                            # some kernel of the chain does not test the flag at this shape
+            y, pref = fresh()
+            chain(y, pref)
+            return y, pref
+        if st.usable is None:                             # first call: fill the cache, computing under a flag of 1 to learn who tests it
+            st.y, st.pref = fresh()
+            st.iframe = FM.empty(B, H, W, iframe8.C, device=dev)
+            st.flag = torch.ones(1, dtype=torch.int32, device=dev)
+            ops.copy_cast(iframe8, st.iframe)
+        else:
+            ops.frame_changed(iframe8, st.iframe, st.flag)
+        with ops.predicate(st.flag) as log:
+            chain(st.y, st.pref)
+        st.log = list(log)
+        y, pref = st.y, st.pref
+        if not all(log):
+            # a kernel outside the predicated set ran in full behind producers that may have skipped: compute again without the flag and
+            # stop caching for this key
+            if st.usable is not None:
+                chain(y, pref)
+            st.usable = False
+            st.y = st.iframe = st.pref = st.flag = None
+        else:
+            st.usable = True
+        return y, pref

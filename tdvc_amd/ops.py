@@ -42,6 +42,47 @@ TAPE = None
 _IN_BACKWARD = False      # set by Tape.backward(): ops called from backward closures are not recorded
 
 
+# ----------------------------------------------------------------------------- launch predicate
+_PRED_LOG = None          # inside `with predicate(flag)`: one tdvc_last_launch_predicated() answer per kernel conv / conv_pair / avgpool_k launched
+
+
+class predicate:
+    """`with ops.predicate(flag) as log:` -- the launches inside carry the device flag (int32 tensor of one element, written on
+    this stream by `frame_changed`) wherever their kernel tests it (tdvc_set_predicate): conv_c8, conv_pair, conv_row and both
+    kernels of avgpool_k return at once, outputs untouched, when the flag is 0; any other kernel runs in full.  `log` collects,
+    per kernel launched by conv / conv_pair / avgpool_k, whether it carried the flag: a chain may only rely on the skipping
+    when every entry is true (a skipped producer in front of a consumer that ran would feed it stale memory)."""
+
+    def __init__(self, flag: torch.Tensor):
+        assert flag.dtype == torch.int32 and flag.is_cuda and flag.numel() >= 1
+        self.flag = flag
+
+    def __enter__(self):
+        global _PRED_LOG
+        if _PRED_LOG is not None:
+            raise L.TdvcHipError("ops.predicate does not nest")
+        L.check(L.lib().tdvc_set_predicate(self.flag.data_ptr()), "set_predicate")
+        _PRED_LOG = []
+        return _PRED_LOG
+
+    def __exit__(self, *exc):
+        global _PRED_LOG
+        _PRED_LOG = None
+        L.lib().tdvc_set_predicate(None)
+        return False
+
+
+def _log_predicated(kernels=1):
+    if _PRED_LOG is not None:
+        _PRED_LOG.extend([bool(L.lib().tdvc_last_launch_predicated())] * kernels)
+
+
+def frame_changed(cur: FM, cache: FM, flag: torch.Tensor) -> None:
+    """flag[0] = (cur != cache) as exact 16-byte words, and cache = cur when they differ; all on the stream, no host wait"""
+    dc, dk = cur.desc(), cache.desc()
+    L.check(L.lib().tdvc_frame_changed(C.byref(dc), C.byref(dk), flag.data_ptr(), _stream()), "frame_changed")
+
+
 def _rec(name, *args):
     """record a differentiable op on the active tape (no-op outside `autograd.record()`)"""
     if TAPE is not None and not _IN_BACKWARD:
@@ -492,6 +533,7 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
         _rec("conv", x, rec_pc, None if nchw_out is not None else ret, act, slope, res, res2, gdn, aux, square, nchw_out)
         return ret
     L.check(L.lib().tdvc_conv2d(C.byref(d), _stream()), "conv2d")
+    _log_predicated()
     _rec("conv", x, rec_pc, None if nchw_out is not None else ret, act, slope, res, res2, gdn, aux, square, nchw_out)
     return ret
 
@@ -556,6 +598,7 @@ def conv_pair(x: FM, pp: PackedConvPair, out: FM | None = None, act1=ACT_RELU, s
                             bytes=2.0 * x.N * x.H * x.W * 128))
         return out
     L.check(L.lib().tdvc_conv_pair(C.byref(d), _stream()), "conv_pair")
+    _log_predicated()
     return out
 
 
@@ -1004,13 +1047,15 @@ def resize_bilinear_backward(dy: FM, dx: FM, chscale: torch.Tensor | None = None
 
 
 # ----------------------------------------------------------------------------- in-loop filter matching
-def avgpool_k(x: FM, scale: int) -> torch.Tensor:
+def avgpool_k(x: FM, scale: int, out: torch.Tensor | None = None) -> torch.Tensor:
     hp, wp = x.H // scale, x.W // scale
-    pooled = torch.empty((x.N, hp, wp, x.C), dtype=torch.float32, device=x.t.device)
+    pooled = torch.empty((x.N, hp, wp, x.C), dtype=torch.float32, device=x.t.device) if out is None else out
+    assert pooled.shape == (x.N, hp, wp, x.C) and pooled.dtype == torch.float32 and pooled.is_contiguous()
     nwork = L.lib().tdvc_avgpool_k_work_floats(x.N, hp, wp, x.C, scale)
     work = torch.empty((nwork,), dtype=torch.float32, device=x.t.device)
     dx = x.desc()
     L.check(L.lib().tdvc_avgpool_k(C.byref(dx), scale, pooled.data_ptr(), hp, wp, work.data_ptr(), nwork, _stream()), "avgpool_k")
+    _log_predicated(2)               # strip pass + final pass
     return pooled
 
 
