@@ -79,7 +79,9 @@ typedef struct {
                              stored but broadcast-added over the bcast_T channel slices of width y.C that start at y:
                              y[:, t] = lrelu(y[:, t] + b), in place (y's pixel stride covers the slices) -- Bottleneck3D's temporal
                              conv + `out + temporal` + LeakyReLU (pnet.py:304-314) as ONE pass over the 4-frame buffer.  The conv
-                             input may be channels of the same buffer (a 1x1 conv reads only the pixels it then overwrites). */
+                             input may be channels of the same buffer (a 1x1 conv reads only the pixels it then overwrites).
+                             ABI 8: with `res` given (fp16, 64 channels, y's geometry, pixel stride >= 4 * 64) the four slices are READ
+                             at res and WRITTEN at y -- the out-of-place form, same arithmetic and traffic; res is left as it was. */
   float bcast_slope;
   float* chan_sum;        /* ABI 4.  not NULL: next to storing y the launch writes partial per-channel sums of the STORED fp16 values,
                              chan_sum[n][row][cout] for row < tdvc_conv_chan_sum_rows(d) (fp32; every row is written) -- the
@@ -110,10 +112,23 @@ const char* tdvc_last_conv_kernel(void);
  * on this thread passed the predicate into its kernel(s), else 0. */
 int tdvc_set_predicate(const int* flag);
 int tdvc_last_launch_predicated(void);
+/* ABI 8.  Per-image form: `flags` are n <= TDVC_MAX_PREDICATE_IMAGES ints of device memory (tdvc_frames_changed writes them).  While set
+ * (thread-local; NULL or n == 0 clears it; it and tdvc_set_predicate exclude each other), a launch of conv_c8 or conv_pair over
+ * exactly N == n images computes image i only when flags[i] != 0 and leaves the other images' outputs as they were.  Every workgroup
+ * reads the flags once at its top (plain loads, before any barrier, LDS-DMA, weight load or store), returns when no image is active
+ * and otherwise walks the job space of the ACTIVE images alone, so no workgroup idles on a skipped image; results are byte-equal to
+ * the full launch.  A launch that cannot honour the flags (another kernel, N != n) runs in full and
+ * tdvc_last_launch_predicated() says 0. */
+#define TDVC_MAX_PREDICATE_IMAGES 4
+int tdvc_set_predicate_images(const int* flags, int n);
 /* flag[0] = (cur != cache), compared exactly as 16-byte integer words (NaN payloads and signed zeros count); when they differ
  * `cache` becomes a copy of `cur`, else its bytes are not touched.  fp16 maps of one geometry (N, H, W, C), each with its own
  * pixel / batch strides.  Three enqueued steps: flag = 0, compare, conditional copy. */
 int tdvc_frame_changed(const tdvc_fmap* cur, tdvc_fmap* cache, int* flag, void* stream);
+/* ABI 8.  The same per image, for N <= TDVC_MAX_PREDICATE_IMAGES images: flags[n] = ((force_mask >> n) & 1) | (image n of cur != image n
+ * of cache), then cache[n] = cur[n] for the images whose flag is set (the others' bytes are not touched).  Three enqueued steps for
+ * all images: flags = 0, compare, conditional copy. */
+int tdvc_frames_changed(const tdvc_fmap* cur, tdvc_fmap* cache, int* flags, unsigned force_mask, void* stream);
 
 /* ---------------------------------------------------------------- conv transforms
  * Replaces every torch.nn.Conv2d / Conv3d(1,3,3) / Conv3d(3,1,1) / compressai

@@ -64,8 +64,10 @@ SIGNATURES = {
     "tdvc_last_conv_kernel": (C.c_char_p, []),
     "tdvc_prepare_device": (_i, []),
     "tdvc_set_predicate": (_i, [_P]),
+    "tdvc_set_predicate_images": (_i, [_P, _i]),
     "tdvc_last_launch_predicated": (_i, []),
     "tdvc_frame_changed": (_i, [_FM, _FM, _P, _P]),
+    "tdvc_frames_changed": (_i, [_FM, _FM, _P, C.c_uint, _P]),
     "tdvc_conv_plan": (_i, [_i, _i, _i, _i]),
     "tdvc_conv_packed_bytes": (_i64, [_i, _i, _i, _i]),
     "tdvc_pack_conv_weights": (_i, [_P, _i, _i, _i, _i, _i, _i, _P, _P, _i, _P]),

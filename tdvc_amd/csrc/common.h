@@ -22,11 +22,28 @@ int tdvc_scratch_pages(const void** zeros, void** dump);
 // closed by tdvc_note_launch() (from tdvc_launch_status), which is what tdvc_last_launch_predicated() reports
 const int* tdvc_launch_predicate();
 void tdvc_note_launch();
+// per-image form (tdvc_set_predicate_images), for the launchers of conv_c8 and conv_pair AFTER tdvc_launch_predicate(): the thread's flags
+// when they were set for exactly N images, else null (the launch then runs in full and reports 0)
+const int* tdvc_launch_predicate_images(int N);
 // top of a predicated kernel: one wave-uniform load, before any barrier, LDS-DMA or store
 #define TDVC_PREDICATE_RETURN(pred)                       \
   do {                                                    \
     if ((pred) != nullptr && *(pred) == 0) return;        \
   } while (0)
+
+// Top of a per-image predicated kernel: the active images of a launch of `nimg` <= 4 images as a packed list -- image act[j] in bits
+// [2j, 2j + 2) of `list`, `count` of them.  Plain wave-uniform loads, before any barrier, LDS-DMA or store; null flags: every image.
+struct TdvcActiveImages { unsigned list; int count; };
+__device__ __forceinline__ TdvcActiveImages tdvc_active_images(const int* flags, int nimg) {
+  TdvcActiveImages a = {0xE4u, nimg};                    // identity: 0, 1, 2, 3
+  if (flags != nullptr) {
+    a.list = 0u; a.count = 0;
+    for (int i = 0; i < nimg; ++i)
+      if (flags[i] != 0) { a.list |= (unsigned)i << (2 * a.count); ++a.count; }
+  }
+  return a;
+}
+__device__ __forceinline__ int tdvc_active_image(const TdvcActiveImages& a, int j) { return (int)((a.list >> (2 * j)) & 3u); }
 
 #define TDVC_CHECK(cond, ...)            \
   do {                                   \

@@ -24,8 +24,17 @@ constexpr int NW_C8 = 4, NTHR_C8 = 256;
 constexpr int EW_C8 = 32 * 144;                      // one transposed output row per wave
 constexpr int LDS_C8 = 256 + NW_C8 * EW_C8;          // bias + 4 wave-private regions
 
-__global__ __launch_bounds__(NTHR_C8, 4) void conv_c8_kernel(const ConvParams p, int tiles_x, int total_tiles) {
+// IMG: per-image flags (tdvc_set_predicate_images) of a launch of nimg <= 4 images.  The waves then walk the tiles of the ACTIVE images
+// only (compacted tile j is tile j % per_img of image act[j / per_img]): no wave idles on a skipped image, and a tile's arithmetic is
+// what it was.  The plain instantiation is the kernel as it was, to the register.
+template <bool IMG>
+__global__ __launch_bounds__(NTHR_C8, 4) void conv_c8_kernel(const ConvParams p, int tiles_x, int total_tiles, const int* img, int nimg) {
   TDVC_PREDICATE_RETURN(p.pred);
+  TdvcActiveImages act = {0u, 0};
+  if constexpr (IMG) {
+    act = tdvc_active_images(img, nimg);
+    if (act.count == 0) return;
+  }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* bias_s = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -54,15 +63,23 @@ __global__ __launch_bounds__(NTHR_C8, 4) void conv_c8_kernel(const ConvParams p,
   const int nwaves = (int)gridDim.x * NW_C8;
   const int w0 = (int)blockIdx.x * NW_C8 + wave;
   const int per_img = tiles_x * p.Ho;
+  if constexpr (IMG) total_tiles = act.count * per_img;
   const half8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
   auto load_b = [&](int tile, half8 (&b)[5]) {
-    const int n = tile / per_img, rem = tile - n * per_img;
+    const int ni = tile / per_img, rem = tile - ni * per_img;
+    const int n = IMG ? tdvc_active_image(act, ni) : ni;
     const int oy = rem / tiles_x, ox0 = (rem - oy * tiles_x) * 32;
     const half_t* xn = p.x + (long)n * p.x_sn;
+    // IMG: the image lookup needs a register this kernel does not have (128 VGPRs at four waves per SIMD; any form of it spilled).  The
+    // per-lane tap offsets are therefore worked out again per tile from a lane id the compiler cannot see through, instead of being
+    // held across the loop: a few VALU operations per tile for five registers
+    int lv = lane;
+    if constexpr (IMG) asm volatile("" : "+v"(lv));
 #pragma unroll
     for (int s = 0; s < 5; ++s) {
-      const int iy = oy + tdy[s], ix = ox0 + r + tdx[s];
+      const int tv = min(2 * s + (lv >> 5), 8);
+      const int iy = oy + (IMG ? tv / 3 - 1 : tdy[s]), ix = ox0 + (IMG ? (lv & 31) + tv % 3 - 1 : r + tdx[s]);
       const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       const half_t* src = xn + ((long)(ok ? iy : 0) * p.W + (ok ? ix : 0)) * p.x_sp;
       const half8 v = *reinterpret_cast<const half8*>(src);
@@ -86,7 +103,8 @@ __global__ __launch_bounds__(NTHR_C8, 4) void conv_c8_kernel(const ConvParams p,
     for (int s = 0; s < 5; ++s)
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[mt][s], bcur[s], acc[mt][0], 0, 0, 0);
-    const int n = tile / per_img, rem = tile - n * per_img;
+    const int ni = tile / per_img, rem = tile - ni * per_img;
+    const int n = IMG ? tdvc_active_image(act, ni) : ni;
     const int oy = rem / tiles_x, ox0 = (rem - oy * tiles_x) * 32;
     // lean epilogue without residuals (conv_common.h's epilogue_lean_seq keeps two residual rows in registers: 32 VGPRs this
     // kernel does not have at three waves per SIMD): bias, packed fp16 activation, transpose, four full-line stores
@@ -135,6 +153,8 @@ int launch_conv_c8(const ConvParams& p, int N, hipStream_t st) {
   const long total = (long)N * p.Ho * tiles_x;
   int grid = (int)((total + NW_C8 - 1) / NW_C8);
   if (grid > 256 * 4) grid = 256 * 4;                // four workgroups per CU: 16 persistent waves
-  hipLaunchKernelGGL(conv_c8_kernel, dim3(grid), dim3(NTHR_C8), LDS_C8, st, q, tiles_x, (int)total);
+  const int* img = q.pred ? nullptr : tdvc_launch_predicate_images(N);
+  if (img) hipLaunchKernelGGL(conv_c8_kernel<true>, dim3(grid), dim3(NTHR_C8), LDS_C8, st, q, tiles_x, (int)total, img, N);
+  else hipLaunchKernelGGL(conv_c8_kernel<false>, dim3(grid), dim3(NTHR_C8), LDS_C8, st, q, tiles_x, (int)total, nullptr, 0);
   return tdvc_launch_status("tdvc_conv2d(c8)");
 }

@@ -331,7 +331,8 @@ __device__ __forceinline__ void epilogue_store_row(const ConvParams& p, const Pa
 // ds_read_b128, packed fp16 residual adds, 4 full-line stores: ~90 vector instructions.
 // BCAST (conv_mfma_v5, tdvc_conv_desc::bcast_T == 4): the row is not stored; it is added to the four 64-channel slices that
 // start at y and LeakyReLU'd in place, with the arithmetic of bcast_add_act_kernel (fp32 add of the two fp16 values,
-// v > 0 ? v : v * slope, one rounding) -- bit-identical to the conv followed by tdvc_bcast_add_act.
+// v > 0 ? v : v * slope, one rounding) -- bit-identical to the conv followed by tdvc_bcast_add_act.  With ConvParams::res given the four
+// slices are read there and written at y (the out-of-place form: res is a source, never a residual); same arithmetic, same traffic.
 // CSUM (conv_mfma_v5, tdvc_conv_desc::chan_sum): the lane also adds the values it stores (channels 8 (lane & 7) .. + 8 of four pixels per row)
 // into cs[0..7].
 template <int NTX, bool BIAS_IN_ACC, bool BCAST = false, bool CSUM = false>
@@ -369,7 +370,7 @@ __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&
       opix[k] = ok[k] ? oy * p.Wo + ox : 0;
     }
     half8 r1[4], r2[4];
-    if (has1) {
+    if (has1 && !BCAST) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) r1[k] = *reinterpret_cast<const half8*>(rb1 + (long)opix[k] * p.res.sp);
     }
@@ -406,9 +407,10 @@ __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&
       for (int k = 0; k < 4; ++k) {
         const half8 v = *reinterpret_cast<const half8*>(ew + (k * 8 + prow) * EPS + chunk * 16);
         half_t* yp = yb + (long)opix[k] * p.y.sp;
+        const half_t* sp = has1 ? rb1 + (long)opix[k] * p.res.sp : yp;
         half8 xs[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) xs[t] = *reinterpret_cast<const half8*>(yp + t * 64);
+        for (int t = 0; t < 4; ++t) xs[t] = *reinterpret_cast<const half8*>(sp + t * 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           half8 o;

@@ -84,7 +84,9 @@ bool v3_on_and_eligible(const Pick& k) { return convk::conv_on(convk::SW_V3) && 
 bool bcast_eligible(Pick& k, const ConvParams& p) {
   const tdvc_conv_desc* d = k.d;
   return d->bcast_T == 4 && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->cout == 64 && d->y.C == 64 && d->y.sp >= 4 * 64 &&
-         d->y.dtype == TDVC_F16 && d->out_mode == TDVC_OUT_NHWC && d->act == TDVC_ACT_NONE && !d->gdn && !d->res.p && !d->res2.p &&
+         d->y.dtype == TDVC_F16 && d->out_mode == TDVC_OUT_NHWC && d->act == TDVC_ACT_NONE && !d->gdn && !d->res2.p &&
+         // res: the SOURCE of the four slices (out-of-place form), never a residual
+         (!d->res.p || (d->res.dtype == TDVC_F16 && d->res.C == 64 && d->res.sp >= 4 * 64 && d->res.N == d->y.N && d->res.H == d->y.H && d->res.W == d->y.W)) &&
          !d->square_input && !d->round_before_act && d->bias && d->bcast_slope >= 0.f && d->bcast_slope <= 1.f && conv_v5_eligible(d, k.Ho, k.Wo) &&
          convk::conv_is_lean(p);
 }
@@ -101,7 +103,7 @@ constexpr char kNameV5[] = "conv_mfma_v5", kNameDirect[] = "conv_mfma<%d,%d,%d>"
 const Entry kTable[] = {
     // ---- forms that one kernel alone implements
     {"conv_mfma_v5(bcast)", convk::SW_V5, bcast_eligible, bcast_launch, [](const tdvc_conv_desc* d) { return d->bcast_T != 0; },
-     "tdvc_conv2d: bcast_T needs a plain 1x1 / stride 1 conv to 64 channels of >= 8192 pixels, y a 64-channel window of a buffer with >= 4 slices, bcast_T == 4"},
+     "tdvc_conv2d: bcast_T needs a plain 1x1 / stride 1 conv to 64 channels of >= 8192 pixels, y (and res, the optional source of the slices) a 64-channel window of a buffer with >= 4 slices, bcast_T == 4"},
     {"conv_row(s2d)", convk::SW_ROW, [](Pick& k, const ConvParams& p) { return k.d->s2d && row_eligible(k, p); },
      [](const Pick& k, const ConvParams& p, hipStream_t st) { return launch_conv_row(k.geo, p, k.N(), st); }, nullptr, nullptr},
     {"conv_mfma_v3(s2d)", convk::SW_V3, [](Pick& k, const ConvParams&) { return k.d->s2d && conv_v3_eligible(k.d, k.Ho, k.Wo); },

@@ -120,6 +120,10 @@ struct PairParams {
   float slope1, slope2;     // max(v, v * slope): 1 = none, 0 = ReLU, else LeakyReLU
   int experiment;           // timing diagnostics (tdvc_debug_set_pair_experiment): 1 no DMA after the prologue, 2 stores to the dump line, 4 no barrier
   const int* pred;          // launch predicate (tdvc_set_predicate) or null: the kernel returns at once when *pred == 0
+  // per-image predicate (tdvc_set_predicate_images) or null: flags of the N <= 4 images.  The kernel walks the jobs of the A active
+  // images only; split[A - 1] = seg_rows | segs << 16 is the row-segment split the launcher's search gives a launch of A images
+  const int* img;
+  unsigned split[4];
 };
 
 // swizzle term of pixel q of a ring row (see the LDS image note at the top)
@@ -157,6 +161,16 @@ template <int XRING> __device__ __forceinline__ int pair_slot(int kk) {
 template <int NCB, int A1, int A2, bool ADDX, bool RES2, bool STAMP = false>
 __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, long long* stamps = nullptr, int stamp_cap = 0) {
   TDVC_PREDICATE_RETURN(p.pred);
+  // per-image flags: the compacted job space of the active images -- scalar values only, fixed before anything else happens
+  const TdvcActiveImages act = tdvc_active_images(p.img, p.N);
+  if (act.count == 0) return;
+  int p_seg_rows = p.seg_rows, p_segs = p.segs, p_jobs = p.jobs;
+  if (p.img != nullptr) {
+    const unsigned sp = act.count == 1 ? p.split[0] : (act.count == 2 ? p.split[1] : (act.count == 3 ? p.split[2] : p.split[3]));
+    p_seg_rows = (int)(sp & 0xFFFFu);
+    p_segs = (int)(sp >> 16);
+    p_jobs = act.count * p.strips * p_segs;
+  }
   using G = PairGeo<NCB>;
   constexpr int PW = G::PW, ROWB = G::ROWB, TROWB = G::TROWB, SROW = G::SROW, XRING = G::XRING, PF = G::PF, X0 = G::X0, T0 = G::T0, S0 = G::S0;
   constexpr int NF = 6 * NCB;                  // B fragments of a row
@@ -212,12 +226,12 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
   const int nwg = (int)gridDim.x, b = (int)blockIdx.x;
   int jfirst, jstep, jend;
   if ((nwg & 7) == 0) {
-    const int per = (p.jobs + 7) >> 3;
+    const int per = (p_jobs + 7) >> 3;
     jfirst = (b & 7) * per + (b >> 3);
     jstep = nwg >> 3;
-    jend = min(p.jobs, ((b & 7) + 1) * per);
+    jend = min(p_jobs, ((b & 7) + 1) * per);
   } else {
-    jfirst = b; jstep = nwg; jend = p.jobs;
+    jfirst = b; jstep = nwg; jend = p_jobs;
   }
 
   // activations as max(v, v * slope) in packed fp16 (slope 1: none, 0: ReLU), what the two-launch path computes
@@ -234,10 +248,11 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
   half8 r2v[NIT] = {};
 
   for (int job = jfirst; job < jend; job += jstep) {
-    const int n = job / (p.strips * p.segs);
-    const int rem = job - n * (p.strips * p.segs);
+    const int ni = job / (p.strips * p_segs);
+    const int rem = job - ni * (p.strips * p_segs);
+    const int n = p.img != nullptr ? tdvc_active_image(act, ni) : ni;
     const int seg = rem / p.strips, strip = rem - seg * p.strips;
-    const int c0 = strip * PW, ra = seg * p.seg_rows, rb = min(p.H, ra + p.seg_rows);
+    const int c0 = strip * PW, ra = seg * p_seg_rows, rb = min(p.H, ra + p_seg_rows);
     const int rows = rb - ra;
     const half_t* xn = p.x + (long)n * p.x_sn;
     half_t* yn = p.y + (long)n * p.y_sn;
@@ -584,20 +599,36 @@ extern "C" int tdvc_conv_pair(const tdvc_conv_pair_desc* d, void* stream) {
   const int PWsel = 16 * ncb - 2;
   p.strips = (p.W + PWsel - 1) / PWsel;
   // row segments: fill 256 workgroups evenly; a segment pays 5 extra steps for its vertical halo
-  const long base = (long)p.N * p.strips;
-  int best = 1;
-  double best_eff = 0.;
-  for (int sg = 1; sg <= 64 && (p.H + sg - 1) / sg >= 16; ++sg) {
-    const int sr = (p.H + sg - 1) / sg, nseg = (p.H + sr - 1) / sr;
-    const long jobs = base * nseg;
-    const double eff = (double)jobs / (double)(((jobs + 255) / 256) * 256) * sr / (sr + 5.0);
-    if (eff > best_eff + 1e-9) { best_eff = eff; best = sg; }
-  }
-  p.seg_rows = (p.H + best - 1) / best;
-  p.segs = (p.H + p.seg_rows - 1) / p.seg_rows;
-  p.jobs = (int)(base * p.segs);
-  const int grid = p.jobs < 256 ? p.jobs : 256;
+  auto split_for = [&](int nimg, int& seg_rows, int& segs) {
+    const long base = (long)nimg * p.strips;
+    int best = 1;
+    double best_eff = 0.;
+    for (int sg = 1; sg <= 64 && (p.H + sg - 1) / sg >= 16; ++sg) {
+      const int sr = (p.H + sg - 1) / sg, nseg = (p.H + sr - 1) / sr;
+      const long jobs = base * nseg;
+      const double eff = (double)jobs / (double)(((jobs + 255) / 256) * 256) * sr / (sr + 5.0);
+      if (eff > best_eff + 1e-9) { best_eff = eff; best = sg; }
+    }
+    seg_rows = (p.H + best - 1) / best;
+    segs = (p.H + seg_rows - 1) / seg_rows;
+    return (int)(base * segs);
+  };
+  p.jobs = split_for(p.N, p.seg_rows, p.segs);
+  int grid = p.jobs < 256 ? p.jobs : 256;
   p.pred = tdvc_launch_predicate();
+  p.img = nullptr;
+  memset(p.split, 0, sizeof(p.split));
+  if (!p.pred && p.N <= TDVC_MAX_PREDICATE_IMAGES && p.H < 65536 && (p.img = tdvc_launch_predicate_images(p.N)) != nullptr) {
+    // the split of every possible active count; the grid serves the count with the most jobs (workgroups beyond a count's jobs find
+    // an empty range and leave before their first barrier)
+    for (int a = 1; a <= p.N; ++a) {
+      int sr, sg;
+      const int jobs = split_for(a, sr, sg);
+      p.split[a - 1] = (unsigned)sr | ((unsigned)sg << 16);
+      const int g = jobs < 256 ? jobs : 256;
+      if (g > grid) grid = g;
+    }
+  }
   auto go = [&](auto kern, int lds) -> int {
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (err != hipSuccess) { tdvc_set_error("tdvc_conv_pair: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }

@@ -16,7 +16,7 @@ void tdvc_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int tdvc_abi_version(void) { return 7; }   // 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
+extern "C" int tdvc_abi_version(void) { return 8; }   // 8: per-image launch predicate, tdvc_frames_changed, out-of-place bcast_T; 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
 extern "C" const char* tdvc_last_error(void) { return g_err; }
 
 // ---- launch predicate (tdvc_set_predicate): a device flag the predicated kernels (conv_c8, conv_pair, conv_row, avgpool_k) read at
@@ -24,11 +24,28 @@ extern "C" const char* tdvc_last_error(void) { return g_err; }
 // tail of EVERY launching entry point -- closes the launch with tdvc_note_launch(): the query then says whether that launch carried it.
 static thread_local const int* g_pred = nullptr;
 static thread_local int g_pred_taken = 0, g_pred_last = 0;
+// the per-image form (tdvc_set_predicate_images): n flags, one per image of a launch of exactly n images; the two forms exclude each other
+static thread_local const int* g_pred_img = nullptr;
+static thread_local int g_pred_img_n = 0;
 
 extern "C" int tdvc_set_predicate(const int* flag) {
   if (reinterpret_cast<uintptr_t>(flag) & 3) { tdvc_set_error("tdvc_set_predicate: flag must be 4-byte aligned"); return TDVC_EINVAL; }
+  if (flag && g_pred_img) { tdvc_set_error("tdvc_set_predicate: a per-image predicate is set (clear it first)"); return TDVC_EINVAL; }
   g_pred = flag;
   return TDVC_OK;
+}
+extern "C" int tdvc_set_predicate_images(const int* flags, int n) {
+  if (!flags || n == 0) { g_pred_img = nullptr; g_pred_img_n = 0; return TDVC_OK; }
+  if (reinterpret_cast<uintptr_t>(flags) & 3) { tdvc_set_error("tdvc_set_predicate_images: flags must be 4-byte aligned"); return TDVC_EINVAL; }
+  if (n < 1 || n > TDVC_MAX_PREDICATE_IMAGES) { tdvc_set_error("tdvc_set_predicate_images: 1 <= n <= %d images, got %d", TDVC_MAX_PREDICATE_IMAGES, n); return TDVC_EINVAL; }
+  if (g_pred) { tdvc_set_error("tdvc_set_predicate_images: a launch predicate is set (clear it first)"); return TDVC_EINVAL; }
+  g_pred_img = flags; g_pred_img_n = n;
+  return TDVC_OK;
+}
+const int* tdvc_launch_predicate_images(int N) {
+  if (!g_pred_img || N != g_pred_img_n) return nullptr;      // a launch of another image count runs in full
+  g_pred_taken = 1;
+  return g_pred_img;
 }
 extern "C" int tdvc_last_launch_predicated(void) { return g_pred_last; }
 const int* tdvc_launch_predicate() {

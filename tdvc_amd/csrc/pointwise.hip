@@ -513,6 +513,22 @@ __global__ __launch_bounds__(EW_BLOCK) void frame_refresh_kernel(FMap cur, FMap 
   if (i >= words) return;
   *frame_word(cache, i) = *frame_word(cur, i);
 }
+// The same per image (tdvc_frames_changed): flags[n] = 1 when a word of image n differs or bit n of force_mask is set (the thread of the
+// image's first word stores that one); then image n of the cache is refreshed where flags[n] is set.  per_img: 16-byte words of an image
+__global__ __launch_bounds__(EW_BLOCK) void frames_compare_kernel(FMap cur, FMap cache, long words, long per_img, unsigned force_mask, int* flags) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= words) return;
+  const long n = i / per_img;
+  const u32x4 a = *frame_word(cur, i), b = *frame_word(cache, i);
+  const bool forced = i == n * per_img && ((force_mask >> n) & 1u) != 0u;
+  if (forced || ((a[0] ^ b[0]) | (a[1] ^ b[1]) | (a[2] ^ b[2]) | (a[3] ^ b[3])) != 0u) flags[n] = 1;
+}
+__global__ __launch_bounds__(EW_BLOCK) void frames_refresh_kernel(FMap cur, FMap cache, long words, long per_img, const int* flags) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= words) return;
+  if (flags[i / per_img] == 0) return;
+  *frame_word(cache, i) = *frame_word(cur, i);
+}
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   const int tid = threadIdx.x;
@@ -851,6 +867,18 @@ extern "C" int tdvc_frame_changed(const tdvc_fmap* cur, tdvc_fmap* cache, int* f
   hipLaunchKernelGGL(frame_compare_kernel, grid1d(words), dim3(EW_BLOCK), 0, ST(stream), to_dev(*cur), to_dev(*cache), words, flag);
   hipLaunchKernelGGL(frame_refresh_kernel, grid1d(words), dim3(EW_BLOCK), 0, ST(stream), to_dev(*cur), to_dev(*cache), words, flag);
   return tdvc_launch_status("tdvc_frame_changed");
+}
+
+extern "C" int tdvc_frames_changed(const tdvc_fmap* cur, tdvc_fmap* cache, int* flags, unsigned force_mask, void* stream) {
+  TDVC_CHECK(cur && cache && flags && fmap_ok16(*cur) && fmap_ok16(*cache) && same_geom(*cur, *cache) && cur->C == cache->C &&
+             cur->N <= TDVC_MAX_PREDICATE_IMAGES && (reinterpret_cast<uintptr_t>(flags) & 3) == 0,
+             "tdvc_frames_changed: fp16 maps of one geometry, at most %d images, and 4-byte aligned flags", TDVC_MAX_PREDICATE_IMAGES);
+  const hipError_t err = hipMemsetAsync(flags, 0, sizeof(int) * cur->N, ST(stream));
+  if (err != hipSuccess) { tdvc_set_error("tdvc_frames_changed: hipMemsetAsync failed: %s", hipGetErrorString(err)); return (int)err; }
+  const long per_img = (long)cur->H * cur->W * (cur->C / 8), words = per_img * cur->N;
+  hipLaunchKernelGGL(frames_compare_kernel, grid1d(words), dim3(EW_BLOCK), 0, ST(stream), to_dev(*cur), to_dev(*cache), words, per_img, force_mask, flags);
+  hipLaunchKernelGGL(frames_refresh_kernel, grid1d(words), dim3(EW_BLOCK), 0, ST(stream), to_dev(*cur), to_dev(*cache), words, per_img, flags);
+  return tdvc_launch_status("tdvc_frames_changed");
 }
 
 extern "C" int tdvc_patch_match(const float* pin, const float* pref, int N, int hp, int wp, int C, int32_t* idx, void* stream) {

@@ -72,6 +72,31 @@ class predicate:
         return False
 
 
+class predicate_images:
+    """`with ops.predicate_images(flags) as log:` -- the per-image form (tdvc_set_predicate_images): `flags` is a contiguous int32 device
+    tensor of n <= 4 elements (written on this stream by `frames_changed`); a conv_c8 or conv_pair launch over exactly n images computes
+    image i only when flags[i] != 0 and leaves the others' outputs as they were, its workgroups sharing the active images' work.  Any
+    other launch runs in full.  `log` as for `predicate`; the two forms do not nest, in themselves or in each other."""
+
+    def __init__(self, flags: torch.Tensor):
+        assert flags.dtype == torch.int32 and flags.is_cuda and flags.dim() == 1 and flags.is_contiguous() and 1 <= flags.numel() <= 4
+        self.flags = flags
+
+    def __enter__(self):
+        global _PRED_LOG
+        if _PRED_LOG is not None:
+            raise L.TdvcHipError("ops.predicate_images does not nest")
+        L.check(L.lib().tdvc_set_predicate_images(self.flags.data_ptr(), self.flags.numel()), "set_predicate_images")
+        _PRED_LOG = []
+        return _PRED_LOG
+
+    def __exit__(self, *exc):
+        global _PRED_LOG
+        _PRED_LOG = None
+        L.lib().tdvc_set_predicate_images(None, 0)
+        return False
+
+
 def _log_predicated(kernels=1):
     if _PRED_LOG is not None:
         _PRED_LOG.extend([bool(L.lib().tdvc_last_launch_predicated())] * kernels)
@@ -81,6 +106,14 @@ def frame_changed(cur: FM, cache: FM, flag: torch.Tensor) -> None:
     """flag[0] = (cur != cache) as exact 16-byte words, and cache = cur when they differ; all on the stream, no host wait"""
     dc, dk = cur.desc(), cache.desc()
     L.check(L.lib().tdvc_frame_changed(C.byref(dc), C.byref(dk), flag.data_ptr(), _stream()), "frame_changed")
+
+
+def frames_changed(cur: FM, cache: FM, flags: torch.Tensor, force_mask: int = 0) -> None:
+    """per image n of at most four: flags[n] = bit n of force_mask | (cur[n] != cache[n]) as exact 16-byte words, and cache[n] = cur[n]
+    where the flag is set; all on the stream, no host wait"""
+    assert flags.dtype == torch.int32 and flags.is_cuda and flags.is_contiguous() and flags.numel() >= cur.N
+    dc, dk = cur.desc(), cache.desc()
+    L.check(L.lib().tdvc_frames_changed(C.byref(dc), C.byref(dk), flags.data_ptr(), int(force_mask) & 0xF, _stream()), "frames_changed")
 
 
 def _rec(name, *args):
@@ -506,7 +539,8 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
          res2: FM | None = None, gdn=GDN_NONE, aux: FM | None = None, square=False, out_dtype=None,
          round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0, chan_sum: list | None = None) -> FM | torch.Tensor:
     """`bcast_T` (inference only): the conv result is not stored but broadcast-added, with LeakyReLU(bcast_slope), over the
-    bcast_T channel slices that start at `out` (tdvc_conv_desc::bcast_T).
+    bcast_T channel slices that start at `out` (tdvc_conv_desc::bcast_T); with `res` given the slices are read at `res` and written
+    at `out` (out of place), else in place.
     `chan_sum` (inference only): a list; when the kernel this conv dispatches to can sum the values it stores per channel
     (tdvc_conv_desc::chan_sum), (partial [N][rows][cout] fp32, rows) is appended -- the input of `se_gate(..., partial=)`;
     left empty otherwise (the caller then sums with tdvc_channel_sum)."""

@@ -42,6 +42,7 @@ def refresh_packed(model: torch.nn.Module) -> None:
             continue
         pk = m.__dict__.get("_packed", {})
         pk.pop("iframe_reuse", None)             # FeatureFix: I-frame features computed with the weights of before the step
+        pk.pop("lf_reuse", None)                 # LoopFilter: per-frame maps, likewise
         pcs += [pc for pc in pk.values() if isinstance(pc, ops.PackedConv)]
         for key in [k for k, v in pk.items() if isinstance(v, ops.PackedConvPair)]:
             del pk[key]                              # inference-only fused form (Res_Block): rebuilt from the live weights on next use

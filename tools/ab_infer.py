@@ -1,5 +1,6 @@
-"""A/B inside ONE process: median 1080p P-frame time with two statements toggled (names in scope: net, lib, torch).
-python tools/ab_infer.py "stmt_a" "stmt_b" """
+"""A/B inside ONE process: median 1080p P-frame time with two statements toggled (names in scope: net, lib, torch, and M =
+tdvc_amd.model.modules with its switches LOOPFILTER_REUSE, FEATUREFIX_REUSE, LOOPFILTER_PAIR, LOOPFILTER_BCAST).
+python tools/ab_infer.py "stmt_a" "stmt_b", e.g. "M.LOOPFILTER_REUSE = False" "M.LOOPFILTER_REUSE = True" """
 import ctypes
 import os
 import statistics
@@ -11,6 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tdvc_amd import _lib  # noqa: E402
 from tdvc_amd.codec_utils import pad  # noqa: E402
+import tdvc_amd.model.modules as M  # noqa: E402,F401
 from tdvc_amd.model import VideoCompressor  # noqa: E402
 from tdvc_amd.synth import fill_parameters, make_gop, ref_list  # noqa: E402
 
