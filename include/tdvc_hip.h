@@ -409,6 +409,66 @@ int tdvc_ar_wavefront_lanes(const uint8_t* data, int64_t nbytes, uint8_t* stream
                             const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
                             const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
                             const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
+/* ---------------------------------------------------------------- batched context loop (ABI 9)
+ * The loops above are chains of dependent tiny launches (at 1080p 321 steps per coder, at most 40 positions each): a step costs
+ * its launches, not its arithmetic.  The images of a batch share the position list, the weights and the CDF tables and nothing in
+ * a step couples one image to another, so the *_batch forms handle a step's positions of all B images in the SAME launches.
+ * Layout: y / y_hat / params are fmaps with N = B (their sn / sp strides are honoured: batch views and channel windows of larger
+ * buffers work); `pos` is the shared position list, one (h, w) per k; row b * npos + k (image-major) of the staging maps x1 / pc /
+ * gp belongs to position k of image b, so a step is a (1, B * npos) map to the convs; the raster arrays are [B][H][W][M], the
+ * compact ones [B][H * W][M] with row cbase + k inside image b's block (cbase < 0 selects the raster form).  Rounding, the scale
+ * index and the symbols_in form are those of the single-image entry points; a row's bits do not depend on the row count as long
+ * as tdvc_conv_select names the same kernel for the chain's descriptors (conv_mfma_v9 and conv_f32 compute a pixel as one MFMA
+ * column with a K split that depends on the layer alone), so the result is byte for byte the per-image loop's. */
+int tdvc_ar_gather_batch(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int npos,
+                         const tdvc_fmap* x1, const tdvc_fmap* pc, void* stream);
+int tdvc_ar_quantize_batch(const tdvc_fmap* y, const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
+                           const int32_t* symbols_in, const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream);
+int tdvc_ar_indexes_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, int B, const float* scale_table, int ntable,
+                          int M, int H, int W, int32_t* indexes, int64_t cbase, void* stream);
+/* tdvc_ar_wavefront over B images.  data / nbytes: HOST arrays of the B strings and their sizes (decoder) or NULL (encoder, y
+ * given).  Encoder: nothing but enqueues.  Decoder, per step: one device->host copy of the B * n * M indexes, the B host range
+ * decoders in turn, one host->device copy, the batched quantiser.  Every check -- arguments, sizes, B * n against the staging
+ * width, the steps covering H * W -- is made before anything touches a device. */
+int tdvc_ar_wavefront_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
+                            const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat,
+                            const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
+                            const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
+                            const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
+/* tdvc_ar_decode_serial over B images: position by position in raster order, B rows per step; npos_total must be H * W. */
+int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
+                                const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params,
+                                const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
+                                const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
+                                int32_t* idx_dev, int32_t* sym_dev, void* stream);
+/* B lane-split streams of ONE lane count L in one device buffer: a table uint32 [B][2] = {byte offset of container b, 32-bit words
+ * of its payload}, padded to 16 bytes, then the containers at 16-byte aligned offsets.  tdvc_ar_lanes_batch_layout: -> the bytes
+ * the buffer needs (or < 0) and, when table_out is not NULL, the table (HOST memory, 2 * B words).  The kernels take the buffer
+ * (16-byte aligned, stream_bytes long) and the table in DEVICE memory (an ordinary copy puts it there); a table entry that does
+ * not lie inside the buffer gives its image no words: flagged, never read.  state_dev: [B][L * 4 + 1] words, i.e. B blocks of
+ * tdvc_ar_lanes_state_bytes(L), one sticky error word per image.  The kernels run B workgroups of L threads, workgroup b doing on
+ * image b exactly what the single-image kernels do; no atomics, no spinning, nothing persistent. */
+int64_t tdvc_ar_lanes_batch_layout(const int64_t* nbytes, int B, int L, uint32_t* table_out);
+int tdvc_ar_lanes_init_batch(const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int B, int L, uint32_t* state_dev, void* stream);
+int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
+                                    const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int L,
+                                    const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
+                                    const int32_t* offsets_dev, int32_t ncdfs, uint32_t* state_dev, const tdvc_fmap* y_hat,
+                                    int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream);
+/* tdvc_ar_wavefront_lanes over B images: the B strings (HOST memory) are validated -- all of one lane count -- and uploaded with
+ * their table in one copy into stream_dev (stream_cap >= tdvc_ar_lanes_batch_layout() bytes), then batched init and per step
+ * gather -> convs -> the batched lane decoder; one stream wait.  TDVC_EINVAL when an image's error word is set: the message and
+ * *bad_image (may be NULL; -1 otherwise) name the FIRST such image. */
+int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nbytes, int B, uint8_t* stream_dev, int64_t stream_cap,
+                                  uint32_t* state_dev, const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev,
+                                  const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat,
+                                  const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
+                                  const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
+                                  const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, int32_t* bad_image, void* stream);
+/* Kernel enqueues of the last context-loop call on this thread (tdvc_ar_decode_serial, tdvc_ar_wavefront, tdvc_ar_wavefront_lanes
+ * and their *_batch forms), conv launches included: the launches the library's entry points closed during the call.  Copies are
+ * not counted.  A batched call over B images reports what the single-image call on the same grid reports. */
+int64_t tdvc_ar_last_loop_launches(void);
 /* q[n][h][w][c] = round(z - median[c]) as int32 in the fmap's own order (factorised-prior symbols). */
 int tdvc_round_symbols(const tdvc_fmap* z, const float* median, int32_t* out, void* stream);
 

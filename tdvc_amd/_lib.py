@@ -109,6 +109,17 @@ SIGNATURES = {
     "tdvc_ar_decode_lanes_step": (_i, [_FM, _P, _i, _P, _i, _P, _i64, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _FM, _P, _P, _i64, _P]),
     "tdvc_ar_wavefront_lanes": (_i, [_P, _i64, _P, _i64, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i,
                                      _P, _i, _P, _P, _P]),
+    "tdvc_ar_gather_batch": (_i, [_FM, _FM, _P, _i, _FM, _FM, _P]),
+    "tdvc_ar_quantize_batch": (_i, [_FM, _FM, _P, _i, _P, _i, _P, _FM, _P, _P, _i64, _P]),
+    "tdvc_ar_indexes_batch": (_i, [_FM, _P, _i, _i, _P, _i, _i, _i, _i, _P, _i64, _P]),
+    "tdvc_ar_wavefront_batch": (_i, [_P, _P, _i, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
+    "tdvc_ar_decode_serial_batch": (_i, [_P, _P, _i, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
+    "tdvc_ar_lanes_batch_layout": (_i64, [_P, _i, _i, _P]),
+    "tdvc_ar_lanes_init_batch": (_i, [_P, _i64, _P, _i, _i, _P, _P]),
+    "tdvc_ar_decode_lanes_step_batch": (_i, [_FM, _P, _i, _P, _i, _P, _i64, _P, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _FM, _P, _P, _i64, _P]),
+    "tdvc_ar_wavefront_lanes_batch": (_i, [_P, _P, _i, _P, _i64, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i,
+                                           _P, _i, _P, _P, _P, _P]),
+    "tdvc_ar_last_loop_launches": (_i64, []),
     "tdvc_ssim_level_work_floats": (_i64, [_i] * 5),
     "tdvc_ssim_level": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _f, _f, _P, _P, _P, _i64, _P]),
     "tdvc_avgpool2_pad_f32": (_i, [_P, _i64, _i, _i, _P, _P]),
@@ -169,6 +180,10 @@ _lib = None
 
 class TdvcHipError(RuntimeError):
     pass
+
+
+class TdvcStreamError(TdvcHipError, ValueError):
+    """a damaged y string met by a batched decoder: the message names the image of the call"""
 
 
 def lib():

@@ -85,6 +85,71 @@ __global__ void round_symbols_kernel(FMap z, const float* median, int32_t* out) 
   out[i] = (int)rintf(reinterpret_cast<const float*>(z.p)[(long)n * z.sn + pix * z.sp + c] - median[c]);
 }
 
+// ---- the same three kernels over the step's positions of B images at once (the batched context loop).  The images share the
+// position list; row b * npos + k of the staging maps x1 / pc / gp belongs to position k of image b (image-major), so a step is a
+// (1, B * npos) map to the convs.  y / y_hat / params are fmaps with N = B, addressed through their own batch and pixel strides.
+template <typename T, typename VT>
+__global__ void ar_gather_batch_kernel(FMap yh, FMap pr, const int32_t* pos, int npos, FMap x1, FMap pc) {
+  constexpr int VE = 16 / sizeof(T);
+  const int MV = yh.C / VE;
+  const int per = 12 * MV + pr.C / VE;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)yh.N * npos * per) return;
+  const long row = i / per;
+  const int u = (int)(i % per);
+  const int b = (int)(row / npos), k = (int)(row % npos);
+  const int h = pos[2 * k], w = pos[2 * k + 1];
+  if (u < 12 * MV) {
+    const int t = u / MV, cv = u % MV;
+    const int yy = h + kTapDy[t], xx = w + kTapDx[t];
+    VT v;
+#pragma unroll
+    for (int j = 0; j < VE; ++j) v[j] = (T)0.f;
+    if (yy >= 0 && xx >= 0 && xx < yh.W)
+      v = *reinterpret_cast<const VT*>(reinterpret_cast<const T*>(yh.p) + (long)b * yh.sn + ((long)yy * yh.W + xx) * yh.sp + cv * VE);
+    *reinterpret_cast<VT*>(reinterpret_cast<T*>(x1.p) + row * x1.sp + (t * MV + cv) * VE) = v;
+  } else {
+    const int cv = u - 12 * MV;
+    const VT v = *reinterpret_cast<const VT*>(reinterpret_cast<const T*>(pr.p) + (long)b * pr.sn + ((long)h * pr.W + w) * pr.sp + cv * VE);
+    *reinterpret_cast<VT*>(reinterpret_cast<T*>(pc.p) + row * pc.sp + cv * VE) = v;
+  }
+}
+
+// sym_in / sym / idx: [B][H][W][M] (cbase < 0) or [B][H * W][M] with this launch's position k of image b at row cbase + k of block b
+__global__ void ar_quantize_batch_kernel(FMap y, FMap gp, const int32_t* pos, int npos, const float* table, int ntable,
+                                         const int32_t* sym_in, FMap yh, int32_t* sym, int32_t* idx, long cbase) {
+  const int M = yh.C;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)yh.N * npos * M) return;
+  const long row = i / M;
+  const int c = (int)(i % M);
+  const int b = (int)(row / npos), k = (int)(row % npos);
+  const int h = pos[2 * k], w = pos[2 * k + 1];
+  const float* g = reinterpret_cast<const float*>(gp.p) + row * gp.sp;
+  const float scale = g[c], mean = g[M + c];
+  const long o = ((long)b * yh.H * yh.W + (cbase >= 0 ? cbase + k : (long)h * yh.W + w)) * M + c;
+  int q;
+  if (sym_in) q = sym_in[o];
+  else q = (int)rintf(reinterpret_cast<const float*>(y.p)[(long)b * y.sn + ((long)h * yh.W + w) * y.sp + c] - mean);
+  const long oy = (long)b * yh.sn + ((long)h * yh.W + w) * yh.sp + c;
+  if (yh.f32) reinterpret_cast<float*>(yh.p)[oy] = (float)q + mean;
+  else reinterpret_cast<half_t*>(yh.p)[oy] = (half_t)((float)q + mean);
+  sym[o] = q;
+  idx[o] = scale_index(scale, table, ntable);
+}
+
+__global__ void ar_indexes_batch_kernel(FMap gp, const int32_t* pos, int npos, int B, const float* table, int ntable, int M, int H, int W,
+                                        int32_t* idx, long cbase) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * npos * M) return;
+  const long row = i / M;
+  const int c = (int)(i % M);
+  const int b = (int)(row / npos), k = (int)(row % npos);
+  const int h = pos[2 * k], w = pos[2 * k + 1];
+  const float* g = reinterpret_cast<const float*>(gp.p) + row * gp.sp;
+  idx[((long)b * H * W + (cbase >= 0 ? cbase + k : (long)h * W + w)) * M + c] = scale_index(g[c], table, ntable);
+}
+
 // ---- lane-split y streams (rans_lane.h): the range decoder of one anti-diagonal on the device, one thread per lane.
 // Lane state lives in a device buffer between the steps' launches: uint32 [L][4] = {x low, x high, next word, end word}
 // per lane, then one sticky `bad` word (the only error channel: nothing here faults on a damaged stream, it flags it).
@@ -143,12 +208,15 @@ __device__ __forceinline__ int scale_index_lds(float s, const float* tab64, int 
 // `threadIdx.x` decodes its symbols (k, c), c % L == lane, in stream order (k, then c) -- the serial part; it touches LDS only,
 // apart from the lane's own renormalisation words, so no wait of the state update covers another memory operation.  C (all
 // threads, coalesced): sym at the compact row cbase + k and y_hat(h, w, c) = q + mean.  T: y_hat's element type.
+// The body is shared with the batched kernel below: gp0 is row 0 of this image's rows of gp (pixel stride gp_sp), yh0 the image's
+// y_hat (W, pixel stride yh_sp), sym0 / idx0 the compact row of this launch's position 0.
 template <typename T>
-__global__ void __launch_bounds__(128) ar_decode_lanes_kernel(FMap gp, const int32_t* __restrict__ pos, int npos, const float* __restrict__ table,
-                                                              int ntable, const uint8_t* __restrict__ payload, uint32_t nwords,
-                                                              const uint16_t* __restrict__ cdf16, int n16, const int32_t* __restrict__ cdf_starts,
-                                                              const int32_t* __restrict__ cdf_sizes, const int32_t* __restrict__ offsets,
-                                                              uint32_t* state, FMap yh, int32_t* __restrict__ sym, int32_t* __restrict__ idx, long cbase) {
+__device__ __forceinline__ void ar_decode_lanes_body(const float* __restrict__ gp0, int gp_sp, const int32_t* __restrict__ pos, int npos,
+                                                     const float* __restrict__ table, int ntable, const uint8_t* __restrict__ payload, uint32_t nwords,
+                                                     const uint16_t* __restrict__ cdf16, int n16, const int32_t* __restrict__ cdf_starts,
+                                                     const int32_t* __restrict__ cdf_sizes, const int32_t* __restrict__ offsets,
+                                                     uint32_t* state, T* __restrict__ yh0, int yh_W, int yh_sp, int M,
+                                                     int32_t* __restrict__ sym0, int32_t* __restrict__ idx0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
   uint16_t* s_cdf = reinterpret_cast<uint16_t*>(s_raw);
   int32_t* s_q = reinterpret_cast<int32_t*>(s_raw + kLdsCdf * 2);
@@ -157,7 +225,7 @@ __global__ void __launch_bounds__(128) ar_decode_lanes_kernel(FMap gp, const int
   int32_t* s_off = s_size + 64;
   float* s_table = reinterpret_cast<float*>(s_off + 64);
   uint8_t* s_ci = reinterpret_cast<uint8_t*>(s_table + 64);
-  const int L = (int)blockDim.x, lane = (int)threadIdx.x, M = yh.C;
+  const int L = (int)blockDim.x, lane = (int)threadIdx.x;
   if (lane < 64) s_table[lane] = lane < ntable - 1 ? table[lane] : -INFINITY;       // ntable <= 64 <= L
   if (lane < ntable) {
     const int start = cdf_starts[lane], size = cdf_sizes[lane];
@@ -191,9 +259,9 @@ __global__ void __launch_bounds__(128) ar_decode_lanes_kernel(FMap gp, const int
     const int nk = npos - k0 < kc ? npos - k0 : kc, ne = nk * M;
     for (int e = lane; e < ne; e += L) {                       // A
       const int k = k0 + e / M, c = e % M;
-      const int ci = scale_index_lds((reinterpret_cast<const float*>(gp.p) + (long)k * gp.sp)[c], s_table, ntable);
+      const int ci = scale_index_lds((gp0 + (long)k * gp_sp)[c], s_table, ntable);
       s_ci[e] = (uint8_t)ci;
-      idx[(cbase + k) * M + c] = ci;
+      idx0[(long)k * M + c] = ci;
     }
     __syncthreads();
     for (int k = 0; k < nk; ++k)                               // B
@@ -207,13 +275,69 @@ __global__ void __launch_bounds__(128) ar_decode_lanes_kernel(FMap gp, const int
     for (int e = lane; e < ne; e += L) {                       // C
       const int k = k0 + e / M, c = e % M;
       const int h = pos[2 * k], w = pos[2 * k + 1], q = s_q[e];
-      const float mean = (reinterpret_cast<const float*>(gp.p) + (long)k * gp.sp)[M + c];
-      reinterpret_cast<T*>(yh.p)[((long)h * yh.W + w) * yh.sp + c] = (T)((float)q + mean);
-      sym[(cbase + k) * M + c] = q;
+      const float mean = (gp0 + (long)k * gp_sp)[M + c];
+      yh0[((long)h * yh_W + w) * yh_sp + c] = (T)((float)q + mean);
+      sym0[(long)k * M + c] = q;
     }
     __syncthreads();                                           // s_ci / s_q are free for the next chunk
   }
   lane_store(st, state, lane, L);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(128) ar_decode_lanes_kernel(FMap gp, const int32_t* __restrict__ pos, int npos, const float* __restrict__ table,
+                                                              int ntable, const uint8_t* __restrict__ payload, uint32_t nwords,
+                                                              const uint16_t* __restrict__ cdf16, int n16, const int32_t* __restrict__ cdf_starts,
+                                                              const int32_t* __restrict__ cdf_sizes, const int32_t* __restrict__ offsets,
+                                                              uint32_t* state, FMap yh, int32_t* __restrict__ sym, int32_t* __restrict__ idx, long cbase) {
+  ar_decode_lanes_body<T>(reinterpret_cast<const float*>(gp.p), gp.sp, pos, npos, table, ntable, payload, nwords, cdf16, n16, cdf_starts, cdf_sizes, offsets,
+                          state, reinterpret_cast<T*>(yh.p), yh.W, yh.sp, yh.C, sym + cbase * yh.C, idx + cbase * yh.C);
+}
+
+// ---- B lane-split streams at once: workgroup b is the single-image kernel on image b.  The B containers sit in one device buffer
+// `streams` of `stream_bytes` bytes; tab[b] = {byte offset of container b (a multiple of 16), 32-bit words of its payload}.  The
+// table is device memory a host copy filled: a container that does not lie inside the buffer is given no words, so its lanes flag
+// `bad` and nothing outside the buffer is read.  State: [B][L * 4 + 1] words, one sticky `bad` word per image.
+struct LaneStream { const uint8_t* payload; uint32_t nwords; bool ok; };
+__device__ __forceinline__ LaneStream lane_stream(const uint8_t* streams, long stream_bytes, const uint32_t* tab, int b, int L) {
+  const uint32_t off = tab[2 * b], nw = tab[2 * b + 1];
+  const long pay = (long)off + tdvc_lanes_payload_offset(L);
+  const bool ok = (off & 15u) == 0 && pay + 4 * (long)nw <= stream_bytes;
+  return {streams + (ok ? pay : 0), ok ? nw : 0u, ok};
+}
+
+__global__ void ar_lanes_init_batch_kernel(const uint8_t* streams, long stream_bytes, const uint32_t* tab, uint32_t* state) {
+  const int L = (int)blockDim.x, lane = (int)threadIdx.x, b = (int)blockIdx.x;
+  const LaneStream ls = lane_stream(streams, stream_bytes, tab, b, L);
+  uint32_t* st_b = state + (long)b * (L * kLaneStateWords + 1);
+  TdvcLane st;
+  if (ls.ok) {
+    const uint8_t* lt = ls.payload - 2 * L;                    // the container's length table
+    uint32_t begin = 0;
+    for (int j = 0; j < lane; ++j) begin += (uint32_t)lt[2 * j] | ((uint32_t)lt[2 * j + 1] << 8);
+    const uint32_t len = (uint32_t)lt[2 * lane] | ((uint32_t)lt[2 * lane + 1] << 8);
+    tdvc_lane_init(st, ls.payload, begin, len, ls.nwords);
+  } else {
+    st.x = 0; st.pos = 0; st.end = 0; st.bad = 1;
+  }
+  if (lane == 0) st_b[L * kLaneStateWords] = 0;
+  __syncthreads();
+  lane_store(st, st_b, lane, L);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(128) ar_decode_lanes_batch_kernel(FMap gp, const int32_t* __restrict__ pos, int npos, const float* __restrict__ table,
+                                                                    int ntable, const uint8_t* __restrict__ streams, long stream_bytes,
+                                                                    const uint32_t* __restrict__ tab, const uint16_t* __restrict__ cdf16, int n16,
+                                                                    const int32_t* __restrict__ cdf_starts, const int32_t* __restrict__ cdf_sizes,
+                                                                    const int32_t* __restrict__ offsets, uint32_t* state, FMap yh,
+                                                                    int32_t* __restrict__ sym, int32_t* __restrict__ idx, long cbase) {
+  const int L = (int)blockDim.x, b = (int)blockIdx.x, M = yh.C;
+  const LaneStream ls = lane_stream(streams, stream_bytes, tab, b, L);
+  const long row0 = ((long)b * yh.H * yh.W + cbase) * M;       // image b's block of the compact arrays, row cbase
+  ar_decode_lanes_body<T>(reinterpret_cast<const float*>(gp.p) + (long)b * npos * gp.sp, gp.sp, pos, npos, table, ntable, ls.payload, ls.nwords, cdf16, n16,
+                          cdf_starts, cdf_sizes, offsets, state + (long)b * (L * kLaneStateWords + 1), reinterpret_cast<T*>(yh.p) + (long)b * yh.sn, yh.W, yh.sp,
+                          M, sym + row0, idx + row0);
 }
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -277,6 +401,7 @@ extern "C" int tdvc_ar_decode_serial(const uint8_t* data, int64_t nbytes, const 
                                      const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
                                      const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
                                      int32_t* idx_dev, int32_t* sym_dev, void* stream) {
+  TdvcLoopLaunches count;
   TDVC_CHECK(data && cdfs && cdf_sizes && offsets && y_hat && params && x1 && pc && convs && gp && pos_table && scale_table && idx_dev && sym_dev,
              "tdvc_ar_decode_serial: null argument");
   TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && npos_total >= 1 && M >= 1 && M <= 4096 && W >= 1, "tdvc_ar_decode_serial: bad sizes");
@@ -319,6 +444,7 @@ extern "C" int tdvc_ar_wavefront(const uint8_t* data, int64_t nbytes, const int3
                                  const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
                                  const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
                                  const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream) {
+  TdvcLoopLaunches count;
   TDVC_CHECK(y_hat && params && x1 && pc && convs && gp && pos_dev && step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront: null argument");
   TDVC_CHECK((data != nullptr) != (y != nullptr), "tdvc_ar_wavefront: give y (encoder) or data (decoder), not both");
   TDVC_CHECK(!data || (cdfs && cdf_sizes && offsets && nbytes >= 4), "tdvc_ar_wavefront: the decoder needs the CDF tables");
@@ -359,6 +485,7 @@ extern "C" int tdvc_ar_wavefront(const uint8_t* data, int64_t nbytes, const int3
     } else {
       const long cnt = (long)n * M;
       hipLaunchKernelGGL(ar_indexes_kernel, g1(cnt), dim3(256), 0, st, to_dev(*gp), pos, n, scale_table, ntable, M, W, idx_dev, o);
+      tdvc_count_launch();                               // the quantiser's tdvc_launch_status() below counts one
       hipError_t err = hipMemcpyAsync(host, idx_dev + o * M, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st);
       if (err == hipSuccess) err = hipStreamSynchronize(st);
       if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront: copy / sync failed: %s", hipGetErrorString(err)); rc = (int)err; break; }
@@ -448,6 +575,7 @@ extern "C" int tdvc_ar_wavefront_lanes(const uint8_t* data, int64_t nbytes, uint
                                        const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
                                        const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
                                        const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream) {
+  TdvcLoopLaunches count;
   TDVC_CHECK(data && stream_dev && state_dev && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && params && x1 && pc && convs && gp && pos_dev &&
              step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront_lanes: null argument");
   TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && nsteps >= 1 && M >= 1 && M <= 4096 && W >= 1 && M == y_hat->C, "tdvc_ar_wavefront_lanes: bad sizes");
@@ -492,5 +620,332 @@ extern "C" int tdvc_ar_wavefront_lanes(const uint8_t* data, int64_t nbytes, uint
     tdvc_set_error("tdvc_ar_wavefront_lanes: corrupt or exhausted lane-split stream (a lane ran out of words or met an impossible code)");
     rc = TDVC_EINVAL;
   }
+  return rc;
+}
+
+// ---- the batched context loop: a step handles the step's positions of all B images in the same launches (the images share the
+// position list, the weights and the tables; nothing in a step couples one image to another).  Row b * n + k of x1 / pc / gp is
+// position k of image b, a step is a (1, B * n) map to the convs; y / y_hat / params are fmaps with N = B.
+namespace {
+bool ar_fmap_ok(const tdvc_fmap& f, bool f32) { return f32 ? (fmap_ok32(f) && (f.C % 4) == 0 && (f.sp % 4) == 0 && (f.sn % 4) == 0 && aligned16(f.p)) : fmap_ok16(f); }
+
+// what the three batched drivers check before anything touches a device -> the largest step
+int batch_loop_args(const char* who, int B, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_fmap* gp,
+                    int nconvs, int M, int W, const int32_t* step_sizes, int nsteps, int* nmax_out) {
+  TDVC_CHECK(B >= 1 && B <= 65535, "%s: 1 <= B <= 65535 images expected, got %d", who, B);
+  TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && nsteps >= 1 && M >= 1 && M <= 4096 && W >= 1 && M == y_hat->C && W == y_hat->W, "%s: bad sizes", who);
+  TDVC_CHECK(y_hat->N == B && params->N == B && params->H == y_hat->H && params->W == y_hat->W && y_hat->H >= 1,
+             "%s: y_hat and params must be fmaps of B = %d images of one geometry", who, B);
+  long total = 0;
+  int nmax = 0;
+  for (int s = 0; s < nsteps; ++s) {
+    const long n = step_sizes ? step_sizes[s] : 1;             // no step list: one position per step (the raster-order decoder)
+    TDVC_CHECK(n >= 1 && n <= (1 << 20), "%s: step %d has %ld positions", who, s, n);
+    TDVC_CHECK(B * n <= x1->W && B * n <= pc->W && B * n <= gp->W, "%s: step %d: B * n = %ld rows exceed the staging buffers (x1 %d, pc %d, gp %d)", who, s, B * n,
+               x1->W, pc->W, gp->W);
+    total += n;
+    nmax = n > nmax ? (int)n : nmax;
+  }
+  TDVC_CHECK(total == (long)y_hat->H * y_hat->W, "%s: the steps must cover every position once (%ld of %ld)", who, total, (long)y_hat->H * y_hat->W);
+  *nmax_out = nmax;
+  return TDVC_OK;
+}
+
+// one step's gather -> convs over B * n rows
+int batch_step_front(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int n, int B, const tdvc_fmap* x1, const tdvc_fmap* pc,
+                     tdvc_conv_desc* d, int nconvs, void* stream) {
+  int rc = tdvc_ar_gather_batch(y_hat, params, pos, n, x1, pc, stream);
+  for (int c = 0; c < nconvs && rc == TDVC_OK; ++c) {
+    d[c].x.W = B * n;
+    d[c].y.W = B * n;
+    rc = tdvc_conv2d(&d[c], stream);
+  }
+  return rc;
+}
+
+struct HostDecoders {                                          // the B host range decoders of a call and their pinned staging buffer
+  void* dec[256] = {};
+  int B = 0;
+  int32_t* host = nullptr;
+  ~HostDecoders() {
+    for (int b = 0; b < B; ++b) if (dec[b]) tdvc_rans_decoder_destroy(dec[b]);
+    if (host) (void)hipHostFree(host);
+  }
+};
+int host_decoders(const char* who, HostDecoders& h, const uint8_t* const* data, const int64_t* nbytes, int B, size_t host_ints) {
+  TDVC_CHECK(B <= 256, "%s: the host range decoders take at most 256 images per call, got %d", who, B);
+  h.B = B;
+  for (int b = 0; b < B; ++b) {
+    h.dec[b] = tdvc_rans_decoder_create(data[b], nbytes[b]);
+    if (!h.dec[b]) return TDVC_EINVAL;
+  }
+  const hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&h.host), sizeof(int32_t) * host_ints, hipHostMallocDefault);
+  if (err != hipSuccess) { h.host = nullptr; tdvc_set_error("%s: hipHostMalloc failed: %s", who, hipGetErrorString(err)); return (int)err; }
+  return TDVC_OK;
+}
+
+// the step's indexes of all images to the host (one strided copy), the B decoders in turn, the symbols back (one strided copy):
+// image b's `cnt` values start `img_stride` ints after image b - 1's in the device arrays and are dense in `host`
+int host_decode_step(const char* who, HostDecoders& h, int32_t* idx_at, int32_t* sym_at, long img_stride, long cnt, long half, const int32_t* cdfs, int32_t cdf_stride,
+                     const int32_t* cdf_sizes, const int32_t* offsets, hipStream_t st) {
+  const size_t wb = sizeof(int32_t) * (size_t)cnt, pb = sizeof(int32_t) * (size_t)img_stride;
+  hipError_t err = hipMemcpy2DAsync(h.host, wb, idx_at, pb, wb, (size_t)h.B, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);       // also: the previous step's upload has left `host`
+  if (err != hipSuccess) { tdvc_set_error("%s: copy / sync failed: %s", who, hipGetErrorString(err)); return (int)err; }
+  for (int b = 0; b < h.B; ++b)
+    if (const int rc = tdvc_rans_decoder_decode(h.dec[b], h.host + b * cnt, cnt, cdfs, cdf_stride, cdf_sizes, offsets, h.host + half + b * cnt)) return rc;
+  err = hipMemcpy2DAsync(sym_at, pb, h.host + half, wb, wb, (size_t)h.B, hipMemcpyHostToDevice, st);
+  if (err != hipSuccess) { tdvc_set_error("%s: upload failed: %s", who, hipGetErrorString(err)); return (int)err; }
+  return TDVC_OK;
+}
+}  // namespace
+
+extern "C" int tdvc_ar_gather_batch(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int npos,
+                                    const tdvc_fmap* x1, const tdvc_fmap* pc, void* stream) {
+  TDVC_CHECK(y_hat && params && pos && x1 && pc && npos >= 1, "tdvc_ar_gather_batch: null / empty");
+  const bool f32 = y_hat->dtype == TDVC_F32;
+  TDVC_CHECK(ar_fmap_ok(*y_hat, f32) && ar_fmap_ok(*params, f32) && ar_fmap_ok(*x1, f32) && ar_fmap_ok(*pc, f32),
+             "tdvc_ar_gather_batch: four fp16 fmaps, or four fp32 fmaps (fp32 islands), expected");
+  TDVC_CHECK(params->N == y_hat->N && params->H == y_hat->H && params->W == y_hat->W, "tdvc_ar_gather_batch: params batch / geometry must match y_hat");
+  const long rows = (long)y_hat->N * npos;
+  TDVC_CHECK(x1->C == 12 * y_hat->C && x1->W >= rows && x1->H == 1 && x1->N == 1 && pc->C >= params->C && pc->W >= rows && pc->H == 1 && pc->N == 1,
+             "tdvc_ar_gather_batch: x1 must be (1,1,>=B*npos,12*M), pc (1,1,>=B*npos,>=2M)");
+  const int ve = f32 ? 4 : 8;
+  const long total = rows * (12 * y_hat->C / ve + params->C / ve);
+  if (f32) hipLaunchKernelGGL((ar_gather_batch_kernel<float, f32x4>), g1(total), dim3(256), 0, ST(stream), to_dev(*y_hat), to_dev(*params), pos, npos, to_dev(*x1), to_dev(*pc));
+  else hipLaunchKernelGGL((ar_gather_batch_kernel<half_t, half8>), g1(total), dim3(256), 0, ST(stream), to_dev(*y_hat), to_dev(*params), pos, npos, to_dev(*x1), to_dev(*pc));
+  return tdvc_launch_status("tdvc_ar_gather_batch");
+}
+
+extern "C" int tdvc_ar_quantize_batch(const tdvc_fmap* y, const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
+                                      const int32_t* symbols_in, const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream) {
+  TDVC_CHECK(gp && pos && scale_table && y_hat && symbols && indexes && npos >= 1 && ntable >= 2, "tdvc_ar_quantize_batch: null / empty");
+  TDVC_CHECK(symbols_in || (y && fmap_ok32(*y) && y->N == y_hat->N && y->H == y_hat->H && y->W == y_hat->W && y->C >= y_hat->C),
+             "tdvc_ar_quantize_batch: need y (encoder, y_hat's batch and geometry) or symbols_in (decoder)");
+  TDVC_CHECK(fmap_ok32(*gp) && (y_hat->dtype == TDVC_F32 ? fmap_ok32(*y_hat) : fmap_ok16(*y_hat)) && gp->C >= 2 * y_hat->C && gp->W >= (long)y_hat->N * npos,
+             "tdvc_ar_quantize_batch: bad gp / y_hat");
+  TDVC_CHECK(cbase < 0 || cbase + npos <= (int64_t)y_hat->H * y_hat->W, "tdvc_ar_quantize_batch: compact rows past the image's block");
+  const FMap yd = y ? to_dev(*y) : to_dev(*y_hat);
+  hipLaunchKernelGGL(ar_quantize_batch_kernel, g1((long)y_hat->N * npos * y_hat->C), dim3(256), 0, ST(stream), yd, to_dev(*gp), pos, npos, scale_table, ntable,
+                     symbols_in, to_dev(*y_hat), symbols, indexes, (long)cbase);
+  return tdvc_launch_status("tdvc_ar_quantize_batch");
+}
+
+extern "C" int tdvc_ar_indexes_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, int B, const float* scale_table, int ntable,
+                                     int M, int H, int W, int32_t* indexes, int64_t cbase, void* stream) {
+  TDVC_CHECK(gp && pos && scale_table && indexes && npos >= 1 && B >= 1 && ntable >= 2 && M >= 1 && H >= 1 && W >= 1 && fmap_ok32(*gp) && gp->C >= 2 * M &&
+             gp->W >= (long)B * npos && (cbase < 0 || cbase + npos <= (int64_t)H * W), "tdvc_ar_indexes_batch: bad arguments");
+  hipLaunchKernelGGL(ar_indexes_batch_kernel, g1((long)B * npos * M), dim3(256), 0, ST(stream), to_dev(*gp), pos, npos, B, scale_table, ntable, M, H, W, indexes, (long)cbase);
+  return tdvc_launch_status("tdvc_ar_indexes_batch");
+}
+
+extern "C" int tdvc_ar_wavefront_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
+                                       const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
+                                       const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp, const int32_t* pos_dev,
+                                       const int32_t* step_sizes, int nsteps, int M, int W, const float* scale_table, int ntable, int32_t* idx_dev,
+                                       int32_t* sym_dev, void* stream) {
+  TdvcLoopLaunches count;
+  TDVC_CHECK(y_hat && params && x1 && pc && convs && gp && pos_dev && step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront_batch: null argument");
+  TDVC_CHECK((data != nullptr) != (y != nullptr), "tdvc_ar_wavefront_batch: give y (encoder) or data (decoder), not both");
+  TDVC_CHECK(!data || (nbytes && cdfs && cdf_sizes && offsets), "tdvc_ar_wavefront_batch: the decoder needs the strings' sizes and the CDF tables");
+  int nmax = 0;
+  if (const int rc = batch_loop_args("tdvc_ar_wavefront_batch", B, y_hat, params, x1, pc, gp, nconvs, M, W, step_sizes, nsteps, &nmax)) return rc;
+  if (data)
+    for (int b = 0; b < B; ++b) TDVC_CHECK(data[b] && nbytes[b] >= 4, "tdvc_ar_wavefront_batch: image %d: null / empty string", b);
+  hipStream_t st = ST(stream);
+  tdvc_conv_desc d[8];
+  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
+  const long HW = (long)y_hat->H * y_hat->W, half = (long)B * nmax * M;
+  HostDecoders h;                                            // [2][B * nmax * M] indexes | symbols, pinned
+  if (data)
+    if (const int rc = host_decoders("tdvc_ar_wavefront_batch", h, data, nbytes, B, 2 * (size_t)half)) return rc;
+  int rc = TDVC_OK;
+  long o = 0;
+  for (int s = 0; s < nsteps && rc == TDVC_OK; ++s) {
+    const int n = step_sizes[s];
+    const int32_t* pos = pos_dev + 2 * o;
+    rc = batch_step_front(y_hat, params, pos, n, B, x1, pc, d, nconvs, stream);
+    if (rc != TDVC_OK) break;
+    if (!data) {
+      rc = tdvc_ar_quantize_batch(y, gp, pos, n, scale_table, ntable, nullptr, y_hat, sym_dev, idx_dev, -1, stream);
+    } else {
+      rc = tdvc_ar_indexes_batch(gp, pos, n, B, scale_table, ntable, M, y_hat->H, W, idx_dev, o, stream);
+      if (rc == TDVC_OK)
+        rc = host_decode_step("tdvc_ar_wavefront_batch", h, idx_dev + o * M, sym_dev + o * M, HW * M, (long)n * M, half, cdfs, cdf_stride, cdf_sizes, offsets, st);
+      if (rc == TDVC_OK) rc = tdvc_ar_quantize_batch(nullptr, gp, pos, n, scale_table, ntable, sym_dev, y_hat, sym_dev, idx_dev, o, stream);
+    }
+    o += n;
+  }
+  if (data) (void)hipStreamSynchronize(st);                   // before `h` frees the pinned buffer
+  return rc;
+}
+
+extern "C" int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
+                                           const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params,
+                                           const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
+                                           const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
+                                           int32_t* idx_dev, int32_t* sym_dev, void* stream) {
+  TdvcLoopLaunches count;
+  TDVC_CHECK(data && nbytes && cdfs && cdf_sizes && offsets && y_hat && params && x1 && pc && convs && gp && pos_table && scale_table && idx_dev && sym_dev,
+             "tdvc_ar_decode_serial_batch: null argument");
+  int nmax = 0;
+  if (const int rc = batch_loop_args("tdvc_ar_decode_serial_batch", B, y_hat, params, x1, pc, gp, nconvs, M, W, nullptr, npos_total > 0 ? npos_total : 1, &nmax)) return rc;
+  for (int b = 0; b < B; ++b) TDVC_CHECK(data[b] && nbytes[b] >= 4, "tdvc_ar_decode_serial_batch: image %d: null / empty string", b);
+  hipStream_t st = ST(stream);
+  tdvc_conv_desc d[8];
+  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
+  const long HW = (long)y_hat->H * y_hat->W, half = (long)B * M;
+  HostDecoders h;                                            // [2][B * M] indexes | symbols, pinned
+  if (const int rc = host_decoders("tdvc_ar_decode_serial_batch", h, data, nbytes, B, 2 * (size_t)half)) return rc;
+  int rc = TDVC_OK;
+  for (long k = 0; k < npos_total && rc == TDVC_OK; ++k) {    // raster order: position k = h * W + w owns row k of every image's block
+    const int32_t* pos = pos_table + 2 * k;
+    rc = batch_step_front(y_hat, params, pos, 1, B, x1, pc, d, nconvs, stream);
+    if (rc == TDVC_OK) rc = tdvc_ar_indexes_batch(gp, pos, 1, B, scale_table, ntable, M, y_hat->H, W, idx_dev, -1, stream);
+    if (rc == TDVC_OK)
+      rc = host_decode_step("tdvc_ar_decode_serial_batch", h, idx_dev + k * M, sym_dev + k * M, HW * M, M, half, cdfs, cdf_stride, cdf_sizes, offsets, st);
+    if (rc == TDVC_OK) rc = tdvc_ar_quantize_batch(nullptr, gp, pos, 1, scale_table, ntable, sym_dev, y_hat, sym_dev, idx_dev, -1, stream);
+  }
+  (void)hipStreamSynchronize(st);
+  return rc;
+}
+
+// ---- B lane-split streams.  Device buffer layout (tdvc_ar_lanes_batch_layout): the table uint32 [B][2] = {byte offset of container
+// b, words of its payload}, padded to 16 bytes, then the containers, each at a 16-byte aligned offset.
+extern "C" int64_t tdvc_ar_lanes_batch_layout(const int64_t* nbytes, int B, int L, uint32_t* table_out) {
+  if (!nbytes || B < 1 || B > 65535 || L < 1) { tdvc_set_error("tdvc_ar_lanes_batch_layout: null sizes, or B = %d / L = %d out of range", B, L); return TDVC_EINVAL; }
+  int64_t off = ((int64_t)B * 8 + 15) / 16 * 16;
+  const int64_t pay = tdvc_lanes_payload_offset(L);
+  for (int b = 0; b < B; ++b) {
+    if (nbytes[b] < pay || (nbytes[b] - pay) % 4 != 0 || (nbytes[b] - pay) / 4 > (int64_t)L * kLanesMaxWords) {
+      tdvc_set_error("tdvc_ar_lanes_batch_layout: image %d: bad stream size %lld", b, (long long)nbytes[b]);
+      return TDVC_EINVAL;
+    }
+    if (table_out) { table_out[2 * b] = (uint32_t)off; table_out[2 * b + 1] = (uint32_t)((nbytes[b] - pay) / 4); }
+    off += (nbytes[b] + 15) / 16 * 16;
+    if (off > 0xFFFFFFF0ll) { tdvc_set_error("tdvc_ar_lanes_batch_layout: the strings exceed 4 GB"); return TDVC_EINVAL; }
+  }
+  return off;
+}
+
+namespace {
+int lanes_batch_args(const char* who, const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int B, int L, int M, const uint32_t* state_dev) {
+  TDVC_CHECK(streams_dev && table_dev && state_dev && B >= 1 && B <= 65535, "%s: null stream / table / state buffer, or B = %d out of range", who, B);
+  TDVC_CHECK((L == 64 || L == 128) && M >= L && M % L == 0, "%s: the device decoder takes 64 or 128 lanes that divide the channel count (L = %d, M = %d)", who, L, M);
+  TDVC_CHECK(aligned16(streams_dev) && (((uintptr_t)table_dev) & 3) == 0 && (((uintptr_t)state_dev) & 3) == 0 && stream_bytes >= 16,
+             "%s: the stream buffer must be 16-byte aligned, the table / state buffers 4-byte aligned", who);
+  return TDVC_OK;
+}
+}  // namespace
+
+extern "C" int tdvc_ar_lanes_init_batch(const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int B, int L, uint32_t* state_dev, void* stream) {
+  if (const int rc = lanes_batch_args("tdvc_ar_lanes_init_batch", streams_dev, stream_bytes, table_dev, B, L, L, state_dev)) return rc;
+  hipLaunchKernelGGL(ar_lanes_init_batch_kernel, dim3(B), dim3(L), 0, ST(stream), streams_dev, (long)stream_bytes, table_dev, state_dev);
+  return tdvc_launch_status("tdvc_ar_lanes_init_batch");
+}
+
+extern "C" int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
+                                               const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int L,
+                                               const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
+                                               const int32_t* offsets_dev, int32_t ncdfs, uint32_t* state_dev, const tdvc_fmap* y_hat,
+                                               int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream) {
+  TDVC_CHECK(gp && pos && scale_table && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && symbols && indexes && npos >= 1 && cbase >= 0,
+             "tdvc_ar_decode_lanes_step_batch: null / empty");
+  TDVC_CHECK(ntable >= 2 && ntable <= 64 && ncdfs >= ntable, "tdvc_ar_decode_lanes_step_batch: 2..64 scale-table entries, one CDF per entry expected");
+  TDVC_CHECK(n16 >= 8 && n16 % 8 == 0 && aligned16(cdf16_dev), "tdvc_ar_decode_lanes_step_batch: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
+  TDVC_CHECK(n16 <= kLdsCdf, "tdvc_ar_decode_lanes_step_batch: %d packed CDF entries, the kernel's LDS holds %d", n16, kLdsCdf);
+  const int B = y_hat->N;
+  TDVC_CHECK(fmap_ok32(*gp) && (y_hat->dtype == TDVC_F32 ? fmap_ok32(*y_hat) : fmap_ok16(*y_hat)) && gp->C >= 2 * y_hat->C && gp->W >= (long)B * npos &&
+             cbase + npos <= (int64_t)y_hat->H * y_hat->W, "tdvc_ar_decode_lanes_step_batch: bad gp / y_hat / rows");
+  if (const int rc = lanes_batch_args("tdvc_ar_decode_lanes_step_batch", streams_dev, stream_bytes, table_dev, B, L, y_hat->C, state_dev)) return rc;
+  TDVC_CHECK(y_hat->C <= kChunkSyms, "tdvc_ar_decode_lanes_step_batch: more than %d channels", kChunkSyms);
+  static TdvcPerDeviceFlag attr;
+  if (!attr.flag()) {
+    for (const void* k : {reinterpret_cast<const void*>(&ar_decode_lanes_batch_kernel<float>), reinterpret_cast<const void*>(&ar_decode_lanes_batch_kernel<half_t>)}) {
+      const hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLanesLds);
+      if (err != hipSuccess) { tdvc_set_error("tdvc_ar_decode_lanes_step_batch: cannot reserve %d bytes of LDS: %s", kLanesLds, hipGetErrorString(err)); return (int)err; }
+    }
+    attr.flag() = true;
+  }
+  if (y_hat->dtype == TDVC_F32)
+    hipLaunchKernelGGL(ar_decode_lanes_batch_kernel<float>, dim3(B), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, streams_dev,
+                       (long)stream_bytes, table_dev, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
+  else
+    hipLaunchKernelGGL(ar_decode_lanes_batch_kernel<half_t>, dim3(B), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, streams_dev,
+                       (long)stream_bytes, table_dev, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
+  return tdvc_launch_status("tdvc_ar_decode_lanes_step_batch");
+}
+
+// tdvc_ar_wavefront_lanes over B images: the B strings are validated, packed behind their table in pinned memory and uploaded with
+// one copy, then per step gather -> convs -> ar_decode_lanes_batch_kernel (B workgroups) with no synchronisation; the B sticky
+// `bad` words come back with the call's one stream wait.
+extern "C" int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nbytes, int B, uint8_t* stream_dev, int64_t stream_cap,
+                                             uint32_t* state_dev, const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev,
+                                             const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat,
+                                             const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
+                                             const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
+                                             const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, int32_t* bad_image, void* stream) {
+  TdvcLoopLaunches count;
+  if (bad_image) *bad_image = -1;
+  TDVC_CHECK(data && nbytes && stream_dev && state_dev && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && params && x1 && pc && convs && gp &&
+             pos_dev && step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront_lanes_batch: null argument");
+  int nmax = 0;
+  if (const int rc = batch_loop_args("tdvc_ar_wavefront_lanes_batch", B, y_hat, params, x1, pc, gp, nconvs, M, W, step_sizes, nsteps, &nmax)) return rc;
+  TDVC_CHECK(B <= 4096, "tdvc_ar_wavefront_lanes_batch: at most 4096 images per call, got %d", B);
+  int L = 0;
+  for (int b = 0; b < B; ++b) {
+    int Lb = 0;
+    if (const char* why = tdvc_lanes_check(data[b], nbytes[b], M, &Lb)) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: image %d: %s", b, why); return TDVC_EINVAL; }
+    TDVC_CHECK(b == 0 || Lb == L, "tdvc_ar_wavefront_lanes_batch: image %d declares %d lanes, image 0 %d: all images of a call must have the same lane count", b, Lb, L);
+    L = Lb;
+  }
+  TDVC_CHECK(L == 64 || L == 128, "tdvc_ar_wavefront_lanes_batch: the device decoder takes 64 or 128 lanes (L = %d)", L);
+  uint32_t table[2 * 4096];
+  const int64_t total = tdvc_ar_lanes_batch_layout(nbytes, B, L, table);
+  if (total < 0) return (int)total;
+  TDVC_CHECK(total <= stream_cap, "tdvc_ar_wavefront_lanes_batch: the device stream buffer holds %lld bytes, the strings and their table need %lld", (long long)stream_cap,
+             (long long)total);
+  hipStream_t st = ST(stream);
+  tdvc_conv_desc d[8];
+  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
+  uint8_t* pinned = nullptr;                                   // table | containers, as the device buffer holds them
+  hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&pinned), (size_t)total, hipHostMallocDefault);
+  if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: hipHostMalloc failed: %s", hipGetErrorString(err)); return (int)err; }
+  memset(pinned, 0, (size_t)total);
+  memcpy(pinned, table, sizeof(uint32_t) * 2 * (size_t)B);
+  for (int b = 0; b < B; ++b) memcpy(pinned + table[2 * b], data[b], (size_t)nbytes[b]);
+  const uint32_t* table_dev = reinterpret_cast<const uint32_t*>(stream_dev);
+  const long sw = (long)L * kLaneStateWords + 1;               // state words per image
+  int rc = TDVC_OK;
+  err = hipMemcpyAsync(stream_dev, pinned, (size_t)total, hipMemcpyHostToDevice, st);
+  if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: upload failed: %s", hipGetErrorString(err)); rc = (int)err; }
+  if (rc == TDVC_OK) rc = tdvc_ar_lanes_init_batch(stream_dev, total, table_dev, B, L, state_dev, stream);
+  long o = 0;
+  for (int s = 0; s < nsteps && rc == TDVC_OK; ++s) {
+    const int n = step_sizes[s];
+    const int32_t* pos = pos_dev + 2 * o;
+    rc = batch_step_front(y_hat, params, pos, n, B, x1, pc, d, nconvs, stream);
+    if (rc == TDVC_OK)
+      rc = tdvc_ar_decode_lanes_step_batch(gp, pos, n, scale_table, ntable, stream_dev, total, table_dev, L, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev,
+                                           ncdfs, state_dev, y_hat, sym_dev, idx_dev, o, stream);
+    o += n;
+  }
+  uint32_t* bad = reinterpret_cast<uint32_t*>(pinned);        // the table's place, once the upload is done (stream order): B words
+  if (rc == TDVC_OK) {
+    err = hipMemcpy2DAsync(bad, sizeof(uint32_t), state_dev + (long)L * kLaneStateWords, sizeof(uint32_t) * (size_t)sw, sizeof(uint32_t), (size_t)B,
+                           hipMemcpyDeviceToHost, st);
+    if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: reading the error words failed: %s", hipGetErrorString(err)); rc = (int)err; }
+  }
+  err = hipStreamSynchronize(st);
+  if (rc == TDVC_OK && err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: stream wait failed: %s", hipGetErrorString(err)); rc = (int)err; }
+  if (rc == TDVC_OK)
+    for (int b = 0; b < B; ++b)
+      if (bad[b]) {
+        if (bad_image) *bad_image = b;
+        tdvc_set_error("tdvc_ar_wavefront_lanes_batch: image %d: corrupt or exhausted lane-split stream (a lane ran out of words or met an impossible code)", b);
+        rc = TDVC_EINVAL;
+        break;
+      }
+  (void)hipHostFree(pinned);
   return rc;
 }

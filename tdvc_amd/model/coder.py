@@ -146,6 +146,9 @@ def subpel_conv3x3(cin, cout, r=1):
 
 LR = dict(act=ACT_LRELU, slope=0.01)
 STREAM_ORDERS = ("raster", "wavefront", "lanes")
+# compress() / decompress() of a batch: True -> one pass of the context loop handles every step's positions of all images in the
+# same launches (tdvc_ar_*_batch; byte for byte the per-image result), False -> one pass per image (the A/B and the fallback)
+AR_BATCH = True
 
 # host range coding off the critical path (compress(defer=True), VideoCompressor.encode): the coder library releases the GIL
 _RANS_POOL = None
@@ -614,8 +617,9 @@ class Cheng2020Anchor(nn.Module, PackCache):
         return steps
 
     def _ar_setup(self, H, W, adt, dev, B):
-        """per (grid, dtype): the wavefront position list, the step sizes, the staging chain and pinned host buffers for the
-        symbols / indexes of B images -- built once (the position list alone is 2 ms of Python at 68 x 120)"""
+        """per (grid, dtype, batch): the wavefront position list, the step sizes and the staging chain for B x H rows (a step of a
+        batch of B is a (1, B x n) map) -- built once (the position list alone is 2 ms of Python at 68 x 120); `_ar_host` and
+        `_ar_serial` add what only the encoder / only the raster-order decoder needs"""
         cache = self.__dict__.setdefault("_ar_cache", {})
         key = (H, W, adt, str(dev), B)
         c = cache.get(key)
@@ -624,15 +628,60 @@ class Cheng2020Anchor(nn.Module, PackCache):
         if c is None:
             steps = self.wavefront_steps(H, W)
             flat = torch.tensor([p for st in steps for p in st], dtype=torch.int32, device=dev)
-            c = dict(flat=flat, fl=flat.long(), sizes=np.array([len(st) for st in steps], dtype=np.int32), chain=self._ar_chain(H, adt, dev),
-                     host=[(torch.empty((H * W, self.M), dtype=torch.int32).pin_memory(), torch.empty((H * W, self.M), dtype=torch.int32).pin_memory())
-                           for _ in range(B)])
+            c = dict(flat=flat, fl=flat.long(), sizes=np.array([len(st) for st in steps], dtype=np.int32), chain=self._ar_chain(B * H, adt, dev),
+                     key=key)
             cache.clear()                # one geometry at a time (the staging buffers are not small)
             cache[key] = c
         return c
 
+    def _ar_host(self, st):
+        """pinned host buffers for the symbols / indexes of the B images of compress()"""
+        if "host" not in st:
+            H, W, _, _, B = st["key"]
+            st["host"] = [(torch.empty((H * W, self.M), dtype=torch.int32).pin_memory(), torch.empty((H * W, self.M), dtype=torch.int32).pin_memory())
+                          for _ in range(B)]
+        return st["host"]
+
+    def _ar_serial(self, st):
+        """the raster-order decoder's chain (B rows: one position of every image per step) and its position table"""
+        if "serial" not in st:
+            H, W, adt, _, B = st["key"]
+            dev = st["flat"].device
+            st["serial"] = (self._ar_chain(B, adt, dev), torch.tensor([[h, w] for h in range(H) for w in range(W)], dtype=torch.int32, device=dev))
+        return st["serial"]
+
+    @staticmethod
+    def _ar_groups(descs, B, nmax):
+        """group sizes for a batch of B (ops.ar_batch_groups: images share a loop only while the conv selection does not change with
+        the row count); all 1 with AR_BATCH off"""
+        return ops.ar_batch_groups(descs, B, nmax) if AR_BATCH and B > 1 else [1] * B
+
+    # -- the transforms around the context loop, for a batch as one call or image by image.  The forward conv dispatch counts pixels
+    # over the batch (conv_v9_eligible), so a layer may run on another kernel -- with other last bits -- in a batch than alone;
+    # `per_image` keeps every image on the kernels of a call of one, which makes a batch's strings those of B single calls
+    @staticmethod
+    def _image(x: FM, b: int) -> FM:
+        """image b of a batch as an FM of its own (N = 1), as a call of one would hand it in"""
+        return FM(x.t[b:b + 1], x.off, 1, x.C)
+
+    def _g_a_h_a(self, x: FM):
+        y32, y16 = self.run_g_a(x)
+        return y32, self.run_h_a(y16)
+
+    def _h_s(self, z_hat: FM, params: FM, per_image: bool):
+        if per_image and z_hat.N > 1:
+            for b in range(z_hat.N):
+                self.run_h_s(self._image(z_hat, b), out=self._image(params, b))
+        else:
+            self.run_h_s(z_hat, out=params)
+
+    def _g_s(self, y_hat: FM, per_image: bool) -> FM:
+        if per_image and y_hat.N > 1:
+            return FM(torch.cat([self.run_g_s(self._image(y_hat, b)).t for b in range(y_hat.N)], 0))
+        return self.run_g_s(y_hat)
+
     @torch.no_grad()
-    def compress(self, x: FM, f32=False, order="raster", defer=False, lanes=64):
+    def compress(self, x: FM, f32=False, order="raster", defer=False, lanes=64, per_image=False):
         """-> {"strings": [y_strings, z_strings], "shape": (h, w)} like compressai's compress()
         (`f32`: the fp32-island mode, see run()).
 
@@ -647,7 +696,10 @@ class Cheng2020Anchor(nn.Module, PackCache):
         reference's decoder.  "lanes" is the wavefront sequence split over `lanes` (64 or 128) independent rANS sub-streams, channel
         c in lane c % lanes (ops.rans_encode_lanes: a 4-byte header, a length table, the sub-streams), which lets decompress() run
         the range decoder on the GPU, one thread per lane, with no host round trip inside the loop; it costs about 8 bytes per
-        lane and, like "wavefront", the reference's decoder cannot read it.  The GPU side of all three orders is the same."""
+        lane and, like "wavefront", the reference's decoder cannot read it.  The GPU side of all three orders is the same.
+
+        `per_image`: g_a, h_a and h_s run image by image (the context loop still takes the batch in one pass): the strings are
+        then those of B calls of one image, whatever kernels the batch as a whole would be dispatched to."""
         if order not in STREAM_ORDERS:
             raise ValueError(f"order must be one of {STREAM_ORDERS}, got {order!r}")
         if order == "lanes" and (lanes not in ops.LANE_COUNTS or self.M % lanes):
@@ -658,29 +710,42 @@ class Cheng2020Anchor(nn.Module, PackCache):
         if f32:
             x = self._as_f32(x)
         adt = torch.float32 if f32 else torch.float16
-        y32, y16 = self.run_g_a(x)
-        z = self.run_h_a(y16)
+        if per_image and x.N > 1:
+            ya, za = zip(*[self._g_a_h_a(self._image(x, b)) for b in range(x.N)])
+            y32, z = FM(torch.cat([t.t for t in ya], 0)), FM(torch.cat([t.t for t in za], 0))
+        else:
+            y32, z = self._g_a_h_a(x)
         B, H, W = y32.N, y32.H, y32.W
         med = self.entropy_bottleneck.quantiles.detach()[:, 0, 1].float().contiguous()
         zsym = ops.round_symbols(z, med)                                           # (B, h, w, C) int32
         z_hat = FM((zsym.float() + med).to(adt))
         params = FM.empty(B, H, W, 2 * M, dtype=adt, device=dev)
-        self.run_h_s(z_hat, out=params)
+        self._h_s(z_hat, params, per_image)
         zs = zsym.permute(0, 3, 1, 2).contiguous().cpu().numpy()                   # compressai order (C, h, w)
         zidx = np.broadcast_to(np.arange(M, dtype=np.int32)[:, None, None], zs.shape[1:])
         z_strings = [ops.rans_encode(zs[b], zidx, ebt) for b in range(B)]
         st = self._ar_setup(H, W, adt, dev, B)
         flat, sizes, chain, fl = st["flat"], st["sizes"], st["chain"], st["fl"]
+        host = self._ar_host(st)
+        # every position is written exactly once and only causal (already written) neighbours are read: no zero fill
+        y_hat_all = FM.empty(B, H, W, M, dtype=adt, device=dev)
+        sym_all = torch.empty((B, H, W, M), dtype=torch.int32, device=dev)
+        idx_all = torch.empty((B, H, W, M), dtype=torch.int32, device=dev)
+        # the W + 3(H-1) steps run natively (gather -> context conv -> entropy_parameters -> quantise), for a group of images in the
+        # same launches (tdvc_ar_wavefront_batch) or image by image (tdvc_ar_wavefront)
+        b0 = 0
+        for g in self._ar_groups(chain["descs"], B, int(sizes.max())):
+            if g > 1:
+                ops.ar_wavefront_batch(None, None, y32.batch(b0, g), y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
+                                       chain["gp"], flat, sizes, M, W, table, idx_all[b0:b0 + g], sym_all[b0:b0 + g])
+            else:
+                ops.ar_wavefront(None, None, y32.batch(b0, 1), y_hat_all.batch(b0, 1), params.batch(b0, 1), chain["x1"], chain["pc"], chain["descs"],
+                                 chain["gp"], flat, sizes, M, W, table, idx_all[b0], sym_all[b0])
+            b0 += g
         y_jobs, dbg = [], []
         for b in range(B):
-            # every position is written exactly once and only causal (already written) neighbours are read: no zero fill
-            y_hat = FM.empty(1, H, W, M, dtype=adt, device=dev)
-            sym = torch.empty((H, W, M), dtype=torch.int32, device=dev)
-            idx = torch.empty((H, W, M), dtype=torch.int32, device=dev)
-            # the W + 3(H-1) steps run natively (tdvc_ar_wavefront: gather -> context conv -> entropy_parameters -> quantise)
-            ops.ar_wavefront(None, None, y32.batch(b, 1), y_hat, params.batch(b, 1), chain["x1"], chain["pc"], chain["descs"], chain["gp"],
-                             flat, sizes, M, W, table, idx, sym)
-            hs, hi = st["host"][b]
+            sym, idx = sym_all[b], idx_all[b]
+            hs, hi = host[b]
             if order != "raster":
                 hs.copy_(sym[fl[:, 0], fl[:, 1]], non_blocking=True)
                 hi.copy_(idx[fl[:, 0], fl[:, 1]], non_blocking=True)
@@ -696,17 +761,17 @@ class Cheng2020Anchor(nn.Module, PackCache):
                     return ops.rans_encode_lanes(hs.numpy(), hi.numpy(), gct, lanes)
                 return ops.rans_encode(hs.numpy(), hi.numpy(), gct)
             y_jobs.append(_rans_pool().submit(job) if defer else job())
-            dbg.append({"y_hat": y_hat, "symbols": sym, "indexes": idx})
+            dbg.append({"y_hat": FM(y_hat_all.t[b:b + 1]), "symbols": sym, "indexes": idx})
         if defer:
             return {"strings": PendingStrings(y_jobs, z_strings), "shape": (z.H, z.W), "_debug": dbg}
         return {"strings": [y_jobs, z_strings], "shape": (z.H, z.W), "_debug": dbg}
 
     @torch.no_grad()
-    def decompress(self, strings, shape, synth=True, f32=False, order="raster"):
+    def decompress(self, strings, shape, synth=True, f32=False, order="raster", per_image=False):
         """strings as returned by compress(); "raster": serial position-by-position context decoding (the stream order of
         compressai's bitstream); "wavefront": one anti-diagonal per step (W + 3(H-1) steps instead of H*W), the range decoder on
         the host; "lanes": the same steps with the range decoder on the GPU (the lane count is read from the string's header).
-        -> {"x_hat": FM, "y_hat": FM}.  `f32` and `order` must match the encoder's."""
+        -> {"x_hat": FM, "y_hat": FM}.  `f32` and `order` must match the encoder's; `per_image` as in compress() (h_s, g_s)."""
         if order not in STREAM_ORDERS:
             raise ValueError(f"order must be one of {STREAM_ORDERS}, got {order!r}")
         dev = self.context_prediction.weight.device
@@ -722,22 +787,41 @@ class Cheng2020Anchor(nn.Module, PackCache):
         zsym = torch.from_numpy(zs).to(dev).permute(0, 2, 3, 1).contiguous()
         z_hat = FM((zsym.float() + med).to(adt))
         params = FM.empty(B, H, W, 2 * M, dtype=adt, device=dev)
-        self.run_h_s(z_hat, out=params)
+        self._h_s(z_hat, params, per_image)
         y_hat_all = FM.zeros(B, H, W, M, dtype=adt, device=dev)
-        sym = torch.zeros((H, W, M), dtype=torch.int32, device=dev)
-        idx = torch.zeros((H, W, M), dtype=torch.int32, device=dev)
+        st = self._ar_setup(H, W, adt, dev, B)
+        ys = list(strings[0])
+        if len(ys) != B:
+            raise ValueError(f"{len(ys)} y strings for {B} z strings")
         if order != "raster":
-            for b in range(B):
-                self._decode_wavefront(strings[0][b], gct, table, y_hat_all.batch(b, 1), params.batch(b, 1), lanes=order == "lanes")
-            return {"x_hat": self.run_g_s(y_hat_all) if synth else None, "y_hat": y_hat_all}
-        # the per-position chain over one-position staging buffers; the loop itself runs natively
-        # (tdvc_ar_decode_serial: Python drove it at ~230 us per position)
-        chain = self._ar_chain(1, adt, dev)
-        pos_table = torch.tensor([[h, w] for h in range(H) for w in range(W)], dtype=torch.int32, device=dev)
-        for b in range(B):
-            ops.ar_decode_serial(strings[0][b], gct, y_hat_all.batch(b, 1), params.batch(b, 1), chain["x1"], chain["pc"], chain["descs"],
-                                 chain["gp"], pos_table, M, W, table, idx, sym)
-        return {"x_hat": self.run_g_s(y_hat_all) if synth else None, "y_hat": y_hat_all}
+            lanes = order == "lanes"
+            classes = {}                                          # strings of one call that declare different lane counts: grouped by L
+            for b, s in enumerate(ys):
+                nl = ops.lanes_of(s) if lanes else 0
+                if lanes and (nl not in ops.LANE_COUNTS or M % nl):
+                    raise ValueError(f"the y stream declares {nl} lanes; the decoder takes {ops.LANE_COUNTS} dividing M = {M}")
+                classes.setdefault(nl, []).append(b)
+            for members in classes.values():
+                o = 0
+                for g in self._ar_groups(st["chain"]["descs"], len(members), int(st["sizes"].max())):
+                    self._decode_wavefront_group(members[o:o + g], ys, gct, table, y_hat_all, params, st, lanes)
+                    o += g
+            return {"x_hat": self._g_s(y_hat_all, per_image) if synth else None, "y_hat": y_hat_all}
+        # the per-position chain over staging buffers of one position per image; the loop itself runs natively
+        # (tdvc_ar_decode_serial / tdvc_ar_decode_serial_batch: Python drove it at ~230 us per position)
+        chain, pos_table = self._ar_serial(st)
+        sym = torch.zeros((B, H, W, M), dtype=torch.int32, device=dev)
+        idx = torch.zeros((B, H, W, M), dtype=torch.int32, device=dev)
+        b0 = 0
+        for g in self._ar_groups(chain["descs"], B, 1):
+            if g > 1:
+                ops.ar_decode_serial_batch(ys[b0:b0 + g], gct, y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
+                                           chain["gp"], pos_table, M, W, table, idx[b0:b0 + g], sym[b0:b0 + g])
+            else:
+                ops.ar_decode_serial(ys[b0], gct, y_hat_all.batch(b0, 1), params.batch(b0, 1), chain["x1"], chain["pc"], chain["descs"],
+                                     chain["gp"], pos_table, M, W, table, idx[b0], sym[b0])
+            b0 += g
+        return {"x_hat": self._g_s(y_hat_all, per_image) if synth else None, "y_hat": y_hat_all}
 
     def _ar_chain(self, cap, adt, dev):
         """the per-step chain as conv descriptors over staging buffers of `cap` positions: context conv (1x1 over the gathered
@@ -762,26 +846,39 @@ class Cheng2020Anchor(nn.Module, PackCache):
         e = self.entropy_parameters
         return [self._ctx_1x1(), pk_conv(self, "ep0", e[0]), pk_conv(self, "ep2", e[2]), pk_conv(self, "ep4", e[4])]
 
-    def _decode_wavefront(self, data, gct, table, y_hat, params, lanes=False):
-        """one image of a wavefront-ordered y stream (tdvc_ar_wavefront, decoder direction), or with `lanes` of a lane-split one
-        (tdvc_ar_wavefront_lanes: the string goes to the device once, the range decoder runs there)"""
-        dev, M = y_hat.t.device, self.M
-        H, W = y_hat.H, y_hat.W
-        steps = self.wavefront_steps(H, W)
-        flat = torch.tensor([p for st in steps for p in st], dtype=torch.int32, device=dev)
-        chain = self._ar_chain(H, y_hat.t.dtype, dev)
-        sym = torch.zeros((H * W, M), dtype=torch.int32, device=dev)          # wavefront order
-        idx = torch.zeros((H * W, M), dtype=torch.int32, device=dev)
-        sizes = np.array([len(st) for st in steps], dtype=np.int32)
+    def _decode_wavefront_group(self, members, ys, gct, table, y_hat_all, params, st, lanes):
+        """images `members` (indexes into the call's batch, one lane count) of wavefront-ordered y streams in one pass of the loop:
+        tdvc_ar_wavefront[_batch] (range decoder on the host) or with `lanes` tdvc_ar_wavefront_lanes[_batch] (the strings go to the
+        device once, the range decoder runs there).  One member: the single-image drivers."""
+        dev, M = y_hat_all.t.device, self.M
+        H, W, g = y_hat_all.H, y_hat_all.W, len(members)
+        flat, sizes, chain = st["flat"], st["sizes"], st["chain"]
+        data = [ys[b] for b in members]
+        if members == list(range(members[0], members[0] + g)):
+            yh, pr, scatter = y_hat_all.batch(members[0], g), params.batch(members[0], g), False
+        else:                                                         # e.g. mixed lane counts: the group's images are not neighbours
+            yh, pr, scatter = FM.zeros(g, H, W, M, dtype=y_hat_all.t.dtype, device=dev), FM(params.t[members].contiguous()), True
+        sym = torch.zeros((g, H * W, M), dtype=torch.int32, device=dev)          # wavefront order
+        idx = torch.zeros((g, H * W, M), dtype=torch.int32, device=dev)
+        args = (yh, pr, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, M, W, table, idx, sym)
         if lanes:
-            nl = ops.lanes_of(data)
-            if nl not in ops.LANE_COUNTS or M % nl:
-                raise ValueError(f"the y stream declares {nl} lanes; the decoder takes {ops.LANE_COUNTS} dividing M = {M}")
-            stream_dev = torch.empty((len(data) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
-            ops.ar_wavefront_lanes(data, gct, stream_dev, ops.ar_lanes_state(nl, dev), y_hat, params, chain["x1"], chain["pc"], chain["descs"],
-                                   chain["gp"], flat, sizes, M, W, table, idx, sym)
-            return
-        ops.ar_wavefront(data, gct, None, y_hat, params, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, M, W, table, idx, sym)
+            nl = ops.lanes_of(data[0])
+            if g > 1:
+                stream_dev = torch.empty(ops.ar_lanes_batch_layout([len(d) for d in data], nl)[0], dtype=torch.uint8, device=dev)
+                try:
+                    ops.ar_wavefront_lanes_batch(data, gct, stream_dev, ops.ar_lanes_state_batch(nl, g, dev), *args)
+                except ops.L.TdvcStreamError as e:
+                    raise ops.L.TdvcStreamError(f"decompress: image {members[e.image]} of the batch: corrupt or exhausted lane-split stream "
+                                                "(a lane ran out of words or met an impossible code)") from None
+            else:
+                stream_dev = torch.empty((len(data[0]) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+                ops.ar_wavefront_lanes(data[0], gct, stream_dev, ops.ar_lanes_state(nl, dev), *args)
+        elif g > 1:
+            ops.ar_wavefront_batch(data, gct, None, *args)
+        else:
+            ops.ar_wavefront(data[0], gct, None, *args)
+        if scatter:
+            y_hat_all.t[members] = yh.t
 
 def _g_a(N):
     return nn.Sequential(

@@ -175,6 +175,8 @@ class VideoCompressor(nn.Module):
         The reconstruction is the DECODER's: it is built from the coded symbols, so a closed-loop encoder and the decoder
         stay bit-identical."""
         assert not self.training
+        if refer_frames.shape[0] > 1:
+            return self._encode_batch(input_image, refer_frames)
         B, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames)
         x = input_image.float()
         f_cur = self.extra_fea.run(ops.from_nchw(x, Cpad=8), feats.ch(0, 64))
@@ -195,10 +197,67 @@ class VideoCompressor(nn.Module):
         mvs, rss = mv["strings"].result(), rs["strings"].result()                     # join the range coders
         return {"strings": [mvs[0], mvs[1], rss[0], rss[1]], "shapes": [mv["shape"], rs["shape"]], "recon": recon}
 
+    # ---- a batch of frames: the networks run image by image, each coder's context loop once for all images.  The forward conv
+    # dispatch counts pixels over the batch, so a layer can land on another kernel (other last bits) in a batch than alone; run this
+    # way, frame b's strings and reconstruction are those of a call with frame b alone, whatever the batch size (tools/predict
+    # --gop-batch writes the files of --gop-batch 1), and the loops -- launch-latency bound, the part a batch speeds up -- are shared
+    def _front(self, refer_frames, b, input_image=None):
+        _, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames[b:b + 1])
+        im = dict(H=H, W=W, dev=dev, refs8=refs8, iframe8=iframe8, feats=feats)
+        if input_image is not None:
+            x = input_image[b:b + 1].float()
+            im["f_cur"] = self.extra_fea.run(ops.from_nchw(x, Cpad=8), feats.ch(0, 64))
+            im["estmv"] = self.motion_est.run(feats, ops.from_nchw(x, Cpad=4, dtype=torch.float32), ops.from_nchw(last, Cpad=4, dtype=torch.float32))
+        return im
+
+    def _predict(self, im, mv_y_hat: FM) -> FM:
+        mv_hat = self.mvCoder.run_g_s(mv_y_hat)
+        xt = FM.empty(1, im["H"], im["W"], 256, device=im["dev"])
+        self.mcnet.run(mv_hat, im["feats"], xt.ch(192, 64))
+        pred = FM.empty(1, im["H"], im["W"], 64, device=im["dev"])
+        self.mcfilter.run(xt, im["refs8"], pred)
+        return pred
+
+    def _finish(self, im, res_y_hat: FM, pred: FM):
+        return self.loopfilter.run(self.resCoder.run_g_s(res_y_hat, res=pred), im["iframe8"], training=False)
+
+    @staticmethod
+    def _dense(fms) -> FM:
+        """images given as FMs of N = 1 -> one dense batch FM"""
+        return FM(torch.cat([f.t[..., f.off:f.off + f.C] if (f.off or f.C != f.t.shape[3]) else f.t for f in fms], 0).contiguous())
+
+    def _encode_batch(self, input_image, refer_frames):
+        B = refer_frames.shape[0]
+        ims = [self._front(refer_frames, b, input_image) for b in range(B)]
+        self.mvCoder.update()
+        self.resCoder.update()
+        kw = dict(f32=self.coder_fp32, order=self.stream_order, defer=True, lanes=self.stream_lanes, per_image=True)
+        mv = self.mvCoder.compress(self._dense([im["estmv"] for im in ims]), **kw)
+        preds = [self._predict(im, d["y_hat"]) for im, d in zip(ims, mv["_debug"])]
+        resid = [ops.scale_act_res(im["f_cur"], FM.empty(1, im["H"], im["W"], 64, device=im["dev"]), res=p, res_sign=-1.0) for im, p in zip(ims, preds)]
+        rs = self.resCoder.compress(self._dense(resid), **kw)
+        recon = torch.cat([self._finish(im, d["y_hat"], p) for im, d, p in zip(ims, rs["_debug"], preds)], 0)
+        mvs, rss = mv["strings"].result(), rs["strings"].result()                     # join the range coders
+        return {"strings": [mvs[0], mvs[1], rss[0], rss[1]], "shapes": [mv["shape"], rs["shape"]], "recon": recon}
+
+    def _decode_batch(self, strings, shapes, refer_frames):
+        B = refer_frames.shape[0]
+        ims = [self._front(refer_frames, b) for b in range(B)]
+        self.mvCoder.update()
+        self.resCoder.update()
+        kw = dict(synth=False, f32=self.coder_fp32, order=self.stream_order, per_image=True)
+        mv = self.mvCoder.decompress([strings[0], strings[1]], shapes[0], **kw)["y_hat"]
+        image = self.mvCoder._image
+        preds = [self._predict(im, image(mv, b)) for b, im in enumerate(ims)]
+        res = self.resCoder.decompress([strings[2], strings[3]], shapes[1], **kw)["y_hat"]
+        return torch.cat([self._finish(im, image(res, b), preds[b]) for b, im in enumerate(ims)], 0)
+
     @torch.no_grad()
     def decode(self, strings, shapes, refer_frames):
         """inverse of encode(): strings [mv_y, mv_z, res_y, res_z] + z shapes + the reference list -> (B,3,H,W)"""
         assert not self.training
+        if refer_frames.shape[0] > 1:
+            return self._decode_batch(strings, shapes, refer_frames)
         B, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames)
         self.mvCoder.update()
         self.resCoder.update()

@@ -1351,6 +1351,189 @@ def ar_wavefront_lanes(data: bytes, t: CdfTables, stream_dev: torch.Tensor, stat
             "ar_wavefront_lanes")
 
 
+# ---- the batched context loop (tdvc_ar_*_batch): a step's positions of all B images in the same launches.  y / y_hat / params are
+# FMs with N = B; row b * npos + k of x1 / pc / gp is position k of image b; symbols / indexes are [B][H][W][M] or [B][H * W][M].
+def ar_last_loop_launches() -> int:
+    """kernel enqueues of this thread's last context-loop call (`tdvc_ar_last_loop_launches`), conv launches included"""
+    return int(L.lib().tdvc_ar_last_loop_launches())
+
+
+def ar_chain_kernels(descs: list, rows: int) -> tuple:
+    """the kernels `tdvc_conv_select` names for the context loop's conv descriptors when a step has `rows` rows (None: rejected).
+    Host arithmetic on the descriptors alone: needs no device."""
+    out = []
+    for d0 in descs:
+        d = L.ConvDesc.from_buffer_copy(d0)
+        d.x.W = d.y.W = rows
+        name = L.lib().tdvc_conv_select(C.byref(d))
+        out.append(name.decode() if name else None)
+    return tuple(out)
+
+
+def ar_batch_ok(descs: list, g: int, nmax: int) -> bool:
+    """may `g` images share the launches of a context loop whose largest step has `nmax` positions?  A row's bits must not depend
+    on the row count (any encoder batch size decodes at any decoder batch size).  The kernels the chain runs on are row-count
+    independent each (conv_mfma_v9, conv_f32: a pixel is one MFMA column, the K split depends on the layer alone); the SELECTION
+    is not (conv_v9_eligible leaves v9 above LARGE_MAP_PIXELS pixels and, where v3 is eligible, above conv_v9_work_limit() pixels x
+    cout).  So: one and the same kernel per descriptor at 1 row, at the largest single-image step and at g times that."""
+    one = ar_chain_kernels(descs, 1)
+    return g == 1 or (None not in one and one == ar_chain_kernels(descs, nmax) == ar_chain_kernels(descs, g * nmax))
+
+
+def ar_batch_groups(descs: list, B: int, nmax: int) -> list:
+    """B images as the largest groups `ar_batch_ok` allows, in order -> the group sizes (they add up to B); 1 = the per-image loop"""
+    out, left = [], B
+    while left > 0:
+        g = next(g for g in range(left, 0, -1) if ar_batch_ok(descs, g, nmax))
+        out.append(g)
+        left -= g
+    return out
+
+
+def ar_gather_batch(y_hat: FM, params: FM, pos: torch.Tensor, npos: int, x1: FM, pc: FM):
+    assert pos.numel() >= 2 * npos
+    dy, dp, dx, dc = y_hat.desc(), params.desc(), x1.desc(), pc.desc()
+    L.check(L.lib().tdvc_ar_gather_batch(C.byref(dy), C.byref(dp), pos.data_ptr(), npos, C.byref(dx), C.byref(dc), _stream()), "ar_gather_batch")
+
+
+def _ar_rows_ok(a: torch.Tensor, y_hat: FM, cbase: int, npos: int) -> bool:
+    return a.dtype == torch.int32 and a.is_contiguous() and a.numel() >= y_hat.N * y_hat.H * y_hat.W * y_hat.C and cbase + npos <= y_hat.H * y_hat.W
+
+
+def ar_quantize_batch(y: FM | None, gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, y_hat: FM, symbols: torch.Tensor,
+                      indexes: torch.Tensor, symbols_in: torch.Tensor | None = None, cbase: int = -1):
+    """`cbase` < 0: the arrays are raster [B][H][W][M]; else compact [B][H * W][M], this call's position k at row cbase + k of a block"""
+    assert pos.numel() >= 2 * npos and all(_ar_rows_ok(a, y_hat, cbase, npos) for a in (symbols, indexes) + ((symbols_in,) if symbols_in is not None else ()))
+    dg, dh = gp.desc(), y_hat.desc()
+    dy = y.desc() if y is not None else None
+    L.check(L.lib().tdvc_ar_quantize_batch(C.byref(dy) if dy is not None else None, C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(),
+                                           symbols_in.data_ptr() if symbols_in is not None else None, C.byref(dh), symbols.data_ptr(), indexes.data_ptr(),
+                                           cbase, _stream()), "ar_quantize_batch")
+
+
+def ar_indexes_batch(gp: FM, pos: torch.Tensor, npos: int, B: int, table: torch.Tensor, M: int, H: int, W: int, indexes: torch.Tensor, cbase: int = -1):
+    assert pos.numel() >= 2 * npos and indexes.dtype == torch.int32 and indexes.numel() >= B * H * W * M and cbase + npos <= H * W
+    dg = gp.desc()
+    L.check(L.lib().tdvc_ar_indexes_batch(C.byref(dg), pos.data_ptr(), npos, B, table.data_ptr(), table.numel(), M, H, W, indexes.data_ptr(), cbase,
+                                          _stream()), "ar_indexes_batch")
+
+
+def _host_strings(strings):
+    """the B strings of a batched decoder call as the drivers take them: (keep-alive buffers, pointer array, size array)"""
+    bufs = [np.frombuffer(s, dtype=np.uint8) for s in strings]
+    ptrs = (C.c_void_p * len(bufs))(*[b.ctypes.data if b.size else None for b in bufs])
+    sizes = (C.c_int64 * len(bufs))(*[b.size for b in bufs])
+    return bufs, ptrs, sizes
+
+
+def ar_wavefront_batch(strings, t: CdfTables | None, y: FM | None, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM,
+                       pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
+    """the context loop of the B = y_hat.N images of a batch in one pass (`tdvc_ar_wavefront_batch`): encoder with `y` (idx / sym
+    raster [B][H][W][M]), decoder with `strings` (B byte strings) + `t` (idx / sym [B][H * W][M] in wavefront order)"""
+    B = y_hat.N
+    assert sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
+    assert strings is None or len(strings) == B
+    keep, ptrs, sizes = _host_strings(strings) if strings is not None else (None, None, None)
+    arr = (L.ConvDesc * len(descs))(*descs)
+    ss = np.ascontiguousarray(step_sizes, dtype=np.int32)
+    assert pos.numel() >= 2 * int(ss.sum())
+    dyh, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
+    dy = y.desc() if y is not None else None
+    L.check(L.lib().tdvc_ar_wavefront_batch(ptrs, sizes, B, t.cdf.ctypes.data if t else None, t.stride if t else 0, t.sizes.ctypes.data if t else None,
+                                            t.offsets.ctypes.data if t else None, C.byref(dy) if dy is not None else None, C.byref(dyh), C.byref(dp),
+                                            C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W,
+                                            scale_table.data_ptr(), scale_table.numel(), idx.data_ptr(), sym.data_ptr(), _stream()), "ar_wavefront_batch")
+
+
+def ar_decode_serial_batch(strings, t: CdfTables, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM, pos_table: torch.Tensor,
+                           M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
+    """the raster-order decoder over the B = y_hat.N images at once, B rows per position (`tdvc_ar_decode_serial_batch`);
+    idx / sym [B][H][W][M]"""
+    B = y_hat.N
+    assert len(strings) == B and sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
+    assert pos_table.shape[0] == y_hat.H * y_hat.W
+    keep, ptrs, sizes = _host_strings(strings)
+    arr = (L.ConvDesc * len(descs))(*descs)
+    dy, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
+    L.check(L.lib().tdvc_ar_decode_serial_batch(ptrs, sizes, B, t.cdf.ctypes.data, t.stride, t.sizes.ctypes.data, t.offsets.ctypes.data,
+                                                C.byref(dy), C.byref(dp), C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg),
+                                                pos_table.data_ptr(), pos_table.shape[0], M, W, scale_table.data_ptr(), scale_table.numel(),
+                                                idx.data_ptr(), sym.data_ptr(), _stream()), "ar_decode_serial_batch")
+
+
+def ar_lanes_batch_layout(sizes, lanes: int):
+    """-> (bytes of the device buffer that holds B lane-split containers behind their table, the table as uint32 [B][2] =
+    {byte offset, payload words}) (`tdvc_ar_lanes_batch_layout`)"""
+    n = (C.c_int64 * len(sizes))(*[int(v) for v in sizes])
+    table = np.zeros((len(sizes), 2), dtype=np.uint32)
+    total = int(L.lib().tdvc_ar_lanes_batch_layout(n, len(sizes), int(lanes), table.ctypes.data))
+    if total < 0:
+        L.check(total, "ar_lanes_batch_layout")
+    return total, table
+
+
+def ar_lanes_pack_batch(strings, lanes: int, device):
+    """the B containers packed as the batched lane kernels read them -> (device uint8 buffer: table | containers, table as numpy)"""
+    total, table = ar_lanes_batch_layout([len(s) for s in strings], lanes)
+    host = np.zeros(total, dtype=np.uint8)
+    host[:table.nbytes] = table.reshape(-1).view(np.uint8)
+    for (off, _), s in zip(table, strings):
+        host[off:off + len(s)] = np.frombuffer(s, dtype=np.uint8)
+    return torch.from_numpy(host).to(device), table
+
+
+def ar_lanes_state_batch(lanes: int, B: int, device) -> torch.Tensor:
+    """[B][lanes * 4 + 1] int32: per image the lane states and the sticky error word"""
+    return torch.zeros((B, int(L.lib().tdvc_ar_lanes_state_bytes(int(lanes))) // 4), dtype=torch.int32, device=device)
+
+
+def ar_lanes_init_batch(streams_dev: torch.Tensor, B: int, lanes: int, state: torch.Tensor) -> None:
+    """lane states of B containers from their length tables; `streams_dev` as `ar_lanes_pack_batch` lays it out (table at its head)"""
+    assert streams_dev.dtype == torch.uint8 and streams_dev.numel() >= 16 and state.numel() * 4 >= B * L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
+    L.check(L.lib().tdvc_ar_lanes_init_batch(streams_dev.data_ptr(), streams_dev.numel(), streams_dev.data_ptr(), B, int(lanes), state.data_ptr(), _stream()),
+            "ar_lanes_init_batch")
+
+
+def ar_decode_lanes_step_batch(gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, streams_dev: torch.Tensor, lanes: int, t: CdfTables,
+                               state: torch.Tensor, y_hat: FM, symbols: torch.Tensor, indexes: torch.Tensor, cbase: int) -> None:
+    """one step of the on-device decoder over B = y_hat.N lane-split streams (`tdvc_ar_decode_lanes_step_batch`), B workgroups"""
+    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
+    assert streams_dev.dtype == torch.uint8 and state.numel() * 4 >= y_hat.N * L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
+    assert pos.numel() >= 2 * npos and _ar_rows_ok(symbols, y_hat, cbase, npos) and _ar_rows_ok(indexes, y_hat, cbase, npos)
+    dg, dh = gp.desc(), y_hat.desc()
+    L.check(L.lib().tdvc_ar_decode_lanes_step_batch(C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(), streams_dev.data_ptr(),
+                                                    streams_dev.numel(), streams_dev.data_ptr(), int(lanes), cdf16.data_ptr(), cdf16.numel(), starts.data_ptr(),
+                                                    sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), state.data_ptr(), C.byref(dh), symbols.data_ptr(),
+                                                    indexes.data_ptr(), cbase, _stream()), "ar_decode_lanes_step_batch")
+
+
+def ar_wavefront_lanes_batch(strings, t: CdfTables, stream_dev: torch.Tensor, state: torch.Tensor, y_hat: FM, params: FM, x1: FM, pc: FM,
+                             descs: list, gp: FM, pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor,
+                             idx: torch.Tensor, sym: torch.Tensor) -> None:
+    """the decoder's context loop of B = y_hat.N lane-split streams of one lane count in one pass (`tdvc_ar_wavefront_lanes_batch`);
+    a damaged stream raises TdvcStreamError (a ValueError) whose `image` is the first image of the call whose error word is set"""
+    B = y_hat.N
+    lanes = lanes_of(strings[0])
+    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
+    assert len(strings) == B and stream_dev.dtype == torch.uint8 and state.numel() * 4 >= B * L.lib().tdvc_ar_lanes_state_bytes(lanes)
+    assert sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
+    keep, ptrs, nbytes = _host_strings(strings)
+    arr = (L.ConvDesc * len(descs))(*descs)
+    ss = np.ascontiguousarray(step_sizes, dtype=np.int32)
+    assert pos.numel() >= 2 * int(ss.sum())
+    dyh, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
+    bad = C.c_int32(-1)
+    rc = L.lib().tdvc_ar_wavefront_lanes_batch(ptrs, nbytes, B, stream_dev.data_ptr(), stream_dev.numel(), state.data_ptr(), cdf16.data_ptr(), cdf16.numel(),
+                                               starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), C.byref(dyh), C.byref(dp), C.byref(dx),
+                                               C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W, scale_table.data_ptr(),
+                                               scale_table.numel(), idx.data_ptr(), sym.data_ptr(), C.byref(bad), _stream())
+    if rc != 0 and bad.value >= 0:
+        e = L.TdvcStreamError(L.lib().tdvc_last_error().decode("utf-8", "replace"))
+        e.image = bad.value
+        raise e
+    L.check(rc, "ar_wavefront_lanes_batch")
+
+
 def ar_gather(y_hat: FM, params: FM, pos: torch.Tensor, npos: int, x1: FM, pc: FM):
     dy, dp, dx, dc = y_hat.desc(), params.desc(), x1.desc(), pc.desc()
     L.check(L.lib().tdvc_ar_gather(C.byref(dy), C.byref(dp), pos.data_ptr(), npos, C.byref(dx), C.byref(dc), _stream()), "ar_gather")

@@ -9,6 +9,7 @@ given by --pretrain), one process per GPU with GOPs sharded round-robin across r
 
   python -m tdvc_amd.tools.predict --gops 2 --height 1080 --width 1920
   python -m tdvc_amd.tools.predict --gops 1 --height 128 --width 192 --bitstream-dir /tmp/tdvc_bits     # real bitstreams
+  python -m tdvc_amd.tools.predict --gops 8 --height 480 --width 832 --bitstream-dir /tmp/tdvc_bits --stream-order lanes --gop-batch 4
   python -m torch.distributed.run --nproc-per-node 8 -m tdvc_amd.tools.predict --gops 16
 """
 from __future__ import annotations
@@ -42,48 +43,65 @@ def code_gop(net, frames: torch.Tensor, enable_amp: bool = True, bitstream_dir: 
     """frames: (T,3,h,w) on the GPU, frame 0 = I-frame reconstruction. Returns per-P-frame stats.
     With `bitstream_dir` every frame is really coded (`VideoCompressor.encode`), written as a container file in the
     record layout of tools/utils/encoder.py:61-68, read back and decoded; the decoder's frame must equal the encoder's."""
+    if bitstream_dir:
+        return code_gops(net, frames[None], bitstream_dir, [tag])[0]
     h, w = frames.shape[-2:]
     refs = [pad(frames[0:1], 64)]
     stats = []
     for t in range(1, frames.shape[0]):
         x = pad(frames[t:t + 1], 64)
-        if bitstream_dir:
-            from .. import bitstream
-            rl = ref_list(refs)
-            torch.cuda.synchronize()
-            t_e = time.time()
-            enc = net.encode(x, rl)
-            torch.cuda.synchronize()
-            t_e = time.time() - t_e
-            flat = [s[0] for s in enc["strings"]]
-            # first shape word: the reference writes the batch index (always 0); the y records of a wavefront-ordered
-            # stream carry 1 there, those of a lane-split stream 2, so that a reader cannot mistake them for compressai's raster order
-            wf = STREAM_ORDER_FLAGS[net.stream_order]
-            shp = [(wf if i % 2 == 0 else 0, 128, *enc["shapes"][i // 2]) for i in range(4)]
-            path = os.path.join(bitstream_dir, f"{tag}frame{t:03d}.bin")
-            with open(path, "wb") as f:
-                nbytes = bitstream.write_records(f, flat, shp)
-            with open(path, "rb") as f:
-                strings, shapes = bitstream.read_records(f, 4)
-            if shapes[0][0] != wf or shapes[2][0] != wf:
-                raise RuntimeError(f"{path}: stream order flag {shapes[0][0]} does not match the decoder's ({net.stream_order})")
-            t_d = time.time()
-            recon = net.decode([[s] for s in strings], [shapes[0][2:], shapes[2][2:]], rl)
-            torch.cuda.synchronize()
-            t_d = time.time() - t_d
-            assert torch.equal(recon, enc["recon"]), "decoder / encoder reconstruction mismatch"
-            refs.append(recon)
-            rc, xc = crop(recon, (h, w)), crop(x, (h, w))
-            bpp = 8.0 * nbytes / (x.shape[-2] * x.shape[-1])
-            stats.append({"frame": t, "psnr": psnr(rc, xc), "msssim": _msssim(rc, xc), "bpp": bpp, "bpp_mv": 8.0 * (len(flat[0]) + len(flat[1])) / (x.shape[-2] * x.shape[-1]),
-                          "bpp_res": 8.0 * (len(flat[2]) + len(flat[3])) / (x.shape[-2] * x.shape[-1]), "bytes": nbytes,
-                          "encode_s": t_e, "decode_s": t_d})
-            continue
         recon, bpp_res, bpp_mv = net(x, ref_list(refs), enable_amp)
         refs.append(recon)                                   # padded reconstruction re-enters the list (:68)
         rc, xc = crop(recon, (h, w)), crop(x, (h, w))
         stats.append({"frame": t, "psnr": psnr(rc, xc), "msssim": _msssim(rc, xc), "bpp": float(bpp_res + bpp_mv),
                       "bpp_mv": float(bpp_mv), "bpp_res": float(bpp_res)})
+    return stats
+
+
+def code_gops(net, frames: torch.Tensor, bitstream_dir: str, tags: list):
+    """Real coding of K GOPs in lockstep: frames (K,T,3,h,w) on the GPU, frame t of all K GOPs is one batch of K frames through
+    `VideoCompressor.encode` / `decode` (the coders' context loops then handle the K images in the same launches).  Every GOP gets
+    the files it gets alone -- `tags[k]` + frameNNN.bin, byte for byte -- and its own per-frame stats; the encode / decode times
+    of a frame are the batch's divided by K.  -> K lists of per-P-frame stats."""
+    from .. import bitstream
+    K, h, w = frames.shape[0], *frames.shape[-2:]
+    refs = [pad(frames[:, 0], 64)]
+    stats = [[] for _ in range(K)]
+    for t in range(1, frames.shape[1]):
+        x = pad(frames[:, t], 64)
+        rl = ref_list(refs)
+        torch.cuda.synchronize()
+        t_e = time.time()
+        enc = net.encode(x, rl)
+        torch.cuda.synchronize()
+        t_e = time.time() - t_e
+        # first shape word: the reference writes the batch index (always 0); the y records of a wavefront-ordered
+        # stream carry 1 there, those of a lane-split stream 2, so that a reader cannot mistake them for compressai's raster order
+        wf = STREAM_ORDER_FLAGS[net.stream_order]
+        shp = [(wf if i % 2 == 0 else 0, 128, *enc["shapes"][i // 2]) for i in range(4)]
+        flats, nbytes, read = [], [], []
+        for k in range(K):
+            flats.append([s[k] for s in enc["strings"]])
+            path = os.path.join(bitstream_dir, f"{tags[k]}frame{t:03d}.bin")
+            with open(path, "wb") as f:
+                nbytes.append(bitstream.write_records(f, flats[k], shp))
+            with open(path, "rb") as f:
+                strings, shapes = bitstream.read_records(f, 4)
+            if shapes[0][0] != wf or shapes[2][0] != wf:
+                raise RuntimeError(f"{path}: stream order flag {shapes[0][0]} does not match the decoder's ({net.stream_order})")
+            read.append(strings)
+        t_d = time.time()
+        recon = net.decode([[r[i] for r in read] for i in range(4)], [shapes[0][2:], shapes[2][2:]], rl)
+        torch.cuda.synchronize()
+        t_d = time.time() - t_d
+        assert torch.equal(recon, enc["recon"]), "decoder / encoder reconstruction mismatch"
+        refs.append(recon)
+        npx = x.shape[-2] * x.shape[-1]
+        for k in range(K):
+            rc, xc, flat = crop(recon[k:k + 1], (h, w)), crop(x[k:k + 1], (h, w)), flats[k]
+            stats[k].append({"frame": t, "psnr": psnr(rc, xc), "msssim": _msssim(rc, xc), "bpp": 8.0 * nbytes[k] / npx,
+                             "bpp_mv": 8.0 * (len(flat[0]) + len(flat[1])) / npx, "bpp_res": 8.0 * (len(flat[2]) + len(flat[3])) / npx,
+                             "bytes": nbytes[k], "encode_s": t_e / K, "decode_s": t_d / K})
     return stats
 
 
@@ -105,8 +123,12 @@ def main():
                     help="with --bitstream-dir: y-symbol order (raster = the reference's; wavefront = diagonal-parallel decoding; "
                          "lanes = wavefront order split over rANS sub-streams, range decoder on the GPU)")
     ap.add_argument("--stream-lanes", type=int, default=64, choices=(64, 128), help="with --stream-order lanes: sub-streams per y string")
+    ap.add_argument("--gop-batch", type=int, default=1, help="with --bitstream-dir: a rank codes this many GOPs of its shard in lockstep, frame t of all "
+                                                            "of them as one batch (same files and stats as 1; a last group smaller than this runs at its own size)")
     ap.add_argument("--coder-fp32", action="store_true", help="both coders as fp32 islands (the reference's precision), also with enable_amp: True")
     a = ap.parse_args()
+    if a.gop_batch < 1 or (a.gop_batch > 1 and not a.bitstream_dir):
+        ap.error("--gop-batch needs a value >= 1 and, above 1, --bitstream-dir (it batches the real coding)")
     opt = {"model": "pnet", "pretrain": a.pretrain, "val_dataset": "synthetic", "class": "-", "enable_amp": True}
     if a.cfg:
         opt.update(yaml.safe_load(open(a.cfg)))
@@ -137,6 +159,16 @@ def main():
         opt.update(val_dataset=a.val_dataset, **{"class": a.cls if a.val_dataset == "HEVC" else "-"})
         dataset = (data.HEVCDataSet(a.dataset_root, a.train_lambda, 10, a.cls, testfull=True, isTrain=False) if a.val_dataset == "HEVC" else
                    data.UVGDataSet(a.dataset_root, a.train_lambda, 12, testfull=True, isTrain=False))
+    pending = []                                         # (gop, frames) waiting to be coded in lockstep (--gop-batch)
+
+    def flush():
+        if pending:
+            for (g, _), gs in zip(pending, code_gops(net, torch.stack([f for _, f in pending]), a.bitstream_dir, [f"gop{g:03d}_" for g, _ in pending])):
+                for s in gs:
+                    s["gop"] = g
+                    stats.append(s)
+            pending.clear()
+
     with torch.no_grad():
         for g in shard_gops(len(dataset) if dataset is not None else a.gops, world, rank):
             if dataset is not None:
@@ -149,9 +181,16 @@ def main():
                 frames = make_gop(2000 + g, a.gop_size, a.height, a.width).to(dev)
             if a.bitstream_dir:
                 os.makedirs(a.bitstream_dir, exist_ok=True)
-            for s in code_gop(net, frames, bool(opt["enable_amp"]), a.bitstream_dir, f"gop{g:03d}_"):
+                if pending and pending[0][1].shape != frames.shape:
+                    flush()                                  # only GOPs of one length and size run in lockstep
+                pending.append((g, frames))
+                if len(pending) == a.gop_batch:
+                    flush()
+                continue
+            for s in code_gop(net, frames, bool(opt["enable_amp"])):
                 s["gop"] = g
                 stats.append(s)
+        flush()
     torch.cuda.synchronize()
     allstats = gather_frame_stats(stats)
     if rank == 0:
