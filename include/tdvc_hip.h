@@ -158,7 +158,7 @@ const char* tdvc_conv_select(const tdvc_conv_desc* d);
 /* The fp32 islands: main/model/pnet.py:33-49,57-73 run both coders with autocast OFF (and enabled_amp=False runs the
  * whole model fp32).  Same descriptor with an fp32 input fmap (C %% 8 == 0) and `w` = the fp32 packing below; fp32
  * accumulation on v_mfma_f32_32x32x2_f32; aux / residual / output fmaps fp32 or fp16.  tdvc_conv2d forwards here
- * when d->x.dtype == TDVC_F32, so fixed descriptor chains (tdvc_ar_decode_serial) run in either precision. */
+ * when d->x.dtype == TDVC_F32, so fixed descriptor chains (tdvc_ar_decode_serial_batch) run in either precision. */
 int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream);
 
 /* ---------------------------------------------------------------- fused conv pair
@@ -322,7 +322,7 @@ void tdvc_rans_decoder_destroy(void* handle);
  * image, given as [npos][M] in wavefront order, are split over L independent sub-streams ("lanes"), symbol c of a position
  * going to lane c % L.  Container: 4 bytes {'L', 1, L, 0}, L little-endian uint16 sub-stream lengths in 32-bit words, then
  * the L sub-streams, lane l's being exactly what tdvc_rans_encode emits for lane l's symbols in that order.  L must divide
- * M; the host entry points take 1 <= L <= 255, the device decoder (tdvc_ar_decode_lanes_step) 64 or 128.
+ * M; the host entry points take 1 <= L <= 255, the device decoder (tdvc_ar_decode_lanes_step_batch) 64 or 128.
  * encode: -> bytes written or < 0 (a lane of more than 65 535 words included).  decode: the reference decoder, over the
  * decode routine the device kernel uses (csrc/rans_lane.h); validates the header and the length table against nbytes. */
 int64_t tdvc_rans_encode_lanes(const int32_t* symbols, const int32_t* indexes, int64_t npos, int M, int L,
@@ -336,118 +336,84 @@ int tdvc_rans_decode_lanes(const uint8_t* data, int64_t nbytes, const int32_t* i
  * main/model/pnet.py:47,71): pmf[n] -> quantised cdf[n+1] at `precision` bits, every bin >= 1. Host code. */
 int tdvc_pmf_to_quantized_cdf(const float* pmf, int n, int precision, int32_t* cdf_out);
 
-/* ---------------------------------------------------------------- autoregressive context model (compress)
+/* ---------------------------------------------------------------- autoregressive context model: the context loop
  * `_compress_ar` / `_decompress_ar` of compressai's JointAutoregressiveHierarchicalPriors, called from
  * main/model/pnet.py:48,72.  Position (h, w) depends on rows h-2..h within +-2 columns, so positions
  * with equal w + 3h are independent: the encoder walks W + 3(H-1) anti-diagonal steps, each step a
  * batch of <= H positions whose 12-tap neighbourhoods are gathered into a dense matrix
- * (tdvc_ar_gather), pushed through the context conv and entropy_parameters as 1x1 MFMA convs, then
- * quantised and written back (tdvc_ar_quantize).
- * pos: int32 [npos][2] = (h, w) on the device.  y_hat: fp16 fmap (H, W, M), zero-initialised.
- * params: fp16 fmap (H, W, 2M) (h_s output).  x1: fp16 fmap (1, 1, npos, 12*M) neighbourhoods in tap-major
- * order; pc: fp16 fmap (1, 1, npos, 4M): channels [0, 2M) receive params of the positions. */
-int tdvc_ar_gather(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int npos,
-                   const tdvc_fmap* x1, const tdvc_fmap* pc, void* stream);
-/* gp: fp32 fmap (1, 1, npos, 2M) [scales | means].  Encoder (symbols_in == NULL): q = round(y - mean);
- * decoder: q = symbols_in[h][w][c].  Writes y_hat[h][w][c] = q + mean, symbols[h][w][c] = q (int32,
- * [H][W][M]) and indexes[h][w][c] = #{table entries < max(scale, 0.11)} clipped to ntable-1
- * (GaussianConditional.build_indexes).  scale_table: ntable floats. */
-int tdvc_ar_quantize(const tdvc_fmap* y, const tdvc_fmap* gp, const int32_t* pos, int npos,
-                     const float* scale_table, int ntable, const int32_t* symbols_in,
-                     const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, void* stream);
-/* indexes only (decoder: needed before the symbols can be read from the stream). */
-int tdvc_ar_indexes(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
-                    int M, int W, int32_t* indexes, void* stream);
-/* The decoder's whole context loop for ONE image, natively: positions pos_table[0 .. npos_total) in raster (stream)
- * order, per position tdvc_ar_gather -> convs[0 .. nconvs) (the caller's descriptors: context conv over x1 into pc,
- * entropy_parameters into gp; fixed buffers) -> tdvc_ar_indexes -> host range decoder on `data` (tables as in
- * tdvc_rans_decode, HOST memory) -> tdvc_ar_quantize.  idx_dev / sym_dev: device int32 [H][W][M]; y_hat is filled.
- * Synchronises the stream once per position (the stream order of compressai's bitstream leaves no other choice). */
-int tdvc_ar_decode_serial(const uint8_t* data, int64_t nbytes, const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
-                          const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
-                          const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                          const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
-                          int32_t* idx_dev, int32_t* sym_dev, void* stream);
-/* The context loop of ONE image over anti-diagonals (wavefront order), natively, in either direction.  pos_dev: device
- * int32 [H*W][2] in wavefront order, step s owning step_sizes[s] (HOST array) consecutive entries; x1 / pc / gp and the
- * conv descriptors' x / y maps are (1, 1, >= max step, C) staging buffers whose width is set to the step's size per step.
- * Encoder (y != NULL, data == NULL; replaces `_compress_ar`'s position loop, main/model/pnet.py:48,72): gather -> convs ->
- * tdvc_ar_quantize per step; sym_dev / idx_dev are raster [H][W][M]; nothing synchronises.
- * Decoder (data != NULL, y == NULL) of a stream whose symbols were emitted in wavefront order (an extension: the
- * reference's streams are raster-ordered, tdvc_ar_decode_serial reads those): gather -> convs -> indexes -> host range
- * decoder -> quantise, one stream synchronisation per step; sym_dev / idx_dev are [H*W][M] in wavefront order. */
-int tdvc_ar_wavefront(const uint8_t* data, int64_t nbytes, const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
-                      const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat, const tdvc_fmap* params,
-                      const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                      const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
-                      const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
-/* Device decoder of a lane-split stream (tdvc_rans_encode_lanes).  stream_dev: the whole container in DEVICE memory
- * (4-byte aligned, nbytes long); state_dev: device buffer of tdvc_ar_lanes_state_bytes(L) bytes holding the L lane states
- * and one sticky error word (its last uint32), which is the only error channel: a damaged stream is flagged, every read
- * stays inside the payload.  The tables of tdvc_rans_decode in DEVICE memory, packed: cdf16_dev holds every table's entries end
- * to end as uint16 (the last entry of a table, 1 << 16, wraps to 0 and is implied), n16 entries in all (16-byte aligned, padded
- * to a multiple of 8); table t = cdf_sizes_dev[t] entries from cdf_starts_dev[t]; offsets_dev[t]; ncdfs >= ntable tables.  The
- * kernel keeps the first 27 648 entries in LDS (compressai's 64 Gaussian tables have 27 256).
- * tdvc_ar_lanes_init: lane states from the container's length table (and error word = 0).
- * tdvc_ar_decode_lanes_step: one step of npos positions: one workgroup of L threads, thread l decoding the symbols (k, c),
- * c % L == l, in stream order; does what tdvc_ar_indexes + the range decoder + tdvc_ar_quantize do: indexes / symbols at the
- * compact rows cbase + k of [..][M] arrays, y_hat(h, w, c) = q + mean in y_hat's dtype.  Lane states carry over in state_dev. */
-int64_t tdvc_ar_lanes_state_bytes(int L);
-int tdvc_ar_lanes_init(const uint8_t* stream_dev, int64_t nbytes, int L, uint32_t* state_dev, void* stream);
-int tdvc_ar_decode_lanes_step(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
-                              const uint8_t* stream_dev, int64_t nbytes, int L, const uint16_t* cdf16_dev, int32_t n16,
-                              const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs,
-                              uint32_t* state_dev,
-                              const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream);
-/* tdvc_ar_wavefront's decoder direction for a lane-split stream: `data` (HOST memory) is validated and uploaded once into
- * stream_dev (>= nbytes of stream_cap bytes), then per step gather -> convs -> tdvc_ar_decode_lanes_step with no
- * synchronisation; after the last step the error word is read back with the call's only stream wait, TDVC_EINVAL if it is
- * set.  Allocates nothing.  sym_dev / idx_dev are [H*W][M] in wavefront order. */
-int tdvc_ar_wavefront_lanes(const uint8_t* data, int64_t nbytes, uint8_t* stream_dev, int64_t stream_cap, uint32_t* state_dev,
-                            const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
-                            const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
-                            const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                            const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
-                            const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
-/* ---------------------------------------------------------------- batched context loop (ABI 9)
- * The loops above are chains of dependent tiny launches (at 1080p 321 steps per coder, at most 40 positions each): a step costs
- * its launches, not its arithmetic.  The images of a batch share the position list, the weights and the CDF tables and nothing in
- * a step couples one image to another, so the *_batch forms handle a step's positions of all B images in the SAME launches.
+ * (tdvc_ar_gather_batch), pushed through the context conv and entropy_parameters as 1x1 MFMA convs, then
+ * quantised and written back (tdvc_ar_quantize_batch).
+ * The loop is a chain of dependent tiny launches (at 1080p 321 steps per coder, at most 40 positions each): a step costs its
+ * launches, not its arithmetic.  The images of a batch share the position list, the weights and the CDF tables and nothing in a
+ * step couples one image to another, so every entry point handles a step's positions of all B images of the call in the SAME
+ * launches.  A single image is B = y_hat->N = 1 and there is no other form: ABI 10 removed the single-image entry points of ABI <= 9
+ * (tdvc_ar_gather, tdvc_ar_quantize, tdvc_ar_indexes, tdvc_ar_lanes_init, tdvc_ar_decode_lanes_step, tdvc_ar_decode_serial,
+ * tdvc_ar_wavefront, tdvc_ar_wavefront_lanes); the *_batch entry points are those of ABI 9, unchanged.
  * Layout: y / y_hat / params are fmaps with N = B (their sn / sp strides are honoured: batch views and channel windows of larger
- * buffers work); `pos` is the shared position list, one (h, w) per k; row b * npos + k (image-major) of the staging maps x1 / pc /
- * gp belongs to position k of image b, so a step is a (1, B * npos) map to the convs; the raster arrays are [B][H][W][M], the
- * compact ones [B][H * W][M] with row cbase + k inside image b's block (cbase < 0 selects the raster form).  Rounding, the scale
- * index and the symbols_in form are those of the single-image entry points; a row's bits do not depend on the row count as long
- * as tdvc_conv_select names the same kernel for the chain's descriptors (conv_mfma_v9 and conv_f32 compute a pixel as one MFMA
- * column with a K split that depends on the layer alone), so the result is byte for byte the per-image loop's. */
+ * buffers work); `pos` is the shared position list, int32 [npos][2] = (h, w) on the device; row b * npos + k (image-major) of the
+ * staging maps x1 / pc / gp belongs to position k of image b, so a step is a (1, B * npos) map to the convs; the raster arrays are
+ * [B][H][W][M], the compact ones [B][H * W][M] with row cbase + k inside image b's block (cbase < 0 selects the raster form).  A
+ * row's bits do not depend on the row count as long as tdvc_conv_select names the same kernel for the chain's descriptors
+ * (conv_mfma_v9 and conv_f32 compute a pixel as one MFMA column with a K split that depends on the layer alone), so a batch's
+ * result is byte for byte that of B calls of one image.
+ * tdvc_ar_gather_batch.  y_hat: fp16 (or, fp32 islands, fp32) fmap (B, H, W, M); only causal -- already written -- neighbours are
+ * read.  params: fmap (B, H, W, 2M) of y_hat's dtype (h_s output).  x1: fmap (1, 1, >= B * npos, 12*M), neighbourhoods in tap-major
+ * order, zeros outside the image; pc: fmap (1, 1, >= B * npos, 4M): channels [0, 2M) receive params of the positions. */
 int tdvc_ar_gather_batch(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int npos,
                          const tdvc_fmap* x1, const tdvc_fmap* pc, void* stream);
+/* gp: fp32 fmap (1, 1, >= B * npos, 2M) [scales | means].  Encoder (symbols_in == NULL): q = round(y - mean), y an fp32 fmap of
+ * y_hat's batch and geometry; decoder: q = symbols_in[..][c].  Writes y_hat[b][h][w][c] = q + mean, symbols = q (int32) and
+ * indexes = #{table entries < max(scale, 0.11)} clipped to ntable-1 (GaussianConditional.build_indexes) at the raster or compact
+ * place of the position.  scale_table: ntable floats. */
 int tdvc_ar_quantize_batch(const tdvc_fmap* y, const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
                            const int32_t* symbols_in, const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream);
+/* indexes only (decoder: needed before the symbols can be read from the stream). */
 int tdvc_ar_indexes_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, int B, const float* scale_table, int ntable,
                           int M, int H, int W, int32_t* indexes, int64_t cbase, void* stream);
-/* tdvc_ar_wavefront over B images.  data / nbytes: HOST arrays of the B strings and their sizes (decoder) or NULL (encoder, y
- * given).  Encoder: nothing but enqueues.  Decoder, per step: one device->host copy of the B * n * M indexes, the B host range
- * decoders in turn, one host->device copy, the batched quantiser.  Every check -- arguments, sizes, B * n against the staging
- * width, the steps covering H * W -- is made before anything touches a device. */
+/* The context loop over anti-diagonals (wavefront order), natively, in either direction.  pos_dev: device int32 [H*W][2] in
+ * wavefront order, step s owning step_sizes[s] (HOST array) consecutive entries; x1 / pc / gp and the conv descriptors' x / y maps
+ * (convs[0 .. nconvs): context conv over x1 into pc, entropy_parameters into gp; fixed buffers) are (1, 1, >= B * max step, C)
+ * staging buffers whose width is set to the step's B * n rows per step.  data / nbytes: HOST arrays of the B strings and their
+ * sizes (decoder) or NULL (encoder, y given).
+ * Encoder (replaces `_compress_ar`'s position loop, main/model/pnet.py:48,72): gather -> convs -> quantise per step; sym_dev /
+ * idx_dev are raster [B][H][W][M]; nothing but enqueues, nothing synchronises.
+ * Decoder of streams whose symbols were emitted in wavefront order (an extension: the reference's streams are raster-ordered,
+ * tdvc_ar_decode_serial_batch reads those), per step: gather -> convs -> indexes -> one device->host copy of the B * n * M indexes,
+ * the B host range decoders in turn (tables as in tdvc_rans_decode, HOST memory), one host->device copy -> quantise; one stream
+ * synchronisation per step; sym_dev / idx_dev are [B][H*W][M] in wavefront order.
+ * Every check -- arguments, sizes, B * n against the staging width, the steps covering H * W -- is made before anything touches a
+ * device. */
 int tdvc_ar_wavefront_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
                             const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat,
                             const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
                             const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
                             const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
-/* tdvc_ar_decode_serial over B images: position by position in raster order, B rows per step; npos_total must be H * W. */
+/* The decoder's whole context loop for raster-ordered streams (compressai's bitstream), natively: positions pos_table[0 ..
+ * npos_total), npos_total = H * W, in raster order, B rows per step: gather -> convs -> indexes -> host range decoders -> quantise.
+ * idx_dev / sym_dev: device int32 [B][H][W][M]; y_hat is filled.  Synchronises the stream once per position (the stream order of
+ * compressai's bitstream leaves no other choice). */
 int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
                                 const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params,
                                 const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
                                 const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
                                 int32_t* idx_dev, int32_t* sym_dev, void* stream);
-/* B lane-split streams of ONE lane count L in one device buffer: a table uint32 [B][2] = {byte offset of container b, 32-bit words
- * of its payload}, padded to 16 bytes, then the containers at 16-byte aligned offsets.  tdvc_ar_lanes_batch_layout: -> the bytes
- * the buffer needs (or < 0) and, when table_out is not NULL, the table (HOST memory, 2 * B words).  The kernels take the buffer
- * (16-byte aligned, stream_bytes long) and the table in DEVICE memory (an ordinary copy puts it there); a table entry that does
- * not lie inside the buffer gives its image no words: flagged, never read.  state_dev: [B][L * 4 + 1] words, i.e. B blocks of
- * tdvc_ar_lanes_state_bytes(L), one sticky error word per image.  The kernels run B workgroups of L threads, workgroup b doing on
- * image b exactly what the single-image kernels do; no atomics, no spinning, nothing persistent. */
+/* Device decoder of lane-split streams (tdvc_rans_encode_lanes).  B containers of ONE lane count L in one device buffer: a table
+ * uint32 [B][2] = {byte offset of container b, 32-bit words of its payload}, padded to 16 bytes, then the containers at 16-byte
+ * aligned offsets.  tdvc_ar_lanes_batch_layout: -> the bytes the buffer needs (or < 0) and, when table_out is not NULL, the table
+ * (HOST memory, 2 * B words).  The kernels take the buffer (16-byte aligned, stream_bytes long) and the table in DEVICE memory (an
+ * ordinary copy puts it there); a table entry that does not lie inside the buffer gives its image no words: flagged, never read.
+ * state_dev: [B][L * 4 + 1] words, i.e. B blocks of tdvc_ar_lanes_state_bytes(L) holding the L lane states and one sticky error
+ * word (the block's last uint32), which is the only error channel: a damaged stream is flagged, every read stays inside the
+ * payload.  The tables of tdvc_rans_decode in DEVICE memory, packed: cdf16_dev holds every table's entries end to end as uint16
+ * (the last entry of a table, 1 << 16, wraps to 0 and is implied), n16 entries in all (16-byte aligned, padded to a multiple of
+ * 8); table t = cdf_sizes_dev[t] entries from cdf_starts_dev[t]; offsets_dev[t]; ncdfs >= ntable tables.  The kernel keeps the
+ * first 27 648 entries in LDS (compressai's 64 Gaussian tables have 27 256).
+ * tdvc_ar_lanes_init_batch: lane states from the containers' length tables (and error words = 0).
+ * tdvc_ar_decode_lanes_step_batch: one step of npos positions: B workgroups of L threads, thread l of workgroup b decoding the
+ * symbols (k, c) of image b, c % L == l, in stream order; does what tdvc_ar_indexes_batch + the range decoder +
+ * tdvc_ar_quantize_batch do: indexes / symbols at the compact rows cbase + k, y_hat(b, h, w, c) = q + mean in y_hat's dtype.  Lane
+ * states carry over in state_dev.  No atomics, no spinning, nothing persistent. */
+int64_t tdvc_ar_lanes_state_bytes(int L);
 int64_t tdvc_ar_lanes_batch_layout(const int64_t* nbytes, int B, int L, uint32_t* table_out);
 int tdvc_ar_lanes_init_batch(const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int B, int L, uint32_t* state_dev, void* stream);
 int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
@@ -455,19 +421,21 @@ int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_t* pos, int
                                     const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
                                     const int32_t* offsets_dev, int32_t ncdfs, uint32_t* state_dev, const tdvc_fmap* y_hat,
                                     int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream);
-/* tdvc_ar_wavefront_lanes over B images: the B strings (HOST memory) are validated -- all of one lane count -- and uploaded with
- * their table in one copy into stream_dev (stream_cap >= tdvc_ar_lanes_batch_layout() bytes), then batched init and per step
- * gather -> convs -> the batched lane decoder; one stream wait.  TDVC_EINVAL when an image's error word is set: the message and
- * *bad_image (may be NULL; -1 otherwise) name the FIRST such image. */
+/* tdvc_ar_wavefront_batch's decoder direction for lane-split streams: the B strings (HOST memory) are validated -- all of one
+ * lane count -- and uploaded behind their table, B + 1 copies, into stream_dev (stream_cap >= tdvc_ar_lanes_batch_layout() bytes),
+ * then tdvc_ar_lanes_init_batch and per step gather -> convs -> tdvc_ar_decode_lanes_step_batch with no synchronisation; after the
+ * last step the error words are read back with the call's only stream wait.  TDVC_EINVAL when an image's error word is set: the
+ * message and *bad_image (may be NULL; -1 otherwise) name the FIRST such image.  sym_dev / idx_dev are [B][H*W][M] in wavefront
+ * order.  Allocates nothing. */
 int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nbytes, int B, uint8_t* stream_dev, int64_t stream_cap,
                                   uint32_t* state_dev, const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev,
                                   const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat,
                                   const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
                                   const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
                                   const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, int32_t* bad_image, void* stream);
-/* Kernel enqueues of the last context-loop call on this thread (tdvc_ar_decode_serial, tdvc_ar_wavefront, tdvc_ar_wavefront_lanes
- * and their *_batch forms), conv launches included: the launches the library's entry points closed during the call.  Copies are
- * not counted.  A batched call over B images reports what the single-image call on the same grid reports. */
+/* Kernel enqueues of the last context-loop call on this thread (tdvc_ar_decode_serial_batch, tdvc_ar_wavefront_batch,
+ * tdvc_ar_wavefront_lanes_batch), conv launches included: the launches the library's entry points closed during the call.  Copies
+ * are not counted.  The count does not depend on B. */
 int64_t tdvc_ar_last_loop_launches(void);
 /* q[n][h][w][c] = round(z - median[c]) as int32 in the fmap's own order (factorised-prior symbols). */
 int tdvc_round_symbols(const tdvc_fmap* z, const float* median, int32_t* out, void* stream);

@@ -102,13 +102,7 @@ SIGNATURES = {
     "tdvc_eb_aux": (_i, [_P, _P, _f, _P, _P, _i, _P]),
     "tdvc_gc_backward": (_i, [_FM, _FM, _FM, _f, _FM, _FM, _P]),
     "tdvc_dcn_columns": (_i, [_FM, _FM, _i, _FM, _P]),
-    "tdvc_ar_decode_serial": (_i, [_P, _i64, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
-    "tdvc_ar_wavefront": (_i, [_P, _i64, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
     "tdvc_ar_lanes_state_bytes": (_i64, [_i]),
-    "tdvc_ar_lanes_init": (_i, [_P, _i64, _i, _P, _P]),
-    "tdvc_ar_decode_lanes_step": (_i, [_FM, _P, _i, _P, _i, _P, _i64, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _FM, _P, _P, _i64, _P]),
-    "tdvc_ar_wavefront_lanes": (_i, [_P, _i64, _P, _i64, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i,
-                                     _P, _i, _P, _P, _P]),
     "tdvc_ar_gather_batch": (_i, [_FM, _FM, _P, _i, _FM, _FM, _P]),
     "tdvc_ar_quantize_batch": (_i, [_FM, _FM, _P, _i, _P, _i, _P, _FM, _P, _P, _i64, _P]),
     "tdvc_ar_indexes_batch": (_i, [_FM, _P, _i, _i, _P, _i, _i, _i, _i, _P, _i64, _P]),
@@ -169,9 +163,6 @@ SIGNATURES = {
     "tdvc_rans_decoder_decode": (_i, [_P, _P, _i64, _P, C.c_int32, _P, _P, _P]),
     "tdvc_rans_decoder_destroy": (None, [_P]),
     "tdvc_pmf_to_quantized_cdf": (_i, [_P, _i, _i, _P]),
-    "tdvc_ar_gather": (_i, [_FM, _FM, _P, _i, _FM, _FM, _P]),
-    "tdvc_ar_quantize": (_i, [_FM, _FM, _P, _i, _P, _i, _P, _FM, _P, _P, _P]),
-    "tdvc_ar_indexes": (_i, [_FM, _P, _i, _P, _i, _i, _i, _P, _P]),
     "tdvc_round_symbols": (_i, [_FM, _P, _P, _P]),
 }
 

@@ -11,67 +11,11 @@ namespace {
 __constant__ int8_t kTapDy[12] = {-2, -2, -2, -2, -2, -1, -1, -1, -1, -1, 0, 0};
 __constant__ int8_t kTapDx[12] = {-2, -1, 0, 1, 2, -2, -1, 0, 1, 2, -2, -1};
 
-// T = half_t (default coders) or float (fp32 islands); VT = the 16-byte vector of T (8 halves / 4 floats)
-template <typename T, typename VT>
-__global__ void ar_gather_kernel(FMap yh, FMap pr, const int32_t* pos, int npos, FMap x1, FMap pc) {
-  constexpr int VE = 16 / sizeof(T);              // elements per 16-byte chunk
-  const int MV = yh.C / VE;                       // 16-byte chunks per position
-  const int per = 12 * MV + pr.C / VE;            // chunks to move per position
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)npos * per) return;
-  const int k = (int)(i / per), u = (int)(i % per);
-  const int h = pos[2 * k], w = pos[2 * k + 1];
-  if (u < 12 * MV) {
-    const int t = u / MV, cv = u % MV;
-    const int yy = h + kTapDy[t], xx = w + kTapDx[t];
-    VT v;
-#pragma unroll
-    for (int j = 0; j < VE; ++j) v[j] = (T)0.f;
-    if (yy >= 0 && xx >= 0 && xx < yh.W)
-      v = *reinterpret_cast<const VT*>(reinterpret_cast<const T*>(yh.p) + ((long)yy * yh.W + xx) * yh.sp + cv * VE);
-    *reinterpret_cast<VT*>(reinterpret_cast<T*>(x1.p) + (long)k * x1.sp + (t * MV + cv) * VE) = v;
-  } else {
-    const int cv = u - 12 * MV;
-    const VT v = *reinterpret_cast<const VT*>(reinterpret_cast<const T*>(pr.p) + ((long)h * pr.W + w) * pr.sp + cv * VE);
-    *reinterpret_cast<VT*>(reinterpret_cast<T*>(pc.p) + (long)k * pc.sp + cv * VE) = v;
-  }
-}
-
 __device__ __forceinline__ int scale_index(float s, const float* table, int n) {
   s = fmaxf(s, 0.11f);
   int idx = n - 1;
   for (int j = 0; j < n - 1; ++j) idx -= (s <= table[j]) ? 1 : 0;
   return idx;
-}
-
-__global__ void ar_quantize_kernel(FMap y, FMap gp, const int32_t* pos, int npos, const float* table, int ntable,
-                                   const int32_t* sym_in, FMap yh, int32_t* sym, int32_t* idx, long cbase) {
-  // cbase < 0: sym_in / sym / idx are raster arrays [H][W][M]; cbase >= 0: they are compact arrays in the order of the
-  // position list, this launch's position k at row cbase + k (the wavefront-ordered decoder)
-  const int M = y.C;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)npos * M) return;
-  const int k = (int)(i / M), c = (int)(i % M);
-  const int h = pos[2 * k], w = pos[2 * k + 1];
-  const float* g = reinterpret_cast<const float*>(gp.p) + (long)k * gp.sp;
-  const float scale = g[c], mean = g[M + c];
-  const long o = (cbase >= 0 ? cbase + k : (long)h * y.W + w) * M + c;
-  int q;
-  if (sym_in) q = sym_in[o];
-  else q = (int)rintf(reinterpret_cast<const float*>(y.p)[((long)h * y.W + w) * y.sp + c] - mean);
-  if (yh.f32) reinterpret_cast<float*>(yh.p)[((long)h * yh.W + w) * yh.sp + c] = (float)q + mean;
-  else reinterpret_cast<half_t*>(yh.p)[((long)h * yh.W + w) * yh.sp + c] = (half_t)((float)q + mean);
-  sym[o] = q;
-  idx[o] = scale_index(scale, table, ntable);
-}
-
-__global__ void ar_indexes_kernel(FMap gp, const int32_t* pos, int npos, const float* table, int ntable, int M, int W, int32_t* idx, long cbase) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)npos * M) return;
-  const int k = (int)(i / M), c = (int)(i % M);
-  const int h = pos[2 * k], w = pos[2 * k + 1];
-  const float* g = reinterpret_cast<const float*>(gp.p) + (long)k * gp.sp;
-  idx[(cbase >= 0 ? cbase + k : (long)h * W + w) * M + c] = scale_index(g[c], table, ntable);
 }
 
 __global__ void round_symbols_kernel(FMap z, const float* median, int32_t* out) {
@@ -85,14 +29,15 @@ __global__ void round_symbols_kernel(FMap z, const float* median, int32_t* out) 
   out[i] = (int)rintf(reinterpret_cast<const float*>(z.p)[(long)n * z.sn + pix * z.sp + c] - median[c]);
 }
 
-// ---- the same three kernels over the step's positions of B images at once (the batched context loop).  The images share the
+// ---- a step's positions of the B = y_hat.N images of a call in one launch (a single image is B = 1).  The images share the
 // position list; row b * npos + k of the staging maps x1 / pc / gp belongs to position k of image b (image-major), so a step is a
 // (1, B * npos) map to the convs.  y / y_hat / params are fmaps with N = B, addressed through their own batch and pixel strides.
+// T = half_t (default coders) or float (fp32 islands); VT = the 16-byte vector of T (8 halves / 4 floats)
 template <typename T, typename VT>
 __global__ void ar_gather_batch_kernel(FMap yh, FMap pr, const int32_t* pos, int npos, FMap x1, FMap pc) {
-  constexpr int VE = 16 / sizeof(T);
-  const int MV = yh.C / VE;
-  const int per = 12 * MV + pr.C / VE;
+  constexpr int VE = 16 / sizeof(T);              // elements per 16-byte chunk
+  const int MV = yh.C / VE;                       // 16-byte chunks per position
+  const int per = 12 * MV + pr.C / VE;            // chunks to move per position
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)yh.N * npos * per) return;
   const long row = i / per;
@@ -115,7 +60,8 @@ __global__ void ar_gather_batch_kernel(FMap yh, FMap pr, const int32_t* pos, int
   }
 }
 
-// sym_in / sym / idx: [B][H][W][M] (cbase < 0) or [B][H * W][M] with this launch's position k of image b at row cbase + k of block b
+// cbase < 0: sym_in / sym / idx are raster arrays [B][H][W][M]; cbase >= 0: they are compact arrays [B][H * W][M] in the order of the
+// position list, this launch's position k of image b at row cbase + k of block b (the wavefront-ordered decoder)
 __global__ void ar_quantize_batch_kernel(FMap y, FMap gp, const int32_t* pos, int npos, const float* table, int ntable,
                                          const int32_t* sym_in, FMap yh, int32_t* sym, int32_t* idx, long cbase) {
   const int M = yh.C;
@@ -161,24 +107,10 @@ __device__ __forceinline__ void lane_store(const TdvcLane& st, uint32_t* state, 
   if (st.bad) state[L * kLaneStateWords] = 1;                  // every writer stores the same value
 }
 
-// one workgroup of L threads; data: the whole container on the device, nwords: 32-bit words of its payload
-__global__ void ar_lanes_init_kernel(const uint8_t* data, uint32_t nwords, uint32_t* state) {
-  const int L = (int)blockDim.x, lane = (int)threadIdx.x;
-  const uint8_t* tab = data + kLanesHeaderBytes;
-  uint32_t begin = 0;
-  for (int j = 0; j < lane; ++j) begin += (uint32_t)tab[2 * j] | ((uint32_t)tab[2 * j + 1] << 8);
-  const uint32_t len = (uint32_t)tab[2 * lane] | ((uint32_t)tab[2 * lane + 1] << 8);
-  TdvcLane st;
-  tdvc_lane_init(st, data + tdvc_lanes_payload_offset(L), begin, len, nwords);
-  if (lane == 0) state[L * kLaneStateWords] = 0;
-  __syncthreads();
-  lane_store(st, state, lane, L);
-}
-
 // The CDF tables as the kernel reads them: every table's entries packed end to end as uint16 (table t at cdf16[starts[t]],
 // sizes[t] entries; the last entry of a table is 1 << 16, which does not fit and is implied), n16 <= kLdsCdf entries in all.
 // They are copied into LDS at the start of a launch -- the 64 tables of compressai's scale table have 27 256 entries -- so
-// that the bin search's dependent probes are LDS reads; a larger table set is refused by tdvc_ar_decode_lanes_step.
+// that the bin search's dependent probes are LDS reads; a larger table set is refused by tdvc_ar_decode_lanes_step_batch.
 constexpr int kLdsCdf = 27648;                                  // 54 KB
 constexpr int kChunkSyms = 6144;                                // symbols between two barriers: 48 positions of 128 channels
 constexpr int kLanesLds = kLdsCdf * 2 + kChunkSyms * 4 + 64 * 4 * 4 + kChunkSyms;      // cdf | q | starts, sizes, offsets, scale table | ci
@@ -203,101 +135,10 @@ __device__ __forceinline__ int scale_index_lds(float s, const float* tab64, int 
   return ntable - 1 - cnt;
 }
 
-// What ar_indexes_kernel + the host range decoder + ar_quantize_kernel do for one step of a wavefront-ordered stream, in three
-// phases per chunk of positions.  A (all threads, coalesced): scale -> CDF index of every symbol, into LDS and `idx`.  B: lane
-// `threadIdx.x` decodes its symbols (k, c), c % L == lane, in stream order (k, then c) -- the serial part; it touches LDS only,
-// apart from the lane's own renormalisation words, so no wait of the state update covers another memory operation.  C (all
-// threads, coalesced): sym at the compact row cbase + k and y_hat(h, w, c) = q + mean.  T: y_hat's element type.
-// The body is shared with the batched kernel below: gp0 is row 0 of this image's rows of gp (pixel stride gp_sp), yh0 the image's
-// y_hat (W, pixel stride yh_sp), sym0 / idx0 the compact row of this launch's position 0.
-template <typename T>
-__device__ __forceinline__ void ar_decode_lanes_body(const float* __restrict__ gp0, int gp_sp, const int32_t* __restrict__ pos, int npos,
-                                                     const float* __restrict__ table, int ntable, const uint8_t* __restrict__ payload, uint32_t nwords,
-                                                     const uint16_t* __restrict__ cdf16, int n16, const int32_t* __restrict__ cdf_starts,
-                                                     const int32_t* __restrict__ cdf_sizes, const int32_t* __restrict__ offsets,
-                                                     uint32_t* state, T* __restrict__ yh0, int yh_W, int yh_sp, int M,
-                                                     int32_t* __restrict__ sym0, int32_t* __restrict__ idx0) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  uint16_t* s_cdf = reinterpret_cast<uint16_t*>(s_raw);
-  int32_t* s_q = reinterpret_cast<int32_t*>(s_raw + kLdsCdf * 2);
-  int32_t* s_start = s_q + kChunkSyms;
-  int32_t* s_size = s_start + 64;
-  int32_t* s_off = s_size + 64;
-  float* s_table = reinterpret_cast<float*>(s_off + 64);
-  uint8_t* s_ci = reinterpret_cast<uint8_t*>(s_table + 64);
-  const int L = (int)blockDim.x, lane = (int)threadIdx.x;
-  if (lane < 64) s_table[lane] = lane < ntable - 1 ? table[lane] : -INFINITY;       // ntable <= 64 <= L
-  if (lane < ntable) {
-    const int start = cdf_starts[lane], size = cdf_sizes[lane];
-    const bool ok = start >= 0 && size >= 0 && start <= n16 && size <= n16 - start;
-    s_start[lane] = ok ? start : 0;
-    s_size[lane] = ok ? size : 0;                              // a table outside the array has no entries: the decode flags it
-    s_off[lane] = offsets[lane];
-  }
-  const int nchunk = n16 / 8;                                  // 16-byte chunks, 1 <= nchunk <= kLdsCdf / 8
-  for (int c0 = lane; c0 < nchunk; c0 += L * 8) {              // eight loads in flight per thread, no branch between them:
-    int ix[8];                                                 // an index past the end is clamped, which re-copies the last
-    uint4 v[8];                                                // chunk onto itself
-#pragma unroll
-    for (int u = 0; u < 8; ++u) ix[u] = min(c0 + u * L, nchunk - 1);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = reinterpret_cast<const uint4*>(cdf16)[ix[u]];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) reinterpret_cast<uint4*>(s_cdf)[ix[u]] = v[u];
-  }
-  TdvcLane st;
-  {
-    const uint32_t* s = state + lane * kLaneStateWords;
-    st.x = (uint64_t)s[0] | ((uint64_t)s[1] << 32);
-    st.end = s[3] < nwords ? s[3] : nwords;                    // whatever the buffer holds, no read leaves the payload
-    st.pos = s[2] < st.end ? s[2] : st.end;
-    st.bad = 0;
-  }
-  __syncthreads();
-  const int per = M / L, kc = kChunkSyms / M;                  // positions per chunk (M <= kChunkSyms)
-  for (int k0 = 0; k0 < npos; k0 += kc) {
-    const int nk = npos - k0 < kc ? npos - k0 : kc, ne = nk * M;
-    for (int e = lane; e < ne; e += L) {                       // A
-      const int k = k0 + e / M, c = e % M;
-      const int ci = scale_index_lds((gp0 + (long)k * gp_sp)[c], s_table, ntable);
-      s_ci[e] = (uint8_t)ci;
-      idx0[(long)k * M + c] = ci;
-    }
-    __syncthreads();
-    for (int k = 0; k < nk; ++k)                               // B
-      for (int j = 0; j < per; ++j) {
-        const int e = k * M + lane + j * L, ci = s_ci[e];
-        const int size = s_size[ci];
-        const CdfDev cdf{(lds_u16_ptr)s_cdf, s_start[ci], size};
-        s_q[e] = tdvc_lane_decode(st, payload, cdf, size) + s_off[ci];
-      }
-    __syncthreads();
-    for (int e = lane; e < ne; e += L) {                       // C
-      const int k = k0 + e / M, c = e % M;
-      const int h = pos[2 * k], w = pos[2 * k + 1], q = s_q[e];
-      const float mean = (gp0 + (long)k * gp_sp)[M + c];
-      yh0[((long)h * yh_W + w) * yh_sp + c] = (T)((float)q + mean);
-      sym0[(long)k * M + c] = q;
-    }
-    __syncthreads();                                           // s_ci / s_q are free for the next chunk
-  }
-  lane_store(st, state, lane, L);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(128) ar_decode_lanes_kernel(FMap gp, const int32_t* __restrict__ pos, int npos, const float* __restrict__ table,
-                                                              int ntable, const uint8_t* __restrict__ payload, uint32_t nwords,
-                                                              const uint16_t* __restrict__ cdf16, int n16, const int32_t* __restrict__ cdf_starts,
-                                                              const int32_t* __restrict__ cdf_sizes, const int32_t* __restrict__ offsets,
-                                                              uint32_t* state, FMap yh, int32_t* __restrict__ sym, int32_t* __restrict__ idx, long cbase) {
-  ar_decode_lanes_body<T>(reinterpret_cast<const float*>(gp.p), gp.sp, pos, npos, table, ntable, payload, nwords, cdf16, n16, cdf_starts, cdf_sizes, offsets,
-                          state, reinterpret_cast<T*>(yh.p), yh.W, yh.sp, yh.C, sym + cbase * yh.C, idx + cbase * yh.C);
-}
-
-// ---- B lane-split streams at once: workgroup b is the single-image kernel on image b.  The B containers sit in one device buffer
-// `streams` of `stream_bytes` bytes; tab[b] = {byte offset of container b (a multiple of 16), 32-bit words of its payload}.  The
-// table is device memory a host copy filled: a container that does not lie inside the buffer is given no words, so its lanes flag
-// `bad` and nothing outside the buffer is read.  State: [B][L * 4 + 1] words, one sticky `bad` word per image.
+// The B containers of a call sit in one device buffer `streams` of `stream_bytes` bytes; tab[b] = {byte offset of container b (a
+// multiple of 16), 32-bit words of its payload}.  The table is device memory a host copy filled: a container that does not lie inside
+// the buffer is given no words, so its lanes flag `bad` and nothing outside the buffer is read.  State: [B][L * 4 + 1] words, one
+// sticky `bad` word per image.  Workgroup b of L threads works on image b.
 struct LaneStream { const uint8_t* payload; uint32_t nwords; bool ok; };
 __device__ __forceinline__ LaneStream lane_stream(const uint8_t* streams, long stream_bytes, const uint32_t* tab, int b, int L) {
   const uint32_t off = tab[2 * b], nw = tab[2 * b + 1];
@@ -325,6 +166,11 @@ __global__ void ar_lanes_init_batch_kernel(const uint8_t* streams, long stream_b
   lane_store(st, st_b, lane, L);
 }
 
+// What ar_indexes_batch_kernel + the host range decoder + ar_quantize_batch_kernel do for one step of a wavefront-ordered stream, in
+// three phases per chunk of positions.  A (all threads, coalesced): scale -> CDF index of every symbol, into LDS and `idx`.  B: lane
+// `threadIdx.x` decodes its symbols (k, c), c % L == lane, in stream order (k, then c) -- the serial part; it touches LDS only,
+// apart from the lane's own renormalisation words, so no wait of the state update covers another memory operation.  C (all
+// threads, coalesced): sym at the compact row cbase + k of the image's block and y_hat(b, h, w, c) = q + mean.  T: y_hat's element type.
 template <typename T>
 __global__ void __launch_bounds__(128) ar_decode_lanes_batch_kernel(FMap gp, const int32_t* __restrict__ pos, int npos, const float* __restrict__ table,
                                                                     int ntable, const uint8_t* __restrict__ streams, long stream_bytes,
@@ -332,12 +178,78 @@ __global__ void __launch_bounds__(128) ar_decode_lanes_batch_kernel(FMap gp, con
                                                                     const int32_t* __restrict__ cdf_starts, const int32_t* __restrict__ cdf_sizes,
                                                                     const int32_t* __restrict__ offsets, uint32_t* state, FMap yh,
                                                                     int32_t* __restrict__ sym, int32_t* __restrict__ idx, long cbase) {
-  const int L = (int)blockDim.x, b = (int)blockIdx.x, M = yh.C;
+  const int L = (int)blockDim.x, lane = (int)threadIdx.x, b = (int)blockIdx.x, M = yh.C;
   const LaneStream ls = lane_stream(streams, stream_bytes, tab, b, L);
+  const float* __restrict__ gp0 = reinterpret_cast<const float*>(gp.p) + (long)b * npos * gp.sp;       // row 0 of image b's rows of gp
+  T* __restrict__ yh0 = reinterpret_cast<T*>(yh.p) + (long)b * yh.sn;
   const long row0 = ((long)b * yh.H * yh.W + cbase) * M;       // image b's block of the compact arrays, row cbase
-  ar_decode_lanes_body<T>(reinterpret_cast<const float*>(gp.p) + (long)b * npos * gp.sp, gp.sp, pos, npos, table, ntable, ls.payload, ls.nwords, cdf16, n16,
-                          cdf_starts, cdf_sizes, offsets, state + (long)b * (L * kLaneStateWords + 1), reinterpret_cast<T*>(yh.p) + (long)b * yh.sn, yh.W, yh.sp,
-                          M, sym + row0, idx + row0);
+  sym += row0;
+  idx += row0;
+  state += (long)b * (L * kLaneStateWords + 1);
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  uint16_t* s_cdf = reinterpret_cast<uint16_t*>(s_raw);
+  int32_t* s_q = reinterpret_cast<int32_t*>(s_raw + kLdsCdf * 2);
+  int32_t* s_start = s_q + kChunkSyms;
+  int32_t* s_size = s_start + 64;
+  int32_t* s_off = s_size + 64;
+  float* s_table = reinterpret_cast<float*>(s_off + 64);
+  uint8_t* s_ci = reinterpret_cast<uint8_t*>(s_table + 64);
+  if (lane < 64) s_table[lane] = lane < ntable - 1 ? table[lane] : -INFINITY;       // ntable <= 64 <= L
+  if (lane < ntable) {
+    const int start = cdf_starts[lane], size = cdf_sizes[lane];
+    const bool ok = start >= 0 && size >= 0 && start <= n16 && size <= n16 - start;
+    s_start[lane] = ok ? start : 0;
+    s_size[lane] = ok ? size : 0;                              // a table outside the array has no entries: the decode flags it
+    s_off[lane] = offsets[lane];
+  }
+  const int nchunk = n16 / 8;                                  // 16-byte chunks, 1 <= nchunk <= kLdsCdf / 8
+  for (int c0 = lane; c0 < nchunk; c0 += L * 8) {              // eight loads in flight per thread, no branch between them:
+    int ix[8];                                                 // an index past the end is clamped, which re-copies the last
+    uint4 v[8];                                                // chunk onto itself
+#pragma unroll
+    for (int u = 0; u < 8; ++u) ix[u] = min(c0 + u * L, nchunk - 1);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = reinterpret_cast<const uint4*>(cdf16)[ix[u]];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) reinterpret_cast<uint4*>(s_cdf)[ix[u]] = v[u];
+  }
+  TdvcLane st;
+  {
+    const uint32_t* s = state + lane * kLaneStateWords;
+    st.x = (uint64_t)s[0] | ((uint64_t)s[1] << 32);
+    st.end = s[3] < ls.nwords ? s[3] : ls.nwords;                    // whatever the buffer holds, no read leaves the payload
+    st.pos = s[2] < st.end ? s[2] : st.end;
+    st.bad = 0;
+  }
+  __syncthreads();
+  const int per = M / L, kc = kChunkSyms / M;                  // positions per chunk (M <= kChunkSyms)
+  for (int k0 = 0; k0 < npos; k0 += kc) {
+    const int nk = npos - k0 < kc ? npos - k0 : kc, ne = nk * M;
+    for (int e = lane; e < ne; e += L) {                       // A
+      const int k = k0 + e / M, c = e % M;
+      const int ci = scale_index_lds((gp0 + (long)k * gp.sp)[c], s_table, ntable);
+      s_ci[e] = (uint8_t)ci;
+      idx[(long)k * M + c] = ci;
+    }
+    __syncthreads();
+    for (int k = 0; k < nk; ++k)                               // B
+      for (int j = 0; j < per; ++j) {
+        const int e = k * M + lane + j * L, ci = s_ci[e];
+        const int size = s_size[ci];
+        const CdfDev cdf{(lds_u16_ptr)s_cdf, s_start[ci], size};
+        s_q[e] = tdvc_lane_decode(st, ls.payload, cdf, size) + s_off[ci];
+      }
+    __syncthreads();
+    for (int e = lane; e < ne; e += L) {                       // C
+      const int k = k0 + e / M, c = e % M;
+      const int h = pos[2 * k], w = pos[2 * k + 1], q = s_q[e];
+      const float mean = (gp0 + (long)k * gp.sp)[M + c];
+      yh0[((long)h * yh.W + w) * yh.sp + c] = (T)((float)q + mean);
+      sym[(long)k * M + c] = q;
+    }
+    __syncthreads();                                           // s_ci / s_q are free for the next chunk
+  }
+  lane_store(st, state, lane, L);
 }
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -345,291 +257,19 @@ inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
 
-extern "C" int tdvc_ar_gather(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int npos,
-                              const tdvc_fmap* x1, const tdvc_fmap* pc, void* stream) {
-  TDVC_CHECK(y_hat && params && pos && x1 && pc && npos >= 1, "tdvc_ar_gather: null / empty");
-  const bool f32 = y_hat->dtype == TDVC_F32;
-  auto okv = [&](const tdvc_fmap& f) {               // all four of one dtype; 16-byte chunks
-    return f32 ? (fmap_ok32(f) && (f.C % 4) == 0 && (f.sp % 4) == 0 && aligned16(f.p)) : fmap_ok16(f);
-  };
-  TDVC_CHECK(okv(*y_hat) && okv(*params) && okv(*x1) && okv(*pc), "tdvc_ar_gather: four fp16 fmaps, or four fp32 fmaps (fp32 islands), expected");
-  TDVC_CHECK(y_hat->N == 1 && params->N == 1 && params->H == y_hat->H && params->W == y_hat->W, "tdvc_ar_gather: one image at a time, params geometry must match y_hat");
-  TDVC_CHECK(x1->C == 12 * y_hat->C && x1->W >= npos && x1->H == 1 && pc->C >= params->C && pc->W >= npos && pc->H == 1,
-             "tdvc_ar_gather: x1 must be (1,1,>=npos,12*M), pc (1,1,>=npos,>=2M)");
-  const int ve = f32 ? 4 : 8;
-  const long total = (long)npos * (12 * y_hat->C / ve + params->C / ve);
-  if (f32) hipLaunchKernelGGL((ar_gather_kernel<float, f32x4>), g1(total), dim3(256), 0, ST(stream), to_dev(*y_hat), to_dev(*params), pos, npos, to_dev(*x1), to_dev(*pc));
-  else hipLaunchKernelGGL((ar_gather_kernel<half_t, half8>), g1(total), dim3(256), 0, ST(stream), to_dev(*y_hat), to_dev(*params), pos, npos, to_dev(*x1), to_dev(*pc));
-  return tdvc_launch_status("tdvc_ar_gather");
-}
-
-extern "C" int tdvc_ar_quantize(const tdvc_fmap* y, const tdvc_fmap* gp, const int32_t* pos, int npos,
-                                const float* scale_table, int ntable, const int32_t* symbols_in,
-                                const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, void* stream) {
-  TDVC_CHECK(gp && pos && scale_table && y_hat && symbols && indexes && npos >= 1 && ntable >= 2, "tdvc_ar_quantize: null / empty");
-  TDVC_CHECK(symbols_in || (y && fmap_ok32(*y)), "tdvc_ar_quantize: need y (encoder) or symbols_in (decoder)");
-  TDVC_CHECK(fmap_ok32(*gp) && (y_hat->dtype == TDVC_F32 ? fmap_ok32(*y_hat) : fmap_ok16(*y_hat)) && y_hat->N == 1 && gp->C >= 2 * y_hat->C && gp->W >= npos,
-             "tdvc_ar_quantize: bad gp / y_hat");
-  FMap yd = y ? to_dev(*y) : to_dev(*y_hat);
-  yd.C = y_hat->C; yd.W = y_hat->W; yd.H = y_hat->H;
-  hipLaunchKernelGGL(ar_quantize_kernel, g1((long)npos * y_hat->C), dim3(256), 0, ST(stream), yd, to_dev(*gp), pos, npos, scale_table, ntable,
-                     symbols_in, to_dev(*y_hat), symbols, indexes, -1L);
-  return tdvc_launch_status("tdvc_ar_quantize");
-}
-
-extern "C" int tdvc_ar_indexes(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
-                               int M, int W, int32_t* indexes, void* stream) {
-  TDVC_CHECK(gp && pos && scale_table && indexes && npos >= 1 && ntable >= 2 && M >= 1 && W >= 1 && fmap_ok32(*gp) && gp->C >= 2 * M,
-             "tdvc_ar_indexes: bad arguments");
-  hipLaunchKernelGGL(ar_indexes_kernel, g1((long)npos * M), dim3(256), 0, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, M, W, indexes, -1L);
-  return tdvc_launch_status("tdvc_ar_indexes");
-}
-
 extern "C" int tdvc_round_symbols(const tdvc_fmap* z, const float* median, int32_t* out, void* stream) {
   TDVC_CHECK(z && median && out && fmap_ok32(*z), "tdvc_round_symbols: bad arguments");
   hipLaunchKernelGGL(round_symbols_kernel, g1((long)z->N * z->H * z->W * z->C), dim3(256), 0, ST(stream), to_dev(*z), median, out);
   return tdvc_launch_status("tdvc_round_symbols");
 }
 
-// The decoder's context loop in native code.  The y stream is in raster order (compressai's bitstream), and position
-// (h, w) needs y_hat(h, w - 1): 8160 strictly serial steps per coder at 1080p.  Per step: gather -> context conv ->
-// entropy_parameters (the caller's conv descriptors, fixed buffers) -> CDF indexes -> host range decoder -> quantise.
-// Driving this from Python cost ~230 us per position (3.7 s per 1080p frame); here a step is seven enqueues, one
-// 512-byte device->host copy + stream wait, the host decoder and one host->device copy.
-extern "C" int tdvc_ar_decode_serial(const uint8_t* data, int64_t nbytes, const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
-                                     const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
-                                     const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                                     const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
-                                     int32_t* idx_dev, int32_t* sym_dev, void* stream) {
-  TdvcLoopLaunches count;
-  TDVC_CHECK(data && cdfs && cdf_sizes && offsets && y_hat && params && x1 && pc && convs && gp && pos_table && scale_table && idx_dev && sym_dev,
-             "tdvc_ar_decode_serial: null argument");
-  TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && npos_total >= 1 && M >= 1 && M <= 4096 && W >= 1, "tdvc_ar_decode_serial: bad sizes");
-  void* dec = tdvc_rans_decoder_create(data, nbytes);
-  if (!dec) return TDVC_EINVAL;
-  int32_t* host = nullptr;                                // [2][M] indexes | symbols, pinned
-  hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(int32_t) * 2 * (size_t)M, hipHostMallocDefault);
-  if (err != hipSuccess) { tdvc_rans_decoder_destroy(dec); tdvc_set_error("tdvc_ar_decode_serial: hipHostMalloc failed: %s", hipGetErrorString(err)); return (int)err; }
-  hipStream_t st = ST(stream);
-  int rc = TDVC_OK;
-  for (int k = 0; k < npos_total && rc == TDVC_OK; ++k) {
-    const int32_t* pos = pos_table + 2 * (long)k;
-    rc = tdvc_ar_gather(y_hat, params, pos, 1, x1, pc, stream);
-    for (int c = 0; c < nconvs && rc == TDVC_OK; ++c) rc = tdvc_conv2d(&convs[c], stream);
-    if (rc == TDVC_OK) rc = tdvc_ar_indexes(gp, pos, 1, scale_table, ntable, M, W, idx_dev, stream);
-    if (rc != TDVC_OK) break;
-    int32_t* idx_k = idx_dev + (long)k * M;               // raster order: position k = h * W + w owns [k*M, (k+1)*M)
-    int32_t* sym_k = sym_dev + (long)k * M;
-    err = hipMemcpyAsync(host, idx_k, sizeof(int32_t) * M, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) { tdvc_set_error("tdvc_ar_decode_serial: copy / sync failed: %s", hipGetErrorString(err)); rc = (int)err; break; }
-    rc = tdvc_rans_decoder_decode(dec, host, M, cdfs, cdf_stride, cdf_sizes, offsets, host + M);
-    if (rc != TDVC_OK) break;
-    err = hipMemcpyAsync(sym_k, host + M, sizeof(int32_t) * M, hipMemcpyHostToDevice, st);
-    if (err != hipSuccess) { tdvc_set_error("tdvc_ar_decode_serial: upload failed: %s", hipGetErrorString(err)); rc = (int)err; break; }
-    // the next iteration's stream wait orders this upload before `host` is written again
-    rc = tdvc_ar_quantize(nullptr, gp, pos, 1, scale_table, ntable, sym_dev, y_hat, sym_dev, idx_dev, stream);
-  }
-  (void)hipStreamSynchronize(st);
-  (void)hipHostFree(host);
-  tdvc_rans_decoder_destroy(dec);
-  return rc;
-}
-
-// The context loop over anti-diagonals in native code, either direction.  Encoder: ~7 enqueues per step and no
-// synchronisation (Python drove a step at ~0.5 ms: 0.33 s per 1080p frame for the two coders).  Decoder of a
-// wavefront-ordered stream: per step the step's indexes to the host, its symbols out of the range decoder, and back.
-extern "C" int tdvc_ar_wavefront(const uint8_t* data, int64_t nbytes, const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
-                                 const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat, const tdvc_fmap* params,
-                                 const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                                 const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
-                                 const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream) {
-  TdvcLoopLaunches count;
-  TDVC_CHECK(y_hat && params && x1 && pc && convs && gp && pos_dev && step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront: null argument");
-  TDVC_CHECK((data != nullptr) != (y != nullptr), "tdvc_ar_wavefront: give y (encoder) or data (decoder), not both");
-  TDVC_CHECK(!data || (cdfs && cdf_sizes && offsets && nbytes >= 4), "tdvc_ar_wavefront: the decoder needs the CDF tables");
-  TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && nsteps >= 1 && M >= 1 && M <= 4096 && W >= 1 && M == y_hat->C, "tdvc_ar_wavefront: bad sizes");
-  long total = 0;
-  int nmax = 0;
-  for (int s = 0; s < nsteps; ++s) {
-    TDVC_CHECK(step_sizes[s] >= 1 && step_sizes[s] <= x1->W && step_sizes[s] <= pc->W && step_sizes[s] <= gp->W, "tdvc_ar_wavefront: a step exceeds the staging buffers");
-    total += step_sizes[s];
-    nmax = step_sizes[s] > nmax ? step_sizes[s] : nmax;
-  }
-  TDVC_CHECK(total == (long)y_hat->H * y_hat->W, "tdvc_ar_wavefront: the steps must cover every position once");
-  hipStream_t st = ST(stream);
-  tdvc_conv_desc d[8];
-  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
-  void* dec = nullptr;
-  int32_t* host = nullptr;                                // [2][nmax * M] indexes | symbols, pinned
-  if (data) {
-    dec = tdvc_rans_decoder_create(data, nbytes);
-    if (!dec) return TDVC_EINVAL;
-    hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(int32_t) * 2 * (size_t)nmax * M, hipHostMallocDefault);
-    if (err != hipSuccess) { tdvc_rans_decoder_destroy(dec); tdvc_set_error("tdvc_ar_wavefront: hipHostMalloc failed: %s", hipGetErrorString(err)); return (int)err; }
-  }
-  int rc = TDVC_OK;
-  long o = 0;
-  for (int s = 0; s < nsteps && rc == TDVC_OK; ++s) {
-    const int n = step_sizes[s];
-    const int32_t* pos = pos_dev + 2 * o;
-    rc = tdvc_ar_gather(y_hat, params, pos, n, x1, pc, stream);
-    for (int c = 0; c < nconvs && rc == TDVC_OK; ++c) {
-      d[c].x.W = n;                                      // the step's positions are the "pixels" of a (1, n) map
-      d[c].y.W = n;
-      rc = tdvc_conv2d(&d[c], stream);
-    }
-    if (rc != TDVC_OK) break;
-    if (!data) {
-      rc = tdvc_ar_quantize(y, gp, pos, n, scale_table, ntable, nullptr, y_hat, sym_dev, idx_dev, stream);
-    } else {
-      const long cnt = (long)n * M;
-      hipLaunchKernelGGL(ar_indexes_kernel, g1(cnt), dim3(256), 0, st, to_dev(*gp), pos, n, scale_table, ntable, M, W, idx_dev, o);
-      tdvc_count_launch();                               // the quantiser's tdvc_launch_status() below counts one
-      hipError_t err = hipMemcpyAsync(host, idx_dev + o * M, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st);
-      if (err == hipSuccess) err = hipStreamSynchronize(st);
-      if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront: copy / sync failed: %s", hipGetErrorString(err)); rc = (int)err; break; }
-      rc = tdvc_rans_decoder_decode(dec, host, cnt, cdfs, cdf_stride, cdf_sizes, offsets, host + (long)nmax * M);
-      if (rc != TDVC_OK) break;
-      err = hipMemcpyAsync(sym_dev + o * M, host + (long)nmax * M, sizeof(int32_t) * cnt, hipMemcpyHostToDevice, st);
-      if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront: upload failed: %s", hipGetErrorString(err)); rc = (int)err; break; }
-      // the next step's stream wait orders this upload before `host` is written again
-      FMap yd = to_dev(*y_hat);
-      hipLaunchKernelGGL(ar_quantize_kernel, g1(cnt), dim3(256), 0, st, yd, to_dev(*gp), pos, n, scale_table, ntable, sym_dev, yd, sym_dev, idx_dev, o);
-      rc = tdvc_launch_status("tdvc_ar_wavefront");
-    }
-    o += n;
-  }
-  if (data) {
-    (void)hipStreamSynchronize(st);
-    (void)hipHostFree(host);
-    tdvc_rans_decoder_destroy(dec);
-  }
-  return rc;
-}
-
-// ---- lane-split y streams: the decoder's loop with the range decoder on the device
-namespace {
-struct LanesArgs {                                             // what every launch of the lane kernels needs, validated once
-  const uint8_t* stream_dev; uint32_t nwords; int L;
-};
-int lanes_args(const char* who, const uint8_t* stream_dev, int64_t nbytes, int L, int M, uint32_t* state_dev, LanesArgs* a) {
-  TDVC_CHECK(stream_dev && state_dev, "%s: null stream / state buffer", who);
-  TDVC_CHECK((L == 64 || L == 128) && M >= L && M % L == 0, "%s: the device decoder takes 64 or 128 lanes that divide the channel count (L = %d, M = %d)", who, L, M);
-  const int64_t off = tdvc_lanes_payload_offset(L);
-  TDVC_CHECK(nbytes >= off && (nbytes - off) % 4 == 0 && (nbytes - off) / 4 <= (int64_t)L * kLanesMaxWords, "%s: bad stream size %lld", who, (long long)nbytes);
-  TDVC_CHECK((((uintptr_t)stream_dev) & 3) == 0 && (((uintptr_t)state_dev) & 3) == 0, "%s: the stream / state buffers must be 4-byte aligned", who);
-  a->stream_dev = stream_dev; a->nwords = (uint32_t)((nbytes - off) / 4); a->L = L;
-  return TDVC_OK;
-}
-}  // namespace
-
-extern "C" int64_t tdvc_ar_lanes_state_bytes(int L) { return L >= 1 ? (int64_t)sizeof(uint32_t) * ((int64_t)L * kLaneStateWords + 1) : TDVC_EINVAL; }
-
-extern "C" int tdvc_ar_lanes_init(const uint8_t* stream_dev, int64_t nbytes, int L, uint32_t* state_dev, void* stream) {
-  LanesArgs a;
-  if (int rc = lanes_args("tdvc_ar_lanes_init", stream_dev, nbytes, L, L, state_dev, &a)) return rc;
-  hipLaunchKernelGGL(ar_lanes_init_kernel, dim3(1), dim3(L), 0, ST(stream), a.stream_dev, a.nwords, state_dev);
-  return tdvc_launch_status("tdvc_ar_lanes_init");
-}
-
-extern "C" int tdvc_ar_decode_lanes_step(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
-                                         const uint8_t* stream_dev, int64_t nbytes, int L, const uint16_t* cdf16_dev, int32_t n16,
-                                         const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs,
-                                         uint32_t* state_dev,
-                                         const tdvc_fmap* y_hat, int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream) {
-  TDVC_CHECK(gp && pos && scale_table && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && symbols && indexes && npos >= 1 && cbase >= 0,
-             "tdvc_ar_decode_lanes_step: null / empty");
-  TDVC_CHECK(ntable >= 2 && ntable <= 64 && ncdfs >= ntable, "tdvc_ar_decode_lanes_step: 2..64 scale-table entries, one CDF per entry expected");
-  TDVC_CHECK(n16 >= 8 && n16 % 8 == 0 && aligned16(cdf16_dev), "tdvc_ar_decode_lanes_step: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
-  TDVC_CHECK(n16 <= kLdsCdf, "tdvc_ar_decode_lanes_step: %d packed CDF entries, the kernel's LDS holds %d", n16, kLdsCdf);
-  TDVC_CHECK(fmap_ok32(*gp) && (y_hat->dtype == TDVC_F32 ? fmap_ok32(*y_hat) : fmap_ok16(*y_hat)) && y_hat->N == 1 && gp->C >= 2 * y_hat->C && gp->W >= npos,
-             "tdvc_ar_decode_lanes_step: bad gp / y_hat");
-  LanesArgs a;
-  if (int rc = lanes_args("tdvc_ar_decode_lanes_step", stream_dev, nbytes, L, y_hat->C, state_dev, &a)) return rc;
-  const uint8_t* payload = a.stream_dev + tdvc_lanes_payload_offset(L);
-  TDVC_CHECK(y_hat->C <= kChunkSyms, "tdvc_ar_decode_lanes_step: more than %d channels", kChunkSyms);
-  static TdvcPerDeviceFlag attr;
-  if (!attr.flag()) {
-    for (const void* k : {reinterpret_cast<const void*>(&ar_decode_lanes_kernel<float>), reinterpret_cast<const void*>(&ar_decode_lanes_kernel<half_t>)}) {
-      const hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLanesLds);
-      if (err != hipSuccess) { tdvc_set_error("tdvc_ar_decode_lanes_step: cannot reserve %d bytes of LDS: %s", kLanesLds, hipGetErrorString(err)); return (int)err; }
-    }
-    attr.flag() = true;
-  }
-  if (y_hat->dtype == TDVC_F32)
-    hipLaunchKernelGGL(ar_decode_lanes_kernel<float>, dim3(1), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, payload, a.nwords,
-                       cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
-  else
-    hipLaunchKernelGGL(ar_decode_lanes_kernel<half_t>, dim3(1), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, payload, a.nwords,
-                       cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
-  return tdvc_launch_status("tdvc_ar_decode_lanes_step");
-}
-
-// The decoder's loop over anti-diagonals for a lane-split stream: one upload of the string, then per step gather -> convs ->
-// ar_decode_lanes_kernel, the encoder's enqueue count and like it no synchronisation until the image is done; then the sticky
-// `bad` word comes back with the one stream wait of the call.  Nothing is allocated here.
-extern "C" int tdvc_ar_wavefront_lanes(const uint8_t* data, int64_t nbytes, uint8_t* stream_dev, int64_t stream_cap, uint32_t* state_dev,
-                                       const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
-                                       const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
-                                       const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                                       const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
-                                       const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream) {
-  TdvcLoopLaunches count;
-  TDVC_CHECK(data && stream_dev && state_dev && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && params && x1 && pc && convs && gp && pos_dev &&
-             step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront_lanes: null argument");
-  TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && nsteps >= 1 && M >= 1 && M <= 4096 && W >= 1 && M == y_hat->C, "tdvc_ar_wavefront_lanes: bad sizes");
-  int L = 0;
-  if (const char* why = tdvc_lanes_check(data, nbytes, M, &L)) { tdvc_set_error("tdvc_ar_wavefront_lanes: %s", why); return TDVC_EINVAL; }
-  TDVC_CHECK(nbytes <= stream_cap, "tdvc_ar_wavefront_lanes: the device stream buffer holds %lld bytes, the string has %lld", (long long)stream_cap, (long long)nbytes);
-  long total = 0;
-  for (int s = 0; s < nsteps; ++s) {
-    TDVC_CHECK(step_sizes[s] >= 1 && step_sizes[s] <= x1->W && step_sizes[s] <= pc->W && step_sizes[s] <= gp->W, "tdvc_ar_wavefront_lanes: a step exceeds the staging buffers");
-    total += step_sizes[s];
-  }
-  TDVC_CHECK(total == (long)y_hat->H * y_hat->W, "tdvc_ar_wavefront_lanes: the steps must cover every position once");
-  hipStream_t st = ST(stream);
-  tdvc_conv_desc d[8];
-  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
-  hipError_t err = hipMemcpyAsync(stream_dev, data, (size_t)nbytes, hipMemcpyHostToDevice, st);
-  if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes: upload failed: %s", hipGetErrorString(err)); return (int)err; }
-  int rc = tdvc_ar_lanes_init(stream_dev, nbytes, L, state_dev, stream);
-  long o = 0;
-  for (int s = 0; s < nsteps && rc == TDVC_OK; ++s) {
-    const int n = step_sizes[s];
-    const int32_t* pos = pos_dev + 2 * o;
-    rc = tdvc_ar_gather(y_hat, params, pos, n, x1, pc, stream);
-    for (int c = 0; c < nconvs && rc == TDVC_OK; ++c) {
-      d[c].x.W = n;
-      d[c].y.W = n;
-      rc = tdvc_conv2d(&d[c], stream);
-    }
-    if (rc == TDVC_OK)
-      rc = tdvc_ar_decode_lanes_step(gp, pos, n, scale_table, ntable, stream_dev, nbytes, L, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, ncdfs,
-                                     state_dev, y_hat, sym_dev, idx_dev, o, stream);
-    o += n;
-  }
-  uint32_t bad = 0;
-  if (rc == TDVC_OK) {
-    err = hipMemcpyAsync(&bad, state_dev + (long)L * kLaneStateWords, sizeof(bad), hipMemcpyDeviceToHost, st);
-    if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes: reading the error word failed: %s", hipGetErrorString(err)); rc = (int)err; }
-  }
-  err = hipStreamSynchronize(st);                             // also: `data` and `bad` are the caller's / this frame's memory
-  if (rc == TDVC_OK && err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes: stream wait failed: %s", hipGetErrorString(err)); rc = (int)err; }
-  if (rc == TDVC_OK && bad) {
-    tdvc_set_error("tdvc_ar_wavefront_lanes: corrupt or exhausted lane-split stream (a lane ran out of words or met an impossible code)");
-    rc = TDVC_EINVAL;
-  }
-  return rc;
-}
-
-// ---- the batched context loop: a step handles the step's positions of all B images in the same launches (the images share the
-// position list, the weights and the tables; nothing in a step couples one image to another).  Row b * n + k of x1 / pc / gp is
-// position k of image b, a step is a (1, B * n) map to the convs; y / y_hat / params are fmaps with N = B.
+// ---- the context loop in native code: a step handles the step's positions of all B images of the call in the same launches (the
+// images share the position list, the weights and the tables; nothing in a step couples one image to another).  Row b * n + k of
+// x1 / pc / gp is position k of image b, a step is a (1, B * n) map to the convs; y / y_hat / params are fmaps with N = B.
 namespace {
 bool ar_fmap_ok(const tdvc_fmap& f, bool f32) { return f32 ? (fmap_ok32(f) && (f.C % 4) == 0 && (f.sp % 4) == 0 && (f.sn % 4) == 0 && aligned16(f.p)) : fmap_ok16(f); }
 
-// what the three batched drivers check before anything touches a device -> the largest step
+// what the three drivers check before anything touches a device -> the largest step
 int batch_loop_args(const char* who, int B, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_fmap* gp,
                     int nconvs, int M, int W, const int32_t* step_sizes, int nsteps, int* nmax_out) {
   TDVC_CHECK(B >= 1 && B <= 65535, "%s: 1 <= B <= 65535 images expected, got %d", who, B);
@@ -685,16 +325,19 @@ int host_decoders(const char* who, HostDecoders& h, const uint8_t* const* data, 
 }
 
 // the step's indexes of all images to the host (one strided copy), the B decoders in turn, the symbols back (one strided copy):
-// image b's `cnt` values start `img_stride` ints after image b - 1's in the device arrays and are dense in `host`
+// image b's `cnt` values start `img_stride` ints after image b - 1's in the device arrays and are dense in `host`.  One image is
+// one row, copied plainly: a hipMemcpy2DAsync costs ~8 us more than a hipMemcpyAsync, twice per step of a loop whose step is 50-100 us
 int host_decode_step(const char* who, HostDecoders& h, int32_t* idx_at, int32_t* sym_at, long img_stride, long cnt, long half, const int32_t* cdfs, int32_t cdf_stride,
                      const int32_t* cdf_sizes, const int32_t* offsets, hipStream_t st) {
   const size_t wb = sizeof(int32_t) * (size_t)cnt, pb = sizeof(int32_t) * (size_t)img_stride;
-  hipError_t err = hipMemcpy2DAsync(h.host, wb, idx_at, pb, wb, (size_t)h.B, hipMemcpyDeviceToHost, st);
+  hipError_t err = h.B == 1 ? hipMemcpyAsync(h.host, idx_at, wb, hipMemcpyDeviceToHost, st)
+                           : hipMemcpy2DAsync(h.host, wb, idx_at, pb, wb, (size_t)h.B, hipMemcpyDeviceToHost, st);
   if (err == hipSuccess) err = hipStreamSynchronize(st);       // also: the previous step's upload has left `host`
   if (err != hipSuccess) { tdvc_set_error("%s: copy / sync failed: %s", who, hipGetErrorString(err)); return (int)err; }
   for (int b = 0; b < h.B; ++b)
     if (const int rc = tdvc_rans_decoder_decode(h.dec[b], h.host + b * cnt, cnt, cdfs, cdf_stride, cdf_sizes, offsets, h.host + half + b * cnt)) return rc;
-  err = hipMemcpy2DAsync(sym_at, pb, h.host + half, wb, wb, (size_t)h.B, hipMemcpyHostToDevice, st);
+  err = h.B == 1 ? hipMemcpyAsync(sym_at, h.host + half, wb, hipMemcpyHostToDevice, st)
+                 : hipMemcpy2DAsync(sym_at, pb, h.host + half, wb, wb, (size_t)h.B, hipMemcpyHostToDevice, st);
   if (err != hipSuccess) { tdvc_set_error("%s: upload failed: %s", who, hipGetErrorString(err)); return (int)err; }
   return TDVC_OK;
 }
@@ -739,6 +382,9 @@ extern "C" int tdvc_ar_indexes_batch(const tdvc_fmap* gp, const int32_t* pos, in
   return tdvc_launch_status("tdvc_ar_indexes_batch");
 }
 
+// The context loop over anti-diagonals, either direction.  Encoder: ~7 enqueues per step and no synchronisation (Python drove a
+// step at ~0.5 ms: 0.33 s per 1080p frame for the two coders).  Decoder of a wavefront-ordered stream: per step the step's indexes
+// to the host, its symbols out of the B range decoders, and back.
 extern "C" int tdvc_ar_wavefront_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
                                        const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
                                        const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp, const int32_t* pos_dev,
@@ -780,6 +426,11 @@ extern "C" int tdvc_ar_wavefront_batch(const uint8_t* const* data, const int64_t
   return rc;
 }
 
+// The decoder's loop for y streams in raster order (compressai's bitstream): position (h, w) needs y_hat(h, w - 1), 8160 strictly
+// serial steps per coder at 1080p.  Per step: gather -> context conv -> entropy_parameters (the caller's conv descriptors, fixed
+// buffers) -> CDF indexes -> host range decoders -> quantise.  Driving this from Python cost ~230 us per position (3.7 s per 1080p
+// frame); here a step is seven enqueues, one device->host copy of B * M indexes + stream wait, the host decoders and one
+// host->device copy.
 extern "C" int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
                                            const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params,
                                            const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
@@ -810,8 +461,10 @@ extern "C" int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int
   return rc;
 }
 
-// ---- B lane-split streams.  Device buffer layout (tdvc_ar_lanes_batch_layout): the table uint32 [B][2] = {byte offset of container
-// b, words of its payload}, padded to 16 bytes, then the containers, each at a 16-byte aligned offset.
+// ---- lane-split y streams: the decoder's loop with the range decoder on the device.  Device buffer layout
+// (tdvc_ar_lanes_batch_layout): the table uint32 [B][2] = {byte offset of container b, words of its payload}, padded to 16 bytes,
+// then the containers, each at a 16-byte aligned offset.
+extern "C" int64_t tdvc_ar_lanes_state_bytes(int L) { return L >= 1 ? (int64_t)sizeof(uint32_t) * ((int64_t)L * kLaneStateWords + 1) : TDVC_EINVAL; }
 extern "C" int64_t tdvc_ar_lanes_batch_layout(const int64_t* nbytes, int B, int L, uint32_t* table_out) {
   if (!nbytes || B < 1 || B > 65535 || L < 1) { tdvc_set_error("tdvc_ar_lanes_batch_layout: null sizes, or B = %d / L = %d out of range", B, L); return TDVC_EINVAL; }
   int64_t off = ((int64_t)B * 8 + 15) / 16 * 16;
@@ -876,9 +529,10 @@ extern "C" int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_
   return tdvc_launch_status("tdvc_ar_decode_lanes_step_batch");
 }
 
-// tdvc_ar_wavefront_lanes over B images: the B strings are validated, packed behind their table in pinned memory and uploaded with
-// one copy, then per step gather -> convs -> ar_decode_lanes_batch_kernel (B workgroups) with no synchronisation; the B sticky
-// `bad` words come back with the call's one stream wait.
+// The decoder's loop over anti-diagonals for lane-split streams: the B strings are validated and uploaded behind their table, B + 1
+// copies from the caller's memory, then per step gather -> convs -> ar_decode_lanes_batch_kernel (B workgroups), the encoder's
+// enqueue count and like it no synchronisation until the images are done; then the B sticky `bad` words come back with the one
+// stream wait of the call.  Nothing is allocated here (a pinned staging buffer per call cost 0.3-0.5 ms, a fifth of a 448 x 256 loop).
 extern "C" int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nbytes, int B, uint8_t* stream_dev, int64_t stream_cap,
                                              uint32_t* state_dev, const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev,
                                              const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat,
@@ -908,16 +562,12 @@ extern "C" int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const i
   hipStream_t st = ST(stream);
   tdvc_conv_desc d[8];
   for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
-  uint8_t* pinned = nullptr;                                   // table | containers, as the device buffer holds them
-  hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&pinned), (size_t)total, hipHostMallocDefault);
-  if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: hipHostMalloc failed: %s", hipGetErrorString(err)); return (int)err; }
-  memset(pinned, 0, (size_t)total);
-  memcpy(pinned, table, sizeof(uint32_t) * 2 * (size_t)B);
-  for (int b = 0; b < B; ++b) memcpy(pinned + table[2 * b], data[b], (size_t)nbytes[b]);
   const uint32_t* table_dev = reinterpret_cast<const uint32_t*>(stream_dev);
   const long sw = (long)L * kLaneStateWords + 1;               // state words per image
   int rc = TDVC_OK;
-  err = hipMemcpyAsync(stream_dev, pinned, (size_t)total, hipMemcpyHostToDevice, st);
+  // table | containers; the padding between them stays as it is: the kernels read a container's length table and payload only
+  hipError_t err = hipMemcpyAsync(stream_dev, table, sizeof(uint32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, st);
+  for (int b = 0; b < B && err == hipSuccess; ++b) err = hipMemcpyAsync(stream_dev + table[2 * b], data[b], (size_t)nbytes[b], hipMemcpyHostToDevice, st);
   if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: upload failed: %s", hipGetErrorString(err)); rc = (int)err; }
   if (rc == TDVC_OK) rc = tdvc_ar_lanes_init_batch(stream_dev, total, table_dev, B, L, state_dev, stream);
   long o = 0;
@@ -930,7 +580,7 @@ extern "C" int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const i
                                            ncdfs, state_dev, y_hat, sym_dev, idx_dev, o, stream);
     o += n;
   }
-  uint32_t* bad = reinterpret_cast<uint32_t*>(pinned);        // the table's place, once the upload is done (stream order): B words
+  uint32_t* bad = table;                                       // the table's place, once its upload is done (stream order): B words
   if (rc == TDVC_OK) {
     err = hipMemcpy2DAsync(bad, sizeof(uint32_t), state_dev + (long)L * kLaneStateWords, sizeof(uint32_t) * (size_t)sw, sizeof(uint32_t), (size_t)B,
                            hipMemcpyDeviceToHost, st);
@@ -946,6 +596,5 @@ extern "C" int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const i
         rc = TDVC_EINVAL;
         break;
       }
-  (void)hipHostFree(pinned);
   return rc;
 }

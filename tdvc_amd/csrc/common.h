@@ -22,9 +22,8 @@ int tdvc_scratch_pages(const void** zeros, void** dump);
 // closed by tdvc_note_launch() (from tdvc_launch_status), which is what tdvc_last_launch_predicated() reports
 const int* tdvc_launch_predicate();
 void tdvc_note_launch();
-// launch counter (lib.cpp): tdvc_note_launch() counts the launch it closes, tdvc_count_launch() one that no tdvc_launch_status() closes;
-// the context-loop drivers report the difference over a call through tdvc_ar_last_loop_launches()
-void tdvc_count_launch();
+// launch counter (lib.cpp): tdvc_note_launch() counts the launch it closes; the context-loop drivers report the difference over a
+// call through tdvc_ar_last_loop_launches()
 long tdvc_launch_count();
 void tdvc_set_loop_launches(long n);
 struct TdvcLoopLaunches {

@@ -16,7 +16,7 @@ void tdvc_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int tdvc_abi_version(void) { return 9; }   // 9: batched context loop (tdvc_ar_*_batch), tdvc_ar_last_loop_launches; 8: per-image launch predicate, tdvc_frames_changed, out-of-place bcast_T; 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
+extern "C" int tdvc_abi_version(void) { return 10; }   // 10: a single image is B = y_hat->N = 1 of the tdvc_ar_*_batch entry points; removed: tdvc_ar_gather, tdvc_ar_quantize, tdvc_ar_indexes, tdvc_ar_lanes_init, tdvc_ar_decode_lanes_step, tdvc_ar_decode_serial, tdvc_ar_wavefront, tdvc_ar_wavefront_lanes; 9: batched context loop (tdvc_ar_*_batch), tdvc_ar_last_loop_launches; 8: per-image launch predicate, tdvc_frames_changed, out-of-place bcast_T; 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
 extern "C" const char* tdvc_last_error(void) { return g_err; }
 
 // ---- launch predicate (tdvc_set_predicate): a device flag the predicated kernels (conv_c8, conv_pair, conv_row, avgpool_k) read at
@@ -52,15 +52,13 @@ const int* tdvc_launch_predicate() {
   g_pred_taken = g_pred != nullptr;
   return g_pred;
 }
-// ---- launch counter: kernel enqueues of this thread, for tdvc_ar_last_loop_launches().  tdvc_note_launch() counts the launch it
-// closes; a driver that launches a kernel of its own without closing it counts that one with tdvc_count_launch().
+// ---- launch counter: kernel enqueues of this thread, for tdvc_ar_last_loop_launches().  tdvc_note_launch() counts the launch it closes.
 static thread_local long g_launches = 0, g_loop_launches = 0;
 void tdvc_note_launch() {
   g_pred_last = g_pred_taken;
   g_pred_taken = 0;
   ++g_launches;
 }
-void tdvc_count_launch() { ++g_launches; }
 long tdvc_launch_count() { return g_launches; }
 void tdvc_set_loop_launches(long n) { g_loop_launches = n; }
 extern "C" int64_t tdvc_ar_last_loop_launches(void) { return g_loop_launches; }

@@ -147,7 +147,8 @@ def subpel_conv3x3(cin, cout, r=1):
 LR = dict(act=ACT_LRELU, slope=0.01)
 STREAM_ORDERS = ("raster", "wavefront", "lanes")
 # compress() / decompress() of a batch: True -> one pass of the context loop handles every step's positions of all images in the
-# same launches (tdvc_ar_*_batch; byte for byte the per-image result), False -> one pass per image (the A/B and the fallback)
+# same launches (tdvc_ar_*_batch; byte for byte the per-image result), False -> B passes of one image through the same drivers (the
+# A/B of row-count independence: n rows per step against B * n).  The switch chooses group sizes, not code
 AR_BATCH = True
 
 # host range coding off the critical path (compress(defer=True), VideoCompressor.encode): the coder library releases the GIL
@@ -731,16 +732,12 @@ class Cheng2020Anchor(nn.Module, PackCache):
         y_hat_all = FM.empty(B, H, W, M, dtype=adt, device=dev)
         sym_all = torch.empty((B, H, W, M), dtype=torch.int32, device=dev)
         idx_all = torch.empty((B, H, W, M), dtype=torch.int32, device=dev)
-        # the W + 3(H-1) steps run natively (gather -> context conv -> entropy_parameters -> quantise), for a group of images in the
-        # same launches (tdvc_ar_wavefront_batch) or image by image (tdvc_ar_wavefront)
+        # the W + 3(H-1) steps run natively (gather -> context conv -> entropy_parameters -> quantise), a group of images in the
+        # same launches (tdvc_ar_wavefront_batch)
         b0 = 0
         for g in self._ar_groups(chain["descs"], B, int(sizes.max())):
-            if g > 1:
-                ops.ar_wavefront_batch(None, None, y32.batch(b0, g), y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
-                                       chain["gp"], flat, sizes, M, W, table, idx_all[b0:b0 + g], sym_all[b0:b0 + g])
-            else:
-                ops.ar_wavefront(None, None, y32.batch(b0, 1), y_hat_all.batch(b0, 1), params.batch(b0, 1), chain["x1"], chain["pc"], chain["descs"],
-                                 chain["gp"], flat, sizes, M, W, table, idx_all[b0], sym_all[b0])
+            ops.ar_wavefront_batch(None, None, y32.batch(b0, g), y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
+                                   chain["gp"], flat, sizes, M, W, table, idx_all[b0:b0 + g], sym_all[b0:b0 + g])
             b0 += g
         y_jobs, dbg = [], []
         for b in range(B):
@@ -808,18 +805,14 @@ class Cheng2020Anchor(nn.Module, PackCache):
                     o += g
             return {"x_hat": self._g_s(y_hat_all, per_image) if synth else None, "y_hat": y_hat_all}
         # the per-position chain over staging buffers of one position per image; the loop itself runs natively
-        # (tdvc_ar_decode_serial / tdvc_ar_decode_serial_batch: Python drove it at ~230 us per position)
+        # (tdvc_ar_decode_serial_batch: Python drove it at ~230 us per position)
         chain, pos_table = self._ar_serial(st)
         sym = torch.zeros((B, H, W, M), dtype=torch.int32, device=dev)
         idx = torch.zeros((B, H, W, M), dtype=torch.int32, device=dev)
         b0 = 0
         for g in self._ar_groups(chain["descs"], B, 1):
-            if g > 1:
-                ops.ar_decode_serial_batch(ys[b0:b0 + g], gct, y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
-                                           chain["gp"], pos_table, M, W, table, idx[b0:b0 + g], sym[b0:b0 + g])
-            else:
-                ops.ar_decode_serial(ys[b0], gct, y_hat_all.batch(b0, 1), params.batch(b0, 1), chain["x1"], chain["pc"], chain["descs"],
-                                     chain["gp"], pos_table, M, W, table, idx[b0], sym[b0])
+            ops.ar_decode_serial_batch(ys[b0:b0 + g], gct, y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
+                                       chain["gp"], pos_table, M, W, table, idx[b0:b0 + g], sym[b0:b0 + g])
             b0 += g
         return {"x_hat": self._g_s(y_hat_all, per_image) if synth else None, "y_hat": y_hat_all}
 
@@ -848,8 +841,8 @@ class Cheng2020Anchor(nn.Module, PackCache):
 
     def _decode_wavefront_group(self, members, ys, gct, table, y_hat_all, params, st, lanes):
         """images `members` (indexes into the call's batch, one lane count) of wavefront-ordered y streams in one pass of the loop:
-        tdvc_ar_wavefront[_batch] (range decoder on the host) or with `lanes` tdvc_ar_wavefront_lanes[_batch] (the strings go to the
-        device once, the range decoder runs there).  One member: the single-image drivers."""
+        tdvc_ar_wavefront_batch (range decoder on the host) or with `lanes` tdvc_ar_wavefront_lanes_batch (the strings go to the
+        device once, the range decoder runs there)"""
         dev, M = y_hat_all.t.device, self.M
         H, W, g = y_hat_all.H, y_hat_all.W, len(members)
         flat, sizes, chain = st["flat"], st["sizes"], st["chain"]
@@ -863,20 +856,14 @@ class Cheng2020Anchor(nn.Module, PackCache):
         args = (yh, pr, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, M, W, table, idx, sym)
         if lanes:
             nl = ops.lanes_of(data[0])
-            if g > 1:
-                stream_dev = torch.empty(ops.ar_lanes_batch_layout([len(d) for d in data], nl)[0], dtype=torch.uint8, device=dev)
-                try:
-                    ops.ar_wavefront_lanes_batch(data, gct, stream_dev, ops.ar_lanes_state_batch(nl, g, dev), *args)
-                except ops.L.TdvcStreamError as e:
-                    raise ops.L.TdvcStreamError(f"decompress: image {members[e.image]} of the batch: corrupt or exhausted lane-split stream "
-                                                "(a lane ran out of words or met an impossible code)") from None
-            else:
-                stream_dev = torch.empty((len(data[0]) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
-                ops.ar_wavefront_lanes(data[0], gct, stream_dev, ops.ar_lanes_state(nl, dev), *args)
-        elif g > 1:
-            ops.ar_wavefront_batch(data, gct, None, *args)
+            stream_dev = torch.empty(ops.ar_lanes_batch_layout([len(d) for d in data], nl)[0], dtype=torch.uint8, device=dev)
+            try:
+                ops.ar_wavefront_lanes_batch(data, gct, stream_dev, ops.ar_lanes_state_batch(nl, g, dev), *args)
+            except ops.L.TdvcStreamError as e:
+                raise ops.L.TdvcStreamError(f"decompress: image {members[e.image]} of the batch: corrupt or exhausted lane-split stream "
+                                            "(a lane ran out of words or met an impossible code)") from None
         else:
-            ops.ar_wavefront(data[0], gct, None, *args)
+            ops.ar_wavefront_batch(data, gct, None, *args)
         if scatter:
             y_hat_all.t[members] = yh.t
 

@@ -475,7 +475,7 @@ def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=
               res2: FM | None = None, gdn=GDN_NONE, aux: FM | None = None, square=False, out_dtype=None,
               round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0):
     """the `tdvc_conv_desc` a conv() call would launch, without launching it (native loops re-launch fixed descriptors:
-    `tdvc_ar_decode_serial`).  -> (descriptor, result FM / tensor, Ho, Wo, layer form used, layer as recorded)
+    `tdvc_ar_decode_serial_batch`).  -> (descriptor, result FM / tensor, Ho, Wo, layer form used, layer as recorded)
 
     An fp32 input FM selects the fp32 form of the layer (fp32 weights, v_mfma_f32_32x32x2_f32: the fp32 islands of
     pnet.py:33,57); `out_dtype=None` allocates the output in the input's dtype."""
@@ -1189,7 +1189,7 @@ class CdfTables:
         self._dev = {}
 
     def device(self, dev):
-        """device copies for the on-device range decoder (tdvc_ar_decode_lanes_step), made once per device: every table's
+        """device copies for the on-device range decoder (tdvc_ar_decode_lanes_step_batch), made once per device: every table's
         entries end to end as uint16 (a table's last entry, 1 << 16, wraps to 0: the kernel implies it), padded to a
         multiple of 8; per table its start in that array, its size, its offset -> (cdf16, starts, sizes, offsets)"""
         dev = torch.device(dev)
@@ -1240,33 +1240,6 @@ class RansDecoder:
         self.close()
 
 
-def ar_decode_serial(data: bytes, t: CdfTables, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM, pos_table: torch.Tensor,
-                     M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
-    """the decoder's serial context loop of one image (`tdvc_ar_decode_serial`); fills y_hat, sym, idx"""
-    buf = np.frombuffer(data, dtype=np.uint8)
-    arr = (L.ConvDesc * len(descs))(*descs)
-    dy, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
-    L.check(L.lib().tdvc_ar_decode_serial(buf.ctypes.data, buf.size, t.cdf.ctypes.data, t.stride, t.sizes.ctypes.data, t.offsets.ctypes.data,
-                                          C.byref(dy), C.byref(dp), C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg),
-                                          pos_table.data_ptr(), pos_table.shape[0], M, W, scale_table.data_ptr(), scale_table.numel(),
-                                          idx.data_ptr(), sym.data_ptr(), _stream()), "ar_decode_serial")
-
-
-def ar_wavefront(data: bytes | None, t: CdfTables | None, y: FM | None, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM,
-                 pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
-    """the context loop of one image over anti-diagonals (`tdvc_ar_wavefront`): encoder with `y`, decoder with `data` + `t`"""
-    buf = np.frombuffer(data, dtype=np.uint8) if data is not None else None
-    arr = (L.ConvDesc * len(descs))(*descs)
-    ss = np.ascontiguousarray(step_sizes, dtype=np.int32)
-    dyh, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
-    dy = y.desc() if y is not None else None
-    L.check(L.lib().tdvc_ar_wavefront(buf.ctypes.data if buf is not None else None, buf.size if buf is not None else 0,
-                                      t.cdf.ctypes.data if t else None, t.stride if t else 0, t.sizes.ctypes.data if t else None,
-                                      t.offsets.ctypes.data if t else None, C.byref(dy) if dy is not None else None, C.byref(dyh), C.byref(dp),
-                                      C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W,
-                                      scale_table.data_ptr(), scale_table.numel(), idx.data_ptr(), sym.data_ptr(), _stream()), "ar_wavefront")
-
-
 LANE_COUNTS = (64, 128)          # what the device decoder of a lane-split stream takes
 
 
@@ -1305,54 +1278,8 @@ def lanes_of(data: bytes) -> int:
     return data[2]
 
 
-def ar_lanes_state(lanes: int, device) -> torch.Tensor:
-    """device buffer of the lane states + the sticky error word (its last element) for `ar_decode_lanes_step`"""
-    return torch.zeros(int(L.lib().tdvc_ar_lanes_state_bytes(int(lanes))) // 4, dtype=torch.int32, device=device)
-
-
-def ar_lanes_init(stream_dev: torch.Tensor, nbytes: int, lanes: int, state: torch.Tensor) -> None:
-    """lane states from the length table of the container in `stream_dev` (uint8, device)"""
-    assert stream_dev.dtype == torch.uint8 and stream_dev.numel() >= nbytes and state.numel() * 4 >= L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
-    L.check(L.lib().tdvc_ar_lanes_init(stream_dev.data_ptr(), nbytes, int(lanes), state.data_ptr(), _stream()), "ar_lanes_init")
-
-
-def ar_decode_lanes_step(gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, stream_dev: torch.Tensor, nbytes: int, lanes: int,
-                         t: CdfTables, state: torch.Tensor, y_hat: FM, symbols: torch.Tensor, indexes: torch.Tensor, cbase: int) -> None:
-    """one step of the on-device decoder of a lane-split stream (`tdvc_ar_decode_lanes_step`): the range decoder, the CDF
-    indexes and the quantiser's write-back of `npos` positions; symbols / indexes rows cbase .. cbase + npos of [..][M]"""
-    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
-    assert stream_dev.dtype == torch.uint8 and stream_dev.numel() >= nbytes and state.numel() * 4 >= L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
-    assert symbols.numel() >= (cbase + npos) * y_hat.C and indexes.numel() >= (cbase + npos) * y_hat.C and pos.numel() >= 2 * npos
-    dg, dh = gp.desc(), y_hat.desc()
-    L.check(L.lib().tdvc_ar_decode_lanes_step(C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(), stream_dev.data_ptr(), nbytes,
-                                              int(lanes), cdf16.data_ptr(), cdf16.numel(), starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(),
-                                              sizes.numel(), state.data_ptr(), C.byref(dh), symbols.data_ptr(), indexes.data_ptr(), cbase, _stream()),
-            "ar_decode_lanes_step")
-
-
-def ar_wavefront_lanes(data: bytes, t: CdfTables, stream_dev: torch.Tensor, state: torch.Tensor, y_hat: FM, params: FM, x1: FM, pc: FM,
-                       descs: list, gp: FM, pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor,
-                       idx: torch.Tensor, sym: torch.Tensor) -> None:
-    """the decoder's context loop of one image for a lane-split stream (`tdvc_ar_wavefront_lanes`): the string is uploaded once
-    into `stream_dev`, every step's range decoding runs on the device, one stream wait at the end"""
-    buf = np.frombuffer(data, dtype=np.uint8)
-    lanes = lanes_of(data)
-    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
-    assert stream_dev.dtype == torch.uint8 and state.numel() * 4 >= L.lib().tdvc_ar_lanes_state_bytes(lanes)
-    assert sym.numel() >= y_hat.H * y_hat.W * M and idx.numel() >= y_hat.H * y_hat.W * M
-    arr = (L.ConvDesc * len(descs))(*descs)
-    ss = np.ascontiguousarray(step_sizes, dtype=np.int32)
-    dyh, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
-    L.check(L.lib().tdvc_ar_wavefront_lanes(buf.ctypes.data, buf.size, stream_dev.data_ptr(), stream_dev.numel(), state.data_ptr(),
-                                            cdf16.data_ptr(), cdf16.numel(), starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), C.byref(dyh),
-                                            C.byref(dp),
-                                            C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W,
-                                            scale_table.data_ptr(), scale_table.numel(), idx.data_ptr(), sym.data_ptr(), _stream()),
-            "ar_wavefront_lanes")
-
-
-# ---- the batched context loop (tdvc_ar_*_batch): a step's positions of all B images in the same launches.  y / y_hat / params are
-# FMs with N = B; row b * npos + k of x1 / pc / gp is position k of image b; symbols / indexes are [B][H][W][M] or [B][H * W][M].
+# ---- the context loop (tdvc_ar_*_batch): a step's positions of all B images of a call in the same launches; one image is B = 1.
+# y / y_hat / params are FMs with N = B; row b * npos + k of x1 / pc / gp is position k of image b; symbols / indexes are [B][H][W][M] or [B][H * W][M].
 def ar_last_loop_launches() -> int:
     """kernel enqueues of this thread's last context-loop call (`tdvc_ar_last_loop_launches`), conv launches included"""
     return int(L.lib().tdvc_ar_last_loop_launches())
@@ -1381,7 +1308,7 @@ def ar_batch_ok(descs: list, g: int, nmax: int) -> bool:
 
 
 def ar_batch_groups(descs: list, B: int, nmax: int) -> list:
-    """B images as the largest groups `ar_batch_ok` allows, in order -> the group sizes (they add up to B); 1 = the per-image loop"""
+    """B images as the largest groups `ar_batch_ok` allows, in order -> the group sizes (they add up to B)"""
     out, left = [], B
     while left > 0:
         g = next(g for g in range(left, 0, -1) if ar_batch_ok(descs, g, nmax))
@@ -1428,7 +1355,7 @@ def _host_strings(strings):
 
 def ar_wavefront_batch(strings, t: CdfTables | None, y: FM | None, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM,
                        pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
-    """the context loop of the B = y_hat.N images of a batch in one pass (`tdvc_ar_wavefront_batch`): encoder with `y` (idx / sym
+    """the context loop of the B = y_hat.N images over anti-diagonals in one pass (`tdvc_ar_wavefront_batch`): encoder with `y` (idx / sym
     raster [B][H][W][M]), decoder with `strings` (B byte strings) + `t` (idx / sym [B][H * W][M] in wavefront order)"""
     B = y_hat.N
     assert sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
@@ -1447,8 +1374,8 @@ def ar_wavefront_batch(strings, t: CdfTables | None, y: FM | None, y_hat: FM, pa
 
 def ar_decode_serial_batch(strings, t: CdfTables, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM, pos_table: torch.Tensor,
                            M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
-    """the raster-order decoder over the B = y_hat.N images at once, B rows per position (`tdvc_ar_decode_serial_batch`);
-    idx / sym [B][H][W][M]"""
+    """the decoder's serial context loop for raster-ordered streams over the B = y_hat.N images at once, B rows per position
+    (`tdvc_ar_decode_serial_batch`); fills y_hat, idx / sym [B][H][W][M]"""
     B = y_hat.N
     assert len(strings) == B and sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
     assert pos_table.shape[0] == y_hat.H * y_hat.W
@@ -1473,7 +1400,7 @@ def ar_lanes_batch_layout(sizes, lanes: int):
 
 
 def ar_lanes_pack_batch(strings, lanes: int, device):
-    """the B containers packed as the batched lane kernels read them -> (device uint8 buffer: table | containers, table as numpy)"""
+    """the B containers packed as the lane kernels read them -> (device uint8 buffer: table | containers, table as numpy)"""
     total, table = ar_lanes_batch_layout([len(s) for s in strings], lanes)
     host = np.zeros(total, dtype=np.uint8)
     host[:table.nbytes] = table.reshape(-1).view(np.uint8)
@@ -1483,7 +1410,7 @@ def ar_lanes_pack_batch(strings, lanes: int, device):
 
 
 def ar_lanes_state_batch(lanes: int, B: int, device) -> torch.Tensor:
-    """[B][lanes * 4 + 1] int32: per image the lane states and the sticky error word"""
+    """[B][lanes * 4 + 1] int32: per image the lane states and the sticky error word (the row's last element)"""
     return torch.zeros((B, int(L.lib().tdvc_ar_lanes_state_bytes(int(lanes))) // 4), dtype=torch.int32, device=device)
 
 
@@ -1496,7 +1423,9 @@ def ar_lanes_init_batch(streams_dev: torch.Tensor, B: int, lanes: int, state: to
 
 def ar_decode_lanes_step_batch(gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, streams_dev: torch.Tensor, lanes: int, t: CdfTables,
                                state: torch.Tensor, y_hat: FM, symbols: torch.Tensor, indexes: torch.Tensor, cbase: int) -> None:
-    """one step of the on-device decoder over B = y_hat.N lane-split streams (`tdvc_ar_decode_lanes_step_batch`), B workgroups"""
+    """one step of the on-device decoder over B = y_hat.N lane-split streams (`tdvc_ar_decode_lanes_step_batch`), B workgroups: the
+    range decoder, the CDF indexes and the quantiser's write-back of `npos` positions; symbols / indexes rows cbase .. cbase + npos
+    of every image's block of [B][H * W][M]"""
     cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
     assert streams_dev.dtype == torch.uint8 and state.numel() * 4 >= y_hat.N * L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
     assert pos.numel() >= 2 * npos and _ar_rows_ok(symbols, y_hat, cbase, npos) and _ar_rows_ok(indexes, y_hat, cbase, npos)
@@ -1510,7 +1439,8 @@ def ar_decode_lanes_step_batch(gp: FM, pos: torch.Tensor, npos: int, table: torc
 def ar_wavefront_lanes_batch(strings, t: CdfTables, stream_dev: torch.Tensor, state: torch.Tensor, y_hat: FM, params: FM, x1: FM, pc: FM,
                              descs: list, gp: FM, pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor,
                              idx: torch.Tensor, sym: torch.Tensor) -> None:
-    """the decoder's context loop of B = y_hat.N lane-split streams of one lane count in one pass (`tdvc_ar_wavefront_lanes_batch`);
+    """the decoder's context loop of B = y_hat.N lane-split streams of one lane count in one pass (`tdvc_ar_wavefront_lanes_batch`):
+    the strings are uploaded once into `stream_dev`, every step's range decoding runs on the device, one stream wait at the end;
     a damaged stream raises TdvcStreamError (a ValueError) whose `image` is the first image of the call whose error word is set"""
     B = y_hat.N
     lanes = lanes_of(strings[0])
@@ -1532,26 +1462,6 @@ def ar_wavefront_lanes_batch(strings, t: CdfTables, stream_dev: torch.Tensor, st
         e.image = bad.value
         raise e
     L.check(rc, "ar_wavefront_lanes_batch")
-
-
-def ar_gather(y_hat: FM, params: FM, pos: torch.Tensor, npos: int, x1: FM, pc: FM):
-    dy, dp, dx, dc = y_hat.desc(), params.desc(), x1.desc(), pc.desc()
-    L.check(L.lib().tdvc_ar_gather(C.byref(dy), C.byref(dp), pos.data_ptr(), npos, C.byref(dx), C.byref(dc), _stream()), "ar_gather")
-
-
-def ar_quantize(y: FM | None, gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, y_hat: FM, symbols: torch.Tensor,
-                indexes: torch.Tensor, symbols_in: torch.Tensor | None = None):
-    dg, dh = gp.desc(), y_hat.desc()
-    dy = y.desc() if y is not None else None
-    L.check(L.lib().tdvc_ar_quantize(C.byref(dy) if dy is not None else None, C.byref(dg), pos.data_ptr(), npos, table.data_ptr(),
-                                     table.numel(), symbols_in.data_ptr() if symbols_in is not None else None, C.byref(dh),
-                                     symbols.data_ptr(), indexes.data_ptr(), _stream()), "ar_quantize")
-
-
-def ar_indexes(gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, M: int, W: int, indexes: torch.Tensor):
-    dg = gp.desc()
-    L.check(L.lib().tdvc_ar_indexes(C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(), M, W,
-                                    indexes.data_ptr(), _stream()), "ar_indexes")
 
 
 def round_symbols(z: FM, median: torch.Tensor) -> torch.Tensor:

@@ -1,4 +1,4 @@
-"""Batched context loop, the parts that need no GPU: the ABI, the batched drivers' argument checks (every rejection is made before
+"""The context loop (tdvc_ar_*_batch; one image is B = 1), the parts that need no GPU: the ABI, the drivers' argument checks (every rejection is made before
 anything touches a device: TDVC_EINVAL with a message, never a HIP error code) and the row-count guard -- the table of kernels
 tdvc_conv_select names for the loop's four conv descriptors, and the grouping built on it."""
 import ctypes as C
@@ -16,11 +16,14 @@ EINVAL = -1
 BATCH_SYMBOLS = ["tdvc_ar_gather_batch", "tdvc_ar_quantize_batch", "tdvc_ar_indexes_batch", "tdvc_ar_wavefront_batch", "tdvc_ar_decode_serial_batch",
                  "tdvc_ar_lanes_batch_layout", "tdvc_ar_lanes_init_batch", "tdvc_ar_decode_lanes_step_batch", "tdvc_ar_wavefront_lanes_batch",
                  "tdvc_ar_last_loop_launches"]
+# the single-image entry points ABI 10 removed: B = y_hat->N = 1 of the above is the single image
+REMOVED_SYMBOLS = ["tdvc_ar_gather", "tdvc_ar_quantize", "tdvc_ar_indexes", "tdvc_ar_lanes_init", "tdvc_ar_decode_lanes_step", "tdvc_ar_decode_serial",
+                   "tdvc_ar_wavefront", "tdvc_ar_wavefront_lanes"]
 
 
 def test_abi_and_symbols():
     lib = L.lib()
-    assert lib.tdvc_abi_version() >= 9
+    assert lib.tdvc_abi_version() >= 10
     for s in BATCH_SYMBOLS:
         assert hasattr(lib, s) and s in L.SIGNATURES, s
     for f in ("ar_gather_batch", "ar_quantize_batch", "ar_indexes_batch", "ar_wavefront_batch", "ar_decode_serial_batch", "ar_lanes_init_batch",
@@ -30,10 +33,17 @@ def test_abi_and_symbols():
     assert lib.tdvc_ar_last_loop_launches() >= 0
 
 
+def test_single_image_entry_points_are_gone():
+    lib = L.lib()
+    for s in REMOVED_SYMBOLS:
+        assert not hasattr(lib, s), f"{s} is still exported"
+        assert s not in L.SIGNATURES, f"{s} still has a signature"
+        assert not hasattr(ops, s[len("tdvc_"):]), f"ops.{s[len('tdvc_'):]} is still there"
+
+
 # ---------------------------------------------------------------- driver validation
-# an 8 x 8 grid, B = 3: fmaps over dummy addresses (never dereferenced: every call below is rejected before a device is touched)
-HG, WG, B = 8, 8, 3
-CAP = B * 3                                                           # staging rows: B x the largest step (3 positions at 8 x 8)
+# an 8 x 8 grid, B = 3 or 1: fmaps over dummy addresses (never dereferenced: every call below is rejected before a device is touched)
+HG, WG = 8, 8
 
 
 def chain_descs(rows=1, f32=False):
@@ -64,10 +74,11 @@ def lane_string(lanes, seed):
 
 
 class Call:
-    """the arguments of one batched driver, valid by default; `run(**edits)` -> (rc, message)"""
+    """the arguments of one driver for B images, valid by default; `run()` -> (rc, message)"""
 
-    def __init__(self, driver):
+    def __init__(self, driver, B):
         self.driver = driver
+        CAP = B * 3                                                   # staging rows: B x the largest step (3 positions at 8 x 8)
         self.fm = dict(y=H.fmap(L, H.PX, B, HG, WG, M, dtype=L.F32), y_hat=H.fmap(L, H.PY, B, HG, WG, M), params=H.fmap(L, H.PAUX, B, HG, WG, 2 * M),
                        x1=H.fmap(L, H.PR1, 1, 1, CAP, 12 * M), pc=H.fmap(L, H.PR2, 1, 1, CAP, 4 * M), gp=H.fmap(L, H.PW, 1, 1, CAP, 2 * M, dtype=L.F32))
         self.sizes = wavefront_sizes(HG, WG)
@@ -108,48 +119,49 @@ class Call:
 DRIVERS = ["tdvc_ar_wavefront_batch", "tdvc_ar_decode_serial_batch", "tdvc_ar_wavefront_lanes_batch"]
 
 
-@pytest.mark.parametrize("driver", DRIVERS)
-def test_driver_rejects_before_touching_a_device(driver):
+# B = 3 under the ids the cases had before a single image became B = 1 of these drivers; B = 1 as "<driver>-B1"
+@pytest.mark.parametrize("driver,B", [pytest.param(d, B, id=d if B == 3 else d + "-B1") for B in (3, 1) for d in DRIVERS])
+def test_driver_rejects_before_touching_a_device(driver, B):
     def rejected(c, word):
         rc, msg = c.run()
         assert rc == EINVAL, f"{driver}: rc {rc} ({msg}): a HIP error code means the call reached a device"
         assert driver in msg and word in msg, msg
 
     for name in ("y_hat", "params", "x1", "pc", "gp"):
-        c = Call(driver)
+        c = Call(driver, B)
         c.null = (name,)
         rejected(c, "null")
     for bad in (0, -2):
-        c = Call(driver)
+        c = Call(driver, B)
         c.B = bad
         rejected(c, "images expected")
-    c = Call(driver)                                                  # the steps do not cover H x W
+    c = Call(driver, B)                                               # the steps do not cover H x W
     if driver == "tdvc_ar_decode_serial_batch":
         c.sizes = c.sizes[:-1]
     else:
         c.sizes = c.sizes.copy()
         c.sizes[5] -= 1
     rejected(c, "cover every position")
-    c = Call(driver)                                                  # B * n beyond the staging width
+    c = Call(driver, B)                                               # B * n beyond the staging width
     width = B * int(c.sizes.max()) - 1                                # one row short of the largest step of the batch
     for k in ("x1", "pc", "gp"):
         c.fm[k].W = width
     rejected(c, "exceed the staging buffers")
     for k in ("x1", "pc", "gp"):                                      # each buffer alone, too
-        c = Call(driver)
+        c = Call(driver, B)
         c.fm[k].W = width
         rejected(c, "exceed the staging buffers")
-    c = Call(driver)                                                  # a batch of another size than the fmaps'
+    c = Call(driver, B)                                               # a batch of another size than the fmaps'
     c.fm["y_hat"].N = B - 1
     rejected(c, "fmaps of B")
 
 
 def test_lanes_driver_rejects_unequal_lane_counts_and_bad_strings():
-    c = Call("tdvc_ar_wavefront_lanes_batch")
+    c = Call("tdvc_ar_wavefront_lanes_batch", 3)
     c.strings[1] = lane_string(128, 9)[0]
     rc, msg = c.run()
     assert rc == EINVAL and "image 1 declares 128 lanes, image 0 64" in msg, (rc, msg)
-    c = Call("tdvc_ar_wavefront_lanes_batch")
+    c = Call("tdvc_ar_wavefront_lanes_batch", 3)
     c.strings[2] = c.strings[2][:-4]                                  # the length table no longer adds up
     rc, msg = c.run()
     assert rc == EINVAL and "image 2" in msg, (rc, msg)

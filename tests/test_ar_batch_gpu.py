@@ -1,6 +1,6 @@
-"""Batched context loop on the MI355X path (tdvc_ar_*_batch, coder.AR_BATCH): a step's positions of all B images in the same
-launches.  Nothing about the arithmetic or the stream formats changes, so every comparison here is exact -- torch.equal,
-np.array_equal, == on bytes -- against the single-image kernels and the per-image loop."""
+"""The context loop on the MI355X path (tdvc_ar_*_batch, coder.AR_BATCH): a step's positions of all B images in the same
+launches, one image being B = 1.  All of it is exact arithmetic, so every comparison here is exact -- torch.equal, np.array_equal,
+== on bytes -- against a torch reference of the kernels, the host range decoder and the per-image loop (B calls of one image)."""
 import json
 import os
 import sys
@@ -47,11 +47,60 @@ def window(B, H, W, Cc, dtype, windowed, fill):
     return ops.FM(big).batch(1, B).ch(32, Cc)
 
 
-@pytest.mark.parametrize("windowed", [False, True])
-@pytest.mark.parametrize("f32", [False, True])
-def test_gather_batch(f32, windowed):
+def dense(fm):
+    """the (N, H, W, C) values an FM addresses, as a strided view of its buffer (writes go to the buffer)"""
+    return torch.as_strided(fm.t, (fm.N, fm.H, fm.W, fm.C), (fm.sn, fm.W * fm.sp, fm.sp, 1), fm.t.storage_offset() + fm.off)
+
+
+def with_b1(names, cases):
+    """parametrise over `cases` and B in (3, 1).  B = 3 runs under the ids the cases had before a single image became B = 1 of the same
+    kernels, B = 1 under the id with "-B1" appended"""
+    return pytest.mark.parametrize(names + ",B", [pytest.param(*c, B, id="-".join(str(v) for v in c) + ("" if B == 3 else "-B1"))
+                                                  for B in (3, 1) for c in cases])
+
+
+# ---- what the kernels compute, in torch: moves, one fp32 subtraction, round half to even, one fp32 addition, comparisons -- all exact
+TAPS = [(-2, -2), (-2, -1), (-2, 0), (-2, 1), (-2, 2), (-1, -2), (-1, -1), (-1, 0), (-1, 1), (-1, 2), (0, -2), (0, -1)]      # the type-A 5x5 mask
+
+
+def ref_gather(y_hat, params, pos):
+    """y_hat (B, H, W, M), params (B, H, W, 2M), pos [(h, w)] -> x1 rows (B * n, 12 * M), pc rows (B * n, 2M): row b * n + k, tap t =
+    y_hat[b, h + dy_t, w + dx_t] if that lies in rows >= 0 and columns 0 .. W - 1, else zeros"""
+    B, H, W, Mc = y_hat.shape
+    x1 = torch.zeros((B, len(pos), 12, Mc), dtype=y_hat.dtype, device=y_hat.device)
+    pc = torch.empty((B, len(pos), params.shape[3]), dtype=params.dtype, device=params.device)
+    for k, (h, w) in enumerate(pos):
+        for t, (dy, dx) in enumerate(TAPS):
+            if h + dy >= 0 and 0 <= w + dx < W:
+                x1[:, k, t] = y_hat[:, h + dy, w + dx]
+        pc[:, k] = params[:, h, w]
+    return x1.view(B * len(pos), 12 * Mc), pc.view(B * len(pos), -1)
+
+
+def ref_scale_index(scale, table):
+    """ntable - 1 - #{j < ntable - 1 : max(s, 0.11) <= table[j]} (tests/test_ar_lanes_gpu.py: host_scale_index)"""
+    s = scale.float().clamp(min=0.11)
+    return (table.numel() - 1 - (s[..., None] <= table[:-1]).sum(-1)).to(torch.int32)
+
+
+def ref_quantize(y, gp_rows_, pos, table, adt, symbols_in=None):
+    """y (B, H, W, M) fp32 or None, gp rows (B, n, 2M) [scales | means], symbols_in (B, n, M) or None
+    -> per position of the list: q (B, n, M) int32, y_hat values (B, n, M) in `adt`, CDF indexes (B, n, M) int32"""
+    Mc = gp_rows_.shape[2] // 2
+    scale, mean = gp_rows_[..., :Mc], gp_rows_[..., Mc:]
+    if symbols_in is not None:
+        q = symbols_in
+    else:
+        ph, pw = [p[0] for p in pos], [p[1] for p in pos]
+        q = torch.round(y[:, ph, pw] - mean).to(torch.int32)          # one fp32 subtraction, round half to even (rintf)
+    return q, (q.float() + mean).to(adt), ref_scale_index(scale, table)
+
+
+@with_b1("f32,windowed", [(f, w) for f in (False, True) for w in (False, True)])
+def test_gather_batch(f32, windowed, B):
+    """B = 1 with a windowed FM: a batch window whose sn is larger than dense, on one image"""
     from tdvc_amd import ops
-    B, H, W, n = 3, 8, 8, len(POS)
+    H, W, n = 8, 8, len(POS)
     adt = adt_of(f32)
     fill = lambda *s: randn(*s, seed=3 + len(s) + s[-1])
     y_hat, params = window(B, H, W, M, adt, windowed, fill), window(B, H, W, 2 * M, adt, windowed, fill)
@@ -60,16 +109,16 @@ def test_gather_batch(f32, windowed):
     x1 = ops.FM(torch.full((1, 1, cap, 12 * M), -5.0, dtype=adt, device=DEV))
     pc = ops.FM(torch.full((1, 1, cap, 4 * M), -5.0, dtype=adt, device=DEV))
     ops.ar_gather_batch(y_hat, params, pos, n, x1, pc)
+    want_x1, want_pc = ref_gather(dense(y_hat), dense(params), POS)
     for b in range(B):
-        x1_b = ops.FM(torch.full((1, 1, n, 12 * M), -5.0, dtype=adt, device=DEV))
-        pc_b = ops.FM(torch.full((1, 1, n, 4 * M), -5.0, dtype=adt, device=DEV))
-        ops.ar_gather(y_hat.batch(b, 1), params.batch(b, 1), pos, n, x1_b, pc_b)
-        assert torch.equal(x1.t[0, 0, b * n:(b + 1) * n], x1_b.t[0, 0]), f"image {b}: neighbourhoods"
-        assert torch.equal(pc.t[0, 0, b * n:(b + 1) * n], pc_b.t[0, 0]), f"image {b}: params rows"
-        assert bool((x1_b.t == 0).any()) and bool((x1_b.t[0, 0, 3] != 0).all())          # zero fill at the borders, none inside
+        assert torch.equal(x1.t[0, 0, b * n:(b + 1) * n], want_x1[b * n:(b + 1) * n]), f"image {b}: neighbourhoods"
+        assert torch.equal(pc.t[0, 0, b * n:(b + 1) * n, :2 * M], want_pc[b * n:(b + 1) * n]), f"image {b}: params rows"
+        x1_b = x1.t[0, 0, b * n:(b + 1) * n]
+        assert bool((x1_b == 0).any()) and bool((x1_b[3] != 0).all())                     # zero fill at the borders, none inside
     assert bool((x1.t[0, 0, B * n:] == -5).all()) and bool((pc.t[0, 0, :, 2 * M:] == -5).all())        # nothing else was written
     # the images differ, and the windows' surroundings were not read as data
-    assert not torch.equal(x1.t[0, 0, :n], x1.t[0, 0, n:2 * n]) and not bool((x1.t[0, 0, :B * n] == 777).any())
+    assert B == 1 or not torch.equal(x1.t[0, 0, :n], x1.t[0, 0, n:2 * n])
+    assert not bool((x1.t[0, 0, :B * n] == 777).any())
 
 
 def gp_rows(nrows, seed):
@@ -80,11 +129,11 @@ def gp_rows(nrows, seed):
     return torch.from_numpy(np.concatenate([scale, mean], 1))
 
 
-@pytest.mark.parametrize("f32", [False, True])
-def test_quantize_and_indexes_batch(coder, f32):
+@with_b1("f32", [(False,), (True,)])
+def test_quantize_and_indexes_batch(coder, f32, B):
     from tdvc_amd import ops
     table = coder._coder_tables()[2]
-    B, H, W, n = 3, 8, 8, len(POS)
+    H, W, n = 8, 8, len(POS)
     adt = adt_of(f32)
     pos = torch.tensor(POS, dtype=torch.int32, device=DEV)
     ph, pw = pos[:, 0].long(), pos[:, 1].long()
@@ -94,16 +143,13 @@ def test_quantize_and_indexes_batch(coder, f32):
     sym_in = torch.randint(-40, 40, (B, H, W, M), dtype=torch.int32, device=DEV)
     cbase = 7
     for use_in in (False, True):
-        # per image, the single-image kernels (raster arrays)
+        # the torch reference, scattered into raster arrays and a windowed y_hat whose surroundings stay as they were
+        q, yv, ci = ref_quantize(dense(y), gp.t[0, 0, :B * n].view(B, n, 2 * M), POS, table, adt, symbols_in=sym_in[:, ph, pw] if use_in else None)
         want_yh = window(B, H, W, M, adt, True, lambda *s: torch.zeros(*s))
+        dense(want_yh)[:, ph, pw] = yv
         want_sym = torch.full((B, H, W, M), -9, dtype=torch.int32, device=DEV)
-        want_idx, want_idx2 = torch.full_like(want_sym, -9), torch.full_like(want_sym, -9)
-        for b in range(B):
-            gp_b = ops.FM(gp.t[:, :, b * n:(b + 1) * n])
-            ops.ar_quantize(None if use_in else y.batch(b, 1), gp_b, pos, n, table, want_yh.batch(b, 1), want_sym[b], want_idx[b],
-                            symbols_in=sym_in[b] if use_in else None)
-            ops.ar_indexes(gp_b, pos, n, table, M, W, want_idx2[b])
-        assert torch.equal(want_idx, want_idx2)
+        want_idx = torch.full_like(want_sym, -9)
+        want_sym[:, ph, pw], want_idx[:, ph, pw] = q, ci
         for compact in (False, True):
             yh = window(B, H, W, M, adt, True, lambda *s: torch.zeros(*s))
             shape = (B, H * W, M) if compact else (B, H, W, M)
@@ -124,7 +170,8 @@ def test_quantize_and_indexes_batch(coder, f32):
             else:
                 ws, wi = want_sym, want_idx
             assert torch.equal(sym, ws) and torch.equal(idx, wi) and torch.equal(idx2, wi), what
-        assert bool((want_idx[:, ph, pw] >= 0).all()) and not torch.equal(want_sym[0], want_sym[1])          # written, and the images differ
+        assert bool((want_idx[:, ph, pw] >= 0).all()) and (B == 1 or not torch.equal(want_sym[0], want_sym[1]))          # written, and the images differ
+        assert int(ci.min()) == 0 and int(ci.max()) == table.numel() - 1 and bool((dense(want_yh) != 0).any())            # both ends of the table
 
 
 def lane_case(coder, seed):
@@ -150,43 +197,42 @@ def lane_case(coder, seed):
     return dict(scale=scale, mean=mean, idx=idx, sym=sym, bypass=(v < 0) | (v >= size - 2))
 
 
-@pytest.mark.parametrize("f32", [False, True])
-@pytest.mark.parametrize("lanes", [64, 128])
-def test_lane_decoder_batch(coder, lanes, f32):
+@with_b1("lanes,f32", [(l, f) for f in (False, True) for l in (64, 128)])
+def test_lane_decoder_batch(coder, lanes, f32, B):
     from tdvc_amd import ops
     _, gct, table = coder._coder_tables()
-    B, steps, npos = 3, [1, 3, 40], 44
+    steps, npos = [1, 3, 40], 44
     adt = adt_of(f32)
     cases = [lane_case(coder, 11 + 7 * b) for b in range(B)]
-    assert not np.array_equal(cases[0]["sym"], cases[1]["sym"])
+    assert B == 1 or not np.array_equal(cases[0]["sym"], cases[1]["sym"])
     perm = np.random.default_rng(1).permutation(64)[:npos]
     pos = torch.from_numpy(np.stack([perm // 8, perm % 8], 1).astype(np.int32)).to(DEV)          # one list for all images
     datas = []
     for k in cases:
         assert k["bypass"].reshape(npos, M // lanes, lanes).any((0, 1)).all(), "a lane without a bypass symbol"
         datas.append(ops.rans_encode_lanes(k["sym"], k["idx"], gct, lanes))
-    assert len({len(d) for d in datas}) > 1 or datas[0] != datas[1]
+    assert B == 1 or len({len(d) for d in datas}) > 1 or datas[0] != datas[1]
     rows = [torch.from_numpy(np.concatenate([k["scale"], k["mean"]], 1)).to(DEV) for k in cases]
-    # three runs of the single-image kernel
+    # every image alone: a call of B = 1 with its own packed buffer and state
     single = []
     for b in range(B):
-        data = datas[b]
-        sd = torch.zeros((len(data) + 15) // 16 * 16, dtype=torch.uint8, device=DEV)
-        sd[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(DEV)
-        state = ops.ar_lanes_state(lanes, DEV)
-        ops.ar_lanes_init(sd, len(data), lanes, state)
+        sd, _ = ops.ar_lanes_pack_batch([datas[b]], lanes, DEV)
+        state = ops.ar_lanes_state_batch(lanes, 1, DEV)
+        ops.ar_lanes_init_batch(sd, 1, lanes, state)
         gp = ops.FM.empty(1, 1, max(steps), 2 * M, dtype=torch.float32, device=DEV)
         yh = ops.FM.zeros(1, 8, 8, M, dtype=adt, device=DEV)
-        sym_d = torch.full((npos, M), -12345, dtype=torch.int32, device=DEV)
-        idx_d = torch.full((npos, M), -12345, dtype=torch.int32, device=DEV)
+        sym_d = torch.full((64, M), -12345, dtype=torch.int32, device=DEV)
+        idx_d = torch.full((64, M), -12345, dtype=torch.int32, device=DEV)
         o = 0
         for n in steps:
             gp.t.view(-1, 2 * M)[:n] = rows[b][o:o + n]
-            ops.ar_decode_lanes_step(gp, pos[o:], n, table, sd, len(data), lanes, gct, state, yh, sym_d, idx_d, o)
+            ops.ar_decode_lanes_step_batch(gp, pos[o:], n, table, sd, lanes, gct, state, yh, sym_d, idx_d, o)
             o += n
-        single.append((sym_d, idx_d, yh.t, state))
-        assert np.array_equal(sym_d.cpu().numpy(), cases[b]["sym"]) and np.array_equal(idx_d.cpu().numpy(), cases[b]["idx"])
-    # one run of the batched kernel: B workgroups, rows image-major, y_hat a batch window of a larger buffer
+        single.append((sym_d, idx_d, yh.t, state[0]))
+        assert np.array_equal(sym_d[:npos].cpu().numpy(), cases[b]["sym"]) and np.array_equal(idx_d[:npos].cpu().numpy(), cases[b]["idx"])
+        want_yh = (torch.from_numpy(cases[b]["sym"]).float() + torch.from_numpy(cases[b]["mean"])).to(adt)          # q + mean in fp32, then y_hat's type
+        assert torch.equal(yh.t[0, pos[:, 0].long(), pos[:, 1].long()].cpu(), want_yh), f"image {b}: y_hat"
+    # all images in one call: B workgroups, rows image-major, y_hat a batch window of a larger buffer
     streams, tab = ops.ar_lanes_pack_batch(datas, lanes, DEV)
     assert all(off % 16 == 0 for off, _ in tab)
     state = ops.ar_lanes_state_batch(lanes, B, DEV)
@@ -206,8 +252,8 @@ def test_lane_decoder_batch(coder, lanes, f32):
     torch.cuda.synchronize()
     for b in range(B):
         s_sym, s_idx, s_yh, s_state = single[b]
-        assert torch.equal(sym_d[b, :npos], s_sym), f"image {b}: symbols"
-        assert torch.equal(idx_d[b, :npos], s_idx), f"image {b}: indexes"
+        assert torch.equal(sym_d[b], s_sym), f"image {b}: symbols"
+        assert torch.equal(idx_d[b], s_idx), f"image {b}: indexes"
         assert torch.equal(big[1 + b:2 + b], s_yh), f"image {b}: y_hat"
         assert torch.equal(state[b], s_state), f"image {b}: final lane states"
         assert int(state[b, -1]) == 0
@@ -255,7 +301,7 @@ def test_coder_batched_equals_per_image(coder, monkeypatch, H, W, B, f32, report
         set_batch(monkeypatch, True)
         dec_b = m.decompress(enc_b["strings"], enc_b["shape"], synth=False, f32=f32, order=order)
         assert torch.equal(dec_b["y_hat"].t, dec_s["y_hat"].t) and torch.equal(dec_b["y_hat"].t, want), f"{order}: decoder y_hat"
-        # crosswise, every image alone through compress() / decompress() (B = 1: the single-image drivers): what the batched
+        # crosswise, every image alone through compress() / decompress() (calls of B = 1): what the batched
         # encoder wrote decodes one image at a time, what one-image encoders wrote decodes as a batch
         for b in range(B):
             d1 = m.decompress([[enc_b["strings"][0][b]], [enc_b["strings"][1][b]]], enc_b["shape"], synth=False, f32=f32, order=order)
@@ -266,7 +312,7 @@ def test_coder_batched_equals_per_image(coder, monkeypatch, H, W, B, f32, report
     report(f"batched context loop {H}x{W} B={B} f32={f32}: strings, y_hat, symbols, indexes equal the per-image loop's in all three orders, both directions")
 
 
-LOOPS = ("ar_wavefront", "ar_wavefront_batch", "ar_wavefront_lanes", "ar_wavefront_lanes_batch", "ar_decode_serial", "ar_decode_serial_batch")
+LOOPS = ("ar_wavefront_batch", "ar_wavefront_lanes_batch", "ar_decode_serial_batch")
 
 
 @pytest.fixture
@@ -287,7 +333,9 @@ def loop_calls(monkeypatch):
 
 
 def test_launch_count(coder, monkeypatch, loop_calls, report):
-    """a batch of 3 costs the launches of one image: six per step for the encoder (gather, four convs, quantise)"""
+    """a batch of 3 costs the launches of one image: six per step for the encoder (gather, four convs, quantise); the decoders: seven
+    per step on the host range decoder (indexes and quantise apart), a step being a position in raster order, and six per step plus
+    the lane-state initialisation with the range decoder on the device"""
     from tdvc_amd import ops
     m = coder
     x, xf = batch_input(3, 64, 64)
@@ -308,10 +356,12 @@ def test_launch_count(coder, monkeypatch, loop_calls, report):
         (nb, cb), = run(xf, True, order, dec)
         per_image = run(xf, False, order, dec)
         report(f"loop launches {'decode ' + order if dec else 'encode'}: B=1 {c1} ({n1}), B=3 batched {cb} ({nb}), B=3 per image {[c for _, c in per_image]}")
-        assert c1 > 0 and cb == c1 and nb == n1 + "_batch"
+        assert c1 > 0 and cb == c1 and nb == n1
         assert per_image == [(n1, c1)] * 3 and sum(c for _, c in per_image) == 3 * c1
         if not dec:
             assert c1 == 6 * nsteps
+        else:
+            assert c1 == {"wavefront": 7 * nsteps, "raster": 7 * 4 * 4, "lanes": 6 * nsteps + 1}[order]
 
 
 def test_mixed_lane_counts(coder, monkeypatch):

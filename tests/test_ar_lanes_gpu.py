@@ -1,4 +1,4 @@
-"""Lane-split y streams (order="lanes") on the MI355X path: the on-device range decoder (ar_decode_lanes_kernel) against the
+"""Lane-split y streams (order="lanes") on the MI355X path: the on-device range decoder (ar_decode_lanes_batch_kernel) against the
 host decoder that shares its decode routine, the coder and frame round trips against the "wavefront" order (same symbols,
 same y_hat, bit for bit), and the error report of a damaged stream.  Every comparison is an exact integer / bit comparison."""
 import io
@@ -29,7 +29,7 @@ def coders():
 
 
 def host_scale_index(scale, table):
-    """GaussianConditional.build_indexes as ar_quantize_kernel states it: ntable - 1 - #{j < ntable - 1: max(s, 0.11) <= table[j]}"""
+    """GaussianConditional.build_indexes as ar_quantize_batch_kernel states it: ntable - 1 - #{j < ntable - 1: max(s, 0.11) <= table[j]}"""
     s = np.maximum(scale.astype(np.float32), np.float32(0.11))
     return (table.size - 1 - (s[..., None] <= table[None, None, :-1]).sum(-1)).astype(np.int32)
 
@@ -77,36 +77,36 @@ def test_decode_kernel_equals_host_decoder(coders, kernel_case, lanes, f32, repo
     assert np.array_equal(ops.rans_decode_lanes(data, idx, gct), sym)
     dev = "cuda"
     adt = torch.float32 if f32 else torch.float16
-    stream_dev = torch.zeros((len(data) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
-    stream_dev[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
-    state = ops.ar_lanes_state(lanes, dev)
-    ops.ar_lanes_init(stream_dev, len(data), lanes, state)
+    stream_dev, _ = ops.ar_lanes_pack_batch([data], lanes, dev)                # one image: B = 1 of the entry points
+    state = ops.ar_lanes_state_batch(lanes, 1, dev)
+    ops.ar_lanes_init_batch(stream_dev, 1, lanes, state)
     pos = torch.from_numpy(k["pos"]).to(dev)
     gp = ops.FM.empty(1, 1, max(steps), 2 * M, dtype=torch.float32, device=dev)
     rows = torch.from_numpy(np.concatenate([k["scale"], k["mean"]], 1)).to(dev)
     y_hat, y_want = ops.FM.zeros(1, 8, 8, M, dtype=adt, device=dev), ops.FM.zeros(1, 8, 8, M, dtype=adt, device=dev)
-    sym_d = torch.full((npos, M), -12345, dtype=torch.int32, device=dev)
-    idx_d = torch.full((npos, M), -12345, dtype=torch.int32, device=dev)
-    # what tdvc_ar_quantize writes, given those symbols (its arrays are raster [H][W][M])
-    sym_r = torch.zeros((8, 8, M), dtype=torch.int32, device=dev)
-    sym_r[pos[:, 0].long(), pos[:, 1].long()] = torch.from_numpy(sym).to(dev)
+    sym_d = torch.full((64, M), -12345, dtype=torch.int32, device=dev)           # compact rows of the image's H * W block
+    idx_d = torch.full((64, M), -12345, dtype=torch.int32, device=dev)
+    # what tdvc_ar_quantize_batch writes, given those symbols (raster arrays [1][H][W][M])
+    sym_r = torch.zeros((1, 8, 8, M), dtype=torch.int32, device=dev)
+    sym_r[0, pos[:, 0].long(), pos[:, 1].long()] = torch.from_numpy(sym).to(dev)
     sym_q, idx_q = torch.zeros_like(sym_r), torch.zeros_like(sym_r)
     o = 0
     for n in steps:                                                           # three launches on one state buffer
         gp.t.view(-1, 2 * M)[:n] = rows[o:o + n]
-        ops.ar_decode_lanes_step(gp, pos[o:], n, table, stream_dev, len(data), lanes, gct, state, y_hat, sym_d, idx_d, o)
-        ops.ar_quantize(None, gp, pos[o:], n, table, y_want, sym_q, idx_q, symbols_in=sym_r)
+        ops.ar_decode_lanes_step_batch(gp, pos[o:], n, table, stream_dev, lanes, gct, state, y_hat, sym_d, idx_d, o)
+        ops.ar_quantize_batch(None, gp, pos[o:], n, table, y_want, sym_q, idx_q, symbols_in=sym_r)
         o += n
     torch.cuda.synchronize()
-    st = state.cpu().numpy().view(np.uint32)
+    st = state[0].cpu().numpy().view(np.uint32)                               # image 0's lane states and error word
     report(f"lane decode kernel L={lanes} f32={f32}: {npos * M} symbols, {int(k['bypass'].sum())} bypass, {len(data)} B; bad word {st[-1]}; "
            f"words consumed {int((st[:-1].reshape(lanes, 4)[:, 2]).max())} of {(len(data) - 4 - 2 * lanes) // 4}")
     assert st[-1] == 0
-    assert np.array_equal(sym_d.cpu().numpy(), sym), "symbols differ from the host decoder's"
-    assert np.array_equal(idx_d.cpu().numpy(), idx), "CDF indexes differ from scale_index on the host"
-    assert torch.equal(y_hat.t, y_want.t), "y_hat differs from tdvc_ar_quantize's"
+    assert np.array_equal(sym_d[:npos].cpu().numpy(), sym), "symbols differ from the host decoder's"
+    assert np.array_equal(idx_d[:npos].cpu().numpy(), idx), "CDF indexes differ from scale_index on the host"
+    assert bool((sym_d[npos:] == -12345).all()) and bool((idx_d[npos:] == -12345).all())
+    assert torch.equal(y_hat.t, y_want.t), "y_hat differs from tdvc_ar_quantize_batch's"
     assert bool((y_hat.t != 0).any())
-    assert torch.equal(idx_q[pos[:, 0].long(), pos[:, 1].long()].cpu(), torch.from_numpy(idx))
+    assert torch.equal(idx_q[0, pos[:, 0].long(), pos[:, 1].long()].cpu(), torch.from_numpy(idx))
     # every lane has read its sub-stream to the end, and no further
     assert np.array_equal(st[:-1].reshape(lanes, 4)[:, 2], st[:-1].reshape(lanes, 4)[:, 3])
 

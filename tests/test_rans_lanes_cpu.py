@@ -170,9 +170,9 @@ def test_abi_version_covers_the_lane_entry_points():
     assert lib.tdvc_abi_version() >= 6
     assert lib.tdvc_ar_lanes_state_bytes(64) == 4 * (4 * 64 + 1)
     # the device entry points validate before they touch the GPU
-    assert lib.tdvc_ar_lanes_init(None, 0, 64, None, None) != 0
-    assert lib.tdvc_ar_wavefront_lanes(None, 0, None, 0, None, None, 0, None, None, None, 0, None, None, None, None, None, 0, None, None, None, 0, 0, 0,
-                                       None, 0, None, None, None) != 0
+    assert lib.tdvc_ar_lanes_init_batch(None, 0, None, 1, 64, None, None) != 0
+    assert lib.tdvc_ar_wavefront_lanes_batch(None, None, 1, None, 0, None, None, 0, None, None, None, 0, None, None, None, None, None, 0, None, None, None, 0,
+                                             0, 0, None, 0, None, None, None, None) != 0
 
 
 def test_standalone_program_under_address_and_ub_sanitizers(tmp_path):

@@ -58,7 +58,7 @@ with torch.no_grad():
         sym = torch.zeros((Hl, Wl, 128), dtype=torch.int32, device="cuda")
         idx = torch.zeros((Hl, Wl, 128), dtype=torch.int32, device="cuda")
         sync(); t4 = time.time()
-        ops.ar_wavefront(None, None, y32, y_hat, params, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, 128, Wl, table, idx, sym)
+        ops.ar_wavefront_batch(None, None, y32, y_hat, params, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, 128, Wl, table, idx, sym)
         t5h = time.time()
         sync(); t5 = time.time()
         s_np, i_np = sym.cpu().numpy(), idx.cpu().numpy()
