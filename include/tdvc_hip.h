@@ -87,6 +87,11 @@ typedef struct {
                              chan_sum[n][row][cout] for row < tdvc_conv_chan_sum_rows(d) (fp32; every row is written) -- the
                              SELayer's global average pool (inflate.py:204) without a second pass over y.  Only the convs for which
                              tdvc_conv_chan_sum_rows() returns > 0 accept it. */
+  tdvc_fmap flow;         /* ABI 11.  p != NULL: an fp32 map of >= 2 channels and the output's geometry whose channel 0 is added to the even
+                             and channel 1 to the odd output channels of its pixel, AFTER the bias + activation + residuals + fp16 rounding
+                             of today: stored = fp16(float(fp16 result) + flow) -- byte for byte the conv followed by tdvc_add_flow
+                             (pnet.py:163), without the pass over y.  Only the convs for which tdvc_conv_flow_supported() returns 1
+                             accept it (the lean epilogue of conv_mfma_v5), not together with chan_sum.  p == NULL: nothing changes. */
 } tdvc_conv_desc;
 
 /* ---------------------------------------------------------------- library */
@@ -150,6 +155,10 @@ int tdvc_conv2d(const tdvc_conv_desc* d, void* stream);
 /* Rows per image of tdvc_conv_desc::chan_sum this conv would write, 0 when its kernel has no fused channel sum (the caller then
  * runs tdvc_channel_sum over y), < 0 on a malformed descriptor.  `chan_sum` itself is ignored here. */
 int tdvc_conv_chan_sum_rows(const tdvc_conv_desc* d);
+/* ABI 11.  1 when the kernel tdvc_conv2d would dispatch this descriptor to honours tdvc_conv_desc::flow, else 0 (the caller then runs
+ * tdvc_add_flow over y); < 0 on a malformed descriptor.  Asked with flow.p == NULL it answers for the kernel alone; with a map given,
+ * the map's dtype, channels and geometry count too.  Same validation and selection as tdvc_conv2d, never touches the device. */
+int tdvc_conv_flow_supported(const tdvc_conv_desc* d);
 /* ABI 5.  Name of the kernel tdvc_conv2d would dispatch this descriptor to -- what tdvc_last_conv_kernel() reports after the
  * launch -- or NULL with tdvc_last_error() set when tdvc_conv2d would reject it.  Same validation and selection, no launch:
  * never touches the device (the pointers are only checked for alignment), the launch-parity state or tdvc_last_conv_kernel();
@@ -232,6 +241,12 @@ int tdvc_fmap_to_nchw(const tdvc_fmap* x, int C, float* dst, void* stream);
  * gate NULL => no scaling.  Used for SE scaling (main/model/inflate.py:204-208) and plain add/sub. */
 int tdvc_scale_act_res(const tdvc_fmap* a, const float* gate, int act, float slope,
                        const tdvc_fmap* r, float r_sign, const tdvc_fmap* y, const tdvc_fmap* y2, void* stream);
+/* ABI 11.  The same y, and a second result from it in the same pass: y3 = fp16(float(b) + b_sign * float(y)) on the ROUNDED y -- byte for
+ * byte what tdvc_scale_act_res(b, NULL, NONE, 0, y, b_sign, y3, NULL) computes after reading y back (the residual the
+ * residual coder codes, `f_cur - pred`, out of LoopFilter's last pass).  fp16 maps of one geometry and channel count (C % 8 == 0), each with its own strides;
+ * y3 must not alias a, r or y. */
+int tdvc_scale_act_res3(const tdvc_fmap* a, const float* gate, int act, float slope, const tdvc_fmap* r, float r_sign,
+                        const tdvc_fmap* y, const tdvc_fmap* b, float b_sign, const tdvc_fmap* y3, void* stream);
 /* offset[c] += flow[c & 1] (main/model/pnet.py:163); off fp16 in place, flow fp32 2-channel fmap. */
 int tdvc_add_flow(const tdvc_fmap* off, const tdvc_fmap* flow, void* stream);
 /* x[:, t] = lrelu(x[:, t] + b) for the T channel-slices of width b.C (pnet.py:313-314). */
@@ -251,6 +266,11 @@ int tdvc_se_gate(const float* partial, int nblocks, float inv_count, int N, int 
 int tdvc_upsample2x(const tdvc_fmap* x, const tdvc_fmap* y, void* stream);
 /* 2x2 average pooling, fp32 fmap -> fp32 fmap (F.avg_pool2d, main/model/flownet.py:103-114). */
 int tdvc_avgpool2(const tdvc_fmap* x, const tdvc_fmap* y, void* stream);
+/* ABI 11.  Five chained tdvc_avgpool2 levels of two maps in ONE launch (SPyNet's two image pyramids, flownet.py:103-114): xa / xb are
+ * fp32 maps of one geometry with H and W multiples of 32; ya / yb are arrays of five fp32 maps each, level k (0-based) of
+ * (H >> (k + 1)) x (W >> (k + 1)) pixels, all of the same channel count C <= 4 (<= the inputs').  Every level is computed from the
+ * fp32 values of the level above with tdvc_avgpool2's expression: byte for byte the ten chained calls. */
+int tdvc_avgpool2_pyramid(const tdvc_fmap* xa, const tdvc_fmap* xb, const tdvc_fmap* ya, const tdvc_fmap* yb, void* stream);
 /* One SPyNet level's input assembly — the "bilinear warp" of the path
  * (main/model/flownet.py:119-138 + flow_warp :8-48):
  *   flow_up = 2 * bilinear_x2(flow_lo, align_corners=True)   (zeros if flow_lo == NULL)

@@ -31,7 +31,7 @@ class ConvDesc(C.Structure):
                 ("ck", C.c_int32), ("square_input", C.c_int32), ("gdn", C.c_int32),
                 ("aux", FMapDesc), ("act", C.c_int32), ("slope", C.c_float),
                 ("round_before_act", C.c_int32), ("res", FMapDesc), ("res2", FMapDesc), ("out_mode", C.c_int32), ("s2d", C.c_int32),
-                ("bcast_T", C.c_int32), ("bcast_slope", C.c_float), ("chan_sum", C.c_void_p)]
+                ("bcast_T", C.c_int32), ("bcast_slope", C.c_float), ("chan_sum", C.c_void_p), ("flow", FMapDesc)]
 
 
 class DcnDesc(C.Structure):
@@ -60,6 +60,9 @@ SIGNATURES = {
     "tdvc_abi_version": (_i, []),
     "tdvc_conv_chan_sum_rows": (_i, [C.POINTER(ConvDesc)]),
     "tdvc_conv_select": (C.c_char_p, [C.POINTER(ConvDesc)]),
+    "tdvc_conv_flow_supported": (_i, [C.POINTER(ConvDesc)]),
+    "tdvc_scale_act_res3": (_i, [_FM, _P, _i, _f, _FM, _f, _FM, _FM, _f, _FM, _P]),
+    "tdvc_avgpool2_pyramid": (_i, [_FM, _FM, _FM, _FM, _P]),
     "tdvc_last_error": (C.c_char_p, []),
     "tdvc_last_conv_kernel": (C.c_char_p, []),
     "tdvc_prepare_device": (_i, []),

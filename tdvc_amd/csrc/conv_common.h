@@ -21,12 +21,13 @@ struct ConvParams {
   float* csum;                      // conv_mfma_v5 only: partial channel sums of the stored values (tdvc_conv_desc::chan_sum), or null
   int8_t tap_dy[TDVC_MAX_TAPS], tap_dx[TDVC_MAX_TAPS];
   const int* pred;                  // conv_c8 only: launch predicate (tdvc_set_predicate), or null.  Last: no other field moves
+  FMap flow;                        // conv_mfma_v5 only: fp32 flow added to the rounded output (tdvc_conv_desc::flow), p == null: none.  Behind pred: no other field moves
 };
 
 // ---- host side: what the kernels' eligibility predicates and launchers share (the dispatch table is in conv_dispatch.hip) ------
 // Kernel switches.  conv_on(id) is 0 when TDVC_CONV_V1 or the switch's own TDVC_CONV_NO_* variable is set, else what the
 // tdvc_debug_enable_* setter last stored: 1 by default; for conv_row a mask of its four geometries (15 by default).
-enum ConvSwitch { SW_NONE = -1, SW_V2, SW_V3, SW_V5, SW_V7, SW_V9, SW_V10, SW_V11, SW_ROW, SW_C8, SW_N16, SW_GDN128, SW_COUNT };
+enum ConvSwitch { SW_NONE = -1, SW_V2, SW_V3, SW_V5, SW_V7, SW_V9, SW_V10, SW_V11, SW_ROW, SW_C8, SW_N16, SW_GDN128, SW_HEAD3, SW_COUNT };
 int conv_on(int id);
 long conv_v9_work_limit();      // pixels x output channels above which a v3-eligible layer stays on v3 (tdvc_debug_set_conv_v9_work_limit)
 
@@ -335,7 +336,10 @@ __device__ __forceinline__ void epilogue_store_row(const ConvParams& p, const Pa
 // slices are read there and written at y (the out-of-place form: res is a source, never a residual); same arithmetic, same traffic.
 // CSUM (conv_mfma_v5, tdvc_conv_desc::chan_sum): the lane also adds the values it stores (channels 8 (lane & 7) .. + 8 of four pixels per row)
 // into cs[0..7].
-template <int NTX, bool BIAS_IN_ACC, bool BCAST = false, bool CSUM = false>
+// FLOW (conv_mfma_v5, tdvc_conv_desc::flow): the fp16 value the row would store is widened, the pixel's fp32 flow added (x to even, y to
+// odd channels) and the sum rounded once -- add_flow_kernel's load8 / v[j] += (j & 1) ? fy : fx / store8 on that value: bit-identical to
+// the conv followed by tdvc_add_flow, without the pass over y.
+template <int NTX, bool BIAS_IN_ACC, bool BCAST = false, bool CSUM = false, bool FLOW = false>
 __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&acc)[2][NTX], const float* bias64, unsigned char* ew, int n,
                                                   int cbase, int oy_first, int ox_first, int lane, bool zero_acc, bool full, float* cs = nullptr) {
   constexpr int EPS = 144;
@@ -377,6 +381,16 @@ __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&
     if (has2) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) r2[k] = *reinterpret_cast<const half8*>(rb2 + (long)opix[k] * p.res2.sp);
+    }
+    float fx[4], fy[4];
+    if constexpr (FLOW) {
+      const float* fb = reinterpret_cast<const float*>(p.flow.p) + (long)n * p.flow.sn;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float* fp = fb + (long)opix[k] * p.flow.sp;        // pixel 0 where the lane stores nothing: a valid address
+        fx[k] = fp[0];
+        fy[k] = fp[1];
+      }
     }
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -429,6 +443,14 @@ __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&
       half8 v = *reinterpret_cast<const half8*>(ew + (k * 8 + prow) * EPS + chunk * 16);
       if (has1) v = v + r1[k];
       if (has2) v = v + r2[k];
+      if constexpr (FLOW) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float s = (float)v[j];
+          s += (j & 1) ? fy[k] : fx[k];
+          v[j] = (half_t)s;
+        }
+      }
       if (ok[k]) *reinterpret_cast<half8*>(yb + (long)opix[k] * p.y.sp) = v;
       if constexpr (CSUM) {
 #pragma unroll

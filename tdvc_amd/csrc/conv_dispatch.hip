@@ -29,8 +29,8 @@ int conv_f32_validate(const tdvc_conv_desc* d, int& Ho, int& Wo);
 // to the next kernel of the table.
 namespace {
 const char* const kSwitchEnv[convk::SW_COUNT] = {nullptr, "TDVC_CONV_NO_V3", "TDVC_CONV_NO_V5", "TDVC_CONV_NO_V7", "TDVC_CONV_NO_V9", "TDVC_CONV_NO_V10",
-                                                 "TDVC_CONV_NO_V11", "TDVC_CONV_NO_ROW", "TDVC_CONV_NO_C8", "TDVC_CONV_NO_N16", "TDVC_CONV_NO_GDN128"};
-int g_enabled[convk::SW_COUNT] = {1, 1, 1, 1, 1, 1, 1, 15, 1, 1, 1};       // conv_row: one bit per geometry (conv_row_geometry)
+                                                 "TDVC_CONV_NO_V11", "TDVC_CONV_NO_ROW", "TDVC_CONV_NO_C8", "TDVC_CONV_NO_N16", "TDVC_CONV_NO_GDN128", "TDVC_CONV_NO_HEAD3"};
+int g_enabled[convk::SW_COUNT] = {1, 1, 1, 1, 1, 1, 1, 15, 1, 1, 1, 1};       // conv_row: one bit per geometry (conv_row_geometry)
 long g_v9_work_limit = 1L << 20;
 }  // namespace
 
@@ -53,6 +53,8 @@ extern "C" void tdvc_debug_enable_conv_row(int mask) { g_enabled[convk::SW_ROW] 
 extern "C" void tdvc_debug_enable_conv_c8(int enable) { g_enabled[convk::SW_C8] = enable != 0; }
 extern "C" void tdvc_debug_enable_conv_n16(int enable) { g_enabled[convk::SW_N16] = enable != 0; }
 extern "C" void tdvc_debug_enable_gdn128(int enable) { g_enabled[convk::SW_GDN128] = enable != 0; }
+// conv_n16's RGB-head form (conv_head3.hip): off, the layer runs on conv_n16's own kernel; the name the dispatch reports does not change
+extern "C" void tdvc_debug_enable_conv_head3(int enable) { g_enabled[convk::SW_HEAD3] = enable != 0; }
 extern "C" void tdvc_debug_set_conv_v9_work_limit(long v) { g_v9_work_limit = v; }
 
 // ---- the table ---------------------------------------------------------------------------------------------------------------
@@ -250,27 +252,46 @@ int next_walk_reverse() {
   return g_walk_mode == 1 ? (int)(g_walk_parity++ & 1u) : 0;
 }
 
-// query_rows: validate and select as tdvc_conv2d would, but return the rows of tdvc_conv_desc::chan_sum instead of launching
-int conv2d_impl(const tdvc_conv_desc* d, void* stream, bool query_rows) {
+// tdvc_conv_desc::flow: honoured by the lean epilogue of conv_mfma_v5 (any number of 64-channel blocks), not together with chan_sum
+bool conv_flow_ok(const tdvc_conv_desc* d, const Entry* e, const ConvParams& p) {
+  return e && e->name == kNameV5 && p.simple == 2 && !d->chan_sum;
+}
+// the map itself: fp32, >= 2 channels, the output's geometry
+bool flow_map_ok(const tdvc_conv_desc* d, int Ho, int Wo) {
+  return fmap_ok32(d->flow) && d->flow.C >= 2 && d->flow.N == d->x.N && d->flow.H == Ho && d->flow.W == Wo;
+}
+constexpr char kFlowMsg[] = "tdvc_conv2d: flow on a conv whose kernel does not add it (tdvc_conv_flow_supported() == 0), with chan_sum, or not an fp32 map of >= 2 channels and the output's geometry";
+
+enum Query { LAUNCH = 0, QUERY_ROWS = 1, QUERY_FLOW = 2 };
+// QUERY_ROWS / QUERY_FLOW: validate and select as tdvc_conv2d would, but return the rows of tdvc_conv_desc::chan_sum / whether the kernel
+// honours tdvc_conv_desc::flow instead of launching
+int conv2d_impl(const tdvc_conv_desc* d, void* stream, int query) {
+  const bool query_rows = query == QUERY_ROWS;
   TDVC_CHECK(d, "tdvc_conv2d: null descriptor");
   if (d->x.dtype == TDVC_F32) {           // fp32 islands (pnet.py:33,57): fp32 activations + fp32 packing -> conv_f32.hip
-    if (query_rows) return 0;
+    if (query != LAUNCH) return 0;
     TDVC_CHECK(!d->chan_sum, "tdvc_conv2d: chan_sum is not available on the fp32 path (tdvc_conv_chan_sum_rows() == 0)");
+    TDVC_CHECK(!d->flow.p, "tdvc_conv2d: flow is not available on the fp32 path (tdvc_conv_flow_supported() == 0)");
     snprintf(g_last_kernel, sizeof(g_last_kernel), "conv_f32");
     return tdvc_conv2d_f32(d, stream);
   }
   ConvParams p;
   Pick k = {d, 0, 0, -1};
   if (const int rc = prepare(d, p, k.Ho, k.Wo)) return rc;
-  p.reverse = query_rows ? 0 : next_walk_reverse();      // once per launching call, never on a query
+  p.reverse = query != LAUNCH ? 0 : next_walk_reverse();      // once per launching call, never on a query
   const Entry* e = select(k, p);
   // fused channel sums (tdvc_conv_desc::chan_sum): the lean epilogue of conv_mfma_v5 with one block of 64 output channels
   const bool csum_ok = e && e->name == kNameV5 && k.cout_blocks() == 1 && p.simple == 2;
   if (query_rows) return csum_ok ? conv_v5_chan_sum_rows(k.Ho, k.Wo, 1, k.N()) : 0;
+  if (query == QUERY_FLOW) return conv_flow_ok(d, e, p) && (!d->flow.p || flow_map_ok(d, k.Ho, k.Wo)) ? 1 : 0;
   TDVC_CHECK(!d->chan_sum || (csum_ok && (reinterpret_cast<uintptr_t>(d->chan_sum) & 15) == 0),
              "tdvc_conv2d: chan_sum on a conv whose kernel has no fused channel sum (tdvc_conv_chan_sum_rows() == 0) or unaligned");
   p.csum = d->chan_sum;
   if (!e) return TDVC_EINVAL;
+  if (d->flow.p) {
+    TDVC_CHECK(conv_flow_ok(d, e, p) && flow_map_ok(d, k.Ho, k.Wo), "%s", kFlowMsg);
+    p.flow = to_dev(d->flow);
+  }
   kernel_name(e, k, g_last_kernel);
   return e->launch(k, p, reinterpret_cast<hipStream_t>(stream));
 }
@@ -278,8 +299,9 @@ int conv2d_impl(const tdvc_conv_desc* d, void* stream, bool query_rows) {
 }  // namespace
 
 extern "C" void tdvc_debug_set_conv_walk(int mode) { g_walk_mode = mode; }
-extern "C" int tdvc_conv2d(const tdvc_conv_desc* d, void* stream) { return conv2d_impl(d, stream, false); }
-extern "C" int tdvc_conv_chan_sum_rows(const tdvc_conv_desc* d) { return conv2d_impl(d, nullptr, true); }
+extern "C" int tdvc_conv2d(const tdvc_conv_desc* d, void* stream) { return conv2d_impl(d, stream, LAUNCH); }
+extern "C" int tdvc_conv_chan_sum_rows(const tdvc_conv_desc* d) { return conv2d_impl(d, nullptr, QUERY_ROWS); }
+extern "C" int tdvc_conv_flow_supported(const tdvc_conv_desc* d) { return conv2d_impl(d, nullptr, QUERY_FLOW); }
 extern "C" const char* tdvc_last_conv_kernel(void) { return g_last_kernel; }
 
 extern "C" const char* tdvc_conv_select(const tdvc_conv_desc* d) {
@@ -287,6 +309,7 @@ extern "C" const char* tdvc_conv_select(const tdvc_conv_desc* d) {
   if (!d) { tdvc_set_error("tdvc_conv_select: null descriptor"); return nullptr; }
   if (d->x.dtype == TDVC_F32) {
     int Ho, Wo;
+    if (d->flow.p) { tdvc_set_error("%s", kFlowMsg); return nullptr; }
     return conv_f32_validate(d, Ho, Wo) == TDVC_OK ? "conv_f32" : nullptr;
   }
   ConvParams p;
@@ -294,6 +317,7 @@ extern "C" const char* tdvc_conv_select(const tdvc_conv_desc* d) {
   if (prepare(d, p, k.Ho, k.Wo) != TDVC_OK) return nullptr;
   const Entry* e = select(k, p);
   if (!e) return nullptr;
+  if (d->flow.p && !(conv_flow_ok(d, e, p) && flow_map_ok(d, k.Ho, k.Wo))) { tdvc_set_error("%s", kFlowMsg); return nullptr; }
   kernel_name(e, k, name);
   return name;
 }

@@ -29,7 +29,7 @@ struct V5Extra {
 };
 
 // TL = 16-byte loads per lane per stage: 4 for 1x1 (2 x 32 pixels x 4 chunks / 64 lanes)
-template <int SIMPLE, int TL>      // SIMPLE 0: per-register epilogue4, 1: transposed generic, 2: transposed lean
+template <int SIMPLE, int TL>      // SIMPLE 0: per-register epilogue4, 1: transposed generic, 2: transposed lean, 4: lean + broadcast add, 5: lean + flow add
 __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams p, const V5Extra e) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int* tapoff = reinterpret_cast<int*>(smem);
@@ -160,6 +160,9 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
         // lean + broadcast-add over the four slices at y (tdvc_conv_desc::bcast_T): the wave overwrites exactly the pixels whose
         // input channels it has finished reading (1x1: no halo; the prefetched stages belong to other pixels)
         convk::epilogue_lean_seq<WR, false, true>(p, acc, bias_s, tbuf, n, cb * 64, oy0, tx * TW5, lane, true, false);
+      } else if constexpr (SIMPLE == 5) {
+        // lean + the flow added to the rounded output (tdvc_conv_desc::flow)
+        convk::epilogue_lean_seq<WR, false, false, false, true>(p, acc, bias_s, tbuf, n, cb * 64, oy0, tx * TW5, lane, true, false);
       } else if constexpr (SIMPLE) {
         // the private tile doubles as the transpose scratch (this wave's reads of it are complete:
         // every fragment read was waited for before its MFMA)
@@ -215,7 +218,8 @@ inline int v5_tl(int kh, int kw) { return ((WR + kh - 1) * (TW5 + kw - 1) * 4 + 
 
 template <int TL>
 int launch_tl(const ConvParams& q, const V5Extra& e, int mode, dim3 grid, int lds, hipStream_t st) {
-  const auto go = mode == 4 ? convk::launch_big_lds<&conv_mfma_v5_kernel<4, TL>, ConvParams, V5Extra>
+  const auto go = mode == 5 ? convk::launch_big_lds<&conv_mfma_v5_kernel<5, TL>, ConvParams, V5Extra>
+                  : mode == 4 ? convk::launch_big_lds<&conv_mfma_v5_kernel<4, TL>, ConvParams, V5Extra>
                   : mode == 2 ? convk::launch_big_lds<&conv_mfma_v5_kernel<2, TL>, ConvParams, V5Extra>
                   : mode == 1 ? convk::launch_big_lds<&conv_mfma_v5_kernel<1, TL>, ConvParams, V5Extra>
                               : convk::launch_big_lds<&conv_mfma_v5_kernel<0, TL>, ConvParams, V5Extra>;
@@ -252,7 +256,12 @@ int launch_conv_v5(const ConvParams& p, int cout_blocks, int N, hipStream_t st) 
   if (simple) q.slope = convk::conv_simple_slope(p);
   dim3 grid(v5_grid_x(e.nbtiles, cout_blocks, N), cout_blocks, N);
   const int tl = v5_tl(p.kh, p.kw);
-  if (tl == 4) return launch_tl<4>(q, e, p.bcast_T ? 4 : (simple ? (convk::conv_is_lean(p) ? 2 : 1) : 0), grid, lds, st);
+  const bool lean = simple && convk::conv_is_lean(p);
+  if (p.flow.p && !(lean && !p.bcast_T && !p.csum)) {      // the dispatch (conv_flow_ok, conv_dispatch.hip) never sends such a launch here
+    tdvc_set_error("conv v5: flow needs the lean epilogue without channel sums");
+    return TDVC_EINVAL;
+  }
+  if (tl == 4) return launch_tl<4>(q, e, p.bcast_T ? 4 : (p.flow.p ? 5 : (simple ? (lean ? 2 : 1) : 0)), grid, lds, st);
   tdvc_set_error("conv v5: unsupported window %dx%d", p.kh, p.kw);
   return TDVC_EINVAL;
 }

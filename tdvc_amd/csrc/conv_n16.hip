@@ -166,7 +166,16 @@ bool conv_n16_eligible(const tdvc_conv_desc* d, int Ho, int Wo) {
          n16_lds(cin, d->kh, d->kw, d->ntaps, d->cout <= 16 ? 1 : 2) <= 150 * 1024;
 }
 
+// the RGB head's own form of this kernel (conv_head3.hip): same tile, LDS layout and arithmetic, the next tile's loads in flight under the
+// current tile's MFMAs and stores.  tdvc_debug_enable_conv_head3(0) keeps the layer on the kernel above (A/B, tests); the same bytes
+bool conv_head3_takes(const ConvParams& p);
+int launch_conv_head3(const ConvParams& p, int N, hipStream_t st);
+static thread_local int g_n16_last_form = 0;
+extern "C" int tdvc_debug_conv_n16_last_form(void) { return g_n16_last_form; }      // 1: the last conv_n16 launch of this thread ran conv_head3_kernel
+
 int launch_conv_n16(const ConvParams& p, int N, hipStream_t st) {
+  g_n16_last_form = convk::conv_on(convk::SW_HEAD3) && conv_head3_takes(p);
+  if (g_n16_last_form) return launch_conv_head3(p, N, st);
   const int ncb = p.cout <= 16 ? 1 : 2;
   N16Extra e;
   e.ksteps = n16_ksteps(p.ntaps, p.Cin);

@@ -72,12 +72,16 @@ __global__ void scale_act_res_kernel(FMap a, const float* gate, int act, float s
 // thread keeps U independent 16-byte loads (+ U residual loads) in flight, and the gate comes as two float4 loads instead
 // of eight scalar ones -- with one item per thread and eight extra load instructions per item the kernel sat on the L1's
 // instruction rate at 2.3 TB/s.
-template <int U>
-__global__ __launch_bounds__(256) void scale_act_res16_kernel(FMap a, const float* gate, int act, float slope, FMap r, float rs, FMap y, FMap y2,
-                                                              unsigned total, unsigned chunks, unsigned npix) {
+// Y3 (tdvc_scale_act_res3): a second result from the value about to be stored, y3 = b + rs3 * y on the ROUNDED y -- what a further
+// launch of this kernel (a = b, r = y, rs = rs3, no gate, no activation) would compute after reading y back: one more 16-byte load and
+// one more store per item instead of a pass of three.  The plain kernel below is the body with Y3 = false: its code does not change.
+template <int U, bool Y3>
+__device__ __forceinline__ void scale_act_res16_body(const FMap& a, const float* gate, int act, float slope, const FMap& r, float rs, const FMap& y,
+                                                     const FMap& y2, const FMap& b, float rs3, const FMap& y3, unsigned total, unsigned chunks,
+                                                     unsigned npix) {
   const unsigned T = gridDim.x * 256u;
   for (unsigned base = blockIdx.x * 256u + threadIdx.x; base < total; base += U * T) {
-    half8 av[U], rv[U];
+    half8 av[U], rv[U], bv[U];
     unsigned ck[U], nn[U];
     long pa[U];
     bool ok[U];
@@ -92,6 +96,7 @@ __global__ __launch_bounds__(256) void scale_act_res16_kernel(FMap a, const floa
       pa[u] = (long)(pp - nn[u] * npix);
       av[u] = *reinterpret_cast<const half8*>(reinterpret_cast<const half_t*>(a.p) + (long)nn[u] * a.sn + pa[u] * a.sp + ck[u] * 8);
       if (r.p) rv[u] = *reinterpret_cast<const half8*>(reinterpret_cast<const half_t*>(r.p) + (long)nn[u] * r.sn + pa[u] * r.sp + ck[u] * 8);
+      if constexpr (Y3) bv[u] = *reinterpret_cast<const half8*>(reinterpret_cast<const half_t*>(b.p) + (long)nn[u] * b.sn + pa[u] * b.sp + ck[u] * 8);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -119,8 +124,32 @@ __global__ __launch_bounds__(256) void scale_act_res16_kernel(FMap a, const floa
         *reinterpret_cast<half8*>(reinterpret_cast<half_t*>(y.p) + (long)nn[u] * y.sn + pa[u] * y.sp + ck[u] * 8) = h;
         if (y2.p) *reinterpret_cast<half8*>(reinterpret_cast<half_t*>(y2.p) + (long)nn[u] * y2.sn + pa[u] * y2.sp + ck[u] * 8) = h;
       }
+      if constexpr (Y3) {
+        // the separate launch's expression on its operands: v = (float)b; v += rs3 * (float)y (no contraction: -ffp-contract=off)
+        half8 h3;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float w = (float)bv[u][j];
+          w += rs3 * (float)h[j];
+          h3[j] = (half_t)w;
+        }
+        if (ok[u]) *reinterpret_cast<half8*>(reinterpret_cast<half_t*>(y3.p) + (long)nn[u] * y3.sn + pa[u] * y3.sp + ck[u] * 8) = h3;
+      }
     }
   }
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void scale_act_res16_kernel(FMap a, const float* gate, int act, float slope, FMap r, float rs, FMap y, FMap y2,
+                                                              unsigned total, unsigned chunks, unsigned npix) {
+  scale_act_res16_body<U, false>(a, gate, act, slope, r, rs, y, y2, a, 0.f, a, total, chunks, npix);
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void scale_act_res16_y3_kernel(FMap a, const float* gate, int act, float slope, FMap r, float rs, FMap y, FMap b,
+                                                                 float rs3, FMap y3, unsigned total, unsigned chunks, unsigned npix) {
+  const FMap none = {};
+  scale_act_res16_body<U, true>(a, gate, act, slope, r, rs, y, none, b, rs3, y3, total, chunks, npix);
 }
 
 __global__ void add_flow_kernel(FMap off, FMap flow) {
@@ -305,6 +334,58 @@ __global__ void avgpool2_kernel(FMap x, FMap y) {
   const long p00 = ((long)(2 * oy) * x.W + 2 * ox) * x.sp, p10 = p00 + (long)x.W * x.sp;
   for (int c = 0; c < y.C; ++c)
     yp[c] = (xp[p00 + c] + xp[p00 + x.sp + c] + xp[p10 + c] + xp[p10 + x.sp + c]) * 0.25f;
+}
+
+// Five chained avgpool2 levels of TWO maps in one launch (SPyNet's image pyramids, tdvc_avgpool2_pyramid): below the first level the ten
+// separate launches cost their launch latency, not their bytes.  A workgroup owns a 32 x 32 block of one input map: 256 threads
+// write its 16 x 16 level-1 pixels, then 64 / 16 / 4 / 1 of them the 8 x 8 ... 1 x 1 pixels of the next levels from the fp32 values of
+// the level above, kept in LDS.  Every level is avgpool2_kernel's expression on the same operands in the same order: byte-equal to the
+// chained calls.  blockIdx.z = 2 * image + map.  VEC: every map is made of aligned 4-float pixels (the pyramids' own buffers).
+struct PyramidMaps { FMap x[2]; FMap y[2][5]; };
+template <bool VEC>
+__global__ __launch_bounds__(256) void avgpool2_pyramid_kernel(const PyramidMaps a) {
+  __shared__ __attribute__((aligned(16))) float lv[2][16 * 16 * 4];
+  const int m = blockIdx.z & 1, n = blockIdx.z >> 1, tid = threadIdx.x;
+  const int C = a.y[0][0].C;                            // <= 4, the same for every level of both maps (host)
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  {
+    const FMap x = m ? a.x[1] : a.x[0];              // selects, not an indexed copy of the argument block
+    const int ly = tid >> 4, lx = tid & 15;
+    const int oy = blockIdx.y * 16 + ly, ox = blockIdx.x * 16 + lx;
+    const float* xp = reinterpret_cast<const float*>(x.p) + (long)n * x.sn;
+    const long p00 = ((long)(2 * oy) * x.W + 2 * ox) * x.sp, p10 = p00 + (long)x.W * x.sp;
+    if constexpr (VEC) {
+      const f32x4 q00 = *reinterpret_cast<const f32x4*>(xp + p00), q01 = *reinterpret_cast<const f32x4*>(xp + p00 + x.sp);
+      const f32x4 q10 = *reinterpret_cast<const f32x4*>(xp + p10), q11 = *reinterpret_cast<const f32x4*>(xp + p10 + x.sp);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = (q00[c] + q01[c] + q10[c] + q11[c]) * 0.25f;
+    } else {
+      for (int c = 0; c < C; ++c) v[c] = (xp[p00 + c] + xp[p00 + x.sp + c] + xp[p10 + c] + xp[p10 + x.sp + c]) * 0.25f;
+    }
+  }
+  int S = 16;                                           // side of this level's block of output pixels
+#pragma unroll
+  for (int k = 0; k < 5; ++k, S >>= 1) {
+    const int ly = tid / S, lx = tid - ly * S;
+    const bool mine = tid < S * S;
+    float* cur = lv[k & 1];
+    if (k > 0 && mine) {
+      const float* up = lv[(k - 1) & 1] + ((2 * ly) * (2 * S) + 2 * lx) * 4;      // the level above: (2 S) x (2 S) pixels of 4 floats
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = (up[c] + up[4 + c] + up[2 * S * 4 + c] + up[2 * S * 4 + 4 + c]) * 0.25f;
+    }
+    if (mine) {
+      const FMap y = m ? a.y[1][k] : a.y[0][k];
+      float* yp = reinterpret_cast<float*>(y.p) + (long)n * y.sn + ((long)(blockIdx.y * S + ly) * y.W + blockIdx.x * S + lx) * y.sp;
+      if constexpr (VEC) {
+        *reinterpret_cast<f32x4*>(yp) = f32x4{v[0], v[1], v[2], v[3]};
+      } else {
+        for (int c = 0; c < C; ++c) yp[c] = v[c];
+      }
+      *reinterpret_cast<f32x4*>(cur + (ly * S + lx) * 4) = f32x4{v[0], v[1], v[2], v[3]};
+    }
+    if (k < 4) __syncthreads();                         // level k complete in `cur`; the buffer level k read may be overwritten next
+  }
 }
 
 // flow_up (x2, align_corners=True, *2) + border-clamped bilinear warp + 8-channel assembly
@@ -765,6 +846,24 @@ extern "C" int tdvc_scale_act_res(const tdvc_fmap* a, const float* gate, int act
   return tdvc_launch_status("tdvc_scale_act_res");
 }
 
+extern "C" int tdvc_scale_act_res3(const tdvc_fmap* a, const float* gate, int act, float slope, const tdvc_fmap* r, float r_sign,
+                                   const tdvc_fmap* y, const tdvc_fmap* b, float b_sign, const tdvc_fmap* y3, void* stream) {
+  TDVC_CHECK(a && y && b && y3 && fmap_ok16(*a) && fmap_ok16(*y) && same_geom(*a, *y) && y->C == a->C, "tdvc_scale_act_res3: a / y must be fp16 maps of one geometry");
+  if (r) TDVC_CHECK(fmap_ok16(*r) && same_geom(*a, *r) && r->C == a->C, "tdvc_scale_act_res3: bad residual");
+  TDVC_CHECK(fmap_ok16(*b) && same_geom(*a, *b) && b->C == a->C && fmap_ok16(*y3) && same_geom(*a, *y3) && y3->C == a->C,
+             "tdvc_scale_act_res3: b / y3 must be fp16 maps of a's geometry");
+  TDVC_CHECK(y3->p != y->p && y3->p != a->p && (!r || y3->p != r->p), "tdvc_scale_act_res3: y3 must not alias a, r or y");
+  const long total = (long)a->N * a->H * a->W * (a->C / 8);
+  TDVC_CHECK((!gate || aligned16(gate)) && total < (1L << 31) - (1L << 23), "tdvc_scale_act_res3: gate unaligned or map too large");
+  constexpr int U = 4;
+  long blocks = (total + 256 * U - 1) / (256 * U);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(scale_act_res16_y3_kernel<U>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), to_dev(*a), gate, act, slope,
+                     r ? to_dev(*r) : null_fmap(), r_sign, to_dev(*y), to_dev(*b), b_sign, to_dev(*y3), (unsigned)total, (unsigned)(a->C / 8),
+                     (unsigned)((long)a->H * a->W));
+  return tdvc_launch_status("tdvc_scale_act_res3");
+}
+
 extern "C" int tdvc_add_flow(const tdvc_fmap* off, const tdvc_fmap* flow, void* stream) {
   TDVC_CHECK(off && flow && fmap_ok16(*off) && fmap_ok32(*flow) && flow->C >= 2 && same_geom(*off, *flow), "tdvc_add_flow: bad arguments");
   const long total = (long)off->N * off->H * off->W * (off->C / 8);
@@ -812,6 +911,31 @@ extern "C" int tdvc_avgpool2(const tdvc_fmap* x, const tdvc_fmap* y, void* strea
   const long total = (long)y->N * y->H * y->W;
   hipLaunchKernelGGL(avgpool2_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y));
   return tdvc_launch_status("tdvc_avgpool2");
+}
+
+extern "C" int tdvc_avgpool2_pyramid(const tdvc_fmap* xa, const tdvc_fmap* xb, const tdvc_fmap* ya, const tdvc_fmap* yb, void* stream) {
+  TDVC_CHECK(xa && xb && ya && yb && fmap_ok32(*xa) && fmap_ok32(*xb) && same_geom(*xa, *xb), "tdvc_avgpool2_pyramid: two fp32 maps of one geometry");
+  TDVC_CHECK((xa->H % 32) == 0 && (xa->W % 32) == 0, "tdvc_avgpool2_pyramid: H and W must be multiples of 32 (got %dx%d)", xa->H, xa->W);
+  const int C_ = ya[0].C;
+  TDVC_CHECK(C_ >= 1 && C_ <= 4 && C_ <= xa->C && C_ <= xb->C, "tdvc_avgpool2_pyramid: 1 <= C <= 4 channels, not more than the inputs have");
+  auto pix16 = [](const tdvc_fmap& f) { return f.C == 4 && (f.sp % 4) == 0 && (f.sn % 4) == 0 && aligned16(f.p); };             // whole 4-float pixels
+  bool vec = xa->C >= 4 && xb->C >= 4 && (xa->sp % 4) == 0 && (xb->sp % 4) == 0 && (xa->sn % 4) == 0 && (xb->sn % 4) == 0 && aligned16(xa->p) && aligned16(xb->p);
+  PyramidMaps a;
+  a.x[0] = to_dev(*xa);
+  a.x[1] = to_dev(*xb);
+  for (int m = 0; m < 2; ++m)
+    for (int k = 0; k < 5; ++k) {
+      const tdvc_fmap& y = (m ? yb : ya)[k];
+      TDVC_CHECK(fmap_ok32(y) && y.N == xa->N && y.H == xa->H >> (k + 1) && y.W == xa->W >> (k + 1) && y.C == C_,
+                 "tdvc_avgpool2_pyramid: level %d of map %d must be an fp32 map of %d x %d x %d", k + 1, m, xa->H >> (k + 1), xa->W >> (k + 1), C_);
+      vec = vec && pix16(y);
+      a.y[m][k] = to_dev(y);
+    }
+  TDVC_CHECK(2L * xa->N <= 65535, "tdvc_avgpool2_pyramid: batch too large");
+  const dim3 grid(xa->W / 32, xa->H / 32, 2 * xa->N);
+  if (vec) hipLaunchKernelGGL(avgpool2_pyramid_kernel<true>, grid, dim3(256), 0, ST(stream), a);
+  else hipLaunchKernelGGL(avgpool2_pyramid_kernel<false>, grid, dim3(256), 0, ST(stream), a);
+  return tdvc_launch_status("tdvc_avgpool2_pyramid");
 }
 
 extern "C" int tdvc_spynet_level_input(const tdvc_fmap* ref, const tdvc_fmap* supp, const tdvc_fmap* flow_lo,

@@ -79,10 +79,17 @@ class SELayer(nn.Module, PackCache):
     def gate(self, x: FM, partial=None) -> torch.Tensor:
         return ops.se_gate(x, self.params(), partial=partial)
 
-    def run(self, x: FM, out: FM | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None, out2: FM | None = None, sums: list | None = None):
-        """`sums`: what `ops.conv(..., chan_sum=sums)` left when it produced `x` (empty: no fused sums, one more pass over x)"""
+    def run(self, x: FM, out: FM | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None, out2: FM | None = None, sums: list | None = None,
+            then: tuple | None = None):
+        """`sums`: what `ops.conv(..., chan_sum=sums)` left when it produced `x` (empty: no fused sums, one more pass over x);
+        `then` = (b, sign, out3): a second result of the scaling pass, out3 = b + sign * out (`ops.scale_act_res3`)"""
         out = FM.empty(x.N, x.H, x.W, x.C, dtype=x.t.dtype, device=x.t.device) if out is None else out
-        return ops.scale_act_res(x, out, gate=self.gate(x, sums[0] if sums else None), act=act, slope=slope, res=res, out2=out2)
+        gate = self.gate(x, sums[0] if sums else None)
+        if then is not None:
+            assert out2 is None
+            b, b_sign, out3 = then
+            return ops.scale_act_res3(x, out, b, out3, b_sign, gate=gate, act=act, slope=slope, res=res)
+        return ops.scale_act_res(x, out, gate=gate, act=act, slope=slope, res=res, out2=out2)
 
 
 class Res_Block(nn.Module, PackCache):
@@ -116,6 +123,18 @@ def run_stack(stack, x: FM, out: FM | None = None, res2: FM | None = None) -> FM
 
 
 # --------------------------------------------------------------------------------------
+# A/B switches of the glue fusions.  Each replaces launches by a fused form with the same bytes, in inference only: training, the tape,
+# the per-kernel profile (a table of real work) and traced calls keep the separate launches
+PYRAMID_FUSED = True            # SPyNet's two image pyramids in one launch (ops.avgpool2_pyramid) instead of ten avgpool2
+FLOW_EPILOGUE = True            # OffsetGen: the flow added in the level-1 fusion conv's epilogue (ops.conv(..., flow=)) instead of add_flow
+RESID_FUSED = True              # the residual f_cur - pred as a second result of LoopFilter's last pass (ops.scale_act_res3)
+RGB_HEAD = True                 # FeatureFix.featdown on conv_head3 (a tile's loads in flight under the tile before) instead of conv_n16
+
+
+def glue_fusions_allowed(module: nn.Module, traced: bool = False) -> bool:
+    return not module.training and ops.TAPE is None and ops.PROFILE is None and not traced
+
+
 class SPyNetBasicModule(nn.Module):
     def __init__(self):
         super().__init__()
@@ -133,12 +152,17 @@ class SPyNet(nn.Module, PackCache):
         self.register_buffer("mean", torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
         self.register_buffer("std", torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
 
-    def compute_flow(self, ref: FM, supp: FM) -> FM:
-        """ref/supp: fp32 fmaps (C=4), H, W multiples of 32 -> flow fp32 fmap (C=2)"""
-        refs, supps = [ref], [supp]
-        for _ in range(5):
-            refs.append(ops.avgpool2(refs[-1]))
-            supps.append(ops.avgpool2(supps[-1]))
+    def compute_flow(self, ref: FM, supp: FM, fused: bool = False) -> FM:
+        """ref/supp: fp32 fmaps (C=4), H, W multiples of 32 -> flow fp32 fmap (C=2).  `fused` (inference): both image pyramids in
+        one launch instead of ten (PYRAMID_FUSED); the level buffers stay separate maps, their bytes the same"""
+        if fused and PYRAMID_FUSED and ops.avgpool2_pyramid_supported(ref, supp):
+            lr_, ls_ = ops.avgpool2_pyramid(ref, supp)
+            refs, supps = [ref] + lr_, [supp] + ls_
+        else:
+            refs, supps = [ref], [supp]
+            for _ in range(5):
+                refs.append(ops.avgpool2(refs[-1]))
+                supps.append(ops.avgpool2(supps[-1]))
         refs, supps = refs[::-1], supps[::-1]
         dev = ref.t.device
         flow = None
@@ -153,13 +177,13 @@ class SPyNet(nn.Module, PackCache):
             flow = ops.conv(x, pk_conv(self, f"l{lvl}c4", bm[4].conv), res=up, out_dtype=torch.float32)
         return flow
 
-    def run(self, ref: FM, supp: FM) -> FM:
+    def run(self, ref: FM, supp: FM, fused: bool = False) -> FM:
         H, W = ref.H, ref.W
         Hu = H if H % 32 == 0 else 32 * (H // 32 + 1)
         Wu = W if W % 32 == 0 else 32 * (W // 32 + 1)
         if (Hu, Wu) != (H, W):
             ref, supp = ops.resize_bilinear(ref, Hu, Wu), ops.resize_bilinear(supp, Hu, Wu)
-        flow = self.compute_flow(ref, supp)
+        flow = self.compute_flow(ref, supp, fused)
         if (Hu, Wu) != (H, W):
             sc = torch.tensor([float(W) / float(Wu), float(H) / float(Hu)], dtype=torch.float32, device=flow.t.device)
             flow = ops.resize_bilinear(flow, H, W, sc)
@@ -205,10 +229,12 @@ class OffsetGen(nn.Module, PackCache):
         self.attn = SELayer(64)
         self.feat_fusion_ = nn.Conv2d(nf, nf, 3, 1, 1)
 
-    def run(self, feats: FM, cur32: FM, ref32: FM) -> FM:
+    def run(self, feats: FM, cur32: FM, ref32: FM, traced: bool = False) -> FM:
         """feats: (B,H,W,>=128) buffer with [f_cur | f_ref] in channels 0..127;
         cur32 / ref32: fp32 RGB fmaps.  Returns estmv (B,H,W,64) fp16."""
         B, H, W = feats.N, feats.H, feats.W
+        fuse = glue_fusions_allowed(self, traced)
+        flow = None
         dev = feats.t.device
         lr = dict(act=ACT_LRELU, slope=0.1)
         cat1 = feats.ch(0, 128)
@@ -225,6 +251,9 @@ class OffsetGen(nn.Module, PackCache):
         for i in (3, 2, 1):
             lv = f"l{i}"
             c = cats[i]
+            if i == 1 and fuse and FLOW_EPILOGUE:
+                # the flow depends on the two frames only: computed ahead of the level whose fusion conv adds it in its epilogue
+                flow = self.spynet.run(cur32, ref32, fused=fuse)
             o1 = ops.conv(c, pk_conv(self, "c11" + lv, self.offset_conv11[lv]), **lr)
             if i == 3:
                 if ops.conv_pair_supported(o1):            # inference: offset_conv11_1 + offset_conv12 (both LeakyReLU) in one launch
@@ -236,15 +265,16 @@ class OffsetGen(nn.Module, PackCache):
                     off = ops.conv(o1, pk_conv(self, "c12" + lv, self.offset_conv12[lv]), **lr)
             else:
                 ops.conv(o1, pk_conv(self, "c11_1" + lv, self.offset_conv11_1[lv]), out=up_o1.ch(64, 64), **lr)
-                off = ops.conv(up_o1, pk_conv(self, "ff" + lv, self.feat_fusion[lv]), **lr)
+                off = ops.conv(up_o1, pk_conv(self, "ff" + lv, self.feat_fusion[lv]), flow=flow if i == 1 else None, **lr)
             if i > 1:
                 up = ops.upsample2x(off)
                 up_o1 = FM.empty(B, up.H, up.W, 128, device=dev)      # [upsampled_offset | offset1]
                 ops.conv(up, pk_conv(self, "upc", self.upsample_conv), out=up_o1.ch(0, 64))
-        flow = self.spynet.run(cur32, ref32)
-        if ops.TAPE is not None:
-            off = ops.clone(off)      # keep the fusion conv's own output (LeakyReLU sign) for the backward pass
-        ops.add_flow(off, flow)
+        if flow is None:
+            flow = self.spynet.run(cur32, ref32, fused=fuse)
+            if ops.TAPE is not None:
+                off = ops.clone(off)      # keep the fusion conv's own output (LeakyReLU sign) for the backward pass
+            ops.add_flow(off, flow)
         sums = []
         e = ops.conv(off, pk_conv(self, "ff_", self.feat_fusion_), chan_sum=sums)
         return self.attn.run(e, sums=sums)
@@ -340,23 +370,24 @@ class LoopFilter(nn.Module, PackCache):
             ops.conv(src.as_slices(b, 4, 64), pc, out=dst.as_slices(b, 4, 64),
                      res=res_buf.as_slices(b, 4, 64) if res_buf is not None else None, **kw)
 
-    def run(self, xt: FM, refs8: FM, out: FM) -> FM:
+    def run(self, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM:
         """xt: (B,H,W,256) with prediction1 already in slice 3; refs8: (B*4,H,W,8) fp16 frames
-        [I, r-3, r-2, r-1] per batch item; writes the fused prediction into `out`."""
+        [I, r-3, r-2, r-1] per batch item; writes the fused prediction into `out`.  `then` = (b, sign, out3), inference only: the last
+        pass also writes out3 = b + sign * out (the residual `f_cur - pred`, RESID_FUSED) instead of a launch that reads `out` back."""
         # conv01, conv02 + conv1 and layer1.conv1 + spatial_conv3d do not mix frames, and by the reference-list rule (synth.ref_list) this
         # call's r-3 and r-2 are the previous call's r-2 and r-1: their maps are kept (`_run_reuse`).  Training, the tape, the per-kernel
         # profile (a table of real work), fp32 inputs and shapes the fused kernels do not take compute everything afresh
         if (LOOPFILTER_REUSE and LOOPFILTER_PAIR and LOOPFILTER_BCAST and not self.training and ops.TAPE is None and ops.PROFILE is None
                 and not xt.f32 and not refs8.f32 and xt.H * xt.W >= 8192 and ops.conv_pair_supported(xt.as_slices(0, 4, 64))):
-            r = self._run_reuse(xt, refs8, out)
+            r = self._run_reuse(xt, refs8, out, then)
             if r is not None:
                 return r
-        return self._run_plain(xt, refs8, out)
+        return self._run_plain(xt, refs8, out, then)
 
     def reuse_state(self) -> LoopFilterReuse | None:
         return self.__dict__.get("_packed", {}).get("lf_reuse")
 
-    def _run_reuse(self, xt: FM, refs8: FM, out: FM) -> FM | None:
+    def _run_reuse(self, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM | None:
         """The head of the block on persistent per-frame slots.  Per batch item `ops.frames_changed` compares the three reference frames
         with the frames the window's slots were computed from (exact, on the device; slots that hold nothing comparable are forced) and
         the head's launches run under the per-image flags: conv_c8 and conv_pair compute the images whose flag is set, their workgroups
@@ -373,12 +404,12 @@ class LoopFilter(nn.Module, PackCache):
         if st.usable is False:                            # some launch of the head does not test the flags at this shape
             return None
         try:
-            return self._reuse_call(st, xt, refs8, out)
+            return self._reuse_call(st, xt, refs8, out, then)
         except BaseException:
             cache.pop("lf_reuse", None)                   # slots may be half written: nothing of this state is trusted again
             raise
 
-    def _reuse_call(self, st: LoopFilterReuse, xt: FM, refs8: FM, out: FM) -> FM | None:
+    def _reuse_call(self, st: LoopFilterReuse, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM | None:
         B, H, W = xt.N, xt.H, xt.W
         dev = xt.t.device
         lr = dict(act=ACT_LRELU, slope=0.1)
@@ -433,9 +464,9 @@ class LoopFilter(nn.Module, PackCache):
             ops.conv(s.as_slices(b, 4, 64), pc3, out=o.as_slices(b, 4, 64), res=win(st.A, b, 0, 4))
         sums = []
         f = ops.conv(o, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
-        return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums)
+        return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
 
-    def _run_plain(self, xt: FM, refs8: FM, out: FM) -> FM:
+    def _run_plain(self, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM:
         B, H, W = xt.N, xt.H, xt.W
         dev = xt.t.device
         lr = dict(act=ACT_LRELU, slope=0.1)
@@ -485,7 +516,7 @@ class LoopFilter(nn.Module, PackCache):
         self._slices("b3", l1.conv3, s, o, res_buf=a)
         sums = []
         f = ops.conv(o, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
-        return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums)
+        return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
 
 
 class FeatureExtract(nn.Module, PackCache):
@@ -563,7 +594,8 @@ class FeatureFix(nn.Module, PackCache):
         o2 = self.attn.run(o2, sums=sums, **lr)
         o = run_stack(self.recon_layer, o2, res2=x)
         rgb = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        ops.conv(o, pk_conv(self, "down", self.featdown), act=ops.ACT_CLAMP01, nchw_out=rgb)
+        with ops.rgb_head_kernel(RGB_HEAD and glue_fusions_allowed(self, trace is not None)):
+            ops.conv(o, pk_conv(self, "down", self.featdown), act=ops.ACT_CLAMP01, nchw_out=rgb)
         if trace is not None:
             trace.update(ff_idx=idx, ff_fin=fin, ff_fref=fref)
         return rgb

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops import FM
+from . import modules
 from .coder import MVCoder, ResCoder
 from .modules import FeaExtra, FeatureFix, LoopFilter, MCNet, OffsetGen
 
@@ -108,7 +109,7 @@ class VideoCompressor(nn.Module):
             npx_ = float(B * H * W)
             f_cur = self.extra_fea.run(cur8, feats.ch(0, 64))
             self.extra_fea.run(ref8, feats.ch(64, 64))
-            estmv = self.motion_est.run(feats, cur32, ref32)
+            estmv = self.motion_est.run(feats, cur32, ref32, traced=trace is not None)
 
             tr_mv = {} if trace is not None else None
             mv_hat, mv_bits = self.mvCoder.run(estmv, training=training, trace=tr_mv, noise=noise.get("mv"), f32=f32)
@@ -120,8 +121,12 @@ class VideoCompressor(nn.Module):
             xt = FM.empty(B, H, W, 256, device=dev)                      # 4 frames x 64 ch
             pred1 = self.mcnet.run(mv_hat, feats, xt.ch(192, 64))
             pred = FM.empty(B, H, W, 64, device=dev)
-            self.mcfilter.run(xt, refs8, pred)
-            resid = ops.scale_act_res(f_cur, FM.empty(B, H, W, 64, device=dev), res=pred, res_sign=-1.0)
+            resid = FM.empty(B, H, W, 64, device=dev)
+            if modules.RESID_FUSED and modules.glue_fusions_allowed(self, trace is not None):
+                self.mcfilter.run(xt, refs8, pred, then=(f_cur, -1.0, resid))       # resid = f_cur - pred from the pass that writes pred
+            else:
+                self.mcfilter.run(xt, refs8, pred)
+                ops.scale_act_res(f_cur, resid, res=pred, res_sign=-1.0)
 
             tr_res = {} if trace is not None else None
             recon_f, res_bits = self.resCoder.run(resid, training=training, res=pred, trace=tr_res, noise=noise.get("res"), f32=f32)

@@ -537,8 +537,12 @@ def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=
 
 def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None,
          res2: FM | None = None, gdn=GDN_NONE, aux: FM | None = None, square=False, out_dtype=None,
-         round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0, chan_sum: list | None = None) -> FM | torch.Tensor:
-    """`bcast_T` (inference only): the conv result is not stored but broadcast-added, with LeakyReLU(bcast_slope), over the
+         round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0, chan_sum: list | None = None,
+         flow: FM | None = None) -> FM | torch.Tensor:
+    """`flow` (inference only): an fp32 flow map added to the stored output, x to even and y to odd channels -- in the conv's epilogue
+    (tdvc_conv_desc::flow) when the kernel it dispatches to does that (tdvc_conv_flow_supported), else by `add_flow` behind it; the
+    same bytes either way.
+    `bcast_T` (inference only): the conv result is not stored but broadcast-added, with LeakyReLU(bcast_slope), over the
     bcast_T channel slices that start at `out` (tdvc_conv_desc::bcast_T); with `res` given the slices are read at `res` and written
     at `out` (out of place), else in place.
     `chan_sum` (inference only): a list; when the kernel this conv dispatches to can sum the values it stores per channel
@@ -553,6 +557,16 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
             chan_sum.append((part, rows))
     if bcast_T and TAPE is not None and not _IN_BACKWARD:
         raise L.TdvcHipError("conv: bcast_T is an inference-only fusion (under the tape use conv + bcast_add_act)")
+    if flow is not None:
+        if (TAPE is not None and not _IN_BACKWARD) or chan_sum is not None or nchw_out is not None:
+            raise L.TdvcHipError("conv: flow is an inference-only fusion of an fmap output, not combined with chan_sum (use conv + add_flow)")
+        d.flow = flow.desc()
+        if L.lib().tdvc_conv_flow_supported(C.byref(d)) != 1:       # another kernel: the conv as it is, then one pass over its output
+            d.flow = _NULL_FM
+            L.check(L.lib().tdvc_conv2d(C.byref(d), _stream()), "conv2d")
+            _log_predicated()
+            add_flow(ret, flow)
+            return ret
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -570,6 +584,25 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
     _log_predicated()
     _rec("conv", x, rec_pc, None if nchw_out is not None else ret, act, slope, res, res2, gdn, aux, square, nchw_out)
     return ret
+
+
+class rgb_head_kernel:
+    """`with ops.rgb_head_kernel(False):` -- conv_n16 runs the RGB head (3x3, 64 -> <= 4 planar fp32 channels) on its own kernel instead
+    of its streamed form conv_head3 (the library's debug switch tdvc_debug_enable_conv_head3; process-wide, on by default and on again
+    behind the block).  The same bytes either way.  For the A/B switch, the tests, training and profiled / traced calls."""
+
+    def __init__(self, enable: bool):
+        self.enable = bool(enable)
+
+    def __enter__(self):
+        if not self.enable:
+            L.lib().tdvc_debug_enable_conv_head3(0)
+        return self
+
+    def __exit__(self, *exc):
+        if not self.enable:
+            L.lib().tdvc_debug_enable_conv_head3(1)
+        return False
 
 
 # ----------------------------------------------------------------------------- fused conv pair (inference)
@@ -967,6 +1000,24 @@ def axpy_f32(dst: torch.Tensor, src: torch.Tensor, scale: float) -> None:
 
 
 # ----------------------------------------------------------------------------- elementwise / SE
+def scale_act_res3(a: FM, out: FM, b: FM, out3: FM, b_sign=-1.0, gate: torch.Tensor | None = None, act=ACT_NONE, slope=0.0,
+                   res: FM | None = None, res_sign=1.0) -> FM:
+    """scale_act_res into `out`, and out3 = b + b_sign * out from the rounded `out` -- in the same launch (tdvc_scale_act_res3) when
+    every map is fp16, else as a second launch; the same bytes either way.  Inference only."""
+    if TAPE is not None and not _IN_BACKWARD:
+        raise L.TdvcHipError("scale_act_res3 is an inference-only fusion (under the tape: two scale_act_res calls)")
+    if not (a.f32 or out.f32 or b.f32 or out3.f32 or (res is not None and res.f32)):
+        da, dy, db, d3 = a.desc(), out.desc(), b.desc(), out3.desc()
+        dr = res.desc() if res is not None else None
+        L.check(L.lib().tdvc_scale_act_res3(C.byref(da), gate.data_ptr() if gate is not None else None, act, slope,
+                                            C.byref(dr) if dr is not None else None, res_sign, C.byref(dy), C.byref(db), b_sign,
+                                            C.byref(d3), _stream()), "scale_act_res3")
+        return out
+    scale_act_res(a, out, gate=gate, act=act, slope=slope, res=res, res_sign=res_sign)
+    scale_act_res(b, out3, res=out, res_sign=b_sign)
+    return out
+
+
 def scale_act_res(a: FM, out: FM, gate: torch.Tensor | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None,
                   res_sign=1.0, out2: FM | None = None) -> FM:
     da, dy = a.desc(), out.desc()
@@ -1048,6 +1099,20 @@ def avgpool2(x: FM) -> FM:
     dx, dy = x.desc(), out.desc()
     L.check(L.lib().tdvc_avgpool2(C.byref(dx), C.byref(dy), _stream()), "avgpool2")
     return out
+
+
+def avgpool2_pyramid_supported(a: FM, b: FM) -> bool:
+    return a.f32 and b.f32 and (a.N, a.H, a.W, a.C) == (b.N, b.H, b.W, b.C) and a.C <= 4 and a.H % 32 == 0 and a.W % 32 == 0
+
+
+def avgpool2_pyramid(a: FM, b: FM) -> tuple:
+    """five chained avgpool2 levels of both maps in one launch -> ([a/2, a/4, ..., a/32], [b/2, ..., b/32]), separate buffers"""
+    lv = lambda x: [FM.empty(x.N, x.H >> k, x.W >> k, x.C, dtype=torch.float32, device=x.t.device) for k in range(1, 6)]
+    la, lb = lv(a), lv(b)
+    da, db = a.desc(), b.desc()
+    ya, yb = (L.FMapDesc * 5)(*[f.desc() for f in la]), (L.FMapDesc * 5)(*[f.desc() for f in lb])
+    L.check(L.lib().tdvc_avgpool2_pyramid(C.byref(da), C.byref(db), ya, yb, _stream()), "avgpool2_pyramid")
+    return la, lb
 
 
 def spynet_level_input(ref: FM, supp: FM, flow_lo: FM | None, flow_up: FM, cat8: FM):
