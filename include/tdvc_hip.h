@@ -453,6 +453,33 @@ int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nby
                                   const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
                                   const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
                                   const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, int32_t* bad_image, void* stream);
+/* ABI 12.  Device ENCODER of lane-split streams: the container of tdvc_rans_encode_lanes, byte for byte, from the encoder loop's
+ * raster arrays symbols / indexes [B][H][W][M] in DEVICE memory, so that the symbols never cross the bus.  pos: int32 [npos][2] =
+ * (h, w), the wavefront position list; image b is coded by one workgroup of L threads (L = 64 or 128, L | M), thread l coding lane l
+ * -- channels c = j * L + l of every position -- from the LAST position to the first (rANS emits its words in reverse stream
+ * order) into a scratch region of its own, words [(b * L + l) * lane_words, + lane_words) of scratch, filled downward from its
+ * end; then header, length table and sub-streams are assembled at out + b * out_stride and info[b] = {container bytes, status}:
+ * 0 ok; 1 a lane exceeds 65 535 words (tdvc_rans_encode_lanes' error); 2 a lane ran out of its scratch region (or met an index
+ * outside the tables or a position outside the image).  On a non-zero status the bytes are 0 and nothing of the container is
+ * written; nothing outside scratch, out and info is written at all.
+ * tdvc_ar_encode_lanes_scratch_words: the lane_words that suffice for every input: a lane of n = npos * M / L symbols starts
+ * below 2^32, gains at most 16 + 4 * 9 = 52 bits per symbol and sheds 32 per word: (31 + 52 n) / 32 + 2 words, capped at 65 536 (a
+ * lane that fills or leaves such a region is too long whatever follows: status 1).  tdvc_ar_encode_lanes_out_bytes: the out_stride
+ * that goes with it (a multiple of 16).  A smaller lane_words is legal (status 2 where it does not suffice); out_stride must be a
+ * multiple of 16 of at least 4 + 2 L + 4 L min(lane_words, 65 535).  Tables as in tdvc_ar_decode_lanes_step_batch, ncdfs <= 64.
+ * Every check is made before a device is touched; enqueue-only, no atomics, no spinning, nothing persistent.
+ * tdvc_rans_encode_lanes_dev_ref: the host twin -- the same encode routine (csrc/rans_lane.h), traversal, scratch layout and
+ * assembly over HOST memory, tables as in tdvc_rans_encode (the first ncdfs rows). */
+int64_t tdvc_ar_encode_lanes_scratch_words(int64_t npos, int M, int L);
+int64_t tdvc_ar_encode_lanes_out_bytes(int64_t npos, int M, int L);
+int tdvc_ar_encode_lanes_batch(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos_dev, int npos, int L,
+                               const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
+                               const int32_t* offsets_dev, int32_t ncdfs, uint32_t* scratch_dev, int64_t lane_words, int64_t scratch_cap_words,
+                               uint8_t* out_dev, int64_t out_stride, int64_t out_cap, uint32_t* info_dev, void* stream);
+int tdvc_rans_encode_lanes_dev_ref(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos, int npos, int L,
+                                   const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int32_t ncdfs,
+                                   uint32_t* scratch, int64_t lane_words, int64_t scratch_cap_words, uint8_t* out, int64_t out_stride,
+                                   int64_t out_cap, uint32_t* info);
 /* Kernel enqueues of the last context-loop call on this thread (tdvc_ar_decode_serial_batch, tdvc_ar_wavefront_batch,
  * tdvc_ar_wavefront_lanes_batch), conv launches included: the launches the library's entry points closed during the call.  Copies
  * are not counted.  The count does not depend on B. */

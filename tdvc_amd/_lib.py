@@ -116,6 +116,10 @@ SIGNATURES = {
     "tdvc_ar_decode_lanes_step_batch": (_i, [_FM, _P, _i, _P, _i, _P, _i64, _P, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _FM, _P, _P, _i64, _P]),
     "tdvc_ar_wavefront_lanes_batch": (_i, [_P, _P, _i, _P, _i64, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i,
                                            _P, _i, _P, _P, _P, _P]),
+    "tdvc_ar_encode_lanes_scratch_words": (_i64, [_i64, _i, _i]),
+    "tdvc_ar_encode_lanes_out_bytes": (_i64, [_i64, _i, _i]),
+    "tdvc_ar_encode_lanes_batch": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _i64, _i64, _P, _i64, _i64, _P, _P]),
+    "tdvc_rans_encode_lanes_dev_ref": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _i, _P, C.c_int32, _P, _P, C.c_int32, _P, _i64, _i64, _P, _i64, _i64, _P]),
     "tdvc_ar_last_loop_launches": (_i64, []),
     "tdvc_ssim_level_work_floats": (_i64, [_i] * 5),
     "tdvc_ssim_level": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _f, _f, _P, _P, _P, _i64, _P]),

@@ -252,6 +252,149 @@ __global__ void __launch_bounds__(128) ar_decode_lanes_batch_kernel(FMap gp, con
   lane_store(st, state, lane, L);
 }
 
+// ---- the range ENCODER of the same format on the device: workgroup b of L threads codes image b, thread l lane l, straight
+// from the context loop's raster arrays sym / idx [B][H][W][M], so the symbols never leave the device.  Three phases.  1: the
+// packed CDFs into LDS.  2: per chunk of positions, walked from the LAST position of the wavefront list to the first, A (coalesced
+// loads, twelve symbols in flight per thread) everything about a symbol that does not depend on the coder's state -- its bin's
+// start and range, its escape value (tdvc_lane_symbol) -- into LDS, B thread l pushes its symbols c = j * L + l, j from M / L - 1
+// down to 0, through tdvc_lane_push into its own scratch region, words downward from the region's end: the serial pass is the
+// state update alone (a compare, three 16-bit division steps), fed by LDS reads whose addresses it knows in advance.  3: lane lengths to LDS, prefix-summed; header, length table and the sub-streams, lane by lane, all threads
+// copying, into out + b * out_stride; info[b] = {container bytes, status}.  On a non-zero status nothing of the container is
+// written.  Nothing outside scratch[b], out[b] and info[b] is written; plain loads and stores and LDS only.
+constexpr int kEncMaxPos = 64;                                  // positions per chunk at most (their pixel offsets: one thread each)
+constexpr int kEncLds = kLdsCdf * 2 + kChunkSyms * 8 + 64 * 4 * 3 + kEncMaxPos * 4 + (128 * 3 + 4) * 4 + kChunkSyms;  // cdf | start and range, escape value | starts, sizes, offsets | pixel | lane pos, len, offset, status | kind
+
+__global__ void __launch_bounds__(128) ar_encode_lanes_batch_kernel(const int32_t* __restrict__ sym, const int32_t* __restrict__ idx, int H, int W, int M,
+                                                                    const int32_t* __restrict__ pos, int npos, const uint16_t* __restrict__ cdf16, int n16,
+                                                                    const int32_t* __restrict__ cdf_starts, const int32_t* __restrict__ cdf_sizes,
+                                                                    const int32_t* __restrict__ offsets, int ncdfs, uint32_t* __restrict__ scratch,
+                                                                    uint32_t lane_words, uint8_t* __restrict__ out, long out_stride, uint32_t* __restrict__ info) {
+  const int L = (int)blockDim.x, lane = (int)threadIdx.x, b = (int)blockIdx.x;
+  sym += (long)b * H * W * M;
+  idx += (long)b * H * W * M;
+  scratch += (long)b * L * lane_words;                         // image b's L regions; thread l owns words [l * lane_words, (l + 1) * lane_words)
+  out += (long)b * out_stride;
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  uint16_t* s_cdf = reinterpret_cast<uint16_t*>(s_raw);
+  uint32_t* s_sr = reinterpret_cast<uint32_t*>(s_raw + kLdsCdf * 2);
+  uint32_t* s_esc = s_sr + kChunkSyms;
+  int32_t* s_start = reinterpret_cast<int32_t*>(s_esc + kChunkSyms);
+  int32_t* s_size = s_start + 64;
+  int32_t* s_off = s_size + 64;
+  int32_t* s_pix = s_off + 64;
+  uint32_t* s_lpos = reinterpret_cast<uint32_t*>(s_pix + kEncMaxPos);
+  uint32_t* s_llen = s_lpos + 128;
+  uint32_t* s_loff = s_llen + 128;                              // 128 + 1 prefix sums, then the image's status
+  uint8_t* s_kind = reinterpret_cast<uint8_t*>(s_loff + 128 + 4);
+  // phase 1
+  if (lane < 64) {
+    int start = 0, size = 0, off = 0;
+    if (lane < ncdfs) {
+      start = cdf_starts[lane]; size = cdf_sizes[lane]; off = offsets[lane];
+      if (!(start >= 0 && size >= 0 && start <= n16 && size <= n16 - start)) start = size = 0;      // a table outside the array has no entries: flagged
+    }
+    s_start[lane] = start; s_size[lane] = size; s_off[lane] = off;
+  }
+  const int nchunk = n16 / 8;                                  // as in the decoder: 16-byte chunks, clamped indexes
+  for (int c0 = lane; c0 < nchunk; c0 += L * 8) {
+    int ix[8];
+    uint4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) ix[u] = min(c0 + u * L, nchunk - 1);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = reinterpret_cast<const uint4*>(cdf16)[ix[u]];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) reinterpret_cast<uint4*>(s_cdf)[ix[u]] = v[u];
+  }
+  // phase 2
+  TdvcEncLane st;
+  tdvc_enc_lane_init(st, (uint32_t)lane * lane_words, (uint32_t)(lane + 1) * lane_words);
+  const int per = M / L;
+  const int kc = kChunkSyms / M < kEncMaxPos ? kChunkSyms / M : kEncMaxPos;       // positions per chunk, 1 <= kc <= 64 <= L
+  // pixel offset of position k, or -1 outside the image; thread t < kc fetches the NEXT chunk's while this one is coded
+  auto pixel = [&](int k) -> int {
+    if (k < 0) return -1;
+    const int h = pos[2 * k], w = pos[2 * k + 1];
+    return (h >= 0 && h < H && w >= 0 && w < W) ? h * W + w : -1;
+  };
+  int pix_next = lane < kc ? pixel(npos - 1 - lane) : -1;      // chunk-local slot t holds position k_hi - t
+  for (int k_hi = npos - 1; k_hi >= 0; k_hi -= kc) {
+    const int nk = k_hi + 1 < kc ? k_hi + 1 : kc;
+    if (lane < kc) s_pix[lane] = pix_next;
+    if (lane < kc) pix_next = pixel(k_hi - kc - lane);
+    __syncthreads();                                           // also: the previous chunk's B is over, s_sr / s_esc / s_kind are free
+    constexpr int U = 12;                                      // A: U symbols and U indexes in flight per thread
+    const int ni = nk * per;                                   // a thread's elements: i -> slot i / per, channel (i % per) * L + lane
+    for (int i0 = 0; i0 < ni; i0 += U) {
+      int e[U], c[U], pix[U], q[U], ci[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = min(i0 + u, ni - 1), t = i / per;        // uniform over the workgroup; past the end: the last element again
+        c[u] = (i - t * per) * L + lane;
+        e[u] = t * M + c[u];
+        pix[u] = s_pix[t];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long o = (long)(pix[u] < 0 ? 0 : pix[u]) * M + c[u];
+        q[u] = sym[o]; ci[u] = idx[o];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        TdvcEncSym sy = {0, 0, kEncUnusable};
+        if (pix[u] >= 0 && ci[u] >= 0 && ci[u] < ncdfs && ci[u] < 64) {
+          const int size = s_size[ci[u]];
+          sy = tdvc_lane_symbol(CdfDev{(lds_u16_ptr)s_cdf, s_start[ci[u]], size}, size, (int32_t)((uint32_t)q[u] - (uint32_t)s_off[ci[u]]));
+        }
+        s_kind[e[u]] = (uint8_t)sy.kind;
+        s_sr[e[u]] = sy.start_range;
+        s_esc[e[u]] = sy.raw;
+      }
+    }
+    __syncthreads();
+    for (int t = 0; t < nk; ++t)                               // B: slot 0 is the chunk's LAST position; only the state update is serial
+      for (int j = per - 1; j >= 0; --j) {
+        const int e = t * M + j * L + lane;
+        tdvc_lane_push(st, scratch, s_kind[e], s_sr[e], s_esc[e]);
+      }
+  }
+  // phase 3
+  const uint32_t len = tdvc_enc_lane_finish(st, scratch);
+  s_lpos[lane] = st.pos;
+  s_llen[lane] = len;
+  s_loff[lane] = tdvc_enc_lane_status(st, len);
+  __syncthreads();                                             // every lane's words are written (workgroup scope) and its length is in LDS
+  if (lane == 0) {
+    uint32_t status = 0, words = 0;
+    for (int l = 0; l < L; ++l) {
+      const uint32_t s = s_loff[l];
+      status = s > status ? s : status;
+      s_loff[l] = words;
+      words += s_llen[l];                                      // <= 128 * 65536: no overflow
+    }
+    s_loff[128] = words;
+    s_loff[129] = status;
+  }
+  __syncthreads();
+  const uint32_t status = s_loff[129];
+  if (lane == 0) {
+    info[2 * b] = status ? 0u : (uint32_t)tdvc_lanes_payload_offset(L) + 4u * s_loff[128];
+    info[2 * b + 1] = status;
+  }
+  if (status) return;                                          // uniform: the whole workgroup leaves
+  // every lane is at most min(lane_words, 65535) words here, and the entry point has checked out_stride against L such lanes
+  if (lane == 0) *reinterpret_cast<uint32_t*>(out) = (uint32_t)kLanesMagic | ((uint32_t)kLanesVersion << 8) | ((uint32_t)L << 16);
+  reinterpret_cast<uint16_t*>(out + kLanesHeaderBytes)[lane] = (uint16_t)len;
+  uint32_t* payload = reinterpret_cast<uint32_t*>(out + tdvc_lanes_payload_offset(L));
+  for (int l = 0; l < L; ++l) {
+    const uint32_t* __restrict__ src = scratch + s_lpos[l];
+    uint32_t* __restrict__ dst = payload + s_loff[l];
+    const int n = (int)s_llen[l];
+#pragma unroll 4
+    for (int i = lane; i < n; i += L) dst[i] = src[i];
+  }
+}
+
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 
@@ -527,6 +670,31 @@ extern "C" int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_
     hipLaunchKernelGGL(ar_decode_lanes_batch_kernel<half_t>, dim3(B), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, streams_dev,
                        (long)stream_bytes, table_dev, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
   return tdvc_launch_status("tdvc_ar_decode_lanes_step_batch");
+}
+
+// what the device encoder and its host twin (rans.cpp) check before anything is touched; `who` names the entry point
+int tdvc_encode_lanes_args(const char* who, const void* symbols, const void* indexes, int B, int H, int W, int M, const void* pos, int npos, int L, int32_t ncdfs,
+                           const void* scratch, int64_t lane_words, int64_t scratch_cap_words, const void* out, int64_t out_stride, int64_t out_cap, const void* info);
+
+extern "C" int tdvc_ar_encode_lanes_batch(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos_dev, int npos, int L,
+                                          const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
+                                          const int32_t* offsets_dev, int32_t ncdfs, uint32_t* scratch_dev, int64_t lane_words, int64_t scratch_cap_words,
+                                          uint8_t* out_dev, int64_t out_stride, int64_t out_cap, uint32_t* info_dev, void* stream) {
+  TDVC_CHECK(cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev, "tdvc_ar_encode_lanes_batch: null table pointer");
+  if (const int rc = tdvc_encode_lanes_args("tdvc_ar_encode_lanes_batch", symbols, indexes, B, H, W, M, pos_dev, npos, L, ncdfs, scratch_dev, lane_words,
+                                            scratch_cap_words, out_dev, out_stride, out_cap, info_dev)) return rc;
+  TDVC_CHECK(n16 >= 8 && n16 % 8 == 0 && aligned16(cdf16_dev), "tdvc_ar_encode_lanes_batch: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
+  TDVC_CHECK(n16 <= kLdsCdf, "tdvc_ar_encode_lanes_batch: %d packed CDF entries, the kernel's LDS holds %d", n16, kLdsCdf);
+  TDVC_CHECK(M <= kChunkSyms, "tdvc_ar_encode_lanes_batch: more than %d channels", kChunkSyms);
+  static TdvcPerDeviceFlag attr;
+  if (!attr.flag()) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&ar_encode_lanes_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kEncLds);
+    if (err != hipSuccess) { tdvc_set_error("tdvc_ar_encode_lanes_batch: cannot reserve %d bytes of LDS: %s", kEncLds, hipGetErrorString(err)); return (int)err; }
+    attr.flag() = true;
+  }
+  hipLaunchKernelGGL(ar_encode_lanes_batch_kernel, dim3(B), dim3(L), kEncLds, ST(stream), symbols, indexes, H, W, M, pos_dev, npos, cdf16_dev, n16, cdf_starts_dev,
+                     cdf_sizes_dev, offsets_dev, ncdfs, scratch_dev, (uint32_t)lane_words, out_dev, (long)out_stride, info_dev);
+  return tdvc_launch_status("tdvc_ar_encode_lanes_batch");
 }
 
 // The decoder's loop over anti-diagonals for lane-split streams: the B strings are validated and uploaded behind their table, B + 1

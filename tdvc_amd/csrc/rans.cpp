@@ -46,7 +46,7 @@ extern "C" int64_t tdvc_rans_encode(const int32_t* symbols, const int32_t* index
     syms.push_back({(uint16_t)cdf[value], (uint16_t)(cdf[value + 1] - cdf[value]), false});
     if (value == max_value) {
       int32_t nb = 0;
-      while ((raw >> (nb * kBypassBits)) != 0) ++nb;
+      while (nb < 8 && (raw >> (nb * kBypassBits)) != 0) ++nb;       // 8 digits hold all of raw (and raw >> 32 is undefined: the loop did not end for raw >= 1 << 28)
       int32_t v = nb;
       while (v >= kMaxBypass) {
         syms.push_back({(uint16_t)kMaxBypass, (uint16_t)(kMaxBypass + 1), true});
@@ -295,5 +295,86 @@ extern "C" int tdvc_rans_decode_lanes(const uint8_t* data, int64_t nbytes, const
       }
       symbols_out[p * M + c] = v + offsets[ci];
     }
+  return TDVC_OK;
+}
+
+// ---- the encoder of lane-split streams that runs on the device (ar_context.hip: ar_encode_lanes_batch_kernel), its sizes and its
+// host twin: the same encode-one-symbol routine (rans_lane.h), traversal, scratch layout and assembly, on host memory
+
+extern "C" int64_t tdvc_ar_encode_lanes_scratch_words(int64_t npos, int M, int L) {
+  if (npos < 0 || M < 1 || L < 1 || M % L != 0) { tdvc_set_error("tdvc_ar_encode_lanes_scratch_words: bad sizes (npos %lld, M %d, L %d)", (long long)npos, M, L); return TDVC_EINVAL; }
+  return tdvc_lane_scratch_words(npos > kLanesScratchCap ? kLanesScratchCap : npos * (M / L));
+}
+extern "C" int64_t tdvc_ar_encode_lanes_out_bytes(int64_t npos, int M, int L) {
+  const int64_t w = tdvc_ar_encode_lanes_scratch_words(npos, M, L);
+  return w < 0 ? w : (tdvc_lanes_container_bound(L, w) + 15) / 16 * 16;
+}
+
+int tdvc_encode_lanes_args(const char* who, const void* symbols, const void* indexes, int B, int H, int W, int M, const void* pos, int npos, int L, int32_t ncdfs,
+                           const void* scratch, int64_t lane_words, int64_t scratch_cap_words, const void* out, int64_t out_stride, int64_t out_cap, const void* info) {
+  const auto bad = [&](const char* what) { tdvc_set_error("%s: %s", who, what); return TDVC_EINVAL; };
+  if (!symbols || !indexes || !pos || !scratch || !out || !info) return bad("null argument");
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || M < 1 || npos < 1 || (int64_t)H * W > 0x7FFFFFFF) return bad("1 <= B <= 65535 images of H x W x M symbols and npos >= 1 positions expected");
+  if ((L != 64 && L != 128) || M % L != 0) return bad("64 or 128 lanes that divide the channel count expected");
+  if (ncdfs < 1 || ncdfs > 64) return bad("1..64 CDF tables expected");
+  if (lane_words < 2 || lane_words > kLanesScratchCap || (int64_t)B * L * lane_words > scratch_cap_words)
+    return bad("2..65536 scratch words per lane expected, B * L * lane_words of them inside the scratch buffer");
+  if (out_stride % 16 != 0 || out_stride < tdvc_lanes_container_bound(L, lane_words) || (int64_t)B * out_stride > out_cap)
+    return bad("the output stride must be a multiple of 16 that holds L lanes of min(lane_words, 65535) words behind header and length table, B strides inside the output buffer");
+  if ((((uintptr_t)symbols) | ((uintptr_t)indexes) | ((uintptr_t)pos) | ((uintptr_t)scratch) | ((uintptr_t)info)) & 3 || ((uintptr_t)out) & 15)
+    return bad("symbols / indexes / positions / scratch / info must be 4-byte aligned, the output buffer 16-byte aligned");
+  return TDVC_OK;
+}
+
+extern "C" int tdvc_rans_encode_lanes_dev_ref(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos, int npos, int L,
+                                              const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int32_t ncdfs,
+                                              uint32_t* scratch, int64_t lane_words, int64_t scratch_cap_words, uint8_t* out, int64_t out_stride,
+                                              int64_t out_cap, uint32_t* info) {
+  if (!cdfs || !cdf_sizes || !offsets || cdf_stride < 1) { tdvc_set_error("tdvc_rans_encode_lanes_dev_ref: null table pointer"); return TDVC_EINVAL; }
+  if (const int rc = tdvc_encode_lanes_args("tdvc_rans_encode_lanes_dev_ref", symbols, indexes, B, H, W, M, pos, npos, L, ncdfs, scratch, lane_words,
+                                            scratch_cap_words, out, out_stride, out_cap, info)) return rc;
+  const int per = M / L;
+  std::vector<uint32_t> lpos((size_t)L), llen((size_t)L);
+  for (int b = 0; b < B; ++b) {
+    const int32_t* sym = symbols + (int64_t)b * H * W * M;
+    const int32_t* idx = indexes + (int64_t)b * H * W * M;
+    uint32_t* sc = scratch + (int64_t)b * L * lane_words;
+    uint8_t* o = out + (int64_t)b * out_stride;
+    uint32_t status = 0, words = 0;
+    for (int l = 0; l < L; ++l) {
+      TdvcEncLane st;
+      tdvc_enc_lane_init(st, (uint32_t)(l * lane_words), (uint32_t)((l + 1) * lane_words));
+      for (int p = npos - 1; p >= 0; --p) {
+        const int h = pos[2 * p], w = pos[2 * p + 1];
+        const bool inside = h >= 0 && h < H && w >= 0 && w < W;
+        for (int j = per - 1; j >= 0; --j) {
+          const int64_t e = inside ? ((int64_t)h * W + w) * M + (int64_t)j * L + l : 0;
+          const int32_t ci = idx[e];
+          if (!inside || ci < 0 || ci >= ncdfs) { st.bad = 1; continue; }
+          int32_t size = cdf_sizes[ci];
+          if (size > cdf_stride) size = cdf_stride;
+          tdvc_lane_encode(st, sc, TdvcCdf32{cdfs + (int64_t)ci * cdf_stride}, size, (int32_t)((uint32_t)sym[e] - (uint32_t)offsets[ci]));
+        }
+      }
+      const uint32_t len = tdvc_enc_lane_finish(st, sc);
+      const uint32_t s = tdvc_enc_lane_status(st, len);
+      status = s > status ? s : status;
+      lpos[(size_t)l] = st.pos; llen[(size_t)l] = len;
+      words += len;
+    }
+    info[2 * b] = status ? 0u : (uint32_t)tdvc_lanes_payload_offset(L) + 4u * words;
+    info[2 * b + 1] = status;
+    if (status) continue;                                      // nothing of the container is written
+    o[0] = kLanesMagic; o[1] = kLanesVersion; o[2] = (uint8_t)L; o[3] = 0;
+    uint8_t* q = o + tdvc_lanes_payload_offset(L);
+    for (int l = 0; l < L; ++l) {
+      o[kLanesHeaderBytes + 2 * l] = (uint8_t)(llen[(size_t)l] & 0xFF);
+      o[kLanesHeaderBytes + 2 * l + 1] = (uint8_t)(llen[(size_t)l] >> 8);
+      for (uint32_t i = 0; i < llen[(size_t)l]; ++i, q += 4) {
+        const uint32_t w = sc[lpos[(size_t)l] + i];
+        q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24);
+      }
+    }
+  }
   return TDVC_OK;
 }

@@ -9,6 +9,7 @@ PixelShuffle is a store pattern; the rate terms are fused elementwise kernels.
 from __future__ import annotations
 
 import math
+import threading
 
 import numpy as np
 import torch
@@ -163,14 +164,51 @@ def _rans_pool():
     return _RANS_POOL
 
 
+# bytes compress() has copied device-to-host for y streams (symbols and indexes for the host coder, containers and their info
+# words for the device coder), for tools/time_codec_batch.py; worker threads add to it too
+Y_BUS_BYTES = 0
+_Y_BUS_LOCK = threading.Lock()
+
+
+def note_y_bus_bytes(n: int) -> None:
+    global Y_BUS_BYTES
+    with _Y_BUS_LOCK:
+        Y_BUS_BYTES += n
+
+
 class PendingStrings:
     """the byte strings of a compress(defer=True) call: `result()` -> [y_strings, z_strings] once the worker threads are done"""
 
-    def __init__(self, y_futs, z_strings):
+    def __init__(self, y_futs, z_strings, keep=None):
         self._y, self._z = y_futs, z_strings
+        self._keep = keep          # device buffers a kernel on another stream still reads or writes: alive until the join
 
     def result(self):
-        return [[f.result() for f in self._y], self._z]
+        out = [[f.result() for f in self._y], self._z]
+        self._keep = None
+        return out
+
+
+class _Pick:
+    """image b of a future that yields the strings of a whole batch"""
+
+    def __init__(self, fut, b):
+        self._fut, self._b = fut, b
+
+    def result(self):
+        return self._fut.result()[self._b]
+
+
+STREAM_CODERS = ("host", "device")
+_CODER_STREAMS = {}
+
+
+def _coder_stream(dev) -> "torch.cuda.Stream":
+    """the side stream of the device range encoder, one per device"""
+    key = str(dev)
+    if key not in _CODER_STREAMS:
+        _CODER_STREAMS[key] = torch.cuda.Stream(device=dev)
+    return _CODER_STREAMS[key]
 
 
 class ResidualBlock(nn.Module, PackCache):
@@ -681,8 +719,50 @@ class Cheng2020Anchor(nn.Module, PackCache):
             return FM(torch.cat([self.run_g_s(self._image(y_hat, b)).t for b in range(y_hat.N)], 0))
         return self.run_g_s(y_hat)
 
+    @staticmethod
+    def _encode_lanes_device(sym_all, idx_all, flat, gct, lanes):
+        """compress(coder="device"): the range encoder of the B images' y symbols as one launch on the side stream, behind an event
+        the caller's stream records after the context loop, so what the caller enqueues next (the synthesis) is not held up.
+        -> (join, keep).  join() -- on a worker thread or inline -- waits for the kernel and the two words per image it leaves
+        ({bytes, status}, a small copy into pinned memory), turns a status into the host coder's error and copies exactly the
+        containers' bytes -> the B strings.  keep: what the kernel reads and writes.  sym_all / idx_all were allocated on the
+        caller's stream and are read on another, so they must stay referenced until join() is over (PendingStrings holds `keep`);
+        the encoder's own buffers are allocated, used and freed under the side stream."""
+        dev, B = sym_all.device, sym_all.shape[0]
+        side = _coder_stream(dev)
+        gct.device(dev)                                           # the tables' device copies, made (once) on the caller's stream
+        ev = torch.cuda.Event()
+        ev.record()
+        with torch.cuda.stream(side):
+            side.wait_event(ev)
+            enc = ops.ar_encode_lanes_batch(sym_all, idx_all, flat, gct, lanes)
+            info_h = torch.empty((B, 2), dtype=torch.int32, pin_memory=True)
+            info_h.copy_(enc.info, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(side)
+        keep = [enc, sym_all, idx_all, flat]
+
+        def join(keep=keep):                                      # the closure holds them too: a dropped PendingStrings frees nothing early
+            with torch.cuda.device(dev):
+                done.synchronize()
+                info = info_h.numpy().view(np.uint32)
+                ops.lanes_check_status(info, "compress")
+                sizes = [int(n) for n in info[:, 0]]
+                offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+                host = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=True)
+                with torch.cuda.stream(side):
+                    for b in range(B):
+                        host[offs[b]:offs[b + 1]].copy_(enc.out[b, :sizes[b]], non_blocking=True)
+                    end = torch.cuda.Event()
+                    end.record(side)
+                end.synchronize()
+                note_y_bus_bytes(int(offs[-1]) + info.nbytes)
+                a = host.numpy()
+                return [a[offs[b]:offs[b + 1]].tobytes() for b in range(B)]
+        return join, keep
+
     @torch.no_grad()
-    def compress(self, x: FM, f32=False, order="raster", defer=False, lanes=64, per_image=False):
+    def compress(self, x: FM, f32=False, order="raster", defer=False, lanes=64, per_image=False, coder="host"):
         """-> {"strings": [y_strings, z_strings], "shape": (h, w)} like compressai's compress()
         (`f32`: the fp32-island mode, see run()).
 
@@ -700,9 +780,19 @@ class Cheng2020Anchor(nn.Module, PackCache):
         lane and, like "wavefront", the reference's decoder cannot read it.  The GPU side of all three orders is the same.
 
         `per_image`: g_a, h_a and h_s run image by image (the context loop still takes the batch in one pass): the strings are
-        then those of B calls of one image, whatever kernels the batch as a whole would be dispatched to."""
+        then those of B calls of one image, whatever kernels the batch as a whole would be dispatched to.
+
+        `coder`: where the y stream's range coder runs.  "host" (the default): as described above.  "device" (order "lanes" only):
+        the encoder runs on the GPU too (ops.ar_encode_lanes_batch, one workgroup per image, one thread per lane, on a side stream
+        behind the context loop), reading the loop's symbols where they lie: no gathers, no pinned symbol buffers, no symbol
+        copies; what crosses the bus for y is the finished containers and two words per image.  The strings are byte for byte
+        those of "host".  The z stream stays on the host."""
         if order not in STREAM_ORDERS:
             raise ValueError(f"order must be one of {STREAM_ORDERS}, got {order!r}")
+        if coder not in STREAM_CODERS:
+            raise ValueError(f"coder must be one of {STREAM_CODERS}, got {coder!r}")
+        if coder == "device" and order != "lanes":
+            raise ValueError(f"coder=\"device\" codes lane-split streams only (order=\"lanes\"), got order={order!r}")
         if order == "lanes" and (lanes not in ops.LANE_COUNTS or self.M % lanes):
             raise ValueError(f"lanes must be one of {ops.LANE_COUNTS} and divide M = {self.M}, got {lanes!r}")
         dev = x.t.device
@@ -727,7 +817,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
         z_strings = [ops.rans_encode(zs[b], zidx, ebt) for b in range(B)]
         st = self._ar_setup(H, W, adt, dev, B)
         flat, sizes, chain, fl = st["flat"], st["sizes"], st["chain"], st["fl"]
-        host = self._ar_host(st)
+        host = self._ar_host(st) if coder == "host" else None
         # every position is written exactly once and only causal (already written) neighbours are read: no zero fill
         y_hat_all = FM.empty(B, H, W, M, dtype=adt, device=dev)
         sym_all = torch.empty((B, H, W, M), dtype=torch.int32, device=dev)
@@ -739,6 +829,13 @@ class Cheng2020Anchor(nn.Module, PackCache):
             ops.ar_wavefront_batch(None, None, y32.batch(b0, g), y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
                                    chain["gp"], flat, sizes, M, W, table, idx_all[b0:b0 + g], sym_all[b0:b0 + g])
             b0 += g
+        if coder == "device":
+            dbg = [{"y_hat": FM(y_hat_all.t[b:b + 1]), "symbols": sym_all[b], "indexes": idx_all[b]} for b in range(B)]
+            join, keep = self._encode_lanes_device(sym_all, idx_all, flat, gct, lanes)
+            if defer:
+                fut = _rans_pool().submit(join)
+                return {"strings": PendingStrings([_Pick(fut, b) for b in range(B)], z_strings, keep), "shape": (z.H, z.W), "_debug": dbg}
+            return {"strings": [join(), z_strings], "shape": (z.H, z.W), "_debug": dbg}
         y_jobs, dbg = [], []
         for b in range(B):
             sym, idx = sym_all[b], idx_all[b]
@@ -751,6 +848,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
                 hi.copy_(idx.view(H * W, M), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
+            note_y_bus_bytes(hs.numel() * 4 + hi.numel() * 4)
 
             def job(ev=ev, hs=hs, hi=hi):
                 ev.synchronize()

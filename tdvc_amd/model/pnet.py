@@ -16,7 +16,7 @@ import torch.nn as nn
 from .. import ops
 from ..ops import FM
 from . import modules
-from .coder import MVCoder, ResCoder
+from .coder import STREAM_CODERS, MVCoder, ResCoder
 from .modules import FeaExtra, FeatureFix, LoopFilter, MCNet, OffsetGen
 
 
@@ -47,6 +47,10 @@ class VideoCompressor(nn.Module):
         # GPU kernel reads, one thread per lane, with no host round trip inside the loop; decode() reads the count from the stream)
         self.stream_order = "raster"
         self.stream_lanes = 64
+        # where encode()'s range coder of the y streams runs: "host" (worker threads, the symbols copied off the device) or "device"
+        # (stream_order "lanes" only: the encoder kernel on a side stream; only the finished strings leave the device).  The strings
+        # are the same byte for byte
+        self.stream_coder = "host"
         self.mvCoder = MVCoder(N=128)
         self.resCoder = ResCoder(N=128)
         self.extra_fea = FeaExtra(2)
@@ -180,6 +184,10 @@ class VideoCompressor(nn.Module):
         The reconstruction is the DECODER's: it is built from the coded symbols, so a closed-loop encoder and the decoder
         stay bit-identical."""
         assert not self.training
+        if self.stream_coder not in STREAM_CODERS:
+            raise ValueError(f"stream_coder must be one of {STREAM_CODERS}, got {self.stream_coder!r}")
+        if self.stream_coder == "device" and self.stream_order != "lanes":
+            raise ValueError(f"stream_coder=\"device\" needs stream_order=\"lanes\", got {self.stream_order!r}")
         if refer_frames.shape[0] > 1:
             return self._encode_batch(input_image, refer_frames)
         B, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames)
@@ -189,13 +197,14 @@ class VideoCompressor(nn.Module):
         self.mvCoder.update()
         self.resCoder.update()
         f32 = self.coder_fp32
-        mv = self.mvCoder.compress(estmv, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes)       # range coding on worker threads
+        mv = self.mvCoder.compress(estmv, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes,
+                                    coder=self.stream_coder)                  # range coding on worker threads, or on a side stream
         cat = lambda dbg: FM(torch.cat([d["y_hat"].t for d in dbg], 0))
         out = {}
 
         def res_y_hat(pred):
             resid = ops.scale_act_res(f_cur, FM.empty(B, H, W, 64, device=dev), res=pred, res_sign=-1.0)
-            out["res"] = self.resCoder.compress(resid, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes)
+            out["res"] = self.resCoder.compress(resid, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes, coder=self.stream_coder)
             return cat(out["res"]["_debug"])
         recon = self._reconstruct(cat(mv["_debug"]), res_y_hat, feats, refs8, iframe8)
         rs = out["res"]
@@ -236,7 +245,7 @@ class VideoCompressor(nn.Module):
         ims = [self._front(refer_frames, b, input_image) for b in range(B)]
         self.mvCoder.update()
         self.resCoder.update()
-        kw = dict(f32=self.coder_fp32, order=self.stream_order, defer=True, lanes=self.stream_lanes, per_image=True)
+        kw = dict(f32=self.coder_fp32, order=self.stream_order, defer=True, lanes=self.stream_lanes, per_image=True, coder=self.stream_coder)
         mv = self.mvCoder.compress(self._dense([im["estmv"] for im in ims]), **kw)
         preds = [self._predict(im, d["y_hat"]) for im, d in zip(ims, mv["_debug"])]
         resid = [ops.scale_act_res(im["f_cur"], FM.empty(1, im["H"], im["W"], 64, device=im["dev"]), res=p, res_sign=-1.0) for im, p in zip(ims, preds)]

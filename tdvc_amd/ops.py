@@ -1336,6 +1336,106 @@ def rans_decode_lanes(data: bytes, indexes: np.ndarray, t: CdfTables) -> np.ndar
     return out
 
 
+LANES_ENC_STATUS = {1: "a lane needs more than 65535 words, the length table holds at most 65535",
+                    2: "a lane ran out of its scratch region (or met an index outside the tables / a position outside the image)"}
+
+
+def ar_encode_lanes_sizes(npos: int, M: int, lanes: int):
+    """-> (scratch words per lane, bytes of one image's container at most) for the device encoder of lane-split streams
+    (`tdvc_ar_encode_lanes_scratch_words`, `tdvc_ar_encode_lanes_out_bytes`)"""
+    w = int(L.lib().tdvc_ar_encode_lanes_scratch_words(int(npos), int(M), int(lanes)))
+    o = int(L.lib().tdvc_ar_encode_lanes_out_bytes(int(npos), int(M), int(lanes)))
+    if w < 0 or o < 0:
+        L.check(min(w, o), "ar_encode_lanes_sizes")
+    return w, o
+
+
+def _lanes_out_stride(lanes: int, lane_words: int) -> int:
+    return (4 + 2 * lanes + 4 * lanes * min(lane_words, 65535) + 15) // 16 * 16
+
+
+def lanes_check_status(info: np.ndarray, who: str) -> None:
+    """info words [B][2] = {bytes, status} of an encoder call (host array): a status is an error: 1 the host coder's ValueError,
+    2 a RuntimeError"""
+    for b in range(info.shape[0]):
+        status = int(info[b, 1])
+        if status == 1:
+            raise ValueError(f"{who}: image {b}: {LANES_ENC_STATUS[1]}")
+        if status:
+            raise RuntimeError(f"{who}: image {b}: {LANES_ENC_STATUS.get(status, f'status {status}')}")
+
+
+def lanes_strings(out: np.ndarray, info: np.ndarray, who: str):
+    """the containers of an encoder call from its output buffer [B][stride] and info words (host arrays), statuses checked"""
+    lanes_check_status(info, who)
+    return [out[b, :int(info[b, 0])].tobytes() for b in range(info.shape[0])]
+
+
+def rans_encode_lanes_dev_ref(symbols: np.ndarray, indexes: np.ndarray, pos: np.ndarray, t: CdfTables, lanes: int = 64, lane_words: int | None = None,
+                              raw: bool = False):
+    """the host twin of the device encoder (`tdvc_rans_encode_lanes_dev_ref`): symbols / indexes [B][H][W][M] as the context loop
+    leaves them, pos [npos][2] the wavefront position list -> the B containers.  `lane_words`: scratch words per lane (default: what
+    always suffices).  `raw`: -> (out [B][stride] uint8, info [B][2] uint32, scratch [B][lanes][lane_words] uint32) untouched by
+    any check of the status"""
+    s = np.ascontiguousarray(symbols, dtype=np.int32)
+    i = np.ascontiguousarray(indexes, dtype=np.int32)
+    p = np.ascontiguousarray(pos, dtype=np.int32)
+    if s.ndim != 4 or s.shape != i.shape or p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("rans_encode_lanes_dev_ref: symbols and indexes must both be [B][H][W][M], pos [npos][2]")
+    B, H, W, M = s.shape
+    if lane_words is None:
+        lane_words = ar_encode_lanes_sizes(p.shape[0], M, lanes)[0]
+    stride = _lanes_out_stride(int(lanes), int(lane_words))
+    scratch = np.zeros((B, int(lanes), int(lane_words)), dtype=np.uint32)
+    out = np.zeros((B, stride), dtype=np.uint8)
+    if out.ctypes.data % 16:                                          # numpy aligns to 16 in practice; the entry point insists
+        out = np.zeros(B * stride + 16, dtype=np.uint8)
+        out = out[(-out.ctypes.data) % 16:][:B * stride].reshape(B, stride)
+    info = np.full((B, 2), 0xFFFFFFFF, dtype=np.uint32)
+    L.check(L.lib().tdvc_rans_encode_lanes_dev_ref(s.ctypes.data, i.ctypes.data, B, H, W, M, p.ctypes.data, p.shape[0], int(lanes), t.cdf.ctypes.data, t.stride,
+                                                   t.sizes.ctypes.data, t.offsets.ctypes.data, len(t.sizes), scratch.ctypes.data, int(lane_words), scratch.size,
+                                                   out.ctypes.data, stride, out.size, info.ctypes.data), "rans_encode_lanes_dev_ref")
+    if raw:
+        return out, info, scratch
+    return lanes_strings(out, info, "rans_encode_lanes_dev_ref")
+
+
+class LanesEncoding:
+    """the buffers of one `ar_encode_lanes_batch` call: they belong to the kernel until it is done, so the object is kept until then
+    (the symbols / indexes it read included: they may have been allocated on another stream than the kernel's)"""
+
+    def __init__(self, out, info, scratch, keep):
+        self.out, self.info, self.scratch, self.keep = out, info, scratch, keep
+
+
+def ar_encode_lanes_batch(symbols: torch.Tensor, indexes: torch.Tensor, pos: torch.Tensor, t: CdfTables, lanes: int = 64, lane_words: int | None = None,
+                          scratch: torch.Tensor | None = None, out: torch.Tensor | None = None) -> LanesEncoding:
+    """the range encoder of lane-split y streams on the device (`tdvc_ar_encode_lanes_batch`), enqueue-only: symbols / indexes int32
+    [B][H][W][M] as `ar_wavefront_batch` leaves them, pos int32 [npos][2] (the wavefront position list) -> LanesEncoding with
+    out uint8 [B][stride] (image b's container at row b), info int32 [B][2] = {container bytes, status} (`lanes_strings` reads
+    both once they are on the host).  `lane_words` / `scratch` / `out`: scratch words per lane and caller-provided buffers
+    (default: what always suffices, allocated here)"""
+    assert symbols.dtype == torch.int32 and indexes.dtype == torch.int32 and pos.dtype == torch.int32 and symbols.is_contiguous() and indexes.is_contiguous()
+    assert symbols.dim() == 4 and symbols.shape == indexes.shape and pos.dim() == 2 and pos.shape[1] == 2 and pos.is_contiguous()
+    B, H, W, M = symbols.shape
+    dev = symbols.device
+    if lane_words is None:
+        lane_words = ar_encode_lanes_sizes(pos.shape[0], M, lanes)[0]
+    stride = _lanes_out_stride(int(lanes), int(lane_words))
+    if scratch is None:
+        scratch = torch.empty((B, int(lanes), int(lane_words)), dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty((B, stride), dtype=torch.uint8, device=dev)
+    assert scratch.dtype == torch.int32 and out.dtype == torch.uint8 and scratch.is_contiguous() and out.is_contiguous()
+    info = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    cdf16, starts, sizes, offsets = t.device(dev)
+    L.check(L.lib().tdvc_ar_encode_lanes_batch(symbols.data_ptr(), indexes.data_ptr(), B, H, W, M, pos.data_ptr(), pos.shape[0], int(lanes), cdf16.data_ptr(),
+                                               cdf16.numel(), starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), scratch.data_ptr(),
+                                               int(lane_words), scratch.numel(), out.data_ptr(), stride, out.numel(), info.data_ptr(), _stream()),
+            "ar_encode_lanes_batch")
+    return LanesEncoding(out, info, scratch, (symbols, indexes, pos, cdf16, starts, sizes, offsets))
+
+
 def lanes_of(data: bytes) -> int:
     """the lane count a lane-split container declares"""
     if len(data) < 4 or data[0:2] != b"L\x01" or data[3] != 0:

@@ -123,12 +123,16 @@ def main():
                     help="with --bitstream-dir: y-symbol order (raster = the reference's; wavefront = diagonal-parallel decoding; "
                          "lanes = wavefront order split over rANS sub-streams, range decoder on the GPU)")
     ap.add_argument("--stream-lanes", type=int, default=64, choices=(64, 128), help="with --stream-order lanes: sub-streams per y string")
+    ap.add_argument("--range-coder", default="host", choices=("host", "device"),
+                    help="with --bitstream-dir: where the encoder's range coder of the y streams runs (device: --stream-order lanes only; the same bytes)")
     ap.add_argument("--gop-batch", type=int, default=1, help="with --bitstream-dir: a rank codes this many GOPs of its shard in lockstep, frame t of all "
                                                             "of them as one batch (same files and stats as 1; a last group smaller than this runs at its own size)")
     ap.add_argument("--coder-fp32", action="store_true", help="both coders as fp32 islands (the reference's precision), also with enable_amp: True")
     a = ap.parse_args()
     if a.gop_batch < 1 or (a.gop_batch > 1 and not a.bitstream_dir):
         ap.error("--gop-batch needs a value >= 1 and, above 1, --bitstream-dir (it batches the real coding)")
+    if a.range_coder == "device" and a.stream_order != "lanes":
+        ap.error("--range-coder device needs --stream-order lanes")
     opt = {"model": "pnet", "pretrain": a.pretrain, "val_dataset": "synthetic", "class": "-", "enable_amp": True}
     if a.cfg:
         opt.update(yaml.safe_load(open(a.cfg)))
@@ -151,6 +155,7 @@ def main():
     net.coder_fp32 = bool(opt.get("coder_fp32", False)) or a.coder_fp32
     net.stream_order = a.stream_order
     net.stream_lanes = a.stream_lanes
+    net.stream_coder = a.range_coder
     t0 = time.time()
     stats = []
     dataset = None
