@@ -159,7 +159,7 @@ __device__ __forceinline__ void epilogue4(const ConvParams& p, int n, int oy, in
   }
 }
 
-// XCD-aware tile walk of the persistent kernels (v3, v7).  Workgroups are dispatched round-robin over the 8 XCDs, each
+// XCD-aware tile walk of the persistent kernels (v3, v5, v7, v10, v11).  Workgroups are dispatched round-robin over the 8 XCDs, each
 // with its own L2, so workgroup x of a launch runs on XCD x % 8.  The raster of tiles is cut into 8 contiguous bands,
 // one per XCD, and a workgroup walks its XCD's band with the stride of that XCD's workgroup count: neighbouring tiles
 // (shared halo rows / columns) and consecutive tile rows are fetched through ONE L2 instead of eight.  Needs
@@ -179,6 +179,10 @@ __device__ __forceinline__ void xcd_tile_walk(int ntiles, int& first, int& strid
     stride = gx;
     my_tiles = (ntiles - first + stride - 1) / stride;
   }
+}
+// tile_i-th tile of that walk; alternate launches walk the raster backwards (ConvParams::reverse)
+__device__ __forceinline__ int walk_tile(const ConvParams& p, int ntiles, int first, int stride, int tile_i) {
+  return p.reverse ? ntiles - 1 - (first + tile_i * stride) : first + tile_i * stride;
 }
 
 // Which layers take the transposed epilogue below (everything else uses epilogue4).
@@ -339,6 +343,21 @@ __device__ __forceinline__ void epilogue_store_row(const ConvParams& p, const Pa
 // FLOW (conv_mfma_v5, tdvc_conv_desc::flow): the fp16 value the row would store is widened, the pixel's fp32 flow added (x to even, y to
 // odd channels) and the sum rounded once -- add_flow_kernel's load8 / v[j] += (j & 1) ? fy : fx / store8 on that value: bit-identical to
 // the conv followed by tdvc_add_flow, without the pass over y.
+// The packed-fp16 pack of every lean epilogue: four fp32 values -> fp16 -> activation as packed fp16 math.  relu / act are
+// wave-uniform (slope 0 / slope != 1): ReLU is one packed max against zero, no activation is no packed math at all.
+__device__ __forceinline__ half4 lean_pack4(float v0, float v1, float v2, float v3, bool relu, bool act, half2v sl2) {
+  const half2v zero2 = {(half_t)0.f, (half_t)0.f};
+  half2v lo = {(half_t)v0, (half_t)v1}, hi = {(half_t)v2, (half_t)v3};
+  if (relu) {
+    lo = __builtin_elementwise_max(lo, zero2);
+    hi = __builtin_elementwise_max(hi, zero2);
+  } else if (act) {
+    lo = __builtin_elementwise_max(lo, lo * sl2);
+    hi = __builtin_elementwise_max(hi, hi * sl2);
+  }
+  return half4{lo[0], lo[1], hi[0], hi[1]};
+}
+
 template <int NTX, bool BIAS_IN_ACC, bool BCAST = false, bool CSUM = false, bool FLOW = false>
 __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&acc)[2][NTX], const float* bias64, unsigned char* ew, int n,
                                                   int cbase, int oy_first, int ox_first, int lane, bool zero_acc, bool full, float* cs = nullptr) {
@@ -350,7 +369,7 @@ __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&
   const int cc = ch_ok ? co : 0;
   const bool has1 = p.res.p != nullptr, has2 = p.res2.p != nullptr;       // wave-uniform
   const half_t sl = (half_t)p.slope;
-  const half2v sl2 = {sl, sl}, zero2 = {(half_t)0.f, (half_t)0.f};
+  const half2v sl2 = {sl, sl};
   const bool act = p.slope != 1.f, relu = p.slope == 0.f;                  // wave-uniform
   half_t* yb = reinterpret_cast<half_t*>(p.y.p) + (long)n * p.y.sn + cc;
   const half_t* rb1 = reinterpret_cast<const half_t*>(p.res.p) + (long)n * p.res.sn + cc;
@@ -405,16 +424,7 @@ __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&
             if (zero_acc) acc[mt][nt][4 * g + i] = 0.f;
           }
         }
-        half2v lo = {(half_t)v[0], (half_t)v[1]}, hi = {(half_t)v[2], (half_t)v[3]};
-        if (relu) {
-          lo = __builtin_elementwise_max(lo, zero2);
-          hi = __builtin_elementwise_max(hi, zero2);
-        } else if (act) {
-          lo = __builtin_elementwise_max(lo, lo * sl2);
-          hi = __builtin_elementwise_max(hi, hi * sl2);
-        }
-        const half4 o = {lo[0], lo[1], hi[0], hi[1]};
-        *reinterpret_cast<half4*>(ew + r * EPS + (mt * 32 + 8 * g + 4 * hh) * 2) = o;
+        *reinterpret_cast<half4*>(ew + r * EPS + (mt * 32 + 8 * g + 4 * hh) * 2) = lean_pack4(v[0], v[1], v[2], v[3], relu, act, sl2);
       }
     if constexpr (BCAST) {
 #pragma unroll
@@ -460,8 +470,8 @@ __device__ __forceinline__ void epilogue_lean_seq(const ConvParams& p, f32x16 (&
   }
 }
 
-// immediate form used by conv_mfma (v1), v2, v3, v5 and v7 (v7: generic only, its counted wait is checked against ONE
-// epilogue's store count)
+// The entry point of conv_mfma (v1), v2, v3, v5 and v7: all rows of the wave's tile, stored as they are packed (v7: generic only,
+// its counted wait is checked against ONE epilogue's store count; v10 and v11 have deferred / half-line epilogues of their own)
 // MODE: 1 = generic form only, 2 = lean form only (the kernel instantiation was chosen on the host), 3 = both, chosen at run
 // time from ConvParams::simple (conv_mfma v1, whose many instantiations are not multiplied again)
 template <int NTX, bool BIAS_IN_ACC = false, int MODE = 3>
@@ -484,97 +494,10 @@ __device__ __forceinline__ void epilogue_simple_rows(const ConvParams& p, f32x16
   for (int nt = 0; nt < NTX; ++nt) epilogue_store_row(p, rows[nt], ew, n, cbase, oy_first + nt, ox_first, lane, full);
 }
 
-// Lean epilogue of the weight-stationary 3x3 kernel (conv_mfma_v10): what `conv_is_lean` admits -- fp16 NHWC output,
-// no GDN, no PixelShuffle, bias already in the accumulators, activation max(v, v * slope), NRES fp16 residuals known at
-// compile time.  The generic transposed epilogue above carries every mode as run-time branches (1.4 k vector instructions
-// per 16x32 tile per wave, 0.9 k s_nop of hazard padding between its fp32 conversions); with one wave per SIMD those
-// instructions are serial time in which the matrix pipe idles.  Here a 2-row round is: residual loads first (their
-// latency runs under the packing), 64 accumulators -> packed fp16 (v_cvt_pk_f16_f32), activation as packed fp16 math
-// (what the reference's autocast computes: the conv result is an fp16 tensor, LeakyReLU runs on it), 16 ds_write_b64 into
-// two wave-private 32 x 144 B regions, 8 ds_read_b128, packed fp16 residual adds, 8 full-line stores.
+// What the lean epilogues admit (epilogue_lean_seq above, and the kernels with an epilogue of their own: v10, v11, conv_row,
+// conv_c8): fp16 NHWC output, no GDN, no PixelShuffle, activation max(v, v * slope), fp16 residuals.
 inline bool conv_is_lean(const ConvParams& p) {
   return conv_is_simple(p) && p.out_mode == TDVC_OUT_NHWC && !p.gdn;
-}
-
-template <int NRES, int NR, bool STAMPED = false>
-__device__ __forceinline__ void epilogue_lean_rows(const ConvParams& p, const f32x16 (&acc)[2][NR], unsigned char* ew, int n,
-                                                   int cbase, int oy, int ox_first, int lane, bool full, long long* st = nullptr) {
-#define EST(i) do { if constexpr (STAMPED) { if (st) st[i] = clock64(); } } while (0)
-  static_assert(NR % 2 == 0, "two rows per round");
-  constexpr int EPS = 144, EROW = 32 * EPS;
-  const int hh = lane >> 5, r = lane & 31;
-  const int chunk = lane & 7, prow = lane >> 3;
-  const int co = cbase + chunk * 8;
-  const bool ch_ok = co < p.y.C && co < ((p.cout + 63) & ~63);
-  const int cc = ch_ok ? co : 0;
-  int opix[NR][4];
-  bool ok[NR][4];
-#pragma unroll
-  for (int j = 0; j < NR; ++j)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int ox = ox_first + k * 8 + prow;
-      ok[j][k] = full ? ch_ok : (ch_ok && oy + j < p.Ho && ox < p.Wo);
-      opix[j][k] = ok[j][k] ? (oy + j) * p.Wo + ox : 0;
-    }
-  // every residual load of the tile goes out before the first store: the compiler's waits on them are then counted
-  // (vmcnt(k), k = younger stores) instead of draining the previous round's stores
-  half8 r1[NR][4], r2[NR][4];
-  if constexpr (NRES >= 1) {
-    const half_t* rb = reinterpret_cast<const half_t*>(p.res.p) + (long)n * p.res.sn + cc;
-#pragma unroll
-    for (int j = 0; j < NR; ++j)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) r1[j][k] = *reinterpret_cast<const half8*>(rb + (long)opix[j][k] * p.res.sp);
-  }
-  if constexpr (NRES >= 2) {
-    const half_t* rb = reinterpret_cast<const half_t*>(p.res2.p) + (long)n * p.res2.sn + cc;
-#pragma unroll
-    for (int j = 0; j < NR; ++j)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) r2[j][k] = *reinterpret_cast<const half8*>(rb + (long)opix[j][k] * p.res2.sp);
-  }
-  const half_t sl = (half_t)p.slope;
-  const half2v sl2 = {sl, sl};
-  const bool act = p.slope != 1.f;                       // wave-uniform: no activation -> no packed math at all
-  half_t* yb = reinterpret_cast<half_t*>(p.y.p) + (long)n * p.y.sn + cc;
-  EST(0);
-#pragma unroll
-  for (int j0 = 0; j0 < NR; j0 += 2) {
-#pragma unroll
-    for (int j = j0; j < j0 + 2; ++j)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          half2v lo = {(half_t)acc[mt][j][4 * g + 0], (half_t)acc[mt][j][4 * g + 1]};
-          half2v hi = {(half_t)acc[mt][j][4 * g + 2], (half_t)acc[mt][j][4 * g + 3]};
-          if (act) {
-            lo = __builtin_elementwise_max(lo, lo * sl2);
-            hi = __builtin_elementwise_max(hi, hi * sl2);
-          }
-          half4 o = {lo[0], lo[1], hi[0], hi[1]};
-          *reinterpret_cast<half4*>(ew + (j & 1) * EROW + r * EPS + (mt * 32 + 8 * g + 4 * hh) * 2) = o;
-        }
-    EST(1 + 3 * (j0 / 2));                 // packed + written to LDS (issue)
-    half8 h[2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) h[j][k] = *reinterpret_cast<const half8*>(ew + j * EROW + (k * 8 + prow) * EPS + chunk * 16);
-    EST(2 + 3 * (j0 / 2));                 // transposed values back (clock64 drains lgkmcnt)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        half8 v = h[j][k];
-        if constexpr (NRES >= 1) v = v + r1[j0 + j][k];
-        if constexpr (NRES >= 2) v = v + r2[j0 + j][k];
-        if (ok[j0 + j][k]) *reinterpret_cast<half8*>(yb + (long)opix[j0 + j][k] * p.y.sp) = v;
-      }
-    EST(3 + 3 * (j0 / 2));                 // stores issued
-  }
-#undef EST
 }
 
 }  // namespace convk

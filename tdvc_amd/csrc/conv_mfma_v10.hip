@@ -6,9 +6,8 @@
 // + 5.6k of epilogue in which no wave issues an MFMA.  v7's wave computes 64 couts x (2 rows x 32 px): one LDS fragment
 // read per MFMA, and the two waves of a SIMD fight for the issue port.
 //
-// v10 keeps v7's memory system (persistent workgroup per CU, all weights resident in LDS, 16x32-px tiles in 32-channel
-// stages by LDS-DMA into two buffers, XOR-swizzled lane-linear image, counted vmcnt + one barrier per stage, XCD-aware
-// tile walk) and changes the register tile:
+// v10 runs on the shared halo-tile pipeline (conv_dma.h; DESIGN.md, "The shared halo-tile pipeline") with 4 loader waves and
+// the weight-stationary LDS map, as v7 does, and changes the register tile:
 //   * 4 waves, ONE PER SIMD (256 threads, up to 512 VGPRs): a wave owns the matrix pipe of its SIMD, nobody arbitrates;
 //   * each wave computes 64 couts x (4 rows x 32 px): 2 x 4 accumulators (128 registers);
 //   * row reuse: for a fixed (k-half s2, dx) the B fragment of input row ir serves output rows ir, ir-1, ir-2 (dy = 0, 1, 2),
@@ -16,54 +15,32 @@
 //     (v7: 1.0) and half the address arithmetic; the next group's 12 reads are issued under the current group's MFMAs
 //     (768 cycles of cover for ~100 cycles of LDS latency);
 //   * epilogue: two rows at a time through two wave-private LDS regions (the finished tile buffer).
-// LDS map (bytes) as v7: [0, 40K) tile buffer 0 | [40K, 64K) weight slices 0..5 | [64K, 104K) tile buffer 1 |
-// [104K, 152K) weight slices 6..17 | [152K, +512) bias, so that switching buffers is `addr ^ 0x10000`.
-//
 //   * memory traffic kept off the critical path: residual rows are fetched at the start of a tile's second stage, the
 //     epilogue only packs / transposes / adds, and the tile's 16 stores go out under the next tile's first stage; every
 //     vector-memory wait is a plain vmcnt(0) at a stage top (no hand-counted wait: see "epilogue state" in the kernel).
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_dma.h"
 
 using convk::ConvParams;
+using convk::HaloExtra;
+using convk::raw_barrier;
 
 namespace {
 
-constexpr int TH10 = 16, TW10 = 32, NT10 = 4, NW10 = 4, CK10 = 32, NTHR10 = 256;
-constexpr int TIW10 = TW10 + 2, TIH10 = TH10 + 2, NPIX10 = TIW10 * TIH10;   // 34 x 18 = 612 halo pixels
-constexpr int PIECES10 = (NPIX10 + 15) / 16;                                // 39 DMA pieces of 16 pixels x 64 B
-constexpr int DMA10 = (PIECES10 + NW10 - 1) / NW10;                         // 10 per wave
-constexpr int BUF1_10 = 0x10000, WLO10 = 40 * 1024, WHI10 = 104 * 1024, MISC10 = 152 * 1024;
-constexpr int LDS10 = MISC10 + 512;
-constexpr int WSL10 = 4096;
+constexpr int TH10 = convk::HALO_TH, TW10 = convk::HALO_TW, TIW10 = convk::HALO_IW, NT10 = 4, NW10 = 4, NTHR10 = 256;
+using Dma10 = convk::HaloDma<NW10, true, false>;
+constexpr int DMA10 = Dma10::SLOTS;                                         // 10 per wave
+constexpr int BUF1_10 = convk::WS_BUF1, WLO10 = convk::WS_WLO, MISC10 = convk::WS_MISC, LDS10 = convk::WS_LDS, WSL10 = convk::WS_WSL;
 constexpr int EROW10 = 32 * 144;                                            // one transposed output row (epilogue scratch)
-static_assert(DMA10 * NW10 * 1024 <= WLO10, "tile buffer");
 static_assert(NW10 * 2 * EROW10 <= WLO10, "epilogue scratch aliases a tile buffer");
-
-struct V10Extra {
-  int ntiles;
-  const half_t* zeros;      // >= 16 bytes of zeros: the DMA source of out-of-image halo pixels
-};
+static_assert(DMA10 == 2 * 5, "two DMA slots under each of the matrix groups 0..4");
 
 static long long* g_stamp10 = nullptr;
 static int g_stamp10_cap = 0;
 
-__device__ __host__ constexpr int wslice10(int sl) { return sl < 6 ? WLO10 + sl * WSL10 : WHI10 + (sl - 6) * WSL10; }
-
-__device__ __forceinline__ void glds16_10(const half_t* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void raw_barrier10() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 template <int NRES, bool STAMP = false>
-__global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvParams p, const V10Extra e, long long* stamps = nullptr, int stamp_cap = 0) {
+__global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvParams p, const HaloExtra e, long long* stamps = nullptr, int stamp_cap = 0) {
   long long stv[24];
   if constexpr (STAMP) { for (int i = 0; i < 24; ++i) stv[i] = 0; }
 #define ST10(i) do { if constexpr (STAMP) { if (ti == 1 && ch == 1) stv[i] = clock64(); } } while (0)
@@ -81,59 +58,19 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
   convk::xcd_tile_walk(e.ntiles, first, stride, my_tiles);
   if (my_tiles <= 0) return;
 
-  // ---- per-lane DMA item: piece u = j * 4 + wave covers halo pixels q = 16u .. 16u + 15; this lane moves 16-byte slot
-  // (lane & 3) of pixel q = 16u + (lane >> 2), which holds logical chunk c = slot ^ ((q >> 2) & 3).
-  const int csw = (lane & 3) ^ ((lane >> 4) & 3);            // (q >> 2) & 3 == (lane >> 4) & 3 for every piece
-  int it_off[DMA10];
-#pragma unroll
-  for (int j = 0; j < DMA10; ++j) {
-    const int q = 16 * (j * NW10 + wave) + (lane >> 2);
-    const int rr = q / TIW10, cc = q - rr * TIW10;
-    it_off[j] = q < NPIX10 ? (rr * p.W + cc) * p.x_sp + csw * 8 : csw * 8;
-  }
-  const half_t* xn = p.x + (long)n * p.x_sn;
+  Dma10 dma;
+  dma.init(p, e.zeros, n, wave, lane);
 
-  // ---- the tile whose DMA is being issued: (pf_ty, pf_tx) advance by `stride` tiles without a division
-  int pf_iy0 = 0, pf_ix0 = 0, pf_ch = 0;
-  bool pf_interior = false;
-  const half_t* pf_base = xn;
-  auto issue_prep = [&](int ty, int tx, int ch) {
-    pf_iy0 = ty * TH10 - 1;
-    pf_ix0 = tx * TW10 - 1;
-    pf_ch = ch;
-    pf_interior = pf_iy0 >= 0 && pf_ix0 >= 0 && pf_iy0 + TIH10 <= p.H && pf_ix0 + TIW10 <= p.W;
-    pf_base = xn + ((long)pf_iy0 * p.W + pf_ix0) * p.x_sp + ch * CK10;    // only dereferenced when interior
-  };
-  auto issue_one = [&](int j, unsigned dst_buf) {            // j is a compile-time constant at every call site
-    const half_t* src = pf_base + it_off[j];
-    if (!pf_interior) {                  // uniform branch: border tiles (6 % at 1080p) clamp per lane
-      const int q = 16 * (j * NW10 + wave) + (lane >> 2);
-      const int rr = q / TIW10;
-      const int iy = pf_iy0 + rr, ix = pf_ix0 + (q - rr * TIW10);
-      const bool ok = q < NPIX10 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      src = ok ? xn + ((long)iy * p.W + ix) * p.x_sp + pf_ch * CK10 + csw * 8 : e.zeros;
-    }
-    glds16_10(src, dst_buf + (j * NW10 + wave) * 1024);
-  };
-
-  // ---- prologue: first tile's DMA, then bias + resident weights (compiler-tracked loads, younger than the DMA)
+  // ---- prologue: first tile's DMA, then bias + resident weights (compiler-tracked loads, younger than the DMA).
+  // (ty, tx) advance by `tstep` tiles without a division
   const int tile0 = p.reverse ? e.ntiles - 1 - first : first;   // alternate launches walk the raster backwards (tdvc_conv2d)
   const int tstep = p.reverse ? -stride : stride;
   int ty = tile0 / p.tiles_x, tx = tile0 - ty * p.tiles_x;      // the tile being computed
-  issue_prep(ty, tx, 0);
+  dma.prep(p, ty, tx, 0);
 #pragma unroll
-  for (int j = 0; j < DMA10; ++j) issue_one(j, lds0);
+  for (int j = 0; j < DMA10; ++j) dma.issue(p, j, lds0);
 
-  if (tid < 64) bias_s[tid] = p.bias[blockIdx.y * 64 + tid];
-  {
-    constexpr int nslices = nchunks * 9;             // slice (ch, t) = 4 KB [mt 2][s2 2][lane 64][8 halves]
-    for (int i = tid; i < nslices * 256; i += NTHR10) {
-      const int sl = i >> 8, u = i & 255;            // u = q*64 + lane, q = mt*2 + s2
-      const int qq = u >> 6, ln = u & 63;
-      const half_t* src = p.w + ((((long)(cb * 2 + (qq >> 1)) * nslices + sl) * 2 + (qq & 1)) * 64 + ln) * 8;
-      *reinterpret_cast<half8*>(smem + wslice10(sl) + u * 16) = *reinterpret_cast<const half8*>(src);
-    }
-  }
+  convk::ws_load_bias_weights<NTHR10>(p, smem, cb, nchunks, tid);
 
   // ---- B-fragment read offsets (tile buffer 0, s2 = 0): input row ir of this wave, column r + dx, chunk slot hh
   int bq[NT10 + 2][3];
@@ -142,7 +79,7 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const int q = (wave * NT10 + ir) * TIW10 + r + dx;
-      bq[ir][dx] = q * 64 + ((hh ^ ((q >> 2) & 3)) << 4);
+      bq[ir][dx] = convk::halo_frag_off(q, hh, 0);
     }
 
   __syncthreads();                       // bias and weights are visible (no DMA-aware wait here: see top of stage)
@@ -196,11 +133,11 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
       ST10(0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's DMA pieces of the stage (and every older store / load) are done
       ST10(1);
-      raw_barrier10();                   // every wave's pieces landed; every wave is done with the other buffer
+      raw_barrier();                   // every wave's pieces landed; every wave is done with the other buffer
       ST10(2);
       const bool have_next = ch == 0 || !last_tile;
-      if (ch == 0) issue_prep(ty, tx, 1);
-      else if (have_next) issue_prep(nty, ntx, 0);
+      if (ch == 0) dma.prep(p, ty, tx, 1);
+      else if (have_next) dma.prep(p, nty, ntx, 0);
       const unsigned nbuf = lds0 + (bsel ^ BUF1_10);
       if constexpr (ch == 1) {           // this tile's output geometry + residual prefetch (consumed by the epilogue below)
         const int oy = ty * TH10 + wave * NT10, ox_first = tx * TW10;
@@ -246,8 +183,8 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
 
       // matrix phase: 6 groups (s2, dx) of 24 MFMAs; group g+1's 12 fragment reads are issued under group g's MFMAs
       const unsigned char* tb = smem + bsel;
-      const unsigned char* wlo = smem + (ch == 0 ? WLO10 : wslice10(9)) + lane * 16;                          // taps 0..5 of this chunk
-      const unsigned char* whi = smem + (ch == 0 ? wslice10(6) - 6 * WSL10 : wslice10(9)) + lane * 16;        // taps 6..8
+      const unsigned char* wlo = smem + (ch == 0 ? WLO10 : convk::wslice_off(9)) + lane * 16;                          // taps 0..5 of this chunk
+      const unsigned char* whi = smem + (ch == 0 ? convk::wslice_off(6) - 6 * WSL10 : convk::wslice_off(9)) + lane * 16;        // taps 6..8
       half8 fa[2][3][2], fb[2][NT10 + 2];
       auto load_group = [&](int g, int buf) {
         const int s2 = g / 3, dx = g - 3 * s2;
@@ -292,8 +229,8 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
           if (g < NT10 && pend_mask) store_pending(g);     // the group-4 DMA pieces the next stage top waits for
         }
         if (have_next && g < 5) {          // 10 DMA pieces of the next stage, two per group
-          issue_one(2 * g, nbuf);
-          issue_one(2 * g + 1, nbuf);
+          dma.issue(p, 2 * g, nbuf);
+          dma.issue(p, 2 * g + 1, nbuf);
         }
         ST10(8 + g);
       }
@@ -304,7 +241,7 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
 
     {
       constexpr int ch = 1;
-      raw_barrier10();                     // all waves finished reading tile buffer 1: it becomes epilogue scratch
+      raw_barrier();                     // all waves finished reading tile buffer 1: it becomes epilogue scratch
       ST10(4);
       // epilogue: pack (fp16, packed activation) -> wave-private LDS rows -> 8 channels x 4 pixels per lane -> + residuals -> pend
       constexpr int EPS = 144;
@@ -313,7 +250,6 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
       const half2v sl2 = {sl, sl};
       const bool act = p.slope != 1.f;     // wave-uniform: no activation -> no packed math at all
       const bool relu = p.slope == 0.f;    // ReLU: one packed max against zero (half of the 64-channel layers)
-      const half2v zero2 = {(half_t)0.f, (half_t)0.f};
 #pragma unroll
       for (int j0 = 0; j0 < NT10; j0 += 2) {
 #pragma unroll
@@ -322,17 +258,9 @@ __global__ __launch_bounds__(NTHR10, 1) void conv_mfma_v10_kernel(const ConvPara
           for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-              half2v lo = {(half_t)acc[mt][j][4 * g + 0], (half_t)acc[mt][j][4 * g + 1]};
-              half2v hi = {(half_t)acc[mt][j][4 * g + 2], (half_t)acc[mt][j][4 * g + 3]};
-              if (relu) {
-                lo = __builtin_elementwise_max(lo, zero2);
-                hi = __builtin_elementwise_max(hi, zero2);
-              } else if (act) {
-                lo = __builtin_elementwise_max(lo, lo * sl2);
-                hi = __builtin_elementwise_max(hi, hi * sl2);
-              }
-              half4 o = {lo[0], lo[1], hi[0], hi[1]};
-              *reinterpret_cast<half4*>(ew + (j & 1) * EROW10 + r * EPS + (mt * 32 + 8 * g + 4 * hh) * 2) = o;
+              const f32x16& a = acc[mt][j];
+              *reinterpret_cast<half4*>(ew + (j & 1) * EROW10 + r * EPS + (mt * 32 + 8 * g + 4 * hh) * 2) =
+                  convk::lean_pack4(a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3], relu, act, sl2);
             }
 #pragma unroll
         for (int j = j0; j < j0 + 2; ++j)
@@ -371,19 +299,13 @@ bool conv_v10_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int
 }
 
 int launch_conv_v10(const ConvParams& p, int cout_blocks, int N, hipStream_t st) {
-  const void* zeros = nullptr;
-  if (const int zrc = tdvc_scratch_pages(&zeros, nullptr)) return zrc;
-  ConvParams q = p;
-  q.tiles_x = (p.Wo + TW10 - 1) / TW10;
-  const int tiles_y = (p.Ho + TH10 - 1) / TH10;
-  V10Extra e;
-  e.ntiles = q.tiles_x * tiles_y;
-  e.zeros = reinterpret_cast<const half_t*>(zeros);
-  q.slope = convk::conv_simple_slope(p);
-  dim3 grid(convk::persistent_grid_x(256, cout_blocks, N, e.ntiles), cout_blocks, N);
+  ConvParams q;
+  HaloExtra e;
+  dim3 grid;
+  if (const int rc = convk::halo_launch_setup(p, cout_blocks, N, q, e, grid)) return rc;
   const int nres = (p.res.p ? 1 : 0) + (p.res2.p ? 1 : 0);
   if (nres == 1 && !p.res.p) { q.res = q.res2; q.res2 = null_fmap(); }        // a single residual is always `res`
-#define V10_GO(NRES, STAMP) convk::launch_big_lds<&conv_mfma_v10_kernel<NRES, STAMP>, ConvParams, V10Extra, long long*, int>
+#define V10_GO(NRES, STAMP) convk::launch_big_lds<&conv_mfma_v10_kernel<NRES, STAMP>, ConvParams, HaloExtra, long long*, int>
   const auto go = g_stamp10 ? (nres == 0 ? V10_GO(0, true) : nres == 1 ? V10_GO(1, true) : V10_GO(2, true))
                             : (nres == 0 ? V10_GO(0, false) : nres == 1 ? V10_GO(1, false) : V10_GO(2, false));
 #undef V10_GO

@@ -4,8 +4,9 @@
 //
 // These layers are compute-bound (575 FLOP/B at 128->128) but cannot be weight-stationary: 64 couts x 128 cin x 9 taps is
 // 144 KB.  v3 stages tile AND weights of every 32-channel stage global -> VGPR -> LDS (measured: 4.3 k cycles of load-issue
-// back-pressure per 5 k-cycle stage).  v11 keeps v7's pipeline and lets the LDS-DMA carry both:
-//   * a stage = one 32-channel chunk of a 16x32-px tile (39 KB halo image, XOR-swizzled as in v7) + the 64-cout weight
+// back-pressure per 5 k-cycle stage).  v11 runs on the shared halo-tile pipeline (conv_dma.h; DESIGN.md, "The shared halo-tile
+// pipeline") and lets the LDS-DMA carry both:
+//   * a stage = one 32-channel chunk of a 16x32-px tile (39 KB halo image, loaded by waves 0-3) + the 64-cout weight
 //     slice of that chunk (36 KB = 2 cout tiles x 18 k-steps x 1 KB, already in MFMA fragment order in global memory, so
 //     a DMA piece IS a fragment); two stage buffers (2 x 76 KB); stage S+1 streams in during stage S's matrix phase:
 //     75 pieces, waves 0-3 the tile, waves 4-7 the weights (affine slot addressing), hidden behind the partner wave of each SIMD;
@@ -16,22 +17,25 @@
 //     buffer: 32 couts = 64-byte half lines, 2 stores per row, 8 per full tile -- the count the top-of-stage
 //     `s_waitcnt vmcnt(8)` lets stay in flight (checked in the listing at build time, Makefile / check_asm.py).
 // LDS map (bytes): [0, 40K) tile 0 | [40K, 76K) weights 0 | [80K, 120K) tile 1 | [120K, 156K) weights 1 | [156K, +256) bias.
-#include "conv_common.h"
+#include "conv_dma.h"
 
 using convk::ConvParams;
+using convk::glds16;
+using convk::raw_barrier;
 
 namespace {
 
-constexpr int TH11 = 16, TW11 = 32, NT11 = 4, NW11 = 8, CK11 = 32, NTHR11 = 512;
-constexpr int TIW11 = TW11 + 2, TIH11 = TH11 + 2, NPIX11 = TIW11 * TIH11;   // 34 x 18 = 612 halo pixels
-constexpr int TPIECES11 = (NPIX11 + 15) / 16;                               // 39 tile pieces of 16 pixels x 64 B
+constexpr int TH11 = convk::HALO_TH, TW11 = convk::HALO_TW, TIW11 = convk::HALO_IW, NT11 = 4, NW11 = 8, NTHR11 = 512;
+using Dma11 = convk::HaloDma<4, false, true>;                               // waves 0-3; piece 39 (no pixel) is not issued
+constexpr int TPIECES11 = convk::HALO_PIECES;                               // 39 tile pieces of 16 pixels x 64 B
 constexpr int WPIECES11 = 2 * 18;                                           // 36 weight pieces (cout tile, k-step)
 constexpr int PIECES11 = TPIECES11 + WPIECES11;                             // 75 per stage
 constexpr int DMA11 = (PIECES11 + NW11 - 1) / NW11;                         // 10 slots per wave
 constexpr int TILE0_11 = 0, W0_11 = 40 * 1024, BUFSTEP11 = 80 * 1024, MISC11 = 156 * 1024;
 constexpr int LDS11 = MISC11 + 256;
 constexpr int EPS11 = 80, EROW11 = 32 * EPS11;                              // transposed half-line rows (32 px x 64 B + pad)
-static_assert(TPIECES11 * 1024 <= W0_11 && W0_11 + WPIECES11 * 1024 <= BUFSTEP11, "stage buffer layout");
+static_assert(Dma11::IMAGE_BYTES <= W0_11 && W0_11 + WPIECES11 * 1024 <= BUFSTEP11, "stage buffer layout");
+static_assert(Dma11::SLOTS == DMA11 && WPIECES11 <= 4 * 9, "both roles fit the 10 slots (weights: 9 per wave)");
 static_assert(NW11 * 2 * EROW11 <= W0_11, "epilogue scratch aliases a tile buffer");
 
 struct V11Extra {
@@ -39,17 +43,6 @@ struct V11Extra {
   int experiment;           // 0 in every product launch (see g_v11_experiment)
   const half_t* zeros;      // >= 16 bytes of zeros: the DMA source of out-of-image halo pixels
 };
-
-__device__ __forceinline__ void glds16_11(const half_t* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void raw_barrier11() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 static long long* g_stamp11 = nullptr;
 static int g_stamp11_cap = 0;
@@ -90,58 +83,34 @@ __global__ __launch_bounds__(NTHR11, 1) void conv_mfma_v11_kernel(const ConvPara
   const int nstages = my_tiles * nchunks;
   if (nstages <= 0) return;
 
-  // ---- DMA roles.  Waves 0-3 move the TILE: slot j of wave w is piece u = j * 4 + w (10 slots, u < 39): halo pixels 16u ..
-  // 16u + 15; this lane moves 16-byte slot (lane & 3) of pixel 16u + (lane >> 2), logical chunk slot ^ ((q >> 2) & 3).
+  // ---- DMA roles.  Waves 0-3 move the TILE (Dma11: the per-lane slot offsets are recomputed per slot -- ten of them in
+  // registers spilled the 256-VGPR budget).
   // Waves 4-7 move the WEIGHTS: slot j of wave 4 + w is fragment (cout tile w & 1, k-step 2j + (w >> 1)), 9 slots: source and
   // destination are affine in j with wave-constant bases (a piece is lane-linear: the fragment as it is read), so a slot
   // costs one 64-bit add and the M0 write -- the mixed assignment of the first version spent ~35 scalar instructions and
   // 5 v_readlane (spilled SGPRs) per slot.
   const bool tile_role = wave < 4;                           // wave-uniform
   const int w3 = wave & 3;
-  const int csw = (lane & 3) ^ ((lane >> 4) & 3);
-  const int q0 = 16 * w3 + (lane >> 2);                      // halo pixel of this lane in slot 0; slot j: + 64 j
-  const int xrow = p.W * p.x_sp;                             // elements per image row (the per-lane slot offsets are recomputed per
-                                                             // slot: ten of them in registers spilled the 256-VGPR budget)
-  const half_t* xn = p.x + (long)n * p.x_sn;
+  Dma11 dma;
+  dma.init(p, e.zeros, n, w3, lane);
   // weights of cout block cb: [cout tile 2][chunk][k-step 18][lane 64][8]; this wave's fragment column
   const half_t* wsrc0 = p.w + ((long)(cb * 2 + (w3 & 1)) * nchunks * 18 + (w3 >> 1)) * 512 + lane * 8;    // + (ch * 18 + 2j) * 512
   const unsigned wdst0 = W0_11 + ((w3 & 1) * 18 + (w3 >> 1)) * 1024;                                       // + 2j * 1024
 
-  int pf_iy0 = 0, pf_ix0 = 0, pf_ch = 0;
-  bool pf_interior = false;
-  const half_t* pf_base = xn;
   const half_t* pf_w = wsrc0;
   auto issue_prep = [&](int S) {
     const int tile_i = S / nchunks, ch = S - tile_i * nchunks;
-    pf_ch = ch;
     pf_w = wsrc0 + (long)ch * 18 * 512;
     if (tile_role) {
-      const int tile = p.reverse ? e.ntiles - 1 - (first + tile_i * stride) : first + tile_i * stride;
+      const int tile = convk::walk_tile(p, e.ntiles, first, stride, tile_i);
       const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
-      pf_iy0 = ty * TH11 - 1;
-      pf_ix0 = tx * TW11 - 1;
-      pf_interior = pf_iy0 >= 0 && pf_ix0 >= 0 && pf_iy0 + TIH11 <= p.H && pf_ix0 + TIW11 <= p.W;
-      pf_base = xn + ((long)pf_iy0 * p.W + pf_ix0) * p.x_sp + ch * CK11;  // only dereferenced when interior
+      dma.prep(p, ty, tx, ch);
     }
   };
   auto issue_one = [&](int j, unsigned dst_buf) {            // j is a compile-time constant at every call site
     if constexpr (STAMP) { if (e.experiment == 2 || (e.experiment == 1 && !tile_role)) return; }
-    if (tile_role) {
-      const int u = j * 4 + w3;
-      if (u < TPIECES11) {
-        const int q = q0 + 64 * j;
-        const int rr = q / TIW11, cc = q - rr * TIW11;
-        const half_t* src = pf_base + (q < NPIX11 ? rr * xrow + cc * p.x_sp : 0) + csw * 8;
-        if (!pf_interior) {              // uniform branch: border tiles clamp per lane
-          const int iy = pf_iy0 + rr, ix = pf_ix0 + cc;
-          const bool ok = q < NPIX11 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-          src = ok ? xn + ((long)iy * p.W + ix) * p.x_sp + pf_ch * CK11 + csw * 8 : e.zeros;
-        }
-        glds16_11(src, dst_buf + TILE0_11 + u * 1024);
-      }
-    } else if (j < 9) {
-      glds16_11(pf_w + j * 1024, dst_buf + wdst0 + j * 2048);
-    }
+    if (tile_role) dma.issue(p, j, dst_buf + TILE0_11);
+    else if (j < 9) glds16(pf_w + j * 1024, dst_buf + wdst0 + j * 2048);
   };
 
   // ---- prologue: first stage's DMA, then the bias (a compiler-tracked load, younger than the DMA)
@@ -157,7 +126,7 @@ __global__ __launch_bounds__(NTHR11, 1) void conv_mfma_v11_kernel(const ConvPara
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const int q = (rg * NT11 + ir) * TIW11 + r + dx;
-      bq[ir][dx] = TILE0_11 + q * 64 + ((hh ^ ((q >> 2) & 3)) << 4);
+      bq[ir][dx] = TILE0_11 + convk::halo_frag_off(q, hh, 0);
     }
   const int aoff = W0_11 + mt * 18 * 1024 + lane * 16;       // + (tap * 2 + s2) * 1024
 
@@ -172,7 +141,7 @@ __global__ __launch_bounds__(NTHR11, 1) void conv_mfma_v11_kernel(const ConvPara
     if (stores_in_flight) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ST11(1);
-    raw_barrier11();                     // every wave's pieces landed; every wave is done with the other buffer
+    raw_barrier();                     // every wave's pieces landed; every wave is done with the other buffer
     ST11(2);
     const bool have_next = S + 1 < nstages;
     if (have_next) issue_prep(S + 1);
@@ -241,10 +210,10 @@ __global__ __launch_bounds__(NTHR11, 1) void conv_mfma_v11_kernel(const ConvPara
     if (ch != nchunks - 1) continue;
 
     // ---- epilogue: 32 couts x 4 rows of this wave, transposed through the finished tile buffer
-    const int tile = p.reverse ? e.ntiles - 1 - (first + tile_i * stride) : first + tile_i * stride;
+    const int tile = convk::walk_tile(p, e.ntiles, first, stride, tile_i);
     const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
     const bool full = (ty + 1) * TH11 <= p.Ho && (tx + 1) * TW11 <= p.Wo;
-    raw_barrier11();                     // all waves finished reading this stage's buffers: the tile buffer becomes scratch
+    raw_barrier();                     // all waves finished reading this stage's buffers: the tile buffer becomes scratch
     ST11(4);
     {
       unsigned char* ew = smem + bofs + TILE0_11 + wave * (2 * EROW11);
@@ -264,7 +233,7 @@ __global__ __launch_bounds__(NTHR11, 1) void conv_mfma_v11_kernel(const ConvPara
       const int oy0 = ty * TH11 + rg * NT11, ox0 = tx * TW11;
       const bool has1 = p.res.p != nullptr, has2 = p.res2.p != nullptr;    // wave-uniform
       const half_t sl = (half_t)p.slope;
-      const half2v sl2 = {sl, sl}, zero2 = {(half_t)0.f, (half_t)0.f};
+      const half2v sl2 = {sl, sl};
       const bool act = p.slope != 1.f, relu = p.slope == 0.f;
       half_t* yb = reinterpret_cast<half_t*>(p.y.p) + (long)n * p.y.sn + cc;
       const half_t* rb1 = reinterpret_cast<const half_t*>(p.res.p) + (long)n * p.res.sn + cc;
@@ -291,17 +260,9 @@ __global__ __launch_bounds__(NTHR11, 1) void conv_mfma_v11_kernel(const ConvPara
         unsigned char* er = ew + (j & 1) * EROW11;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          half2v lo = {(half_t)acc[j][4 * g + 0], (half_t)acc[j][4 * g + 1]};
-          half2v hi = {(half_t)acc[j][4 * g + 2], (half_t)acc[j][4 * g + 3]};
-          if (relu) {
-            lo = __builtin_elementwise_max(lo, zero2);
-            hi = __builtin_elementwise_max(hi, zero2);
-          } else if (act) {
-            lo = __builtin_elementwise_max(lo, lo * sl2);
-            hi = __builtin_elementwise_max(hi, hi * sl2);
-          }
-          const half4 o = {lo[0], lo[1], hi[0], hi[1]};
-          *reinterpret_cast<half4*>(er + r * EPS11 + (8 * g + 4 * hh) * 2) = o;
+          const f32x16& a = acc[j];
+          *reinterpret_cast<half4*>(er + r * EPS11 + (8 * g + 4 * hh) * 2) =
+              convk::lean_pack4(a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3], relu, act, sl2);
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -340,17 +301,11 @@ bool conv_v11_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int
 }
 
 int launch_conv_v11(const ConvParams& p, int cout_blocks, int N, hipStream_t st) {
-  const void* zeros = nullptr;
-  if (const int zrc = tdvc_scratch_pages(&zeros, nullptr)) return zrc;
-  ConvParams q = p;
-  q.tiles_x = (p.Wo + TW11 - 1) / TW11;
-  const int tiles_y = (p.Ho + TH11 - 1) / TH11;
+  ConvParams q;
   V11Extra e;
-  e.ntiles = q.tiles_x * tiles_y;
-  e.zeros = reinterpret_cast<const half_t*>(zeros);
+  dim3 grid;
+  if (const int rc = convk::halo_launch_setup(p, cout_blocks, N, q, e, grid)) return rc;
   e.experiment = g_v11_experiment;
-  q.slope = convk::conv_simple_slope(p);
-  dim3 grid(convk::persistent_grid_x(256, cout_blocks, N, e.ntiles), cout_blocks, N);
   const auto go = g_stamp11 ? convk::launch_big_lds<&conv_mfma_v11_kernel<true>, ConvParams, V11Extra, long long*, int>
                             : convk::launch_big_lds<&conv_mfma_v11_kernel<false>, ConvParams, V11Extra, long long*, int>;
   return go("tdvc_conv2d(v11)", 160 * 1024, grid, dim3(NTHR11), LDS11, st, q, e, g_stamp11, g_stamp11 ? g_stamp11_cap : 0);

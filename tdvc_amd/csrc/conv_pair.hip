@@ -34,7 +34,10 @@
 // For the DMA-written input rows the XOR sits on the SOURCE address.
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_dma.h"
+
+using convk::glds16;
+using convk::raw_barrier;
 
 namespace {
 
@@ -129,16 +132,6 @@ struct PairParams {
 // swizzle term of pixel q of a ring row (see the LDS image note at the top)
 __device__ __forceinline__ int swz(int q) { return (int)((0x62654210u >> (4 * ((q >> 1) & 7))) & 7u); }
 
-__device__ __forceinline__ void glds16(const half_t* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void pair_barrier(bool skip = false) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (!skip) __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 template <int A>
 __device__ __forceinline__ half4 actk(half4 v, half4 sl) {
   if constexpr (A == 1) {
@@ -368,7 +361,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
         if (kk <= rows + 3) issue_row(kk);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pair_barrier();
+    raw_barrier();
 
     const int K = (rows + 4 + 2 * BI + BI - 1) & ~(BI - 1);      // row steps, a whole number of barrier intervals
     // Before a step's barrier: everything this wave sent more than HD steps ago has landed (NCB = 2: row k + 4 is read from step
@@ -395,7 +388,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
       using S2c = std::integral_constant<int, (PH + 2) % 3>;
       const int i = ra - 2 + k;
       long long t0 = 0, t1 = 0, t2 = 0;
-      if constexpr (STAMP && FULL) t0 = clock64();       // lgkmcnt is 0 here (pair_barrier): the read costs nothing
+      if constexpr (STAMP && FULL) t0 = clock64();       // lgkmcnt is 0 here (raw_barrier): the read costs nothing
       if constexpr (ROLE == 0) {
         // ---- conv1 wave: t row new = slot (PH + 1) % 3, mid = PH, done = (PH + 2) % 3
         int nvm = 0;
@@ -468,7 +461,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
         }
       }
       if constexpr (STAMP && FULL) t2 = clock64();
-      pair_barrier((k & (BI - 1)) != BI - 1 || (p.experiment & 4) != 0);     // one barrier per BI row steps
+      raw_barrier((k & (BI - 1)) != BI - 1 || (p.experiment & 4) != 0);     // one barrier per BI row steps
       if constexpr (STAMP && FULL) {
         const long long t3 = clock64();
         st_busy += t1 - t0; st_vm += t2 - t1; st_bar += t3 - t2; st_n += 1;

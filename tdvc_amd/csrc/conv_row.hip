@@ -36,9 +36,11 @@
 // hold zero weights and are skipped at compile time: 18 fragments per wave, two live output rows).
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_dma.h"
 
 using convk::ConvParams;
+using convk::glds16;
+using convk::raw_barrier;
 
 namespace {
 
@@ -107,21 +109,11 @@ template <int PXB> __device__ __forceinline__ int rw_f(int q) {                 
 __device__ __forceinline__ int rw_sigma(int r) { return r < 4 ? 2 * r : (r >= 12 ? 2 * r - 16 : 2 * r - 7); }   // fragment lane -> pixel of its 16-px block
 __device__ __forceinline__ int rw_g(int q) { return (q >> 1) & 7; }                                      // staging-row swizzle term
 
-__device__ __forceinline__ void rw_glds16(const half_t* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
 // ring slot of row kk: a mask for the 8-row rings; the 6-row rings divide by a constant -- on the scalar unit (kk is wave-uniform; left to
 // itself hipcc did the multiply-high in vector registers, three more live registers in kernels at the 256-register limit)
 template <int XRING> __device__ __forceinline__ int rw_slot(int kk) {
   if constexpr ((XRING & (XRING - 1)) == 0) return kk & (XRING - 1);
   else return __builtin_amdgcn_readfirstlane(kk) % XRING;
-}
-__device__ __forceinline__ void rw_barrier(bool skip = false) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (!skip) __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // which (tap row dy, tap column dx, chunk kc) fragments exist: all of them for a dense window; in the space-to-depth geometry chunk kc
@@ -327,7 +319,7 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
 #pragma unroll
         for (int j = 0; j < NP - 1; ++j) {
           const half_t* src = G::S2D ? base + soff[j] : base + (long)(QSTEP * j) * p.x_sp + soff[0];
-          rw_glds16(((okb >> j) & 1u) ? src : p.zeros, dst + (wq + 4 * j) * 1024);
+          glds16(((okb >> j) & 1u) ? src : p.zeros, dst + (wq + 4 * j) * 1024);
         }
       } else {
         // four regular pieces per loader (the 17-piece rows): a rolled loop, so that the four source addresses are formed one at a time
@@ -335,11 +327,11 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
 #pragma nounroll
         for (int j = 0; j < NP - 1; ++j) {
           const half_t* src = base + (long)(QSTEP * j) * p.x_sp + soff[0];
-          rw_glds16(((okb >> j) & 1u) ? src : p.zeros, dst + (wq + 4 * j) * 1024);
+          glds16(((okb >> j) & 1u) ? src : p.zeros, dst + (wq + 4 * j) * 1024);
         }
       }
       if (G::HD == 4 ? wq == (kk & 3) : wq == 0) {
-        rw_glds16(((okb >> (NP - 1)) & 1u) ? base + soff[SRC - 1] : p.zeros, dst + (G::PIECES - 1) * 1024);
+        glds16(((okb >> (NP - 1)) & 1u) ? base + soff[SRC - 1] : p.zeros, dst + (G::PIECES - 1) * 1024);
         return NP;
       }
       return NP - 1;
@@ -352,7 +344,7 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
         if (kk <= last_in) issue_row(kk);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    rw_barrier();
+    raw_barrier();
 
     const int K = (rows + KH - 1 + RW_BI + RW_BI - 1) & ~(RW_BI - 1);     // steps, a whole number of barrier intervals
     // A loader's count of instructions left in flight is a constant while rows are being issued: HD = 4: the odd piece goes round the four
@@ -456,7 +448,7 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
         }
       }
       if constexpr (LOADER) land_wait(nvm);
-      rw_barrier((k & (RW_BI - 1)) != RW_BI - 1);
+      raw_barrier((k & (RW_BI - 1)) != RW_BI - 1);
     };
     auto steps_of = [&](auto FULLc, int k0, int kend) __attribute__((always_inline)) {    // up to KH steps from k0 (k0 % KH == 0), while < kend
       step(std::integral_constant<int, 0>{}, FULLc, k0);
@@ -470,7 +462,7 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
     for (; k < KF; k += KH) steps_of(std::false_type{}, k, KF);
     for (; k + KH - 1 <= last_in; k += KH) steps_of(std::true_type{}, k, k + KH);
     for (; k < K; k += KH) steps_of(std::false_type{}, k, K);
-    rw_barrier();                              // the next job's prologue overwrites ring rows the slowest wave may still read
+    raw_barrier();                              // the next job's prologue overwrites ring rows the slowest wave may still read
   }
   };
   if (loader) run(std::true_type{});

@@ -9,7 +9,7 @@ Three grades of data, all made here:
   dyadic  x in multiples of 2^-3, w of 2^-6, bias of 2^-9: the accumulation is still exact, the outputs are not fp16 values,
           so the stored bits are decided by the epilogue's rounding sequence, which `epilogue()` restates per form
           (csrc/conv_common.h: "e4" = epilogue4, "generic" = epilogue_pack + epilogue_store_row, "lean" =
-          epilogue_lean_seq / epilogue_lean_rows and the private copies of conv_mfma_v11, conv_row and conv_c8).
+          epilogue_lean_seq and the epilogues of their own in conv_mfma_v10, conv_mfma_v11, conv_row and conv_c8).
   f64     operations that are inexact by nature (GDN's root, the sigmoid) on dyadic data, against float64 with a bound
           derived in `f64_reference()`.
 
