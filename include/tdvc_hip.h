@@ -368,7 +368,8 @@ int tdvc_pmf_to_quantized_cdf(const float* pmf, int n, int precision, int32_t* c
  * step couples one image to another, so every entry point handles a step's positions of all B images of the call in the SAME
  * launches.  A single image is B = y_hat->N = 1 and there is no other form: ABI 10 removed the single-image entry points of ABI <= 9
  * (tdvc_ar_gather, tdvc_ar_quantize, tdvc_ar_indexes, tdvc_ar_lanes_init, tdvc_ar_decode_lanes_step, tdvc_ar_decode_serial,
- * tdvc_ar_wavefront, tdvc_ar_wavefront_lanes); the *_batch entry points are those of ABI 9, unchanged.
+ * tdvc_ar_wavefront, tdvc_ar_wavefront_lanes); the *_batch entry points are those of ABI 9 (ABI 13: the drivers' arguments
+ * come in descriptors).
  * Layout: y / y_hat / params are fmaps with N = B (their sn / sp strides are honoured: batch views and channel windows of larger
  * buffers work); `pos` is the shared position list, int32 [npos][2] = (h, w) on the device; row b * npos + k (image-major) of the
  * staging maps x1 / pc / gp belongs to position k of image b, so a step is a (1, B * npos) map to the convs; the raster arrays are
@@ -390,33 +391,53 @@ int tdvc_ar_quantize_batch(const tdvc_fmap* y, const tdvc_fmap* gp, const int32_
 /* indexes only (decoder: needed before the symbols can be read from the stream). */
 int tdvc_ar_indexes_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, int B, const float* scale_table, int ntable,
                           int M, int H, int W, int32_t* indexes, int64_t cbase, void* stream);
-/* The context loop over anti-diagonals (wavefront order), natively, in either direction.  pos_dev: device int32 [H*W][2] in
- * wavefront order, step s owning step_sizes[s] (HOST array) consecutive entries; x1 / pc / gp and the conv descriptors' x / y maps
- * (convs[0 .. nconvs): context conv over x1 into pc, entropy_parameters into gp; fixed buffers) are (1, 1, >= B * max step, C)
- * staging buffers whose width is set to the step's B * n rows per step.  data / nbytes: HOST arrays of the B strings and their
- * sizes (decoder) or NULL (encoder, y given).
- * Encoder (replaces `_compress_ar`'s position loop, main/model/pnet.py:48,72): gather -> convs -> quantise per step; sym_dev /
- * idx_dev are raster [B][H][W][M]; nothing but enqueues, nothing synchronises.
- * Decoder of streams whose symbols were emitted in wavefront order (an extension: the reference's streams are raster-ordered,
- * tdvc_ar_decode_serial_batch reads those), per step: gather -> convs -> indexes -> one device->host copy of the B * n * M indexes,
- * the B host range decoders in turn (tables as in tdvc_rans_decode, HOST memory), one host->device copy -> quantise; one stream
- * synchronisation per step; sym_dev / idx_dev are [B][H*W][M] in wavefront order.
- * Every check -- arguments, sizes, B * n against the staging width, the steps covering H * W -- is made before anything touches a
- * device. */
-int tdvc_ar_wavefront_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
-                            const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat,
-                            const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
-                            const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
-                            const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, void* stream);
-/* The decoder's whole context loop for raster-ordered streams (compressai's bitstream), natively: positions pos_table[0 ..
- * npos_total), npos_total = H * W, in raster order, B rows per step: gather -> convs -> indexes -> host range decoders -> quantise.
+/* ABI 13.  The context loop's arguments as descriptors: the groups every driver takes, each written once.
+ * tdvc_cdf_tables: the CDF tables in HOST memory, rows as tdvc_rans_decode takes them (ncdfs rows of `stride` ints).
+ * tdvc_cdf_tables_dev: the same tables in DEVICE memory, packed for the lane kernels (see tdvc_ar_decode_lanes_step_batch below).
+ * tdvc_ar_loop: the chain and its staging buffers, the step list, the scale table and the index / symbol arrays.  B = y_hat.N
+ * images, M = y_hat.C channels, W = y_hat.W: the maps are the one source of the sizes.  pos_dev: device int32 [H*W][2] in step
+ * order, step s owning step_sizes[s] (HOST array) consecutive entries; step_sizes == NULL: nsteps steps of one position each (the
+ * raster order).  x1 / pc / gp and the conv descriptors' x / y maps (convs[0 .. nconvs), nconvs <= 8: context conv over x1 into pc,
+ * entropy_parameters into gp; fixed buffers) are (1, 1, >= B * largest step, C) staging buffers whose width is set to the step's
+ * B * n rows per step. */
+typedef struct tdvc_cdf_tables {
+  const int32_t *cdfs, *sizes, *offsets;
+  int32_t stride, ncdfs;
+} tdvc_cdf_tables;
+typedef struct tdvc_cdf_tables_dev {
+  const uint16_t* cdf16;
+  const int32_t *starts, *sizes, *offsets;
+  int32_t n16, ncdfs;
+} tdvc_cdf_tables_dev;
+typedef struct tdvc_ar_loop {
+  tdvc_fmap y_hat, params;
+  tdvc_fmap x1, pc, gp;
+  const tdvc_conv_desc* convs;
+  int32_t nconvs;
+  const int32_t* pos_dev;
+  const int32_t* step_sizes;
+  int32_t nsteps;
+  const float* scale_table;
+  int32_t ntable;
+  int32_t *idx_dev, *sym_dev;
+} tdvc_ar_loop;
+/* The three drivers below are one loop -- per step gather -> convs -> the driver's back end -- and make every check (arguments,
+ * sizes, B * n against the staging width, the steps covering H * W, the strings) before anything touches a device.  data / nbytes:
+ * HOST arrays of the B strings and their sizes.
+ * tdvc_ar_wavefront_batch, the loop over anti-diagonals in either direction.  Encoder (y given, data / nbytes / tables NULL;
+ * replaces `_compress_ar`'s position loop, main/model/pnet.py:48,72): quantise per step; sym_dev / idx_dev are raster
+ * [B][H][W][M]; nothing but enqueues, nothing synchronises.  Decoder (data given, y NULL) of streams whose symbols were emitted in
+ * wavefront order (an extension: the reference's streams are raster-ordered), per step: indexes -> one device->host copy of the
+ * B * n * M indexes, the B host range decoders in turn, one host->device copy -> quantise; one stream synchronisation per step;
+ * sym_dev / idx_dev are [B][H*W][M] in step order. */
+int tdvc_ar_wavefront_batch(const tdvc_ar_loop* loop, const tdvc_fmap* y, const uint8_t* const* data, const int64_t* nbytes,
+                            const tdvc_cdf_tables* tables, void* stream);
+/* The decoder's whole context loop for raster-ordered streams (compressai's bitstream): tdvc_ar_wavefront_batch's decoder over a
+ * loop whose position list is the raster order, H * W steps of one position (step_sizes == NULL, nsteps = H * W), B rows per step.
  * idx_dev / sym_dev: device int32 [B][H][W][M]; y_hat is filled.  Synchronises the stream once per position (the stream order of
  * compressai's bitstream leaves no other choice). */
-int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
-                                const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params,
-                                const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                                const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
-                                int32_t* idx_dev, int32_t* sym_dev, void* stream);
+int tdvc_ar_decode_serial_batch(const tdvc_ar_loop* loop, const uint8_t* const* data, const int64_t* nbytes, const tdvc_cdf_tables* tables,
+                                void* stream);
 /* Device decoder of lane-split streams (tdvc_rans_encode_lanes).  B containers of ONE lane count L in one device buffer: a table
  * uint32 [B][2] = {byte offset of container b, 32-bit words of its payload}, padded to 16 bytes, then the containers at 16-byte
  * aligned offsets.  tdvc_ar_lanes_batch_layout: -> the bytes the buffer needs (or < 0) and, when table_out is not NULL, the table
@@ -424,9 +445,9 @@ int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int64_t* nbyte
  * ordinary copy puts it there); a table entry that does not lie inside the buffer gives its image no words: flagged, never read.
  * state_dev: [B][L * 4 + 1] words, i.e. B blocks of tdvc_ar_lanes_state_bytes(L) holding the L lane states and one sticky error
  * word (the block's last uint32), which is the only error channel: a damaged stream is flagged, every read stays inside the
- * payload.  The tables of tdvc_rans_decode in DEVICE memory, packed: cdf16_dev holds every table's entries end to end as uint16
- * (the last entry of a table, 1 << 16, wraps to 0 and is implied), n16 entries in all (16-byte aligned, padded to a multiple of
- * 8); table t = cdf_sizes_dev[t] entries from cdf_starts_dev[t]; offsets_dev[t]; ncdfs >= ntable tables.  The kernel keeps the
+ * payload.  tdvc_cdf_tables_dev: the tables of tdvc_rans_decode in DEVICE memory, packed: cdf16 holds every table's entries end to
+ * end as uint16 (the last entry of a table, 1 << 16, wraps to 0 and is implied), n16 entries in all (16-byte aligned, padded to a
+ * multiple of 8); table t = sizes[t] entries from starts[t]; offsets[t]; ncdfs >= ntable tables.  The kernel keeps the
  * first 27 648 entries in LDS (compressai's 64 Gaussian tables have 27 256).
  * tdvc_ar_lanes_init_batch: lane states from the containers' length tables (and error words = 0).
  * tdvc_ar_decode_lanes_step_batch: one step of npos positions: B workgroups of L threads, thread l of workgroup b decoding the
@@ -438,21 +459,16 @@ int64_t tdvc_ar_lanes_batch_layout(const int64_t* nbytes, int B, int L, uint32_t
 int tdvc_ar_lanes_init_batch(const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int B, int L, uint32_t* state_dev, void* stream);
 int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
                                     const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int L,
-                                    const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
-                                    const int32_t* offsets_dev, int32_t ncdfs, uint32_t* state_dev, const tdvc_fmap* y_hat,
+                                    const tdvc_cdf_tables_dev* tables, uint32_t* state_dev, const tdvc_fmap* y_hat,
                                     int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream);
 /* tdvc_ar_wavefront_batch's decoder direction for lane-split streams: the B strings (HOST memory) are validated -- all of one
  * lane count -- and uploaded behind their table, B + 1 copies, into stream_dev (stream_cap >= tdvc_ar_lanes_batch_layout() bytes),
- * then tdvc_ar_lanes_init_batch and per step gather -> convs -> tdvc_ar_decode_lanes_step_batch with no synchronisation; after the
+ * then tdvc_ar_lanes_init_batch and per step of the loop tdvc_ar_decode_lanes_step_batch with no synchronisation; after the
  * last step the error words are read back with the call's only stream wait.  TDVC_EINVAL when an image's error word is set: the
  * message and *bad_image (may be NULL; -1 otherwise) name the FIRST such image.  sym_dev / idx_dev are [B][H*W][M] in wavefront
  * order.  Allocates nothing. */
-int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nbytes, int B, uint8_t* stream_dev, int64_t stream_cap,
-                                  uint32_t* state_dev, const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev,
-                                  const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat,
-                                  const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
-                                  const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
-                                  const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, int32_t* bad_image, void* stream);
+int tdvc_ar_wavefront_lanes_batch(const tdvc_ar_loop* loop, const uint8_t* const* data, const int64_t* nbytes, uint8_t* stream_dev,
+                                  int64_t stream_cap, uint32_t* state_dev, const tdvc_cdf_tables_dev* tables, int32_t* bad_image, void* stream);
 /* ABI 12.  Device ENCODER of lane-split streams: the container of tdvc_rans_encode_lanes, byte for byte, from the encoder loop's
  * raster arrays symbols / indexes [B][H][W][M] in DEVICE memory, so that the symbols never cross the bus.  pos: int32 [npos][2] =
  * (h, w), the wavefront position list; image b is coded by one workgroup of L threads (L = 64 or 128, L | M), thread l coding lane l
@@ -469,17 +485,23 @@ int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nby
  * multiple of 16 of at least 4 + 2 L + 4 L min(lane_words, 65 535).  Tables as in tdvc_ar_decode_lanes_step_batch, ncdfs <= 64.
  * Every check is made before a device is touched; enqueue-only, no atomics, no spinning, nothing persistent.
  * tdvc_rans_encode_lanes_dev_ref: the host twin -- the same encode routine (csrc/rans_lane.h), traversal, scratch layout and
- * assembly over HOST memory, tables as in tdvc_rans_encode (the first ncdfs rows). */
+ * assembly over HOST memory, tables as in tdvc_rans_encode (the first ncdfs rows).
+ * tdvc_lanes_enc (ABI 13): the buffers and sizes above, the same for the kernel (DEVICE memory) and its host twin (HOST memory). */
 int64_t tdvc_ar_encode_lanes_scratch_words(int64_t npos, int M, int L);
 int64_t tdvc_ar_encode_lanes_out_bytes(int64_t npos, int M, int L);
-int tdvc_ar_encode_lanes_batch(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos_dev, int npos, int L,
-                               const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
-                               const int32_t* offsets_dev, int32_t ncdfs, uint32_t* scratch_dev, int64_t lane_words, int64_t scratch_cap_words,
-                               uint8_t* out_dev, int64_t out_stride, int64_t out_cap, uint32_t* info_dev, void* stream);
-int tdvc_rans_encode_lanes_dev_ref(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos, int npos, int L,
-                                   const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int32_t ncdfs,
-                                   uint32_t* scratch, int64_t lane_words, int64_t scratch_cap_words, uint8_t* out, int64_t out_stride,
-                                   int64_t out_cap, uint32_t* info);
+typedef struct tdvc_lanes_enc {
+  const int32_t *symbols, *indexes;
+  int32_t B, H, W, M;
+  const int32_t* pos;
+  int32_t npos, L;
+  uint32_t* scratch;
+  int64_t lane_words, scratch_cap_words;
+  uint8_t* out;
+  int64_t out_stride, out_cap;
+  uint32_t* info;
+} tdvc_lanes_enc;
+int tdvc_ar_encode_lanes_batch(const tdvc_lanes_enc* enc, const tdvc_cdf_tables_dev* tables, void* stream);
+int tdvc_rans_encode_lanes_dev_ref(const tdvc_lanes_enc* enc, const tdvc_cdf_tables* tables);
 /* Kernel enqueues of the last context-loop call on this thread (tdvc_ar_decode_serial_batch, tdvc_ar_wavefront_batch,
  * tdvc_ar_wavefront_lanes_batch), conv launches included: the launches the library's entry points closed during the call.  Copies
  * are not counted.  The count does not depend on B. */

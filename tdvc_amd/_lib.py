@@ -53,6 +53,32 @@ class WgradReduceJob(C.Structure):
 
 _P = C.c_void_p
 _FM = C.POINTER(FMapDesc)
+
+
+# ---- the context loop's descriptors (ABI 13); lib.cpp and tests/test_lib_abi.py pin their layout
+class CdfTablesDesc(C.Structure):
+    """tdvc_cdf_tables: HOST memory"""
+    _fields_ = [("cdfs", _P), ("sizes", _P), ("offsets", _P), ("stride", C.c_int32), ("ncdfs", C.c_int32)]
+
+
+class CdfTablesDevDesc(C.Structure):
+    """tdvc_cdf_tables_dev: DEVICE memory, packed uint16"""
+    _fields_ = [("cdf16", _P), ("starts", _P), ("sizes", _P), ("offsets", _P), ("n16", C.c_int32), ("ncdfs", C.c_int32)]
+
+
+class ArLoopDesc(C.Structure):
+    _fields_ = [("y_hat", FMapDesc), ("params", FMapDesc), ("x1", FMapDesc), ("pc", FMapDesc), ("gp", FMapDesc),
+                ("convs", C.POINTER(ConvDesc)), ("nconvs", C.c_int32), ("pos_dev", _P), ("step_sizes", _P), ("nsteps", C.c_int32),
+                ("scale_table", _P), ("ntable", C.c_int32), ("idx_dev", _P), ("sym_dev", _P)]
+
+
+class LanesEncDesc(C.Structure):
+    _fields_ = [("symbols", _P), ("indexes", _P), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_int32), ("pos", _P),
+                ("npos", C.c_int32), ("L", C.c_int32), ("scratch", _P), ("lane_words", C.c_int64), ("scratch_cap_words", C.c_int64),
+                ("out", _P), ("out_stride", C.c_int64), ("out_cap", C.c_int64), ("info", _P)]
+
+
+_LOOP, _CDF, _CDFD, _ENC = C.POINTER(ArLoopDesc), C.POINTER(CdfTablesDesc), C.POINTER(CdfTablesDevDesc), C.POINTER(LanesEncDesc)
 _i, _f, _i64 = C.c_int, C.c_float, C.c_int64
 
 # name -> (restype, argtypes); every symbol declared in include/tdvc_hip.h
@@ -109,17 +135,16 @@ SIGNATURES = {
     "tdvc_ar_gather_batch": (_i, [_FM, _FM, _P, _i, _FM, _FM, _P]),
     "tdvc_ar_quantize_batch": (_i, [_FM, _FM, _P, _i, _P, _i, _P, _FM, _P, _P, _i64, _P]),
     "tdvc_ar_indexes_batch": (_i, [_FM, _P, _i, _i, _P, _i, _i, _i, _i, _P, _i64, _P]),
-    "tdvc_ar_wavefront_batch": (_i, [_P, _P, _i, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
-    "tdvc_ar_decode_serial_batch": (_i, [_P, _P, _i, _P, _i, _P, _P, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _i, _i, _i, _P, _i, _P, _P, _P]),
+    "tdvc_ar_wavefront_batch": (_i, [_LOOP, _FM, _P, _P, _CDF, _P]),
+    "tdvc_ar_decode_serial_batch": (_i, [_LOOP, _P, _P, _CDF, _P]),
     "tdvc_ar_lanes_batch_layout": (_i64, [_P, _i, _i, _P]),
     "tdvc_ar_lanes_init_batch": (_i, [_P, _i64, _P, _i, _i, _P, _P]),
-    "tdvc_ar_decode_lanes_step_batch": (_i, [_FM, _P, _i, _P, _i, _P, _i64, _P, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _FM, _P, _P, _i64, _P]),
-    "tdvc_ar_wavefront_lanes_batch": (_i, [_P, _P, _i, _P, _i64, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _FM, _FM, _FM, _FM, _P, _i, _FM, _P, _P, _i, _i, _i,
-                                           _P, _i, _P, _P, _P, _P]),
+    "tdvc_ar_decode_lanes_step_batch": (_i, [_FM, _P, _i, _P, _i, _P, _i64, _P, _i, _CDFD, _P, _FM, _P, _P, _i64, _P]),
+    "tdvc_ar_wavefront_lanes_batch": (_i, [_LOOP, _P, _P, _P, _i64, _P, _CDFD, C.POINTER(C.c_int32), _P]),
     "tdvc_ar_encode_lanes_scratch_words": (_i64, [_i64, _i, _i]),
     "tdvc_ar_encode_lanes_out_bytes": (_i64, [_i64, _i, _i]),
-    "tdvc_ar_encode_lanes_batch": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _i, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _i64, _i64, _P, _i64, _i64, _P, _P]),
-    "tdvc_rans_encode_lanes_dev_ref": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _i, _P, C.c_int32, _P, _P, C.c_int32, _P, _i64, _i64, _P, _i64, _i64, _P]),
+    "tdvc_ar_encode_lanes_batch": (_i, [_ENC, _CDFD, _P]),
+    "tdvc_rans_encode_lanes_dev_ref": (_i, [_ENC, _CDF]),
     "tdvc_ar_last_loop_launches": (_i64, []),
     "tdvc_ssim_level_work_floats": (_i64, [_i] * 5),
     "tdvc_ssim_level": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _f, _f, _P, _P, _P, _i64, _P]),

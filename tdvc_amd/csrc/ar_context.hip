@@ -411,79 +411,6 @@ extern "C" int tdvc_round_symbols(const tdvc_fmap* z, const float* median, int32
 // x1 / pc / gp is position k of image b, a step is a (1, B * n) map to the convs; y / y_hat / params are fmaps with N = B.
 namespace {
 bool ar_fmap_ok(const tdvc_fmap& f, bool f32) { return f32 ? (fmap_ok32(f) && (f.C % 4) == 0 && (f.sp % 4) == 0 && (f.sn % 4) == 0 && aligned16(f.p)) : fmap_ok16(f); }
-
-// what the three drivers check before anything touches a device -> the largest step
-int batch_loop_args(const char* who, int B, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_fmap* gp,
-                    int nconvs, int M, int W, const int32_t* step_sizes, int nsteps, int* nmax_out) {
-  TDVC_CHECK(B >= 1 && B <= 65535, "%s: 1 <= B <= 65535 images expected, got %d", who, B);
-  TDVC_CHECK(nconvs >= 1 && nconvs <= 8 && nsteps >= 1 && M >= 1 && M <= 4096 && W >= 1 && M == y_hat->C && W == y_hat->W, "%s: bad sizes", who);
-  TDVC_CHECK(y_hat->N == B && params->N == B && params->H == y_hat->H && params->W == y_hat->W && y_hat->H >= 1,
-             "%s: y_hat and params must be fmaps of B = %d images of one geometry", who, B);
-  long total = 0;
-  int nmax = 0;
-  for (int s = 0; s < nsteps; ++s) {
-    const long n = step_sizes ? step_sizes[s] : 1;             // no step list: one position per step (the raster-order decoder)
-    TDVC_CHECK(n >= 1 && n <= (1 << 20), "%s: step %d has %ld positions", who, s, n);
-    TDVC_CHECK(B * n <= x1->W && B * n <= pc->W && B * n <= gp->W, "%s: step %d: B * n = %ld rows exceed the staging buffers (x1 %d, pc %d, gp %d)", who, s, B * n,
-               x1->W, pc->W, gp->W);
-    total += n;
-    nmax = n > nmax ? (int)n : nmax;
-  }
-  TDVC_CHECK(total == (long)y_hat->H * y_hat->W, "%s: the steps must cover every position once (%ld of %ld)", who, total, (long)y_hat->H * y_hat->W);
-  *nmax_out = nmax;
-  return TDVC_OK;
-}
-
-// one step's gather -> convs over B * n rows
-int batch_step_front(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int n, int B, const tdvc_fmap* x1, const tdvc_fmap* pc,
-                     tdvc_conv_desc* d, int nconvs, void* stream) {
-  int rc = tdvc_ar_gather_batch(y_hat, params, pos, n, x1, pc, stream);
-  for (int c = 0; c < nconvs && rc == TDVC_OK; ++c) {
-    d[c].x.W = B * n;
-    d[c].y.W = B * n;
-    rc = tdvc_conv2d(&d[c], stream);
-  }
-  return rc;
-}
-
-struct HostDecoders {                                          // the B host range decoders of a call and their pinned staging buffer
-  void* dec[256] = {};
-  int B = 0;
-  int32_t* host = nullptr;
-  ~HostDecoders() {
-    for (int b = 0; b < B; ++b) if (dec[b]) tdvc_rans_decoder_destroy(dec[b]);
-    if (host) (void)hipHostFree(host);
-  }
-};
-int host_decoders(const char* who, HostDecoders& h, const uint8_t* const* data, const int64_t* nbytes, int B, size_t host_ints) {
-  TDVC_CHECK(B <= 256, "%s: the host range decoders take at most 256 images per call, got %d", who, B);
-  h.B = B;
-  for (int b = 0; b < B; ++b) {
-    h.dec[b] = tdvc_rans_decoder_create(data[b], nbytes[b]);
-    if (!h.dec[b]) return TDVC_EINVAL;
-  }
-  const hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&h.host), sizeof(int32_t) * host_ints, hipHostMallocDefault);
-  if (err != hipSuccess) { h.host = nullptr; tdvc_set_error("%s: hipHostMalloc failed: %s", who, hipGetErrorString(err)); return (int)err; }
-  return TDVC_OK;
-}
-
-// the step's indexes of all images to the host (one strided copy), the B decoders in turn, the symbols back (one strided copy):
-// image b's `cnt` values start `img_stride` ints after image b - 1's in the device arrays and are dense in `host`.  One image is
-// one row, copied plainly: a hipMemcpy2DAsync costs ~8 us more than a hipMemcpyAsync, twice per step of a loop whose step is 50-100 us
-int host_decode_step(const char* who, HostDecoders& h, int32_t* idx_at, int32_t* sym_at, long img_stride, long cnt, long half, const int32_t* cdfs, int32_t cdf_stride,
-                     const int32_t* cdf_sizes, const int32_t* offsets, hipStream_t st) {
-  const size_t wb = sizeof(int32_t) * (size_t)cnt, pb = sizeof(int32_t) * (size_t)img_stride;
-  hipError_t err = h.B == 1 ? hipMemcpyAsync(h.host, idx_at, wb, hipMemcpyDeviceToHost, st)
-                           : hipMemcpy2DAsync(h.host, wb, idx_at, pb, wb, (size_t)h.B, hipMemcpyDeviceToHost, st);
-  if (err == hipSuccess) err = hipStreamSynchronize(st);       // also: the previous step's upload has left `host`
-  if (err != hipSuccess) { tdvc_set_error("%s: copy / sync failed: %s", who, hipGetErrorString(err)); return (int)err; }
-  for (int b = 0; b < h.B; ++b)
-    if (const int rc = tdvc_rans_decoder_decode(h.dec[b], h.host + b * cnt, cnt, cdfs, cdf_stride, cdf_sizes, offsets, h.host + half + b * cnt)) return rc;
-  err = h.B == 1 ? hipMemcpyAsync(sym_at, h.host + half, wb, hipMemcpyHostToDevice, st)
-                 : hipMemcpy2DAsync(sym_at, pb, h.host + half, wb, wb, (size_t)h.B, hipMemcpyHostToDevice, st);
-  if (err != hipSuccess) { tdvc_set_error("%s: upload failed: %s", who, hipGetErrorString(err)); return (int)err; }
-  return TDVC_OK;
-}
 }  // namespace
 
 extern "C" int tdvc_ar_gather_batch(const tdvc_fmap* y_hat, const tdvc_fmap* params, const int32_t* pos, int npos,
@@ -525,85 +452,6 @@ extern "C" int tdvc_ar_indexes_batch(const tdvc_fmap* gp, const int32_t* pos, in
   return tdvc_launch_status("tdvc_ar_indexes_batch");
 }
 
-// The context loop over anti-diagonals, either direction.  Encoder: ~7 enqueues per step and no synchronisation (Python drove a
-// step at ~0.5 ms: 0.33 s per 1080p frame for the two coders).  Decoder of a wavefront-ordered stream: per step the step's indexes
-// to the host, its symbols out of the B range decoders, and back.
-extern "C" int tdvc_ar_wavefront_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes,
-                                       const int32_t* offsets, const tdvc_fmap* y, const tdvc_fmap* y_hat, const tdvc_fmap* params, const tdvc_fmap* x1,
-                                       const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp, const int32_t* pos_dev,
-                                       const int32_t* step_sizes, int nsteps, int M, int W, const float* scale_table, int ntable, int32_t* idx_dev,
-                                       int32_t* sym_dev, void* stream) {
-  TdvcLoopLaunches count;
-  TDVC_CHECK(y_hat && params && x1 && pc && convs && gp && pos_dev && step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront_batch: null argument");
-  TDVC_CHECK((data != nullptr) != (y != nullptr), "tdvc_ar_wavefront_batch: give y (encoder) or data (decoder), not both");
-  TDVC_CHECK(!data || (nbytes && cdfs && cdf_sizes && offsets), "tdvc_ar_wavefront_batch: the decoder needs the strings' sizes and the CDF tables");
-  int nmax = 0;
-  if (const int rc = batch_loop_args("tdvc_ar_wavefront_batch", B, y_hat, params, x1, pc, gp, nconvs, M, W, step_sizes, nsteps, &nmax)) return rc;
-  if (data)
-    for (int b = 0; b < B; ++b) TDVC_CHECK(data[b] && nbytes[b] >= 4, "tdvc_ar_wavefront_batch: image %d: null / empty string", b);
-  hipStream_t st = ST(stream);
-  tdvc_conv_desc d[8];
-  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
-  const long HW = (long)y_hat->H * y_hat->W, half = (long)B * nmax * M;
-  HostDecoders h;                                            // [2][B * nmax * M] indexes | symbols, pinned
-  if (data)
-    if (const int rc = host_decoders("tdvc_ar_wavefront_batch", h, data, nbytes, B, 2 * (size_t)half)) return rc;
-  int rc = TDVC_OK;
-  long o = 0;
-  for (int s = 0; s < nsteps && rc == TDVC_OK; ++s) {
-    const int n = step_sizes[s];
-    const int32_t* pos = pos_dev + 2 * o;
-    rc = batch_step_front(y_hat, params, pos, n, B, x1, pc, d, nconvs, stream);
-    if (rc != TDVC_OK) break;
-    if (!data) {
-      rc = tdvc_ar_quantize_batch(y, gp, pos, n, scale_table, ntable, nullptr, y_hat, sym_dev, idx_dev, -1, stream);
-    } else {
-      rc = tdvc_ar_indexes_batch(gp, pos, n, B, scale_table, ntable, M, y_hat->H, W, idx_dev, o, stream);
-      if (rc == TDVC_OK)
-        rc = host_decode_step("tdvc_ar_wavefront_batch", h, idx_dev + o * M, sym_dev + o * M, HW * M, (long)n * M, half, cdfs, cdf_stride, cdf_sizes, offsets, st);
-      if (rc == TDVC_OK) rc = tdvc_ar_quantize_batch(nullptr, gp, pos, n, scale_table, ntable, sym_dev, y_hat, sym_dev, idx_dev, o, stream);
-    }
-    o += n;
-  }
-  if (data) (void)hipStreamSynchronize(st);                   // before `h` frees the pinned buffer
-  return rc;
-}
-
-// The decoder's loop for y streams in raster order (compressai's bitstream): position (h, w) needs y_hat(h, w - 1), 8160 strictly
-// serial steps per coder at 1080p.  Per step: gather -> context conv -> entropy_parameters (the caller's conv descriptors, fixed
-// buffers) -> CDF indexes -> host range decoders -> quantise.  Driving this from Python cost ~230 us per position (3.7 s per 1080p
-// frame); here a step is seven enqueues, one device->host copy of B * M indexes + stream wait, the host decoders and one
-// host->device copy.
-extern "C" int tdvc_ar_decode_serial_batch(const uint8_t* const* data, const int64_t* nbytes, int B, const int32_t* cdfs, int32_t cdf_stride,
-                                           const int32_t* cdf_sizes, const int32_t* offsets, const tdvc_fmap* y_hat, const tdvc_fmap* params,
-                                           const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs, const tdvc_fmap* gp,
-                                           const int32_t* pos_table, int npos_total, int M, int W, const float* scale_table, int ntable,
-                                           int32_t* idx_dev, int32_t* sym_dev, void* stream) {
-  TdvcLoopLaunches count;
-  TDVC_CHECK(data && nbytes && cdfs && cdf_sizes && offsets && y_hat && params && x1 && pc && convs && gp && pos_table && scale_table && idx_dev && sym_dev,
-             "tdvc_ar_decode_serial_batch: null argument");
-  int nmax = 0;
-  if (const int rc = batch_loop_args("tdvc_ar_decode_serial_batch", B, y_hat, params, x1, pc, gp, nconvs, M, W, nullptr, npos_total > 0 ? npos_total : 1, &nmax)) return rc;
-  for (int b = 0; b < B; ++b) TDVC_CHECK(data[b] && nbytes[b] >= 4, "tdvc_ar_decode_serial_batch: image %d: null / empty string", b);
-  hipStream_t st = ST(stream);
-  tdvc_conv_desc d[8];
-  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
-  const long HW = (long)y_hat->H * y_hat->W, half = (long)B * M;
-  HostDecoders h;                                            // [2][B * M] indexes | symbols, pinned
-  if (const int rc = host_decoders("tdvc_ar_decode_serial_batch", h, data, nbytes, B, 2 * (size_t)half)) return rc;
-  int rc = TDVC_OK;
-  for (long k = 0; k < npos_total && rc == TDVC_OK; ++k) {    // raster order: position k = h * W + w owns row k of every image's block
-    const int32_t* pos = pos_table + 2 * k;
-    rc = batch_step_front(y_hat, params, pos, 1, B, x1, pc, d, nconvs, stream);
-    if (rc == TDVC_OK) rc = tdvc_ar_indexes_batch(gp, pos, 1, B, scale_table, ntable, M, y_hat->H, W, idx_dev, -1, stream);
-    if (rc == TDVC_OK)
-      rc = host_decode_step("tdvc_ar_decode_serial_batch", h, idx_dev + k * M, sym_dev + k * M, HW * M, M, half, cdfs, cdf_stride, cdf_sizes, offsets, st);
-    if (rc == TDVC_OK) rc = tdvc_ar_quantize_batch(nullptr, gp, pos, 1, scale_table, ntable, sym_dev, y_hat, sym_dev, idx_dev, -1, stream);
-  }
-  (void)hipStreamSynchronize(st);
-  return rc;
-}
-
 // ---- lane-split y streams: the decoder's loop with the range decoder on the device.  Device buffer layout
 // (tdvc_ar_lanes_batch_layout): the table uint32 [B][2] = {byte offset of container b, words of its payload}, padded to 16 bytes,
 // then the containers, each at a 16-byte aligned offset.
@@ -642,14 +490,14 @@ extern "C" int tdvc_ar_lanes_init_batch(const uint8_t* streams_dev, int64_t stre
 
 extern "C" int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_t* pos, int npos, const float* scale_table, int ntable,
                                                const uint8_t* streams_dev, int64_t stream_bytes, const uint32_t* table_dev, int L,
-                                               const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
-                                               const int32_t* offsets_dev, int32_t ncdfs, uint32_t* state_dev, const tdvc_fmap* y_hat,
+                                               const tdvc_cdf_tables_dev* tables, uint32_t* state_dev, const tdvc_fmap* y_hat,
                                                int32_t* symbols, int32_t* indexes, int64_t cbase, void* stream) {
-  TDVC_CHECK(gp && pos && scale_table && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && symbols && indexes && npos >= 1 && cbase >= 0,
-             "tdvc_ar_decode_lanes_step_batch: null / empty");
-  TDVC_CHECK(ntable >= 2 && ntable <= 64 && ncdfs >= ntable, "tdvc_ar_decode_lanes_step_batch: 2..64 scale-table entries, one CDF per entry expected");
-  TDVC_CHECK(n16 >= 8 && n16 % 8 == 0 && aligned16(cdf16_dev), "tdvc_ar_decode_lanes_step_batch: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
-  TDVC_CHECK(n16 <= kLdsCdf, "tdvc_ar_decode_lanes_step_batch: %d packed CDF entries, the kernel's LDS holds %d", n16, kLdsCdf);
+  TDVC_CHECK(gp && pos && scale_table && tables && tables->cdf16 && tables->starts && tables->sizes && tables->offsets && y_hat && symbols && indexes && npos >= 1 &&
+             cbase >= 0, "tdvc_ar_decode_lanes_step_batch: null / empty");
+  const tdvc_cdf_tables_dev& t = *tables;
+  TDVC_CHECK(ntable >= 2 && ntable <= 64 && t.ncdfs >= ntable, "tdvc_ar_decode_lanes_step_batch: 2..64 scale-table entries, one CDF per entry expected");
+  TDVC_CHECK(t.n16 >= 8 && t.n16 % 8 == 0 && aligned16(t.cdf16), "tdvc_ar_decode_lanes_step_batch: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
+  TDVC_CHECK(t.n16 <= kLdsCdf, "tdvc_ar_decode_lanes_step_batch: %d packed CDF entries, the kernel's LDS holds %d", t.n16, kLdsCdf);
   const int B = y_hat->N;
   TDVC_CHECK(fmap_ok32(*gp) && (y_hat->dtype == TDVC_F32 ? fmap_ok32(*y_hat) : fmap_ok16(*y_hat)) && gp->C >= 2 * y_hat->C && gp->W >= (long)B * npos &&
              cbase + npos <= (int64_t)y_hat->H * y_hat->W, "tdvc_ar_decode_lanes_step_batch: bad gp / y_hat / rows");
@@ -665,104 +513,235 @@ extern "C" int tdvc_ar_decode_lanes_step_batch(const tdvc_fmap* gp, const int32_
   }
   if (y_hat->dtype == TDVC_F32)
     hipLaunchKernelGGL(ar_decode_lanes_batch_kernel<float>, dim3(B), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, streams_dev,
-                       (long)stream_bytes, table_dev, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
+                       (long)stream_bytes, table_dev, t.cdf16, t.n16, t.starts, t.sizes, t.offsets, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
   else
     hipLaunchKernelGGL(ar_decode_lanes_batch_kernel<half_t>, dim3(B), dim3(L), kLanesLds, ST(stream), to_dev(*gp), pos, npos, scale_table, ntable, streams_dev,
-                       (long)stream_bytes, table_dev, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
+                       (long)stream_bytes, table_dev, t.cdf16, t.n16, t.starts, t.sizes, t.offsets, state_dev, to_dev(*y_hat), symbols, indexes, (long)cbase);
   return tdvc_launch_status("tdvc_ar_decode_lanes_step_batch");
 }
 
 // what the device encoder and its host twin (rans.cpp) check before anything is touched; `who` names the entry point
-int tdvc_encode_lanes_args(const char* who, const void* symbols, const void* indexes, int B, int H, int W, int M, const void* pos, int npos, int L, int32_t ncdfs,
-                           const void* scratch, int64_t lane_words, int64_t scratch_cap_words, const void* out, int64_t out_stride, int64_t out_cap, const void* info);
+int tdvc_encode_lanes_args(const char* who, const tdvc_lanes_enc* enc, int32_t ncdfs);
 
-extern "C" int tdvc_ar_encode_lanes_batch(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos_dev, int npos, int L,
-                                          const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev, const int32_t* cdf_sizes_dev,
-                                          const int32_t* offsets_dev, int32_t ncdfs, uint32_t* scratch_dev, int64_t lane_words, int64_t scratch_cap_words,
-                                          uint8_t* out_dev, int64_t out_stride, int64_t out_cap, uint32_t* info_dev, void* stream) {
-  TDVC_CHECK(cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev, "tdvc_ar_encode_lanes_batch: null table pointer");
-  if (const int rc = tdvc_encode_lanes_args("tdvc_ar_encode_lanes_batch", symbols, indexes, B, H, W, M, pos_dev, npos, L, ncdfs, scratch_dev, lane_words,
-                                            scratch_cap_words, out_dev, out_stride, out_cap, info_dev)) return rc;
-  TDVC_CHECK(n16 >= 8 && n16 % 8 == 0 && aligned16(cdf16_dev), "tdvc_ar_encode_lanes_batch: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
-  TDVC_CHECK(n16 <= kLdsCdf, "tdvc_ar_encode_lanes_batch: %d packed CDF entries, the kernel's LDS holds %d", n16, kLdsCdf);
-  TDVC_CHECK(M <= kChunkSyms, "tdvc_ar_encode_lanes_batch: more than %d channels", kChunkSyms);
+extern "C" int tdvc_ar_encode_lanes_batch(const tdvc_lanes_enc* enc, const tdvc_cdf_tables_dev* tables, void* stream) {
+  TDVC_CHECK(tables && tables->cdf16 && tables->starts && tables->sizes && tables->offsets, "tdvc_ar_encode_lanes_batch: null table pointer");
+  const tdvc_cdf_tables_dev& t = *tables;
+  if (const int rc = tdvc_encode_lanes_args("tdvc_ar_encode_lanes_batch", enc, t.ncdfs)) return rc;
+  const tdvc_lanes_enc& e = *enc;
+  TDVC_CHECK(t.n16 >= 8 && t.n16 % 8 == 0 && aligned16(t.cdf16), "tdvc_ar_encode_lanes_batch: the packed CDFs must be 16-byte aligned, a multiple of 8 entries long");
+  TDVC_CHECK(t.n16 <= kLdsCdf, "tdvc_ar_encode_lanes_batch: %d packed CDF entries, the kernel's LDS holds %d", t.n16, kLdsCdf);
+  TDVC_CHECK(e.M <= kChunkSyms, "tdvc_ar_encode_lanes_batch: more than %d channels", kChunkSyms);
   static TdvcPerDeviceFlag attr;
   if (!attr.flag()) {
     const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&ar_encode_lanes_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kEncLds);
     if (err != hipSuccess) { tdvc_set_error("tdvc_ar_encode_lanes_batch: cannot reserve %d bytes of LDS: %s", kEncLds, hipGetErrorString(err)); return (int)err; }
     attr.flag() = true;
   }
-  hipLaunchKernelGGL(ar_encode_lanes_batch_kernel, dim3(B), dim3(L), kEncLds, ST(stream), symbols, indexes, H, W, M, pos_dev, npos, cdf16_dev, n16, cdf_starts_dev,
-                     cdf_sizes_dev, offsets_dev, ncdfs, scratch_dev, (uint32_t)lane_words, out_dev, (long)out_stride, info_dev);
+  hipLaunchKernelGGL(ar_encode_lanes_batch_kernel, dim3(e.B), dim3(e.L), kEncLds, ST(stream), e.symbols, e.indexes, e.H, e.W, e.M, e.pos, e.npos, t.cdf16, t.n16, t.starts,
+                     t.sizes, t.offsets, t.ncdfs, e.scratch, (uint32_t)e.lane_words, e.out, (long)e.out_stride, e.info);
   return tdvc_launch_status("tdvc_ar_encode_lanes_batch");
 }
 
-// The decoder's loop over anti-diagonals for lane-split streams: the B strings are validated and uploaded behind their table, B + 1
-// copies from the caller's memory, then per step gather -> convs -> ar_decode_lanes_batch_kernel (B workgroups), the encoder's
-// enqueue count and like it no synchronisation until the images are done; then the B sticky `bad` words come back with the one
-// stream wait of the call.  Nothing is allocated here (a pinned staging buffer per call cost 0.3-0.5 ms, a fifth of a 448 x 256 loop).
-extern "C" int tdvc_ar_wavefront_lanes_batch(const uint8_t* const* data, const int64_t* nbytes, int B, uint8_t* stream_dev, int64_t stream_cap,
-                                             uint32_t* state_dev, const uint16_t* cdf16_dev, int32_t n16, const int32_t* cdf_starts_dev,
-                                             const int32_t* cdf_sizes_dev, const int32_t* offsets_dev, int32_t ncdfs, const tdvc_fmap* y_hat,
-                                             const tdvc_fmap* params, const tdvc_fmap* x1, const tdvc_fmap* pc, const tdvc_conv_desc* convs, int nconvs,
-                                             const tdvc_fmap* gp, const int32_t* pos_dev, const int32_t* step_sizes, int nsteps, int M, int W,
-                                             const float* scale_table, int ntable, int32_t* idx_dev, int32_t* sym_dev, int32_t* bad_image, void* stream) {
-  TdvcLoopLaunches count;
-  if (bad_image) *bad_image = -1;
-  TDVC_CHECK(data && nbytes && stream_dev && state_dev && cdf16_dev && cdf_starts_dev && cdf_sizes_dev && offsets_dev && y_hat && params && x1 && pc && convs && gp &&
-             pos_dev && step_sizes && scale_table && idx_dev && sym_dev, "tdvc_ar_wavefront_lanes_batch: null argument");
+// ---- the loop's one driver.  A call is: validate the tdvc_ar_loop and the back end's own arguments (all of it before anything
+// touches a device), copy the conv descriptors, then per step gather -> convs over B * n rows -> the back end's step.  The back ends
+// are what the three entry points differ in: what follows a step's convs and what brackets the loop.
+namespace {
+struct LoopCall { const char* who; const tdvc_ar_loop* l; void* stream; };      // the entry point's name (for the messages), its loop, its stream
+struct LoopBackend {                                           // a back end adds step(call, pos, n, o): a step's n positions, `o` positions into the list, after its convs
+  int check(const LoopCall&) { return TDVC_OK; }               // host only; the loop's own arguments are valid here
+  int begin(const LoopCall&, int /* positions of the largest step */) { return TDVC_OK; }
+  int end(const LoopCall&, int rc) { return rc; }              // rc: the loop's status so far -> the call's
+};
+
+// -> the largest step
+int loop_args(const char* who, const tdvc_ar_loop* l, int* nmax_out) {
+  TDVC_CHECK(l && l->y_hat.p && l->params.p && l->x1.p && l->pc.p && l->gp.p && l->convs && l->pos_dev && l->scale_table && l->idx_dev && l->sym_dev, "%s: null argument", who);
+  const tdvc_fmap &yh = l->y_hat, &pr = l->params;
+  TDVC_CHECK(pr.N == yh.N && pr.H == yh.H && pr.W == yh.W, "%s: y_hat and params must be fmaps of B images of one geometry (y_hat %d x %d x %d, params %d x %d x %d)", who,
+             yh.N, yh.H, yh.W, pr.N, pr.H, pr.W);
+  const long B = yh.N;
+  TDVC_CHECK(B >= 1 && B <= 65535, "%s: 1 <= B <= 65535 images expected, got %ld", who, B);
+  TDVC_CHECK(l->nconvs >= 1 && l->nconvs <= 8 && l->nsteps >= 1 && yh.C >= 1 && yh.C <= 4096 && yh.W >= 1 && yh.H >= 1, "%s: bad sizes", who);
+  long total = 0;
   int nmax = 0;
-  if (const int rc = batch_loop_args("tdvc_ar_wavefront_lanes_batch", B, y_hat, params, x1, pc, gp, nconvs, M, W, step_sizes, nsteps, &nmax)) return rc;
-  TDVC_CHECK(B <= 4096, "tdvc_ar_wavefront_lanes_batch: at most 4096 images per call, got %d", B);
-  int L = 0;
-  for (int b = 0; b < B; ++b) {
-    int Lb = 0;
-    if (const char* why = tdvc_lanes_check(data[b], nbytes[b], M, &Lb)) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: image %d: %s", b, why); return TDVC_EINVAL; }
-    TDVC_CHECK(b == 0 || Lb == L, "tdvc_ar_wavefront_lanes_batch: image %d declares %d lanes, image 0 %d: all images of a call must have the same lane count", b, Lb, L);
-    L = Lb;
+  for (int s = 0; s < l->nsteps; ++s) {
+    const long n = l->step_sizes ? l->step_sizes[s] : 1;       // no step list: one position per step (the raster order)
+    TDVC_CHECK(n >= 1 && n <= (1 << 20), "%s: step %d has %ld positions", who, s, n);
+    TDVC_CHECK(B * n <= l->x1.W && B * n <= l->pc.W && B * n <= l->gp.W, "%s: step %d: B * n = %ld rows exceed the staging buffers (x1 %d, pc %d, gp %d)", who, s, B * n,
+               l->x1.W, l->pc.W, l->gp.W);
+    total += n;
+    nmax = n > nmax ? (int)n : nmax;
   }
-  TDVC_CHECK(L == 64 || L == 128, "tdvc_ar_wavefront_lanes_batch: the device decoder takes 64 or 128 lanes (L = %d)", L);
-  uint32_t table[2 * 4096];
-  const int64_t total = tdvc_ar_lanes_batch_layout(nbytes, B, L, table);
-  if (total < 0) return (int)total;
-  TDVC_CHECK(total <= stream_cap, "tdvc_ar_wavefront_lanes_batch: the device stream buffer holds %lld bytes, the strings and their table need %lld", (long long)stream_cap,
-             (long long)total);
-  hipStream_t st = ST(stream);
+  TDVC_CHECK(total == (long)yh.H * yh.W, "%s: the steps must cover every position once (%ld of %ld)", who, total, (long)yh.H * yh.W);
+  *nmax_out = nmax;
+  return TDVC_OK;
+}
+
+template <class Backend>
+int run_loop(const LoopCall& c, Backend&& be) {
+  const tdvc_ar_loop* l = c.l;
+  int nmax = 0;
+  if (const int rc = loop_args(c.who, l, &nmax)) return rc;
+  if (const int rc = be.check(c)) return rc;
   tdvc_conv_desc d[8];
-  for (int c = 0; c < nconvs; ++c) d[c] = convs[c];
-  const uint32_t* table_dev = reinterpret_cast<const uint32_t*>(stream_dev);
-  const long sw = (long)L * kLaneStateWords + 1;               // state words per image
-  int rc = TDVC_OK;
-  // table | containers; the padding between them stays as it is: the kernels read a container's length table and payload only
-  hipError_t err = hipMemcpyAsync(stream_dev, table, sizeof(uint32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, st);
-  for (int b = 0; b < B && err == hipSuccess; ++b) err = hipMemcpyAsync(stream_dev + table[2 * b], data[b], (size_t)nbytes[b], hipMemcpyHostToDevice, st);
-  if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: upload failed: %s", hipGetErrorString(err)); rc = (int)err; }
-  if (rc == TDVC_OK) rc = tdvc_ar_lanes_init_batch(stream_dev, total, table_dev, B, L, state_dev, stream);
+  for (int k = 0; k < l->nconvs; ++k) d[k] = l->convs[k];
+  const int B = l->y_hat.N;
+  int rc = be.begin(c, nmax);
   long o = 0;
-  for (int s = 0; s < nsteps && rc == TDVC_OK; ++s) {
-    const int n = step_sizes[s];
-    const int32_t* pos = pos_dev + 2 * o;
-    rc = batch_step_front(y_hat, params, pos, n, B, x1, pc, d, nconvs, stream);
-    if (rc == TDVC_OK)
-      rc = tdvc_ar_decode_lanes_step_batch(gp, pos, n, scale_table, ntable, stream_dev, total, table_dev, L, cdf16_dev, n16, cdf_starts_dev, cdf_sizes_dev, offsets_dev,
-                                           ncdfs, state_dev, y_hat, sym_dev, idx_dev, o, stream);
+  for (int s = 0; s < l->nsteps && rc == TDVC_OK; ++s) {
+    const int n = l->step_sizes ? l->step_sizes[s] : 1;
+    const int32_t* pos = l->pos_dev + 2 * o;
+    rc = tdvc_ar_gather_batch(&l->y_hat, &l->params, pos, n, &l->x1, &l->pc, c.stream);
+    for (int k = 0; k < l->nconvs && rc == TDVC_OK; ++k) {
+      d[k].x.W = d[k].y.W = B * n;
+      rc = tdvc_conv2d(&d[k], c.stream);
+    }
+    if (rc == TDVC_OK) rc = be.step(c, pos, n, o);
     o += n;
   }
-  uint32_t* bad = table;                                       // the table's place, once its upload is done (stream order): B words
-  if (rc == TDVC_OK) {
-    err = hipMemcpy2DAsync(bad, sizeof(uint32_t), state_dev + (long)L * kLaneStateWords, sizeof(uint32_t) * (size_t)sw, sizeof(uint32_t), (size_t)B,
-                           hipMemcpyDeviceToHost, st);
-    if (err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: reading the error words failed: %s", hipGetErrorString(err)); rc = (int)err; }
+  return be.end(c, rc);
+}
+
+// Encoder: quantise.  ~7 enqueues per step and no synchronisation (Python drove a step at ~0.5 ms: 0.33 s per 1080p frame for the
+// two coders).  idx / sym are raster arrays.
+struct EncoderSteps : LoopBackend {
+  const tdvc_fmap* y;
+  int step(const LoopCall& c, const int32_t* pos, int n, long) {
+    return tdvc_ar_quantize_batch(y, &c.l->gp, pos, n, c.l->scale_table, c.l->ntable, nullptr, &c.l->y_hat, c.l->sym_dev, c.l->idx_dev, -1, c.stream);
   }
-  err = hipStreamSynchronize(st);
-  if (rc == TDVC_OK && err != hipSuccess) { tdvc_set_error("tdvc_ar_wavefront_lanes_batch: stream wait failed: %s", hipGetErrorString(err)); rc = (int)err; }
-  if (rc == TDVC_OK)
+};
+
+// Decoder on the B host range decoders of a call and their pinned staging buffer [2][B * nmax * M] indexes | symbols.  Per step:
+// CDF indexes -> the step's indexes of all images to the host (one strided copy) and a stream wait, the B decoders in turn, the
+// symbols back (one strided copy) -> quantise.  idx / sym are compact arrays in step order: image b's values of a step start H * W * M
+// ints after image b - 1's on the device and are dense in `host`.  In raster order -- a step per position, 8160 strictly serial
+// steps per coder at 1080p, compressai's bitstream -- compact row k is raster row h * W + w.  Driving that from Python cost ~230 us
+// per position (3.7 s per 1080p frame); here a step is seven enqueues.  One image is one row, copied plainly: a hipMemcpy2DAsync
+// costs ~8 us more than a hipMemcpyAsync, twice per step of a loop whose step is 50-100 us
+struct HostDecoderSteps : LoopBackend {
+  const uint8_t* const* data; const int64_t* nbytes; const tdvc_cdf_tables* t;
+  void* dec[256] = {};
+  int B = 0;
+  long half = 0;
+  int32_t* host = nullptr;
+  ~HostDecoderSteps() {
+    for (int b = 0; b < B; ++b) if (dec[b]) tdvc_rans_decoder_destroy(dec[b]);
+    if (host) (void)hipHostFree(host);
+  }
+  int check(const LoopCall& c) {
+    TDVC_CHECK(data && nbytes && t && t->cdfs && t->sizes && t->offsets, "%s: null argument: the decoder needs the strings, their sizes and the CDF tables", c.who);
+    for (int b = 0; b < c.l->y_hat.N; ++b) TDVC_CHECK(data[b] && nbytes[b] >= 4, "%s: image %d: null / empty string", c.who, b);
+    TDVC_CHECK(c.l->y_hat.N <= 256, "%s: the host range decoders take at most 256 images per call, got %d", c.who, c.l->y_hat.N);
+    return TDVC_OK;
+  }
+  int begin(const LoopCall& c, int nmax) {
+    B = c.l->y_hat.N;
+    half = (long)B * nmax * c.l->y_hat.C;
     for (int b = 0; b < B; ++b)
+      if (!(dec[b] = tdvc_rans_decoder_create(data[b], nbytes[b]))) return TDVC_EINVAL;
+    const hipError_t err = hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(int32_t) * 2 * (size_t)half, hipHostMallocDefault);
+    if (err != hipSuccess) { host = nullptr; tdvc_set_error("%s: hipHostMalloc failed: %s", c.who, hipGetErrorString(err)); return (int)err; }
+    return TDVC_OK;
+  }
+  int step(const LoopCall& c, const int32_t* pos, int n, long o) {
+    const tdvc_ar_loop* l = c.l;
+    const tdvc_fmap& yh = l->y_hat;
+    const int M = yh.C;
+    hipStream_t st = ST(c.stream);
+    int rc = tdvc_ar_indexes_batch(&l->gp, pos, n, B, l->scale_table, l->ntable, M, yh.H, yh.W, l->idx_dev, o, c.stream);
+    if (rc != TDVC_OK) return rc;
+    int32_t *idx_at = l->idx_dev + o * M, *sym_at = l->sym_dev + o * M;
+    const long cnt = (long)n * M;
+    const size_t wb = sizeof(int32_t) * (size_t)cnt, pb = sizeof(int32_t) * (size_t)yh.H * yh.W * M;
+    hipError_t err = B == 1 ? hipMemcpyAsync(host, idx_at, wb, hipMemcpyDeviceToHost, st) : hipMemcpy2DAsync(host, wb, idx_at, pb, wb, (size_t)B, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);     // also: the previous step's upload has left `host`
+    if (err != hipSuccess) { tdvc_set_error("%s: copy / sync failed: %s", c.who, hipGetErrorString(err)); return (int)err; }
+    for (int b = 0; b < B; ++b)
+      if ((rc = tdvc_rans_decoder_decode(dec[b], host + b * cnt, cnt, t->cdfs, t->stride, t->sizes, t->offsets, host + half + b * cnt))) return rc;
+    err = B == 1 ? hipMemcpyAsync(sym_at, host + half, wb, hipMemcpyHostToDevice, st) : hipMemcpy2DAsync(sym_at, pb, host + half, wb, wb, (size_t)B, hipMemcpyHostToDevice, st);
+    if (err != hipSuccess) { tdvc_set_error("%s: upload failed: %s", c.who, hipGetErrorString(err)); return (int)err; }
+    return tdvc_ar_quantize_batch(nullptr, &l->gp, pos, n, l->scale_table, l->ntable, l->sym_dev, &yh, l->sym_dev, l->idx_dev, o, c.stream);
+  }
+  int end(const LoopCall& c, int rc) {
+    (void)hipStreamSynchronize(ST(c.stream));                  // before the pinned buffer is freed
+    return rc;
+  }
+};
+
+// Decoder of lane-split streams with the range decoder on the device.  The B strings are validated and uploaded behind their table,
+// B + 1 copies from the caller's memory, then per step ar_decode_lanes_batch_kernel (B workgroups): the encoder's enqueue count and
+// like it no synchronisation until the images are done; then the B sticky `bad` words come back with the one stream wait of the
+// call.  Nothing is allocated here (a pinned staging buffer per call cost 0.3-0.5 ms, a fifth of a 448 x 256 loop).
+struct LaneDecoderSteps : LoopBackend {
+  const uint8_t* const* data; const int64_t* nbytes; uint8_t* stream_dev; int64_t stream_cap; uint32_t* state_dev; const tdvc_cdf_tables_dev* t; int32_t* bad_image;
+  int B = 0, L = 0;
+  int64_t total = 0;
+  uint32_t table[2 * 4096];
+  int check(const LoopCall& c) {
+    TDVC_CHECK(data && nbytes && stream_dev && state_dev && t && t->cdf16 && t->starts && t->sizes && t->offsets, "%s: null argument", c.who);
+    B = c.l->y_hat.N;
+    TDVC_CHECK(B <= 4096, "%s: at most 4096 images per call, got %d", c.who, B);
+    for (int b = 0; b < B; ++b) {
+      int Lb = 0;
+      if (const char* why = tdvc_lanes_check(data[b], nbytes[b], c.l->y_hat.C, &Lb)) { tdvc_set_error("%s: image %d: %s", c.who, b, why); return TDVC_EINVAL; }
+      TDVC_CHECK(b == 0 || Lb == L, "%s: image %d declares %d lanes, image 0 %d: all images of a call must have the same lane count", c.who, b, Lb, L);
+      L = Lb;
+    }
+    TDVC_CHECK(L == 64 || L == 128, "%s: the device decoder takes 64 or 128 lanes (L = %d)", c.who, L);
+    total = tdvc_ar_lanes_batch_layout(nbytes, B, L, table);
+    if (total < 0) return (int)total;
+    TDVC_CHECK(total <= stream_cap, "%s: the device stream buffer holds %lld bytes, the strings and their table need %lld", c.who, (long long)stream_cap, (long long)total);
+    return TDVC_OK;
+  }
+  int begin(const LoopCall& c, int) {
+    // table | containers; the padding between them stays as it is: the kernels read a container's length table and payload only
+    hipError_t err = hipMemcpyAsync(stream_dev, table, sizeof(uint32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, ST(c.stream));
+    for (int b = 0; b < B && err == hipSuccess; ++b) err = hipMemcpyAsync(stream_dev + table[2 * b], data[b], (size_t)nbytes[b], hipMemcpyHostToDevice, ST(c.stream));
+    if (err != hipSuccess) { tdvc_set_error("%s: upload failed: %s", c.who, hipGetErrorString(err)); return (int)err; }
+    return tdvc_ar_lanes_init_batch(stream_dev, total, reinterpret_cast<const uint32_t*>(stream_dev), B, L, state_dev, c.stream);
+  }
+  int step(const LoopCall& c, const int32_t* pos, int n, long o) {
+    return tdvc_ar_decode_lanes_step_batch(&c.l->gp, pos, n, c.l->scale_table, c.l->ntable, stream_dev, total, reinterpret_cast<const uint32_t*>(stream_dev), L, t, state_dev,
+                                           &c.l->y_hat, c.l->sym_dev, c.l->idx_dev, o, c.stream);
+  }
+  int end(const LoopCall& c, int rc) {
+    hipStream_t st = ST(c.stream);
+    const long sw = (long)L * kLaneStateWords + 1;             // state words per image
+    uint32_t* bad = table;                                     // the table's place, once its upload is done (stream order): B words
+    hipError_t err;
+    if (rc == TDVC_OK) {
+      err = hipMemcpy2DAsync(bad, sizeof(uint32_t), state_dev + (long)L * kLaneStateWords, sizeof(uint32_t) * (size_t)sw, sizeof(uint32_t), (size_t)B, hipMemcpyDeviceToHost, st);
+      if (err != hipSuccess) { tdvc_set_error("%s: reading the error words failed: %s", c.who, hipGetErrorString(err)); rc = (int)err; }
+    }
+    err = hipStreamSynchronize(st);
+    if (rc == TDVC_OK && err != hipSuccess) { tdvc_set_error("%s: stream wait failed: %s", c.who, hipGetErrorString(err)); rc = (int)err; }
+    for (int b = 0; b < B && rc == TDVC_OK; ++b)
       if (bad[b]) {
         if (bad_image) *bad_image = b;
-        tdvc_set_error("tdvc_ar_wavefront_lanes_batch: image %d: corrupt or exhausted lane-split stream (a lane ran out of words or met an impossible code)", b);
+        tdvc_set_error("%s: image %d: corrupt or exhausted lane-split stream (a lane ran out of words or met an impossible code)", c.who, b);
         rc = TDVC_EINVAL;
-        break;
       }
-  return rc;
+    return rc;
+  }
+};
+}  // namespace
+
+extern "C" int tdvc_ar_wavefront_batch(const tdvc_ar_loop* loop, const tdvc_fmap* y, const uint8_t* const* data, const int64_t* nbytes, const tdvc_cdf_tables* tables,
+                                       void* stream) {
+  TdvcLoopLaunches count;
+  TDVC_CHECK((data != nullptr) != (y != nullptr), "tdvc_ar_wavefront_batch: give y (encoder) or data (decoder), not both");
+  const LoopCall c = {"tdvc_ar_wavefront_batch", loop, stream};
+  return y ? run_loop(c, EncoderSteps{{}, y}) : run_loop(c, HostDecoderSteps{{}, data, nbytes, tables});
+}
+
+extern "C" int tdvc_ar_decode_serial_batch(const tdvc_ar_loop* loop, const uint8_t* const* data, const int64_t* nbytes, const tdvc_cdf_tables* tables, void* stream) {
+  TdvcLoopLaunches count;
+  return run_loop({"tdvc_ar_decode_serial_batch", loop, stream}, HostDecoderSteps{{}, data, nbytes, tables});
+}
+
+extern "C" int tdvc_ar_wavefront_lanes_batch(const tdvc_ar_loop* loop, const uint8_t* const* data, const int64_t* nbytes, uint8_t* stream_dev, int64_t stream_cap,
+                                             uint32_t* state_dev, const tdvc_cdf_tables_dev* tables, int32_t* bad_image, void* stream) {
+  TdvcLoopLaunches count;
+  if (bad_image) *bad_image = -1;
+  return run_loop({"tdvc_ar_wavefront_lanes_batch", loop, stream}, LaneDecoderSteps{{}, data, nbytes, stream_dev, stream_cap, state_dev, tables, bad_image});
 }

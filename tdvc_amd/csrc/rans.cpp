@@ -310,29 +310,32 @@ extern "C" int64_t tdvc_ar_encode_lanes_out_bytes(int64_t npos, int M, int L) {
   return w < 0 ? w : (tdvc_lanes_container_bound(L, w) + 15) / 16 * 16;
 }
 
-int tdvc_encode_lanes_args(const char* who, const void* symbols, const void* indexes, int B, int H, int W, int M, const void* pos, int npos, int L, int32_t ncdfs,
-                           const void* scratch, int64_t lane_words, int64_t scratch_cap_words, const void* out, int64_t out_stride, int64_t out_cap, const void* info) {
+int tdvc_encode_lanes_args(const char* who, const tdvc_lanes_enc* enc, int32_t ncdfs) {
   const auto bad = [&](const char* what) { tdvc_set_error("%s: %s", who, what); return TDVC_EINVAL; };
-  if (!symbols || !indexes || !pos || !scratch || !out || !info) return bad("null argument");
-  if (B < 1 || B > 65535 || H < 1 || W < 1 || M < 1 || npos < 1 || (int64_t)H * W > 0x7FFFFFFF) return bad("1 <= B <= 65535 images of H x W x M symbols and npos >= 1 positions expected");
-  if ((L != 64 && L != 128) || M % L != 0) return bad("64 or 128 lanes that divide the channel count expected");
+  if (!enc) return bad("null argument");
+  const tdvc_lanes_enc& e = *enc;
+  if (!e.symbols || !e.indexes || !e.pos || !e.scratch || !e.out || !e.info) return bad("null argument");
+  if (e.B < 1 || e.B > 65535 || e.H < 1 || e.W < 1 || e.M < 1 || e.npos < 1 || (int64_t)e.H * e.W > 0x7FFFFFFF)
+    return bad("1 <= B <= 65535 images of H x W x M symbols and npos >= 1 positions expected");
+  if ((e.L != 64 && e.L != 128) || e.M % e.L != 0) return bad("64 or 128 lanes that divide the channel count expected");
   if (ncdfs < 1 || ncdfs > 64) return bad("1..64 CDF tables expected");
-  if (lane_words < 2 || lane_words > kLanesScratchCap || (int64_t)B * L * lane_words > scratch_cap_words)
+  if (e.lane_words < 2 || e.lane_words > kLanesScratchCap || (int64_t)e.B * e.L * e.lane_words > e.scratch_cap_words)
     return bad("2..65536 scratch words per lane expected, B * L * lane_words of them inside the scratch buffer");
-  if (out_stride % 16 != 0 || out_stride < tdvc_lanes_container_bound(L, lane_words) || (int64_t)B * out_stride > out_cap)
+  if (e.out_stride % 16 != 0 || e.out_stride < tdvc_lanes_container_bound(e.L, e.lane_words) || (int64_t)e.B * e.out_stride > e.out_cap)
     return bad("the output stride must be a multiple of 16 that holds L lanes of min(lane_words, 65535) words behind header and length table, B strides inside the output buffer");
-  if ((((uintptr_t)symbols) | ((uintptr_t)indexes) | ((uintptr_t)pos) | ((uintptr_t)scratch) | ((uintptr_t)info)) & 3 || ((uintptr_t)out) & 15)
+  if ((((uintptr_t)e.symbols) | ((uintptr_t)e.indexes) | ((uintptr_t)e.pos) | ((uintptr_t)e.scratch) | ((uintptr_t)e.info)) & 3 || ((uintptr_t)e.out) & 15)
     return bad("symbols / indexes / positions / scratch / info must be 4-byte aligned, the output buffer 16-byte aligned");
   return TDVC_OK;
 }
 
-extern "C" int tdvc_rans_encode_lanes_dev_ref(const int32_t* symbols, const int32_t* indexes, int B, int H, int W, int M, const int32_t* pos, int npos, int L,
-                                              const int32_t* cdfs, int32_t cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int32_t ncdfs,
-                                              uint32_t* scratch, int64_t lane_words, int64_t scratch_cap_words, uint8_t* out, int64_t out_stride,
-                                              int64_t out_cap, uint32_t* info) {
-  if (!cdfs || !cdf_sizes || !offsets || cdf_stride < 1) { tdvc_set_error("tdvc_rans_encode_lanes_dev_ref: null table pointer"); return TDVC_EINVAL; }
-  if (const int rc = tdvc_encode_lanes_args("tdvc_rans_encode_lanes_dev_ref", symbols, indexes, B, H, W, M, pos, npos, L, ncdfs, scratch, lane_words,
-                                            scratch_cap_words, out, out_stride, out_cap, info)) return rc;
+extern "C" int tdvc_rans_encode_lanes_dev_ref(const tdvc_lanes_enc* enc, const tdvc_cdf_tables* tables) {
+  if (!tables || !tables->cdfs || !tables->sizes || !tables->offsets || tables->stride < 1) { tdvc_set_error("tdvc_rans_encode_lanes_dev_ref: null table pointer"); return TDVC_EINVAL; }
+  if (const int rc = tdvc_encode_lanes_args("tdvc_rans_encode_lanes_dev_ref", enc, tables->ncdfs)) return rc;
+  const int B = enc->B, H = enc->H, W = enc->W, M = enc->M, npos = enc->npos, L = enc->L, ncdfs = tables->ncdfs, cdf_stride = tables->stride;
+  const int32_t *symbols = enc->symbols, *indexes = enc->indexes, *pos = enc->pos, *cdfs = tables->cdfs, *cdf_sizes = tables->sizes, *offsets = tables->offsets;
+  const int64_t lane_words = enc->lane_words, out_stride = enc->out_stride;
+  uint32_t *scratch = enc->scratch, *info = enc->info;
+  uint8_t* out = enc->out;
   const int per = M / L;
   std::vector<uint32_t> lpos((size_t)L), llen((size_t)L);
   for (int b = 0; b < B; ++b) {

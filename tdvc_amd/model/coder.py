@@ -655,39 +655,39 @@ class Cheng2020Anchor(nn.Module, PackCache):
                 steps.append(ps)
         return steps
 
-    def _ar_setup(self, H, W, adt, dev, B):
-        """per (grid, dtype, batch): the wavefront position list, the step sizes and the staging chain for B x H rows (a step of a
-        batch of B is a (1, B x n) map) -- built once (the position list alone is 2 ms of Python at 68 x 120); `_ar_host` and
-        `_ar_serial` add what only the encoder / only the raster-order decoder needs"""
+    def _ar_setup(self, H, W, adt, dev, B) -> ops.ArLoop:
+        """per (grid, dtype, batch): the loop over anti-diagonals -- the wavefront position list, the step sizes and the staging chain
+        for B x H rows (a step of a batch of B is a (1, B x n) map) -- built once (the position list alone is 2 ms of Python at
+        68 x 120); `_ar_host` and `_ar_serial` add what only the encoder / only the raster-order decoder needs"""
         cache = self.__dict__.setdefault("_ar_cache", {})
         key = (H, W, adt, str(dev), B)
-        c = cache.get(key)
-        if c is not None and not all(a is b for a, b in zip(c["chain"]["pcs"], self._ar_packed())):
-            c = None                     # the packed weights were rebuilt since: the cached descriptors point at the old blobs
-        if c is None:
+        lp = cache.get(key)
+        if lp is not None and not all(a is b for a, b in zip(lp.packed, self._ar_packed())):
+            lp = None                    # the packed weights were rebuilt since: the cached descriptors point at the old blobs
+        if lp is None:
             steps = self.wavefront_steps(H, W)
             flat = torch.tensor([p for st in steps for p in st], dtype=torch.int32, device=dev)
-            c = dict(flat=flat, fl=flat.long(), sizes=np.array([len(st) for st in steps], dtype=np.int32), chain=self._ar_chain(B * H, adt, dev),
-                     key=key)
+            lp = self._ar_chain(B * H, adt, dev, flat, np.array([len(st) for st in steps], dtype=np.int32))
+            lp.key = key
             cache.clear()                # one geometry at a time (the staging buffers are not small)
-            cache[key] = c
-        return c
+            cache[key] = lp
+        return lp
 
-    def _ar_host(self, st):
+    def _ar_host(self, lp):
         """pinned host buffers for the symbols / indexes of the B images of compress()"""
-        if "host" not in st:
-            H, W, _, _, B = st["key"]
-            st["host"] = [(torch.empty((H * W, self.M), dtype=torch.int32).pin_memory(), torch.empty((H * W, self.M), dtype=torch.int32).pin_memory())
-                          for _ in range(B)]
-        return st["host"]
+        if lp.host is None:
+            H, W, _, _, B = lp.key
+            lp.host = [(torch.empty((H * W, self.M), dtype=torch.int32).pin_memory(), torch.empty((H * W, self.M), dtype=torch.int32).pin_memory())
+                       for _ in range(B)]
+        return lp.host
 
-    def _ar_serial(self, st):
-        """the raster-order decoder's chain (B rows: one position of every image per step) and its position table"""
-        if "serial" not in st:
-            H, W, adt, _, B = st["key"]
-            dev = st["flat"].device
-            st["serial"] = (self._ar_chain(B, adt, dev), torch.tensor([[h, w] for h in range(H) for w in range(W)], dtype=torch.int32, device=dev))
-        return st["serial"]
+    def _ar_serial(self, lp) -> ops.ArLoop:
+        """the raster-order decoder's loop: a chain of B rows (one position of every image per step) over the raster position list"""
+        if lp.serial is None:
+            H, W, adt, _, B = lp.key
+            dev = lp.pos.device
+            lp.serial = self._ar_chain(B, adt, dev, torch.tensor([[h, w] for h in range(H) for w in range(W)], dtype=torch.int32, device=dev))
+        return lp.serial
 
     @staticmethod
     def _ar_groups(descs, B, nmax):
@@ -815,9 +815,9 @@ class Cheng2020Anchor(nn.Module, PackCache):
         zs = zsym.permute(0, 3, 1, 2).contiguous().cpu().numpy()                   # compressai order (C, h, w)
         zidx = np.broadcast_to(np.arange(M, dtype=np.int32)[:, None, None], zs.shape[1:])
         z_strings = [ops.rans_encode(zs[b], zidx, ebt) for b in range(B)]
-        st = self._ar_setup(H, W, adt, dev, B)
-        flat, sizes, chain, fl = st["flat"], st["sizes"], st["chain"], st["fl"]
-        host = self._ar_host(st) if coder == "host" else None
+        lp = self._ar_setup(H, W, adt, dev, B)
+        flat, fl = lp.pos, lp.pos_long
+        host = self._ar_host(lp) if coder == "host" else None
         # every position is written exactly once and only causal (already written) neighbours are read: no zero fill
         y_hat_all = FM.empty(B, H, W, M, dtype=adt, device=dev)
         sym_all = torch.empty((B, H, W, M), dtype=torch.int32, device=dev)
@@ -825,9 +825,8 @@ class Cheng2020Anchor(nn.Module, PackCache):
         # the W + 3(H-1) steps run natively (gather -> context conv -> entropy_parameters -> quantise), a group of images in the
         # same launches (tdvc_ar_wavefront_batch)
         b0 = 0
-        for g in self._ar_groups(chain["descs"], B, int(sizes.max())):
-            ops.ar_wavefront_batch(None, None, y32.batch(b0, g), y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
-                                   chain["gp"], flat, sizes, M, W, table, idx_all[b0:b0 + g], sym_all[b0:b0 + g])
+        for g in self._ar_groups(lp.descs, B, lp.nmax):
+            ops.ar_wavefront_batch(lp, None, None, y32.batch(b0, g), y_hat_all.batch(b0, g), params.batch(b0, g), table, idx_all[b0:b0 + g], sym_all[b0:b0 + g])
             b0 += g
         if coder == "device":
             dbg = [{"y_hat": FM(y_hat_all.t[b:b + 1]), "symbols": sym_all[b], "indexes": idx_all[b]} for b in range(B)]
@@ -884,7 +883,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
         params = FM.empty(B, H, W, 2 * M, dtype=adt, device=dev)
         self._h_s(z_hat, params, per_image)
         y_hat_all = FM.zeros(B, H, W, M, dtype=adt, device=dev)
-        st = self._ar_setup(H, W, adt, dev, B)
+        lp = self._ar_setup(H, W, adt, dev, B)
         ys = list(strings[0])
         if len(ys) != B:
             raise ValueError(f"{len(ys)} y strings for {B} z strings")
@@ -898,25 +897,25 @@ class Cheng2020Anchor(nn.Module, PackCache):
                 classes.setdefault(nl, []).append(b)
             for members in classes.values():
                 o = 0
-                for g in self._ar_groups(st["chain"]["descs"], len(members), int(st["sizes"].max())):
-                    self._decode_wavefront_group(members[o:o + g], ys, gct, table, y_hat_all, params, st, lanes)
+                for g in self._ar_groups(lp.descs, len(members), lp.nmax):
+                    self._decode_wavefront_group(members[o:o + g], ys, gct, table, y_hat_all, params, lp, lanes)
                     o += g
             return {"x_hat": self._g_s(y_hat_all, per_image) if synth else None, "y_hat": y_hat_all}
         # the per-position chain over staging buffers of one position per image; the loop itself runs natively
         # (tdvc_ar_decode_serial_batch: Python drove it at ~230 us per position)
-        chain, pos_table = self._ar_serial(st)
+        ser = self._ar_serial(lp)
         sym = torch.zeros((B, H, W, M), dtype=torch.int32, device=dev)
         idx = torch.zeros((B, H, W, M), dtype=torch.int32, device=dev)
         b0 = 0
-        for g in self._ar_groups(chain["descs"], B, 1):
-            ops.ar_decode_serial_batch(ys[b0:b0 + g], gct, y_hat_all.batch(b0, g), params.batch(b0, g), chain["x1"], chain["pc"], chain["descs"],
-                                       chain["gp"], pos_table, M, W, table, idx[b0:b0 + g], sym[b0:b0 + g])
+        for g in self._ar_groups(ser.descs, B, 1):
+            ops.ar_decode_serial_batch(ser, ys[b0:b0 + g], gct, y_hat_all.batch(b0, g), params.batch(b0, g), table, idx[b0:b0 + g], sym[b0:b0 + g])
             b0 += g
         return {"x_hat": self._g_s(y_hat_all, per_image) if synth else None, "y_hat": y_hat_all}
 
-    def _ar_chain(self, cap, adt, dev):
+    def _ar_chain(self, cap, adt, dev, pos, step_sizes=None) -> ops.ArLoop:
         """the per-step chain as conv descriptors over staging buffers of `cap` positions: context conv (1x1 over the gathered
-        neighbourhoods) into pc[2M:4M], entropy_parameters into gp"""
+        neighbourhoods) into pc[2M:4M], entropy_parameters into gp; with the position list and the step sizes (None: a step per
+        position) the loop"""
         M, e = self.M, self.entropy_parameters
         x1 = FM.empty(1, 1, cap, 12 * M, dtype=adt, device=dev)
         pc = FM.empty(1, 1, cap, 4 * M, dtype=adt, device=dev)
@@ -931,19 +930,18 @@ class Cheng2020Anchor(nn.Module, PackCache):
                  ops.conv_desc(t1, pcs[3], out=gp, out_dtype=torch.float32)[0]]
         # the descriptors hold raw device pointers into the packed weights (and their fp32 twins): the chain keeps the packed objects
         # alive, and _ar_setup() rebuilds it when the coder's packed forms are no longer these objects (clear_packed, refresh, .to())
-        return {"x1": x1, "pc": pc, "gp": gp, "descs": descs, "keep": (t0, t1), "pcs": pcs}
+        return ops.ArLoop(x1, pc, gp, descs, pcs, (t0, t1), pos, step_sizes)
 
     def _ar_packed(self):
         e = self.entropy_parameters
         return [self._ctx_1x1(), pk_conv(self, "ep0", e[0]), pk_conv(self, "ep2", e[2]), pk_conv(self, "ep4", e[4])]
 
-    def _decode_wavefront_group(self, members, ys, gct, table, y_hat_all, params, st, lanes):
+    def _decode_wavefront_group(self, members, ys, gct, table, y_hat_all, params, lp, lanes):
         """images `members` (indexes into the call's batch, one lane count) of wavefront-ordered y streams in one pass of the loop:
         tdvc_ar_wavefront_batch (range decoder on the host) or with `lanes` tdvc_ar_wavefront_lanes_batch (the strings go to the
         device once, the range decoder runs there)"""
         dev, M = y_hat_all.t.device, self.M
         H, W, g = y_hat_all.H, y_hat_all.W, len(members)
-        flat, sizes, chain = st["flat"], st["sizes"], st["chain"]
         data = [ys[b] for b in members]
         if members == list(range(members[0], members[0] + g)):
             yh, pr, scatter = y_hat_all.batch(members[0], g), params.batch(members[0], g), False
@@ -951,17 +949,16 @@ class Cheng2020Anchor(nn.Module, PackCache):
             yh, pr, scatter = FM.zeros(g, H, W, M, dtype=y_hat_all.t.dtype, device=dev), FM(params.t[members].contiguous()), True
         sym = torch.zeros((g, H * W, M), dtype=torch.int32, device=dev)          # wavefront order
         idx = torch.zeros((g, H * W, M), dtype=torch.int32, device=dev)
-        args = (yh, pr, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, M, W, table, idx, sym)
         if lanes:
             nl = ops.lanes_of(data[0])
             stream_dev = torch.empty(ops.ar_lanes_batch_layout([len(d) for d in data], nl)[0], dtype=torch.uint8, device=dev)
             try:
-                ops.ar_wavefront_lanes_batch(data, gct, stream_dev, ops.ar_lanes_state_batch(nl, g, dev), *args)
+                ops.ar_wavefront_lanes_batch(lp, data, gct, stream_dev, ops.ar_lanes_state_batch(nl, g, dev), yh, pr, table, idx, sym)
             except ops.L.TdvcStreamError as e:
                 raise ops.L.TdvcStreamError(f"decompress: image {members[e.image]} of the batch: corrupt or exhausted lane-split stream "
                                             "(a lane ran out of words or met an impossible code)") from None
         else:
-            ops.ar_wavefront_batch(data, gct, None, *args)
+            ops.ar_wavefront_batch(lp, data, gct, None, yh, pr, table, idx, sym)
         if scatter:
             y_hat_all.t[members] = yh.t
 

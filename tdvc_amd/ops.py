@@ -1251,12 +1251,13 @@ class CdfTables:
         self.sizes = np.ascontiguousarray(lengths.detach().cpu().numpy().reshape(-1), dtype=np.int32)
         self.offsets = np.ascontiguousarray(offsets.detach().cpu().numpy().reshape(-1), dtype=np.int32)
         self.stride = self.cdf.shape[1]
+        self.desc = L.CdfTablesDesc(self.cdf.ctypes.data, self.sizes.ctypes.data, self.offsets.ctypes.data, self.stride, len(self.sizes))      # tdvc_cdf_tables
         self._dev = {}
 
-    def device(self, dev):
-        """device copies for the on-device range decoder (tdvc_ar_decode_lanes_step_batch), made once per device: every table's
-        entries end to end as uint16 (a table's last entry, 1 << 16, wraps to 0: the kernel implies it), padded to a
-        multiple of 8; per table its start in that array, its size, its offset -> (cdf16, starts, sizes, offsets)"""
+    def device(self, dev) -> L.CdfTablesDevDesc:
+        """the tables in device memory as the lane kernels read them (`tdvc_cdf_tables_dev`), made once per device: every table's
+        entries end to end as uint16 (a table's last entry, 1 << 16, wraps to 0: the kernel implies it), padded to a multiple
+        of 8; per table its start in that array, its size, its offset.  The descriptor's `keep` holds the four tensors."""
         dev = torch.device(dev)
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
@@ -1267,7 +1268,10 @@ class CdfTables:
             packed = np.zeros(n16, dtype=np.uint16)
             for t, (o, n) in enumerate(zip(starts, self.sizes)):
                 packed[o:o + n] = self.cdf[t, :n].astype(np.uint16)
-            self._dev[key] = (torch.from_numpy(packed.view(np.int16)).to(dev),) + tuple(torch.from_numpy(a).to(dev) for a in (starts, self.sizes, self.offsets))
+            keep = (torch.from_numpy(packed.view(np.int16)).to(dev),) + tuple(torch.from_numpy(a).to(dev) for a in (starts, self.sizes, self.offsets))
+            d = L.CdfTablesDevDesc(*[a.data_ptr() for a in keep], n16, len(self.sizes))
+            d.keep = keep
+            self._dev[key] = d
         return self._dev[key]
 
 
@@ -1392,9 +1396,10 @@ def rans_encode_lanes_dev_ref(symbols: np.ndarray, indexes: np.ndarray, pos: np.
         out = np.zeros(B * stride + 16, dtype=np.uint8)
         out = out[(-out.ctypes.data) % 16:][:B * stride].reshape(B, stride)
     info = np.full((B, 2), 0xFFFFFFFF, dtype=np.uint32)
-    L.check(L.lib().tdvc_rans_encode_lanes_dev_ref(s.ctypes.data, i.ctypes.data, B, H, W, M, p.ctypes.data, p.shape[0], int(lanes), t.cdf.ctypes.data, t.stride,
-                                                   t.sizes.ctypes.data, t.offsets.ctypes.data, len(t.sizes), scratch.ctypes.data, int(lane_words), scratch.size,
-                                                   out.ctypes.data, stride, out.size, info.ctypes.data), "rans_encode_lanes_dev_ref")
+    enc = L.LanesEncDesc(s.ctypes.data, i.ctypes.data, B, H, W, M, p.ctypes.data, p.shape[0], int(lanes), scratch.ctypes.data, int(lane_words), scratch.size,
+                         out.ctypes.data, stride, out.size, info.ctypes.data)
+    tabs = L.CdfTablesDesc(t.cdf.ctypes.data, t.sizes.ctypes.data, t.offsets.ctypes.data, t.stride, len(t.sizes))      # `t`: a CdfTables or anything with its four fields
+    L.check(L.lib().tdvc_rans_encode_lanes_dev_ref(C.byref(enc), C.byref(tabs)), "rans_encode_lanes_dev_ref")
     if raw:
         return out, info, scratch
     return lanes_strings(out, info, "rans_encode_lanes_dev_ref")
@@ -1428,12 +1433,11 @@ def ar_encode_lanes_batch(symbols: torch.Tensor, indexes: torch.Tensor, pos: tor
         out = torch.empty((B, stride), dtype=torch.uint8, device=dev)
     assert scratch.dtype == torch.int32 and out.dtype == torch.uint8 and scratch.is_contiguous() and out.is_contiguous()
     info = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    cdf16, starts, sizes, offsets = t.device(dev)
-    L.check(L.lib().tdvc_ar_encode_lanes_batch(symbols.data_ptr(), indexes.data_ptr(), B, H, W, M, pos.data_ptr(), pos.shape[0], int(lanes), cdf16.data_ptr(),
-                                               cdf16.numel(), starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), scratch.data_ptr(),
-                                               int(lane_words), scratch.numel(), out.data_ptr(), stride, out.numel(), info.data_ptr(), _stream()),
-            "ar_encode_lanes_batch")
-    return LanesEncoding(out, info, scratch, (symbols, indexes, pos, cdf16, starts, sizes, offsets))
+    td = t.device(dev)
+    enc = L.LanesEncDesc(symbols.data_ptr(), indexes.data_ptr(), B, H, W, M, pos.data_ptr(), pos.shape[0], int(lanes), scratch.data_ptr(), int(lane_words),
+                         scratch.numel(), out.data_ptr(), stride, out.numel(), info.data_ptr())
+    L.check(L.lib().tdvc_ar_encode_lanes_batch(C.byref(enc), C.byref(td), _stream()), "ar_encode_lanes_batch")
+    return LanesEncoding(out, info, scratch, (symbols, indexes, pos, td))
 
 
 def lanes_of(data: bytes) -> int:
@@ -1518,39 +1522,49 @@ def _host_strings(strings):
     return bufs, ptrs, sizes
 
 
-def ar_wavefront_batch(strings, t: CdfTables | None, y: FM | None, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM,
-                       pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
-    """the context loop of the B = y_hat.N images over anti-diagonals in one pass (`tdvc_ar_wavefront_batch`): encoder with `y` (idx / sym
-    raster [B][H][W][M]), decoder with `strings` (B byte strings) + `t` (idx / sym [B][H * W][M] in wavefront order)"""
-    B = y_hat.N
-    assert sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
-    assert strings is None or len(strings) == B
+class ArLoop:
+    """the fixed parts of a `tdvc_ar_loop`, kept between calls on images of one geometry: the staging maps x1 / pc / gp, the conv
+    descriptors over them (`descs`; `convs`: their ctypes array, built once), what they point into (`packed`: the PackedConvs, which
+    Cheng2020Anchor._ar_setup compares with the live ones; `keep`: the chain's inner buffers), the position list `pos` (device int32
+    [H * W][2] in step order) and the steps' sizes (None: a step per position, the raster order).  `key`, `host` and `serial` are the
+    coder's to fill: its cache key, compress()'s pinned buffers, the raster-order loop of the geometry."""
+
+    def __init__(self, x1: FM, pc: FM, gp: FM, descs: list, packed: list, keep, pos: torch.Tensor, step_sizes=None):
+        self.x1, self.pc, self.gp, self.descs, self.packed, self.keep, self.pos = x1, pc, gp, descs, packed, keep, pos
+        ss = self.step_sizes = None if step_sizes is None else np.ascontiguousarray(step_sizes, dtype=np.int32)
+        assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.dim() == 2 and pos.shape[1] == 2 and (ss is None or int(ss.sum()) == pos.shape[0])
+        self.nsteps, self.nmax = (pos.shape[0], 1) if ss is None else (ss.size, int(ss.max()))        # steps, positions of the largest
+        self.convs = (L.ConvDesc * len(descs))(*descs)
+        self.pos_long = pos.long()                                     # for torch indexing with the list
+        self.key = self.host = self.serial = None
+
+    def desc(self, y_hat: FM, params: FM, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> L.ArLoopDesc:
+        """the loop over B = y_hat.N images; idx / sym: int32 arrays of B * H * W * M elements"""
+        assert _ar_rows_ok(idx, y_hat, 0, 0) and _ar_rows_ok(sym, y_hat, 0, 0) and self.pos.shape[0] == y_hat.H * y_hat.W
+        return L.ArLoopDesc(y_hat.desc(), params.desc(), self.x1.desc(), self.pc.desc(), self.gp.desc(), self.convs, len(self.descs), self.pos.data_ptr(),
+                            self.step_sizes.ctypes.data if self.step_sizes is not None else None, self.nsteps, scale_table.data_ptr(), scale_table.numel(),
+                            idx.data_ptr(), sym.data_ptr())
+
+
+def ar_wavefront_batch(loop: ArLoop, strings, t: CdfTables | None, y: FM | None, y_hat: FM, params: FM, scale_table: torch.Tensor, idx: torch.Tensor,
+                       sym: torch.Tensor) -> None:
+    """the context loop of the B = y_hat.N images over the loop's steps in one pass (`tdvc_ar_wavefront_batch`): encoder with `y` (idx / sym
+    raster [B][H][W][M]), decoder with `strings` (B byte strings) + `t` (idx / sym [B][H * W][M] in step order)"""
+    assert strings is None or len(strings) == y_hat.N
     keep, ptrs, sizes = _host_strings(strings) if strings is not None else (None, None, None)
-    arr = (L.ConvDesc * len(descs))(*descs)
-    ss = np.ascontiguousarray(step_sizes, dtype=np.int32)
-    assert pos.numel() >= 2 * int(ss.sum())
-    dyh, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
+    d = loop.desc(y_hat, params, scale_table, idx, sym)
     dy = y.desc() if y is not None else None
-    L.check(L.lib().tdvc_ar_wavefront_batch(ptrs, sizes, B, t.cdf.ctypes.data if t else None, t.stride if t else 0, t.sizes.ctypes.data if t else None,
-                                            t.offsets.ctypes.data if t else None, C.byref(dy) if dy is not None else None, C.byref(dyh), C.byref(dp),
-                                            C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W,
-                                            scale_table.data_ptr(), scale_table.numel(), idx.data_ptr(), sym.data_ptr(), _stream()), "ar_wavefront_batch")
+    L.check(L.lib().tdvc_ar_wavefront_batch(C.byref(d), C.byref(dy) if dy is not None else None, ptrs, sizes, C.byref(t.desc) if t else None, _stream()),
+            "ar_wavefront_batch")
 
 
-def ar_decode_serial_batch(strings, t: CdfTables, y_hat: FM, params: FM, x1: FM, pc: FM, descs: list, gp: FM, pos_table: torch.Tensor,
-                           M: int, W: int, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
+def ar_decode_serial_batch(loop: ArLoop, strings, t: CdfTables, y_hat: FM, params: FM, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
     """the decoder's serial context loop for raster-ordered streams over the B = y_hat.N images at once, B rows per position
-    (`tdvc_ar_decode_serial_batch`); fills y_hat, idx / sym [B][H][W][M]"""
-    B = y_hat.N
-    assert len(strings) == B and sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
-    assert pos_table.shape[0] == y_hat.H * y_hat.W
+    (`tdvc_ar_decode_serial_batch`; `loop`: a raster position list, no step sizes); fills y_hat, idx / sym [B][H][W][M]"""
+    assert len(strings) == y_hat.N and loop.step_sizes is None
     keep, ptrs, sizes = _host_strings(strings)
-    arr = (L.ConvDesc * len(descs))(*descs)
-    dy, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
-    L.check(L.lib().tdvc_ar_decode_serial_batch(ptrs, sizes, B, t.cdf.ctypes.data, t.stride, t.sizes.ctypes.data, t.offsets.ctypes.data,
-                                                C.byref(dy), C.byref(dp), C.byref(dx), C.byref(dc), arr, len(descs), C.byref(dg),
-                                                pos_table.data_ptr(), pos_table.shape[0], M, W, scale_table.data_ptr(), scale_table.numel(),
-                                                idx.data_ptr(), sym.data_ptr(), _stream()), "ar_decode_serial_batch")
+    d = loop.desc(y_hat, params, scale_table, idx, sym)
+    L.check(L.lib().tdvc_ar_decode_serial_batch(C.byref(d), ptrs, sizes, C.byref(t.desc), _stream()), "ar_decode_serial_batch")
 
 
 def ar_lanes_batch_layout(sizes, lanes: int):
@@ -1591,37 +1605,26 @@ def ar_decode_lanes_step_batch(gp: FM, pos: torch.Tensor, npos: int, table: torc
     """one step of the on-device decoder over B = y_hat.N lane-split streams (`tdvc_ar_decode_lanes_step_batch`), B workgroups: the
     range decoder, the CDF indexes and the quantiser's write-back of `npos` positions; symbols / indexes rows cbase .. cbase + npos
     of every image's block of [B][H * W][M]"""
-    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
+    td = t.device(y_hat.t.device)
     assert streams_dev.dtype == torch.uint8 and state.numel() * 4 >= y_hat.N * L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
     assert pos.numel() >= 2 * npos and _ar_rows_ok(symbols, y_hat, cbase, npos) and _ar_rows_ok(indexes, y_hat, cbase, npos)
     dg, dh = gp.desc(), y_hat.desc()
     L.check(L.lib().tdvc_ar_decode_lanes_step_batch(C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(), streams_dev.data_ptr(),
-                                                    streams_dev.numel(), streams_dev.data_ptr(), int(lanes), cdf16.data_ptr(), cdf16.numel(), starts.data_ptr(),
-                                                    sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), state.data_ptr(), C.byref(dh), symbols.data_ptr(),
-                                                    indexes.data_ptr(), cbase, _stream()), "ar_decode_lanes_step_batch")
+                                                    streams_dev.numel(), streams_dev.data_ptr(), int(lanes), C.byref(td), state.data_ptr(), C.byref(dh),
+                                                    symbols.data_ptr(), indexes.data_ptr(), cbase, _stream()), "ar_decode_lanes_step_batch")
 
 
-def ar_wavefront_lanes_batch(strings, t: CdfTables, stream_dev: torch.Tensor, state: torch.Tensor, y_hat: FM, params: FM, x1: FM, pc: FM,
-                             descs: list, gp: FM, pos: torch.Tensor, step_sizes: np.ndarray, M: int, W: int, scale_table: torch.Tensor,
+def ar_wavefront_lanes_batch(loop: ArLoop, strings, t: CdfTables, stream_dev: torch.Tensor, state: torch.Tensor, y_hat: FM, params: FM, scale_table: torch.Tensor,
                              idx: torch.Tensor, sym: torch.Tensor) -> None:
     """the decoder's context loop of B = y_hat.N lane-split streams of one lane count in one pass (`tdvc_ar_wavefront_lanes_batch`):
     the strings are uploaded once into `stream_dev`, every step's range decoding runs on the device, one stream wait at the end;
     a damaged stream raises TdvcStreamError (a ValueError) whose `image` is the first image of the call whose error word is set"""
-    B = y_hat.N
-    lanes = lanes_of(strings[0])
-    cdf16, starts, sizes, offsets = t.device(y_hat.t.device)
-    assert len(strings) == B and stream_dev.dtype == torch.uint8 and state.numel() * 4 >= B * L.lib().tdvc_ar_lanes_state_bytes(lanes)
-    assert sym.numel() >= B * y_hat.H * y_hat.W * M and idx.numel() >= B * y_hat.H * y_hat.W * M
+    assert len(strings) == y_hat.N and stream_dev.dtype == torch.uint8 and state.numel() * 4 >= y_hat.N * L.lib().tdvc_ar_lanes_state_bytes(lanes_of(strings[0]))
     keep, ptrs, nbytes = _host_strings(strings)
-    arr = (L.ConvDesc * len(descs))(*descs)
-    ss = np.ascontiguousarray(step_sizes, dtype=np.int32)
-    assert pos.numel() >= 2 * int(ss.sum())
-    dyh, dp, dx, dc, dg = y_hat.desc(), params.desc(), x1.desc(), pc.desc(), gp.desc()
+    d = loop.desc(y_hat, params, scale_table, idx, sym)
     bad = C.c_int32(-1)
-    rc = L.lib().tdvc_ar_wavefront_lanes_batch(ptrs, nbytes, B, stream_dev.data_ptr(), stream_dev.numel(), state.data_ptr(), cdf16.data_ptr(), cdf16.numel(),
-                                               starts.data_ptr(), sizes.data_ptr(), offsets.data_ptr(), sizes.numel(), C.byref(dyh), C.byref(dp), C.byref(dx),
-                                               C.byref(dc), arr, len(descs), C.byref(dg), pos.data_ptr(), ss.ctypes.data, ss.size, M, W, scale_table.data_ptr(),
-                                               scale_table.numel(), idx.data_ptr(), sym.data_ptr(), C.byref(bad), _stream())
+    rc = L.lib().tdvc_ar_wavefront_lanes_batch(C.byref(d), ptrs, nbytes, stream_dev.data_ptr(), stream_dev.numel(), state.data_ptr(),
+                                               C.byref(t.device(y_hat.t.device)), C.byref(bad), _stream())
     if rc != 0 and bad.value >= 0:
         e = L.TdvcStreamError(L.lib().tdvc_last_error().decode("utf-8", "replace"))
         e.image = bad.value

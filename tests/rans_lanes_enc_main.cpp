@@ -31,6 +31,13 @@ static uint32_t rnd() {                                     // xorshift64*
 static int g_fail = 0;
 #define EXPECT(cond, ...) do { if (!(cond)) { printf("FAIL line %d: ", __LINE__); printf(__VA_ARGS__); printf("\n"); ++g_fail; } } while (0)
 
+// the twin's call: the buffers as a tdvc_lanes_enc, the tables as a tdvc_cdf_tables
+static int twin(const int32_t* sym, const int32_t* idx, int B, int H, int W, int M, const int32_t* pos, int npos, int L, const tdvc_cdf_tables& t, uint32_t* scratch,
+                int64_t lane_words, int64_t scratch_cap_words, uint8_t* out, int64_t out_stride, int64_t out_cap, uint32_t* info) {
+  const tdvc_lanes_enc e = {sym, idx, B, H, W, M, pos, npos, L, scratch, lane_words, scratch_cap_words, out, out_stride, out_cap, info};
+  return tdvc_rans_encode_lanes_dev_ref(&e, &t);
+}
+
 int main() {
   // tables as in rans_lanes_main.cpp: random pmfs through tdvc_pmf_to_quantized_cdf, one wide Gaussian among them
   const int ntab = 7, stride = 2100;
@@ -49,6 +56,7 @@ int main() {
     sizes[t] = n + 1;
     offsets[t] = -(int32_t)(rnd() % 12) - (t == ntab - 1 ? 1000 : 0);
   }
+  const tdvc_cdf_tables tabs = {cdfs.data(), sizes.data(), offsets.data(), stride, ntab};
   const int M = 128, B = 2;
   // 6 and 8 bypass digits; the extremes stay 4096 inside +-(1 << 30) so that tdvc_rans_encode's `2 * (value - max_value)` and
   // `-2 * value - 1`, int products, stay representable whatever the table's offset (the lane routine forms them wider)
@@ -75,8 +83,7 @@ int main() {
       EXPECT(words >= 2 && ostride >= 4 + 2 * L + 8 * L && ostride % 16 == 0, "sizes: %lld %lld %s", (long long)words, (long long)ostride, g_err);
       std::vector<uint32_t> scratch((size_t)(B * L * words)), info(2 * B, 7);
       uint8_t* out = (uint8_t*)aligned_alloc(16, (size_t)(B * ostride));
-      int rc = tdvc_rans_encode_lanes_dev_ref(sym.data(), idx.data(), B, H, W, M, pos.data(), npos, L, cdfs.data(), stride, sizes.data(), offsets.data(), ntab,
-                                              scratch.data(), words, (int64_t)scratch.size(), out, ostride, B * ostride, info.data());
+      int rc = twin(sym.data(), idx.data(), B, H, W, M, pos.data(), npos, L, tabs, scratch.data(), words, (int64_t)scratch.size(), out, ostride, B * ostride, info.data());
       EXPECT(rc == 0, "twin L=%d %dx%d: %s", L, H, W, g_err);
       for (int b = 0; b < B && rc == 0; ++b) {
         EXPECT(info[2 * b + 1] == 0 && info[2 * b] > 0 && (int64_t)info[2 * b] <= ostride, "image %d: status %u, %u bytes", b, info[2 * b + 1], info[2 * b]);
@@ -102,8 +109,7 @@ int main() {
         std::vector<uint32_t> sc4((size_t)(B * L * w4)), info4(2 * B, 7);
         uint8_t* out4 = (uint8_t*)aligned_alloc(16, (size_t)(B * os4));
         memset(out4, 0xEE, (size_t)(B * os4));
-        rc = tdvc_rans_encode_lanes_dev_ref(sym.data(), idx.data(), B, H, W, M, pos.data(), npos, L, cdfs.data(), stride, sizes.data(), offsets.data(), ntab, sc4.data(),
-                                            w4, (int64_t)sc4.size(), out4, os4, B * os4, info4.data());
+        rc = twin(sym.data(), idx.data(), B, H, W, M, pos.data(), npos, L, tabs, sc4.data(), w4, (int64_t)sc4.size(), out4, os4, B * os4, info4.data());
         EXPECT(rc == 0, "small scratch L=%d: %s", L, g_err);
         for (int b = 0; b < B; ++b) EXPECT(info4[2 * b] == 0 && info4[2 * b + 1] == 2, "small scratch image %d: bytes %u status %u", b, info4[2 * b], info4[2 * b + 1]);
         for (int64_t i = 0; i < B * os4; ++i) if (out4[i] != 0xEE) { EXPECT(false, "small scratch: output byte %lld written", (long long)i); break; }
@@ -116,19 +122,15 @@ int main() {
     std::vector<uint32_t> sc(64 * 8), info(2);
     uint8_t* out = (uint8_t*)aligned_alloc(16, 4096);
     const int32_t pos[2] = {0, 0};
-    EXPECT(tdvc_rans_encode_lanes_dev_ref(z.data(), z.data(), 1, 1, 1, 96, pos, 1, 64, cdfs.data(), stride, sizes.data(), offsets.data(), ntab, sc.data(), 8, 512, out, 4096,
-                                          4096, info.data()) != 0, "L=64 with M=96 accepted");
-    EXPECT(tdvc_rans_encode_lanes_dev_ref(z.data(), z.data(), 1, 1, 1, 128, pos, 1, 64, cdfs.data(), stride, sizes.data(), offsets.data(), ntab, sc.data(), 8, 511, out, 4096,
-                                          4096, info.data()) != 0, "scratch capacity below B * L * lane_words accepted");
-    EXPECT(tdvc_rans_encode_lanes_dev_ref(z.data(), z.data(), 1, 1, 1, 128, pos, 1, 64, cdfs.data(), stride, sizes.data(), offsets.data(), ntab, sc.data(), 8, 512, out, 2048,
-                                          4096, info.data()) != 0, "output stride below the bound accepted");
+    EXPECT(twin(z.data(), z.data(), 1, 1, 1, 96, pos, 1, 64, tabs, sc.data(), 8, 512, out, 4096, 4096, info.data()) != 0, "L=64 with M=96 accepted");
+    EXPECT(twin(z.data(), z.data(), 1, 1, 1, 128, pos, 1, 64, tabs, sc.data(), 8, 511, out, 4096, 4096, info.data()) != 0, "scratch capacity below B * L * lane_words accepted");
+    EXPECT(twin(z.data(), z.data(), 1, 1, 1, 128, pos, 1, 64, tabs, sc.data(), 8, 512, out, 2048, 4096, info.data()) != 0, "output stride below the bound accepted");
     // a position outside the image and an index outside the tables: flagged, never read
     const int32_t far[2] = {3, 0};
-    EXPECT(tdvc_rans_encode_lanes_dev_ref(z.data(), z.data(), 1, 1, 1, 128, far, 1, 64, cdfs.data(), stride, sizes.data(), offsets.data(), ntab, sc.data(), 8, 512, out, 4096,
-                                          4096, info.data()) == 0 && info[1] == 2, "position outside the image: status %u", info[1]);
+    EXPECT(twin(z.data(), z.data(), 1, 1, 1, 128, far, 1, 64, tabs, sc.data(), 8, 512, out, 4096, 4096, info.data()) == 0 && info[1] == 2, "position outside the image: status %u", info[1]);
     std::vector<int32_t> wild(128, 1 << 20);
-    EXPECT(tdvc_rans_encode_lanes_dev_ref(z.data(), wild.data(), 1, 1, 1, 128, pos, 1, 64, cdfs.data(), stride, sizes.data(), offsets.data(), ntab, sc.data(), 8, 512, out, 4096,
-                                          4096, info.data()) == 0 && info[1] == 2, "index outside the tables: status %u", info[1]);
+    EXPECT(twin(z.data(), wild.data(), 1, 1, 1, 128, pos, 1, 64, tabs, sc.data(), 8, 512, out, 4096, 4096, info.data()) == 0 && info[1] == 2, "index outside the tables: status %u", info[1]);
+    EXPECT(tdvc_rans_encode_lanes_dev_ref(nullptr, &tabs) != 0 && tdvc_rans_encode_lanes_dev_ref(nullptr, nullptr) != 0, "null descriptors accepted");
     free(out);
   }
   printf(g_fail ? "%d failures\n" : "ok\n", g_fail);

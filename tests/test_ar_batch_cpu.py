@@ -85,6 +85,7 @@ class Call:
         self.B = B
         self.strings = None
         self.null = ()
+        self.null_loop = False
         self.table = None
         if driver == "tdvc_ar_wavefront_lanes_batch":
             pairs = [lane_string(64, s) for s in range(B)]
@@ -95,24 +96,31 @@ class Call:
 
     def run(self):
         lib = L.lib()
-        fm = {k: (None if k in self.null else C.byref(v)) for k, v in self.fm.items()}
+        fm = {k: L.FMapDesc.from_buffer_copy(v) for k, v in self.fm.items()}
+        for k in self.null:                                           # a null map: one whose p is NULL
+            fm[k].p = None
+        if self.B != self.fm["params"].N:                             # a bad B: the drivers read it from the maps' N
+            for k in ("y", "y_hat", "params"):
+                fm[k].N = self.B
         descs = chain_descs()
         arr = (L.ConvDesc * 4)(*descs)
         dummy = H.PB
         ss = np.ascontiguousarray(self.sizes, dtype=np.int32)
+        serial = self.driver == "tdvc_ar_decode_serial_batch"         # raster order: no step list, a step per position
+        loop = L.ArLoopDesc(fm["y_hat"], fm["params"], fm["x1"], fm["pc"], fm["gp"], arr, 4, dummy, None if serial else ss.ctypes.data,
+                            int(ss.sum()) if serial else ss.size, dummy, 64, dummy, dummy)
+        lp = None if self.null_loop else C.byref(loop)
         if self.strings is not None:
             keep, ptrs, nbytes = ops._host_strings(self.strings)
         tab = np.zeros((4, 8), dtype=np.int32)
+        host = L.CdfTablesDesc(tab.ctypes.data, tab.ctypes.data, tab.ctypes.data, 8, 4)
         if self.driver == "tdvc_ar_wavefront_batch":                  # encoder direction
-            rc = lib.tdvc_ar_wavefront_batch(None, None, self.B, None, 0, None, None, fm["y"], fm["y_hat"], fm["params"], fm["x1"], fm["pc"], arr, 4, fm["gp"],
-                                             dummy, ss.ctypes.data, ss.size, M, WG, dummy, 64, dummy, dummy, None)
-        elif self.driver == "tdvc_ar_decode_serial_batch":
-            rc = lib.tdvc_ar_decode_serial_batch(ptrs, nbytes, self.B, tab.ctypes.data, 8, tab.ctypes.data, tab.ctypes.data, fm["y_hat"], fm["params"], fm["x1"],
-                                                 fm["pc"], arr, 4, fm["gp"], dummy, int(ss.sum()), M, WG, dummy, 64, dummy, dummy, None)
+            rc = lib.tdvc_ar_wavefront_batch(lp, C.byref(fm["y"]), None, None, None, None)
+        elif serial:
+            rc = lib.tdvc_ar_decode_serial_batch(lp, ptrs, nbytes, C.byref(host), None)
         else:
-            rc = lib.tdvc_ar_wavefront_lanes_batch(ptrs, nbytes, self.B, dummy, 1 << 30, dummy, dummy, 27256 // 8 * 8, dummy, dummy, dummy, 64, fm["y_hat"],
-                                                   fm["params"], fm["x1"], fm["pc"], arr, 4, fm["gp"], dummy, ss.ctypes.data, ss.size, M, WG, dummy, 64,
-                                                   dummy, dummy, None, None)
+            dev = L.CdfTablesDevDesc(dummy, dummy, dummy, dummy, 27256 // 8 * 8, 64)
+            rc = lib.tdvc_ar_wavefront_lanes_batch(lp, ptrs, nbytes, dummy, 1 << 30, dummy, C.byref(dev), None, None)
         return rc, lib.tdvc_last_error().decode()
 
 
@@ -131,6 +139,9 @@ def test_driver_rejects_before_touching_a_device(driver, B):
         c = Call(driver, B)
         c.null = (name,)
         rejected(c, "null")
+    c = Call(driver, B)                                               # no loop descriptor at all
+    c.null_loop = True
+    rejected(c, "null")
     for bad in (0, -2):
         c = Call(driver, B)
         c.B = bad

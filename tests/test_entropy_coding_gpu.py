@@ -288,18 +288,18 @@ def test_fp32_island_bitstreams_equal_oracle(coders, H, W, report):
         m.run_h_s(z_hat, out=params)
         yh_fm = ops.FM(yh_o.permute(0, 2, 3, 1).contiguous().cuda())
         pos = torch.tensor([[h, w] for h in range(Hl) for w in range(Wl)], dtype=torch.int32, device="cuda")
-        chain = m._ar_chain(npos, torch.float32, "cuda")
-        ops.ar_gather_batch(yh_fm, params, pos, npos, chain["x1"], chain["pc"])
+        chain = m._ar_chain(npos, torch.float32, "cuda", pos)
+        ops.ar_gather_batch(yh_fm, params, pos, npos, chain.x1, chain.pc)
         import ctypes as C
-        for dsc in chain["descs"]:
+        for dsc in chain.descs:
             ops.L.check(ops.L.lib().tdvc_conv2d(C.byref(dsc), ops._stream()), "conv2d")
         table = m._coder_tables()[2]
         sym_t = torch.zeros((Hl, Wl, M), dtype=torch.int32, device="cuda")
         idx_t = torch.zeros((Hl, Wl, M), dtype=torch.int32, device="cuda")
         yh_t = ops.FM.zeros(1, Hl, Wl, M, dtype=torch.float32, device="cuda")
-        ops.ar_quantize_batch(y32, chain["gp"], pos, npos, table, yh_t, sym_t, idx_t)
+        ops.ar_quantize_batch(y32, chain.gp, pos, npos, table, yh_t, sym_t, idx_t)
         sym_t, idx_t = sym_t.cpu().view(-1), idx_t.cpu().view(-1)
-        gp = chain["gp"].t.view(-1, 2 * M)[:npos].cpu()
+        gp = chain.gp.t.view(-1, 2 * M)[:npos].cpu()
         bad = (sym_t != sym_o).nonzero().view(-1)
         dists = ((y_o[bad] - mean_o[bad] - sym_o[bad].float()).abs() - 0.5).abs()
         badi = (idx_t != idx_o).nonzero().view(-1)

@@ -34,6 +34,11 @@ def test_struct_sizes_match_header_layout():
     assert C.sizeof(L.FMapDesc) == 40
     # ConvDesc: 2 fmaps, 2 ptrs, 2 ints, 98 bytes of taps (+2 pad), 7 ints, fmap, int, float, int, 2 fmaps, int
     assert C.sizeof(L.ConvDesc) % 8 == 0 and C.sizeof(L.ConvDesc) >= 5 * 40 + 16 + 98
+    # the context loop's descriptors (ABI 13): size and offset of the last member, the numbers csrc/lib.cpp static_asserts on the header
+    for struct, size, last, off in ((L.CdfTablesDesc, 32, "ncdfs", 28), (L.CdfTablesDevDesc, 40, "ncdfs", 36), (L.ArLoopDesc, 272, "sym_dev", 264),
+                                    (L.LanesEncDesc, 104, "info", 96)):
+        assert C.sizeof(struct) == size and struct._fields_[-1][0] == last and getattr(struct, last).offset == off, struct.__name__
+    assert L.ArLoopDesc.convs.offset == 5 * C.sizeof(L.FMapDesc) and L.lib().tdvc_abi_version() >= 13
 
 
 def test_conv_plan_and_errors():

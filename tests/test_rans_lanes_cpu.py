@@ -4,6 +4,7 @@ The host decoder runs the decode-one-symbol routine of csrc/rans_lane.h, which i
 thread, so these tests exercise the kernel's logic: container layout, byte equality of every lane with the oracle's python
 coder, equivalence of the O(log n) bin search with the single-stream decoder's linear scan, damaged streams, and a
 sanitizer run of a stand-alone program (tests/rans_lanes_main.cpp; host compilation only, nothing sanitised is loaded here)."""
+import ctypes as C
 import os
 import shutil
 import subprocess
@@ -171,8 +172,8 @@ def test_abi_version_covers_the_lane_entry_points():
     assert lib.tdvc_ar_lanes_state_bytes(64) == 4 * (4 * 64 + 1)
     # the device entry points validate before they touch the GPU
     assert lib.tdvc_ar_lanes_init_batch(None, 0, None, 1, 64, None, None) != 0
-    assert lib.tdvc_ar_wavefront_lanes_batch(None, None, 1, None, 0, None, None, 0, None, None, None, 0, None, None, None, None, None, 0, None, None, None, 0,
-                                             0, 0, None, 0, None, None, None, None) != 0
+    assert lib.tdvc_ar_wavefront_lanes_batch(None, None, None, None, 0, None, None, None, None) != 0
+    assert lib.tdvc_ar_wavefront_lanes_batch(C.byref(L.ArLoopDesc()), None, None, None, 0, None, None, None, None) != 0
 
 
 def test_standalone_program_under_address_and_ub_sanitizers(tmp_path):

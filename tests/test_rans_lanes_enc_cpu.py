@@ -6,6 +6,7 @@ assembly, so these tests exercise ar_encode_lanes_batch_kernel's logic: byte equ
 extreme bypass symbols, a table whose last bin ends at 1 << 16, a lane above the length table's limit, a scratch region that
 is too small (bounded writes: canaries), argument checks, and a sanitizer run of a stand-alone program
 (tests/rans_lanes_enc_main.cpp; host compilation only, nothing sanitised is loaded here)."""
+import ctypes as C
 import os
 import shutil
 import subprocess
@@ -183,9 +184,10 @@ def test_scratch_too_small_is_status_2_and_no_write_leaves_a_region(tables):
     o0 = (-outbuf.ctypes.data) % 16
     out = outbuf[o0:o0 + B * stride]
     info = np.full((B, 2), 0xFFFFFFFF, dtype=np.uint32)
-    rc = lib.tdvc_rans_encode_lanes_dev_ref(sym.ctypes.data, idx.ctypes.data, B, H, W, M, pos.ctypes.data, len(pos), lanes, tables.cdf.ctypes.data, tables.stride,
-                                            tables.sizes.ctypes.data, tables.offsets.ctypes.data, len(tables.sizes), scratch.ctypes.data, words, B * lanes * words,
-                                            out.ctypes.data, stride, B * stride, info.ctypes.data)
+    enc = L.LanesEncDesc(sym.ctypes.data, idx.ctypes.data, B, H, W, M, pos.ctypes.data, len(pos), lanes, scratch.ctypes.data, words, B * lanes * words,
+                         out.ctypes.data, stride, B * stride, info.ctypes.data)
+    tabs = L.CdfTablesDesc(tables.cdf.ctypes.data, tables.sizes.ctypes.data, tables.offsets.ctypes.data, tables.stride, len(tables.sizes))
+    rc = lib.tdvc_rans_encode_lanes_dev_ref(C.byref(enc), C.byref(tabs))
     assert rc == 0
     assert info.tolist() == [[0, 2]] * B
     assert (scratch[B * lanes * words:] == CANARY).all()
@@ -223,8 +225,8 @@ def test_bad_arguments_abi_and_the_scratch_helper(tables):
 
     def call(sym=p, idx=p, B=1, H=1, W=1, m=128, pos=p, npos=1, lanes=64, cdf16=p, n16=8, starts=p, sizes=p, offsets=p, ncdfs=1, scratch=p, lane_words=words,
              scratch_cap=64 * words, out=p, out_stride=stride, out_cap=stride, info=p):
-        return lib.tdvc_ar_encode_lanes_batch(sym, idx, B, H, W, m, pos, npos, lanes, cdf16, n16, starts, sizes, offsets, ncdfs, scratch, lane_words, scratch_cap,
-                                              out, out_stride, out_cap, info, None)
+        enc = L.LanesEncDesc(sym, idx, B, H, W, m, pos, npos, lanes, scratch, lane_words, scratch_cap, out, out_stride, out_cap, info)
+        return lib.tdvc_ar_encode_lanes_batch(C.byref(enc), C.byref(L.CdfTablesDevDesc(cdf16, starts, sizes, offsets, n16, ncdfs)), None)
     bad = [dict(sym=None), dict(idx=None), dict(pos=None), dict(cdf16=None), dict(starts=None), dict(sizes=None), dict(offsets=None), dict(scratch=None),
            dict(out=None), dict(info=None), dict(B=0), dict(H=0), dict(npos=0), dict(lanes=32), dict(lanes=96), dict(m=192, lanes=128), dict(ncdfs=0),
            dict(ncdfs=65), dict(lane_words=1), dict(lane_words=65537), dict(scratch_cap=64 * words - 1), dict(out_stride=stride - 16), dict(out_stride=stride + 4),
@@ -232,6 +234,9 @@ def test_bad_arguments_abi_and_the_scratch_helper(tables):
     for kw in bad:
         assert call(**kw) != 0, f"{kw} was accepted"
         assert b"tdvc_ar_encode_lanes_batch" in lib.tdvc_last_error()
+    tabs = C.byref(L.CdfTablesDevDesc(p, p, p, p, 8, 1))
+    for enc, t in ((None, tabs), (C.byref(L.LanesEncDesc()), None)):              # no descriptor at all
+        assert lib.tdvc_ar_encode_lanes_batch(enc, t, None) != 0 and b"tdvc_ar_encode_lanes_batch" in lib.tdvc_last_error()
     from tdvc_amd import ops
     with pytest.raises(L.TdvcHipError):
         ops.rans_encode_lanes_dev_ref(np.zeros((1, 1, 1, 96), np.int32), np.zeros((1, 1, 1, 96), np.int32), np.zeros((1, 2), np.int32), tables, 64)

@@ -53,12 +53,12 @@ with torch.no_grad():
         steps = c.wavefront_steps(Hl, Wl)
         flat = torch.tensor([p for st in steps for p in st], dtype=torch.int32, device="cuda")
         sizes = np.array([len(st) for st in steps], dtype=np.int32)
-        chain = c._ar_chain(Hl, torch.float16, "cuda")
+        loop = c._ar_chain(Hl, torch.float16, "cuda", flat, sizes)
         y_hat = ops.FM.zeros(1, Hl, Wl, 128, device="cuda")
         sym = torch.zeros((Hl, Wl, 128), dtype=torch.int32, device="cuda")
         idx = torch.zeros((Hl, Wl, 128), dtype=torch.int32, device="cuda")
         sync(); t4 = time.time()
-        ops.ar_wavefront_batch(None, None, y32, y_hat, params, chain["x1"], chain["pc"], chain["descs"], chain["gp"], flat, sizes, 128, Wl, table, idx, sym)
+        ops.ar_wavefront_batch(loop, None, None, y32, y_hat, params, table, idx, sym)
         t5h = time.time()
         sync(); t5 = time.time()
         s_np, i_np = sym.cpu().numpy(), idx.cpu().numpy()
