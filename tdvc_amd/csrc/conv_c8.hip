@@ -147,7 +147,6 @@ bool conv_c8_eligible(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int 
 
 int launch_conv_c8(const ConvParams& p, int N, hipStream_t st) {
   ConvParams q = p;
-  q.slope = convk::conv_simple_slope(p);
   q.pred = tdvc_launch_predicate();
   const int tiles_x = (p.Wo + 31) / 32;
   const long total = (long)N * p.Ho * tiles_x;

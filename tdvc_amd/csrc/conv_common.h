@@ -14,7 +14,7 @@ struct ConvParams {
   int nchunks, steps;   // steps per chunk
   int square, gdn, act; float slope; int round16, out_mode;
   int tiles_x;
-  int simple;           // host decision: transposed fast epilogue (conv_is_simple)
+  int simple;           // host decision (tdvc_conv2d): 0 per-register epilogue4, 1 transposed generic epilogue, 2 its lean form; 1, 2: slope is folded
   int s2d, Corig;       // space-to-depth view of a stride-2 conv (v3 only): Corig = channels per parity
   int reverse;          // walk the tile raster backwards (alternate launches: see tdvc_conv2d, "Infinity Cache")
   int bcast_T; float bcast_slope;   // conv_mfma_v5 only: y[:, t] = lrelu(y[:, t] + conv) over bcast_T slices (tdvc_conv_desc::bcast_T)
@@ -159,6 +159,63 @@ __device__ __forceinline__ void epilogue4(const ConvParams& p, int n, int oy, in
   }
 }
 
+// The per-register fallback over epilogue4 of the tiled kernels (direct, v2, v5: every form the transposed epilogues do not
+// take): a lane's 16 accumulators of tile (mt, nt) are 4 groups of 4 consecutive channels of ONE pixel, column nt's being pixel
+// ox of row oy_first + nt of image n.  `ct0` = the wave's first 32-channel tile.  ConvParams BY VALUE: behind a second level of
+// references hipcc re-reads its fields from the kernel arguments at every use (direct kernel <1, 1, 1>: 13 -> 168 scalar loads,
+// 5465 -> 6347 instructions).  conv_f32 keeps a loop of its own (a pixel per column, fp32 maps), v3 too (see there).
+template <int MT, int NT>
+__device__ __forceinline__ void epilogue_regs(const ConvParams p, const f32x16 (&acc)[MT][NT], int n, int oy_first, int ox, int ct0, int hh) {
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int oy = oy_first + nt;
+    if (oy >= p.Ho || ox >= p.Wo) continue;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = acc[mt][nt][4 * g + i];
+        epilogue4(p, n, oy, ox, (ct0 + mt) * 32 + 8 * g + 4 * hh, v);
+      }
+  }
+}
+
+template <int M, int N>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[M][N]) {
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
+}
+
+// One tap of a 32-channel chunk for a wave of the register-staged kernels (v2, v3, v5): 64 output channels x NT x 32 pixels, two
+// k-steps.  `wslot` = the (chunk, tap) weight slice in fragment order (4 x 1 KiB: [mt * 2 + s2]) at this lane's 16 bytes, `tile`
+// the staged tile with base[nt] = the lane's pixel of column nt (+ 16 bytes for the upper half wave), `toff` the tap's offset in it.
+template <int NT>
+__device__ __forceinline__ void mma_tap(f32x16 (&acc)[2][NT], const unsigned char* wslot, const unsigned char* tile, const int (&base)[NT], int toff) {
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    half8 a[2], b[NT];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) a[mt] = *reinterpret_cast<const half8*>(wslot + (mt * 2 + s2) * 1024);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) b[nt] = *reinterpret_cast<const half8*>(tile + base[nt] + toff + s2 * 32);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
+  }
+}
+
+// The tile of a one-tile-per-workgroup launch (direct kernel, v2); alternate launches walk the raster backwards (ConvParams::reverse)
+__device__ __forceinline__ int block_tile(const ConvParams& p) {
+  return p.reverse ? (int)gridDim.x - 1 - tdvc_xcd_tile(blockIdx.x) : tdvc_xcd_tile(blockIdx.x);
+}
+
 // XCD-aware tile walk of the persistent kernels (v3, v5, v7, v10, v11).  Workgroups are dispatched round-robin over the 8 XCDs, each
 // with its own L2, so workgroup x of a launch runs on XCD x % 8.  The raster of tiles is cut into 8 contiguous bands,
 // one per XCD, and a workgroup walks its XCD's band with the stride of that XCD's workgroup count: neighbouring tiles
@@ -201,6 +258,10 @@ inline bool conv_is_simple(const ConvParams& p) {
 inline float conv_simple_slope(const ConvParams& p) {
   return p.act == TDVC_ACT_NONE ? 1.f : (p.act == TDVC_ACT_RELU ? 0.f : p.slope);
 }
+// tdvc_conv2d decides the form ONCE (prepare() in conv_dispatch.hip): ConvParams::simple = 0 (epilogue4) / 1 (transposed generic) /
+// 2 (transposed lean) and, for 1 and 2, ConvParams::slope folded by conv_simple_slope.  The launchers only pick what was decided.
+template <typename F>
+inline F by_form(int simple, F e4, F generic, F lean) { return simple == 2 ? lean : (simple == 1 ? generic : e4); }
 
 // Transposed "simple" epilogue shared by every conv kernel (v1 .. v7): fp16 NHWC output (optionally through
 // PixelShuffle(2)), bias, none / ReLU / LeakyReLU via a slope select, GDN / inverse GDN

@@ -193,7 +193,7 @@ struct HaloExtra {
   const half_t* zeros;      // >= 16 bytes of zeros: the DMA source of out-of-image halo pixels
 };
 
-// What the launchers of the three kernels share: q = p with tiles_x and the epilogue slope, e.ntiles / e.zeros, and the persistent
+// What the launchers of the three kernels share: q = p with tiles_x, e.ntiles / e.zeros, and the persistent
 // grid (256 workgroup slots).  Returns 0 or the error of the zeros page.
 template <typename Extra>
 inline int halo_launch_setup(const ConvParams& p, int cout_blocks, int N, ConvParams& q, Extra& e, dim3& grid) {
@@ -203,7 +203,6 @@ inline int halo_launch_setup(const ConvParams& p, int cout_blocks, int N, ConvPa
   q.tiles_x = (p.Wo + HALO_TW - 1) / HALO_TW;
   e.ntiles = q.tiles_x * ((p.Ho + HALO_TH - 1) / HALO_TH);
   e.zeros = reinterpret_cast<const half_t*>(zeros);
-  q.slope = conv_simple_slope(p);
   grid = dim3(persistent_grid_x(256, cout_blocks, N, e.ntiles), cout_blocks, N);
   return 0;
 }

@@ -74,12 +74,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(const ConvParams p, const
   const float* wp = e.w + ((long)ct0 * T) * 512 + lane * 8;      // tile ct0 + mt: + mt * T * 512
 
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
+  convk::zero_acc(acc);
 
   // software pipeline over k-steps: the operand fragments of step g + 1 (MT + NT loads of 32 bytes per lane) are ISSUED before
   // the 8 * MT * NT MFMAs of step g and consumed after them.  fetch() only issues loads and derives the zeroing multiplier; every

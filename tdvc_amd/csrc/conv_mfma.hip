@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256, LEAN ? 3 : 1) void conv_mfma_kernel(const Conv
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, r = lane & 31;
-  const int tile_id = p.reverse ? (int)gridDim.x - 1 - tdvc_xcd_tile(blockIdx.x) : tdvc_xcd_tile(blockIdx.x);
+  const int tile_id = convk::block_tile(p);
   const int tx = tile_id % p.tiles_x, ty = tile_id / p.tiles_x;
   const int cb = blockIdx.y, n = blockIdx.z;
 
@@ -55,12 +55,7 @@ __global__ __launch_bounds__(256, LEAN ? 3 : 1) void conv_mfma_kernel(const Conv
   for (int nt = 0; nt < 2; ++nt) base[nt] = (((wave * 2 + nt) * STRIDE) * TIWp + r) * PS;
 
   f32x16 acc[MT][2];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
+  convk::zero_acc(acc);
 
   const half_t* xn = p.x + (long)n * p.x_sn;
   const int iy0 = ty * TH * STRIDE - p.pad, ix0 = tx * TW * STRIDE - p.pad;
@@ -141,23 +136,7 @@ __global__ __launch_bounds__(256, LEAN ? 3 : 1) void conv_mfma_kernel(const Conv
       return;
     }
   }
-  const int ox = tx * TW + r;
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int oy = ty * TH + wave * 2 + nt;
-    if (oy >= p.Ho || ox >= p.Wo) continue;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int co = (cb * MT + mt) * 32 + 8 * g + 4 * hh;   // 4 consecutive channels co..co+3
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = acc[mt][nt][4 * g + i];
-        convk::epilogue4(p, n, oy, ox, co, v);
-      }
-    }
-  }
+  convk::epilogue_regs(p, acc, n, ty * TH + wave * 2, tx * TW + r, cb * MT, hh);
 }
 
 template <int CK8, int MT, int STRIDE>

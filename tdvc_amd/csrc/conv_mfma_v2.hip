@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v2_kernel(const ConvParams p
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, r = lane & 31;
-  const int tile_id = p.reverse ? (int)gridDim.x - 1 - tdvc_xcd_tile(blockIdx.x) : tdvc_xcd_tile(blockIdx.x);
+  const int tile_id = convk::block_tile(p);
   const int tx = tile_id % p.tiles_x, ty = tile_id / p.tiles_x;
   const int cb = blockIdx.y, n = blockIdx.z;
   const int TIW = TW2 + p.kw - 1;
@@ -71,12 +71,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v2_kernel(const ConvParams p
   for (int nt = 0; nt < NT; ++nt) base[nt] = ((wave * NT + nt) * TIW + r) * PS + hh * 16;
 
   f32x16 acc[2][NT];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
+  convk::zero_acc(acc);
 
   int T = 0;
   for (int ch = 0; ch < nchunks; ++ch) {
@@ -98,21 +93,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v2_kernel(const ConvParams p
       *reinterpret_cast<half8*>(wring + ((T + 1) & 1) * WSLICE + tid * 16) = wreg;
       wreg = *reinterpret_cast<const half8*>(wsrc(T + 2));
       // (c) matrix work of tap t
-      const unsigned char* wslot = wring + (T & 1) * WSLICE + lane * 16;
-      const int toff = tapoff[t];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        half8 a[2], b[NT];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) a[mt] = *reinterpret_cast<const half8*>(wslot + (mt * 2 + s2) * 1024);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) b[nt] = *reinterpret_cast<const half8*>(tbuf + base[nt] + toff + s2 * 32);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt)
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
-      }
+      convk::mma_tap(acc, wring + (T & 1) * WSLICE + lane * 16, tbuf, base, tapoff[t]);
       // (d) everyone is done with tap t's slot (and, after the last tap, with the tile)
       __syncthreads();
     }
@@ -127,22 +108,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v2_kernel(const ConvParams p
     convk::epilogue_simple_rows<NT, false, SIMPLE>(p, acc, p.bias + cb * 64, tbuf + wave * (32 * 144), n, cb * 64,
                                      ty * TH2 + wave * NT, tx * TW2, lane, false);
   } else {
-    const int ox = tx * TW2 + r;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int oy = ty * TH2 + wave * NT + nt;
-      if (oy >= p.Ho || ox >= p.Wo) continue;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          float v[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = acc[mt][nt][4 * g + i];
-          convk::epilogue4(p, n, oy, ox, (cb * 2 + mt) * 32 + 8 * g + 4 * hh, v);
-        }
-      }
-    }
+    convk::epilogue_regs(p, acc, n, ty * TH2 + wave * NT, tx * TW2 + r, cb * 2, hh);
   }
   if constexpr (STAMP) {
     __builtin_amdgcn_s_waitcnt(0);
@@ -155,6 +121,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v2_kernel(const ConvParams p
 }
 
 inline int v2_lds_bytes(int kh, int kw) { return 256 + 2 * WSLICE + (TH2 + kh - 1) * (TW2 + kw - 1) * PS; }
+
+template <int SIMPLE, bool STAMP = false>
+constexpr auto launch_v2 = convk::launch_big_lds<&conv_mfma_v2_kernel<SIMPLE, STAMP>, ConvParams, long long*, int>;
 
 }  // namespace
 
@@ -170,14 +139,8 @@ int launch_conv_v2(const ConvParams& p, int cout_blocks, int N, hipStream_t st) 
   q.tiles_x = (p.Wo + TW2 - 1) / TW2;
   const int tiles_y = (p.Ho + TH2 - 1) / TH2;
   const int lds = v2_lds_bytes(p.kh, p.kw);
-  // compact epilogue when the layer is the common case: fp16 NHWC out, bias, none/ReLU/LeakyReLU, fp16 residuals
-  const bool simple = convk::conv_is_simple(p);
-  if (simple) q.slope = convk::conv_simple_slope(p);
   dim3 grid(q.tiles_x * tiles_y, cout_blocks, N);
-  const bool stamp = g_stamp_buf && simple;
-  const auto go = stamp ? convk::launch_big_lds<&conv_mfma_v2_kernel<1, true>, ConvParams, long long*, int>
-                  : simple ? (convk::conv_is_lean(p) ? convk::launch_big_lds<&conv_mfma_v2_kernel<2>, ConvParams, long long*, int>
-                                                     : convk::launch_big_lds<&conv_mfma_v2_kernel<1>, ConvParams, long long*, int>)
-                           : convk::launch_big_lds<&conv_mfma_v2_kernel<0>, ConvParams, long long*, int>;
+  const bool stamp = g_stamp_buf && p.simple;
+  const auto go = stamp ? launch_v2<1, true> : convk::by_form(p.simple, launch_v2<0>, launch_v2<1>, launch_v2<2>);
   return go("tdvc_conv2d(v2)", 80 * 1024, grid, dim3(256), lds, st, q, stamp ? g_stamp_buf : nullptr, stamp ? g_stamp_cap : 0);
 }

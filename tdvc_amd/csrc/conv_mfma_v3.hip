@@ -107,6 +107,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v3_kernel(const ConvParams p
 #pragma unroll
   for (int nt = 0; nt < NT3; ++nt) base[nt] = ((wave * NT3 + nt) * TIW + r) * PS3 + hh * 16;
 
+  // spelled out where the other kernels call convk::zero_acc: with the call the <2> instantiation is scheduled differently
+  // (28 instead of 30 vector-memory waits; profiles/r14_conv_reg_shared.txt)
   f32x16 acc[2][NT3];
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
@@ -148,21 +150,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v3_kernel(const ConvParams p
     }
     for (int t = 0; t < ntaps; ++t) {
       if (!((tapmask >> t) & 1u)) continue;
-      const unsigned char* wslot = wlds + t * WSL + lane * 16;
-      const int toff = tapoff[t];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        half8 a[2], b[NT3];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) a[mt] = *reinterpret_cast<const half8*>(wslot + (mt * 2 + s2) * 1024);
-#pragma unroll
-        for (int nt = 0; nt < NT3; ++nt) b[nt] = *reinterpret_cast<const half8*>(tbuf + base[nt] + toff + s2 * 32);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NT3; ++nt)
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
-      }
+      convk::mma_tap(acc, wlds + t * WSL + lane * 16, tbuf, base, tapoff[t]);
     }
 
     ST3(5);
@@ -181,6 +169,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v3_kernel(const ConvParams p
       convk::epilogue_simple_rows<NT3, false, SIMPLE>(p, acc, bias_s, tbuf + wave * (32 * 144), n, cb * 64,
                                        ty * TH3 + wave * NT3, tx * TW3, lane, true);
     } else {
+      // spelled out where the other kernels call convk::epilogue_regs: with the call this instantiation, at 256 VGPRs and
+      // 106 SGPRs, spills one more scalar register (133 -> 134)
       const int ox = tx * TW3 + r;
 #pragma unroll
       for (int nt = 0; nt < NT3; ++nt) {
@@ -204,6 +194,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_v3_kernel(const ConvParams p
 inline int v3_tile_bytes(int kh, int kw) { return (TH3 + kh - 1) * (TW3 + kw - 1) * PS3; }
 inline int v3_lds_bytes(int kh, int kw, int ntaps) { return 512 + v3_tile_bytes(kh, kw) + ntaps * WSL; }
 
+template <int SIMPLE, bool STAMP = false>
+constexpr auto launch_v3 = convk::launch_big_lds<&conv_mfma_v3_kernel<SIMPLE, STAMP>, ConvParams, V3Extra, long long*, int>;
+
 }  // namespace
 
 extern "C" void tdvc_debug_set_stamp_buffer_v3(void* buf, int cap_blocks) { g_stamp3 = (long long*)buf; g_stamp3_cap = cap_blocks; }
@@ -222,14 +215,9 @@ int launch_conv_v3(const ConvParams& p, int cout_blocks, int N, hipStream_t st) 
   e.ntiles = q.tiles_x * tiles_y;
   e.tile_bytes = v3_tile_bytes(p.kh, p.kw);
   const int lds = v3_lds_bytes(p.kh, p.kw, p.ntaps);
-  const bool simple = convk::conv_is_simple(p);
-  if (simple) q.slope = convk::conv_simple_slope(p);
   // persistent grid: two workgroups per CU over all (cout block, image) pairs
   dim3 grid(convk::persistent_grid_x(512, cout_blocks, N, e.ntiles), cout_blocks, N);
-  const bool stamp = g_stamp3 && simple;
-  const auto go = stamp ? convk::launch_big_lds<&conv_mfma_v3_kernel<1, true>, ConvParams, V3Extra, long long*, int>
-                  : simple ? (convk::conv_is_lean(p) ? convk::launch_big_lds<&conv_mfma_v3_kernel<2>, ConvParams, V3Extra, long long*, int>
-                                                     : convk::launch_big_lds<&conv_mfma_v3_kernel<1>, ConvParams, V3Extra, long long*, int>)
-                           : convk::launch_big_lds<&conv_mfma_v3_kernel<0>, ConvParams, V3Extra, long long*, int>;
+  const bool stamp = g_stamp3 && p.simple;
+  const auto go = stamp ? launch_v3<1, true> : convk::by_form(p.simple, launch_v3<0>, launch_v3<1>, launch_v3<2>);
   return go("tdvc_conv2d(v3)", 80 * 1024, grid, dim3(256), lds, st, q, e, stamp ? g_stamp3 : nullptr, stamp ? g_stamp3_cap : 0);
 }

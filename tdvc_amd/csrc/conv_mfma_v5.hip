@@ -10,6 +10,9 @@
 // algorithmic (0.57 of HBM peak) for the same layer.
 // (The same scheme was tried for 3x3 windows — each wave loading its own 4-row halo — and measured 20 %
 // SLOWER than a shared tile, so v5 only takes 1x1; 3x3 is conv_mfma_v7.)
+// A 1x1 window makes the staging geometry a constant: the wave's tile is 2 x 32 pixels x 4 chunks of 16 bytes = 256 items,
+// four per lane; item j * 64 + lane is chunk idx & 3 of pixel idx >> 2, and every tap reads the tile at offset 0 (a descriptor
+// may still list (0, 0) more than once: one weight slice per listed tap).
 #include <type_traits>
 
 #include "conv_common.h"
@@ -22,35 +25,29 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WR = 2, TW5 = 32, CK5 = 32, PS5 = 80, NTHR5 = 512, NWAVE = 8;
 constexpr int WSL5 = 4096;
+constexpr int TL = WR * TW5 * 4 / 64;        // 16-byte loads per lane per stage
+constexpr int WTILE5 = WR * TW5 * PS5;       // private LDS bytes per wave; also the epilogue's transpose scratch
+static_assert(WTILE5 >= 32 * 144, "the wave's tile doubles as the 32 x 144 B transpose scratch");
 
-struct V5Extra {
-  int nbtiles;        // workgroup tiles (16 x 32 output pixels = 8 wave tiles)
-  int wtile_bytes;    // private LDS bytes per wave
-};
-
-// TL = 16-byte loads per lane per stage: 4 for 1x1 (2 x 32 pixels x 4 chunks / 64 lanes)
-template <int SIMPLE, int TL>      // SIMPLE 0: per-register epilogue4, 1: transposed generic, 2: transposed lean, 4: lean + broadcast add, 5: lean + flow add
-__global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams p, const V5Extra e) {
+// nbtiles: workgroup tiles (16 x 32 output pixels = 8 wave tiles)
+template <int SIMPLE>      // 0: per-register epilogue4, 1: transposed generic, 2: transposed lean, 4: lean + broadcast add, 5: lean + flow add
+__global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams p, const int nbtiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int* tapoff = reinterpret_cast<int*>(smem);
-  float* bias_s = reinterpret_cast<float*>(smem + 256);
+  float* bias_s = reinterpret_cast<float*>(smem + 256);               // (the first 256 bytes held tap offsets: all zero for 1x1; the map stays)
   unsigned char* wlds = smem + 512;                                   // nchunks x ntaps x 4 KB, shared, read-only
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned char* tbuf = wlds + p.nchunks * p.ntaps * WSL5 + wave * e.wtile_bytes;   // this wave's private tile
+  unsigned char* tbuf = wlds + p.nchunks * p.ntaps * WSL5 + wave * WTILE5;   // this wave's private tile
 
   const int hh = lane >> 5, r = lane & 31;
   const int cb = blockIdx.y, n = blockIdx.z;
-  const int TIW = TW5 + p.kw - 1, TIH = WR + p.kh - 1;
-  const int total_items = TIH * TIW * 4;
   const int ntaps = p.ntaps, nchunks = p.nchunks;
 
   const int first = blockIdx.x, stride = gridDim.x;
-  const int my_tiles = (e.nbtiles - first + stride - 1) / stride;
+  const int my_tiles = (nbtiles - first + stride - 1) / stride;
   const int nstages = my_tiles * nchunks;
   if (nstages <= 0) return;
 
   if (tid < 64) bias_s[tid] = p.bias ? p.bias[blockIdx.y * 64 + tid] : 0.f;
-  if (tid < ntaps) tapoff[tid] = (p.tap_dy[tid] * TIW + p.tap_dx[tid]) * PS5;
   {
     const int nslices = nchunks * ntaps;
     for (int i = tid; i < nslices * 256; i += NTHR5) {
@@ -60,19 +57,9 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
       *reinterpret_cast<half8*>(wlds + sl * WSL5 + u * 16) = *reinterpret_cast<const half8*>(src);
     }
   }
-  __syncthreads();          // the only barrier: weights, bias and tap offsets are visible
+  __syncthreads();          // the only barrier: weights and bias are visible
 
-  // ---- per-lane constant staging geometry (items of the wave's private tile) ----------------------
-  int it_rr[TL], it_c[TL], it_dst[TL];
-#pragma unroll
-  for (int j = 0; j < TL; ++j) {
-    const int idx = j * 64 + lane;
-    const int c8 = idx & 3, pix = idx >> 2;
-    it_rr[j] = pix / TIW;
-    it_c[j] = pix - it_rr[j] * TIW;
-    it_dst[j] = idx < total_items ? pix * PS5 + c8 * 16 : -1;
-  }
-  const int c8off = (lane & 3) * 8;
+  const int c8off = (lane & 3) * 8;            // item idx = j * 64 + lane: chunk idx & 3 (= lane & 3) of pixel idx >> 2 of the 2 x 32 tile
   const half_t* xn = p.x + (long)n * p.x_sn;
 
   u32x4 treg[2][TL];
@@ -80,7 +67,7 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
   auto issue = [&](auto setc, int S) {
     constexpr int SET = decltype(setc)::value;
     const int tile_i = S / nchunks, ch = S - tile_i * nchunks;
-    const int tile = convk::walk_tile(p, e.nbtiles, first, stride, tile_i);
+    const int tile = convk::walk_tile(p, nbtiles, first, stride, tile_i);
     const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
     const int iy0 = ty * (WR * NWAVE) + wave * WR - p.pad, ix0 = tx * TW5 - p.pad;
     const int cg = ch * CK5 + c8off;
@@ -89,7 +76,8 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
     unsigned m = 0;
 #pragma unroll
     for (int j = 0; j < TL; ++j) {
-      const int iy = (iy0 + it_rr[j]) * p.in_stride, ix = (ix0 + it_c[j]) * p.in_stride;    // in_stride > 1 only for 1x1, pad 0
+      const int pix = (j * 64 + lane) >> 2;
+      const int iy = (iy0 + pix / TW5) * p.in_stride, ix = (ix0 + pix % TW5) * p.in_stride;    // in_stride > 1 only with pad 0
       const bool ok = cok && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       const int iyc = min(max(iy, 0), p.H - 1), ixc = min(max(ix, 0), p.W - 1);
       const half_t* src = xn + ((long)iyc * p.W + ixc) * p.x_sp + cgc;
@@ -103,15 +91,10 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
 
   int base[WR];
 #pragma unroll
-  for (int nt = 0; nt < WR; ++nt) base[nt] = (nt * TIW + r) * PS5 + hh * 16;
+  for (int nt = 0; nt < WR; ++nt) base[nt] = (nt * TW5 + r) * PS5 + hh * 16;
 
   f32x16 acc[2][WR];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < WR; ++nt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
+  convk::zero_acc(acc);
 
   float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // tdvc_conv_desc::chan_sum: this lane's channels 8 (lane & 7) .. + 8 over the pixels it stored
   issue(I0{}, 0);
@@ -130,30 +113,15 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
         hv = hv * hv;
         val = __builtin_bit_cast(u32x4, hv);
       }
-      if (it_dst[j] >= 0) *reinterpret_cast<u32x4*>(tbuf + it_dst[j]) = val;
+      const int idx = j * 64 + lane;
+      *reinterpret_cast<u32x4*>(tbuf + (idx >> 2) * PS5 + (idx & 3) * 16) = val;
     }
 
     const unsigned char* wch = wlds + ch * ntaps * WSL5 + lane * 16;
-    for (int t = 0; t < ntaps; ++t) {
-      const unsigned char* wslot = wch + t * WSL5;
-      const int toff = tapoff[t];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        half8 a[2], b[WR];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) a[mt] = *reinterpret_cast<const half8*>(wslot + (mt * 2 + s2) * 1024);
-#pragma unroll
-        for (int nt = 0; nt < WR; ++nt) b[nt] = *reinterpret_cast<const half8*>(tbuf + base[nt] + toff + s2 * 32);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < WR; ++nt)
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
-      }
-    }
+    for (int t = 0; t < ntaps; ++t) convk::mma_tap(acc, wch + t * WSL5, tbuf, base, 0);
 
     if (ch == nchunks - 1) {
-      const int tile = convk::walk_tile(p, e.nbtiles, first, stride, tile_i);
+      const int tile = convk::walk_tile(p, nbtiles, first, stride, tile_i);
       const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
       const int oy0 = ty * (WR * NWAVE) + wave * WR;
       if constexpr (SIMPLE == 4) {
@@ -169,22 +137,8 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
         if (SIMPLE == 2 && p.csum) convk::epilogue_lean_seq<WR, false, false, true>(p, acc, bias_s, tbuf, n, cb * 64, oy0, tx * TW5, lane, true, false, cs);
         else convk::epilogue_simple_rows<WR, false, SIMPLE>(p, acc, bias_s, tbuf, n, cb * 64, oy0, tx * TW5, lane, true);
       } else {
-        const int ox = tx * TW5 + r;
-#pragma unroll
-        for (int nt = 0; nt < WR; ++nt) {
-          const int oy = oy0 + nt;
-          const bool ok = oy < p.Ho && ox < p.Wo;
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              float v[4];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) { v[i] = acc[mt][nt][4 * g + i]; acc[mt][nt][4 * g + i] = 0.f; }
-              if (ok) convk::epilogue4(p, n, oy, ox, (cb * 2 + mt) * 32 + 8 * g + 4 * hh, v);
-            }
-          }
-        }
+        convk::epilogue_regs(p, acc, n, oy0, tx * TW5 + r, cb * 2, hh);
+        convk::zero_acc(acc);               // the next tile accumulates into the same registers
       }
     }
     if (S + 2 < nstages) issue(setc, S + 2);          // last vector-memory work of the stage
@@ -209,32 +163,19 @@ __global__ __launch_bounds__(NTHR5, 1) void conv_mfma_v5_kernel(const ConvParams
   }
 }
 
-inline int v5_wtile_bytes(int kh, int kw) {
-  const int b = (WR + kh - 1) * (TW5 + kw - 1) * PS5;
-  return b < 32 * 144 ? 32 * 144 : b;               // also the epilogue's transpose scratch
-}
-inline int v5_lds_bytes(int kh, int kw, int ntaps, int nchunks) { return 512 + nchunks * ntaps * WSL5 + NWAVE * v5_wtile_bytes(kh, kw); }
-inline int v5_tl(int kh, int kw) { return ((WR + kh - 1) * (TW5 + kw - 1) * 4 + 63) / 64; }
+inline int v5_lds_bytes(int ntaps, int nchunks) { return 512 + nchunks * ntaps * WSL5 + NWAVE * WTILE5; }
 
-template <int TL>
-int launch_tl(const ConvParams& q, const V5Extra& e, int mode, dim3 grid, int lds, hipStream_t st) {
-  const auto go = mode == 5 ? convk::launch_big_lds<&conv_mfma_v5_kernel<5, TL>, ConvParams, V5Extra>
-                  : mode == 4 ? convk::launch_big_lds<&conv_mfma_v5_kernel<4, TL>, ConvParams, V5Extra>
-                  : mode == 2 ? convk::launch_big_lds<&conv_mfma_v5_kernel<2, TL>, ConvParams, V5Extra>
-                  : mode == 1 ? convk::launch_big_lds<&conv_mfma_v5_kernel<1, TL>, ConvParams, V5Extra>
-                              : convk::launch_big_lds<&conv_mfma_v5_kernel<0, TL>, ConvParams, V5Extra>;
-  return go("tdvc_conv2d(v5)", 160 * 1024, grid, dim3(NTHR5), lds, st, q, e);
-}
+template <int SIMPLE>
+constexpr auto launch_v5 = convk::launch_big_lds<&conv_mfma_v5_kernel<SIMPLE>, ConvParams, int>;
 
 }  // namespace
 
 bool conv_v5_eligible(const tdvc_conv_desc* d, int Ho, int Wo) {
   const int nchunks = (d->x.C + CK5 - 1) / CK5;
-  const int tl = v5_tl(d->kh, d->kw);
-  const bool stride_ok = d->stride == 1 || (d->stride == 2 && d->kh == 1 && d->kw == 1 && d->pad == 0);   // ResidualBlockWithStride skips
-  return d->ck == 32 && stride_ok && d->ntaps >= 1 && d->ntaps <= 9 && d->kh <= 3 && d->kw <= 3 && d->cout >= 64 &&
-         d->x.C >= 32 && !d->s2d && ((long)Ho * Wo >= convk::LARGE_MAP_PIXELS || d->stride == 2) && tl == 4 &&     // stride 2: the only ck = 32 kernel that takes it
-         v5_lds_bytes(d->kh, d->kw, d->ntaps, nchunks) <= 160 * 1024;
+  const bool stride_ok = d->stride == 1 || (d->stride == 2 && d->pad == 0);   // ResidualBlockWithStride skips
+  return d->ck == 32 && stride_ok && d->ntaps >= 1 && d->ntaps <= 9 && d->kh == 1 && d->kw == 1 && d->cout >= 64 &&
+         d->x.C >= 32 && !d->s2d && ((long)Ho * Wo >= convk::LARGE_MAP_PIXELS || d->stride == 2) &&     // stride 2: the only ck = 32 kernel that takes it
+         v5_lds_bytes(d->ntaps, nchunks) <= 160 * 1024;
 }
 
 // workgroups along x for a launch over `nbtiles` tiles (also the row count of tdvc_conv_desc::chan_sum: 8 waves per workgroup)
@@ -248,20 +189,12 @@ int launch_conv_v5(const ConvParams& p, int cout_blocks, int N, hipStream_t st) 
   ConvParams q = p;
   q.tiles_x = (p.Wo + TW5 - 1) / TW5;
   const int tiles_y = (p.Ho + WR * NWAVE - 1) / (WR * NWAVE);
-  V5Extra e;
-  e.nbtiles = q.tiles_x * tiles_y;
-  e.wtile_bytes = v5_wtile_bytes(p.kh, p.kw);
-  const int lds = v5_lds_bytes(p.kh, p.kw, p.ntaps, p.nchunks);
-  const bool simple = convk::conv_is_simple(p);
-  if (simple) q.slope = convk::conv_simple_slope(p);
-  dim3 grid(v5_grid_x(e.nbtiles, cout_blocks, N), cout_blocks, N);
-  const int tl = v5_tl(p.kh, p.kw);
-  const bool lean = simple && convk::conv_is_lean(p);
-  if (p.flow.p && !(lean && !p.bcast_T && !p.csum)) {      // the dispatch (conv_flow_ok, conv_dispatch.hip) never sends such a launch here
+  const int nbtiles = q.tiles_x * tiles_y;
+  dim3 grid(v5_grid_x(nbtiles, cout_blocks, N), cout_blocks, N);
+  if (p.flow.p && !(p.simple == 2 && !p.bcast_T && !p.csum)) {      // the dispatch (conv_flow_ok, conv_dispatch.hip) never sends such a launch here
     tdvc_set_error("conv v5: flow needs the lean epilogue without channel sums");
     return TDVC_EINVAL;
   }
-  if (tl == 4) return launch_tl<4>(q, e, p.bcast_T ? 4 : (p.flow.p ? 5 : (simple ? (lean ? 2 : 1) : 0)), grid, lds, st);
-  tdvc_set_error("conv v5: unsupported window %dx%d", p.kh, p.kw);
-  return TDVC_EINVAL;
+  const auto go = p.bcast_T ? launch_v5<4> : (p.flow.p ? launch_v5<5> : convk::by_form(p.simple, launch_v5<0>, launch_v5<1>, launch_v5<2>));
+  return go("tdvc_conv2d(v5)", 160 * 1024, grid, dim3(NTHR5), v5_lds_bytes(p.ntaps, p.nchunks), st, q, nbtiles);
 }

@@ -509,7 +509,7 @@ static int launch_conv_row_t(const ConvParams& p, int N, hipStream_t st) {
   q.ncb = p.cout / G::CO;
   const bool shuf = p.out_mode == TDVC_OUT_SHUFFLE2;
   q.cq = shuf ? p.cout >> 2 : 0;
-  q.slope = convk::conv_simple_slope(p);
+  q.slope = p.slope;                           // folded by tdvc_conv2d (conv_simple_slope): 1 none, 0 ReLU, else LeakyReLU
   q.reverse = p.reverse;
   q.strips = (q.W + G::SW - 1) / G::SW;
   // 256 workgroups (one per CU), 256 / ncb slots per cout block; fewer when the launch has fewer rows than slots

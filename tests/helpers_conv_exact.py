@@ -151,6 +151,7 @@ CASES = [
     # ---- conv_mfma_v2: 16x32 tiles, one per workgroup; windows v3 does not take (5x5, 7x7, masked)
     C("v2_5x5", "conv_mfma_v2", "lean", 128, 256, W5, 1, 49, 67, act=ACT_RELU, res="f16", density=0.5, switches=(NO_V9,), multi=True, ragged=True),
     C("v2_masked", "conv_mfma_v2", "lean", 128, 64, WM, 2, 49, 67, act=ACT_LRELU, slope=0.25, res="f16", res2="f16", switches=(NO_V9,), multi=True, ragged=True),
+    C("v2_5x5_shuffle", "conv_mfma_v2", "generic", 64, 256, W5, 1, 49, 67, act=ACT_RELU, out="shuffle", res="f16", density=0.5, switches=(NO_V9,), multi=True, ragged=True),   # sub-pixel store: the generic transposed form
     C("v2_7x7_e4", "conv_mfma_v2", "e4", 64, 64, W7, 1, 49, 67, act=ACT_LRELU, slope=0.5, out="f32", density=0.5, switches=(NO_V9,), multi=True, ragged=True),
     C("v2_dy_lean", "conv_mfma_v2", "lean", 64, 64, W5, 1, 49, 67, act=ACT_LRELU, slope=0.1, res="f16", grade="dyadic", density=0.5, switches=(NO_V9,), multi=True, ragged=True),
     C("v2_dy_clamp01", "conv_mfma_v2", "e4", 64, 64, W5, 1, 49, 67, act=ACT_CLAMP01, switches=(NO_V9,), grade="dyadic", density=0.5, multi=True, ragged=True),
