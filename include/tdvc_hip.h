@@ -195,6 +195,27 @@ int tdvc_pack_conv_pair_weights(const float* w1_oihw, const float* w2_oihw, uint
 int tdvc_conv_pair_supported(const tdvc_conv_pair_desc* d);
 int tdvc_conv_pair(const tdvc_conv_pair_desc* d, void* stream);
 
+/* ---------------------------------------------------------------- LoopFilter tail (ABI 14)
+ * The tail of Bottleneck3D (main/model/pnet.py:304-317) in one inference-only launch, out of place:
+ *   T = W_t . [s_0 | s_1 | s_2] per pixel (the temporal (3,1,1) conv, no bias), s'_j = lrelu(s_j + T, slope), y_j = conv3(s'_j) + a_j
+ * for the four 64-channel slices j at channel offsets 0, 64, 128, 192 of a pixel of `s`, `a` and `y` (any pixel stride: dense 256-channel
+ * buffers or windows of a ring of slots).  Byte for byte tdvc_conv2d with bcast_T = 4 and `res` (conv_mfma_v5) followed by tdvc_conv2d of
+ * conv3 over the four slices with residual `a` (conv_row); the intermediate map never reaches memory.  `s` and `a` are only read. */
+typedef struct {
+  tdvc_fmap s, a, y;      /* fp16 maps of 256 channels, one geometry; y overlaps neither s nor a */
+  int32_t nslices;        /* 4 */
+  int32_t slice_stride;   /* 64: channel offset from one slice to the next */
+  const void* wt;         /* temporal conv 192 -> 64 (1x1), packed by tdvc_pack_conv_weights with ck = 32 */
+  const float* bias_t;    /* must be NULL: the zero padding of conv3's input is applied behind the temporal conv */
+  const void* w3;         /* conv3 64 -> 64 (3x3, pad 1), packed with ck = 32 */
+  const float* bias3;     /* [64] fp32 */
+  float slope;            /* LeakyReLU slope of s' */
+} tdvc_lf_tail_desc;
+/* 1 when tdvc_lf_tail takes this descriptor (fp16, 4 x 64 channels, aligned, H * W >= 8192, H >= 16, no temporal bias), else 0.  The same
+ * validation as the launch; never touches the device. */
+int tdvc_lf_tail_supported(const tdvc_lf_tail_desc* d);
+int tdvc_lf_tail(const tdvc_lf_tail_desc* d, void* stream);
+
 /* ---------------------------------------------------------------- deformable conv (motion compensation)
  * Fused modulated deformable 3x3 conv, fp16 NHWC, no column buffer:
  * replaces DCN.forward's `_DCNv2.apply` (main/utils/dcnv2/dcn_v2_amp.py:219-234) =

@@ -44,6 +44,12 @@ class ConvPairDesc(C.Structure):
                 ("act2", C.c_int32), ("slope2", C.c_float), ("add_input", C.c_int32), ("res2", FMapDesc)]
 
 
+class LfTailDesc(C.Structure):
+    """tdvc_lf_tail_desc (ABI 14)"""
+    _fields_ = [("s", FMapDesc), ("a", FMapDesc), ("y", FMapDesc), ("nslices", C.c_int32), ("slice_stride", C.c_int32),
+                ("wt", C.c_void_p), ("bias_t", C.c_void_p), ("w3", C.c_void_p), ("bias3", C.c_void_p), ("slope", C.c_float)]
+
+
 class WgradReduceJob(C.Structure):
     _fields_ = [("work", C.c_void_p), ("bwork", C.c_void_p), ("row_off", C.c_void_p), ("chan_off", C.c_void_p), ("tap_off", C.c_void_p),
                 ("bias_index", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("scale", C.c_float),
@@ -167,6 +173,8 @@ SIGNATURES = {
     "tdvc_pack_conv_pair_weights": (_i, [_P, _P, _P]),
     "tdvc_conv_pair_supported": (_i, [C.POINTER(ConvPairDesc)]),
     "tdvc_conv_pair": (_i, [C.POINTER(ConvPairDesc), _P]),
+    "tdvc_lf_tail_supported": (_i, [C.POINTER(LfTailDesc)]),
+    "tdvc_lf_tail": (_i, [C.POINTER(LfTailDesc), _P]),
     "tdvc_dcn_v2_forward_f32": (_i, [_P] * 6 + [_i] * 14 + [_P]),
     "tdvc_dcn_v2_backward_f32": (_i, [_P] * 12 + [_i] * 14 + [_P]),
     "tdvc_nchw_to_fmap": (_i, [_P, _i, _FM, _P]),

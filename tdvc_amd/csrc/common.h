@@ -30,6 +30,8 @@ struct TdvcLoopLaunches {
   long start = tdvc_launch_count();
   ~TdvcLoopLaunches() { tdvc_set_loop_launches(tdvc_launch_count() - start); }
 };
+// tile-walk parity of tdvc_conv2d (conv_dispatch.hip): count `launches` launches that a fused entry point replaced
+void tdvc_conv_walk_advance(int launches);
 // per-image form (tdvc_set_predicate_images), for the launchers of conv_c8 and conv_pair AFTER tdvc_launch_predicate(): the thread's flags
 // when they were set for exactly N images, else null (the launch then runs in full and reports 0)
 const int* tdvc_launch_predicate_images(int N);

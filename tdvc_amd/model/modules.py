@@ -334,6 +334,7 @@ class Bottleneck3D(nn.Module):
 LOOPFILTER_PAIR = True          # A/B switch (tools/ab_infer.py): layer1.conv1 + spatial_conv3d as one tdvc_conv_pair launch
 LOOPFILTER_BCAST = True         # A/B switch: temporal conv + broadcast add + LeakyReLU as one conv_mfma_v5 launch (bcast_T)
 LOOPFILTER_REUSE = True         # A/B switch: the per-reference-frame maps of LoopFilter's head persist across P-frames (device-predicated per image)
+LOOPFILTER_TAIL = True          # A/B switch: temporal conv + broadcast add + LeakyReLU + conv3 + residual as one tdvc_lf_tail launch (the map between them stays in LDS)
 LOOPFILTER_RING = 9             # slots of per-frame maps; a call's window is four of them and slides by one per call (model/ring.py)
 
 
@@ -383,6 +384,11 @@ class LoopFilter(nn.Module, PackCache):
             if r is not None:
                 return r
         return self._run_plain(xt, refs8, out, then)
+
+    def _tail_ok(self, S: FM, A: FM, o: FM) -> bool:
+        """the fused tail (ops.lf_tail) takes these views: inference without tape or per-kernel profile, fp16, no temporal bias"""
+        return (LOOPFILTER_TAIL and LOOPFILTER_BCAST and not self.training and ops.TAPE is None and ops.PROFILE is None
+                and self.layer1.temporal_conv3d.bias is None and ops.lf_tail_supported(S, A, o))
 
     def reuse_state(self) -> LoopFilterReuse | None:
         return self.__dict__.get("_packed", {}).get("lf_reuse")
@@ -455,13 +461,15 @@ class LoopFilter(nn.Module, PackCache):
         st.usable = True
         st.ring.commit()
         # the temporal conv reads slots p .. p + 2 and rewrites all four slices: out of place, the slots keep what the next call reuses
-        s = FM.empty(B, H, W, 256, device=dev)
-        ops.conv(st.S.ch(64 * p, 192), pk_conv(self, "bt", l1.temporal_conv3d), out=s.ch(0, 64), bcast_T=4, bcast_slope=0.1,
-                 res=st.S.ch(64 * p, 64))
         o = FM.empty(B, H, W, 256, device=dev)
-        pc3 = pk_conv(self, "b3", l1.conv3)
-        for b in range(B):
-            ops.conv(s.as_slices(b, 4, 64), pc3, out=o.as_slices(b, 4, 64), res=win(st.A, b, 0, 4))
+        pct, pc3 = pk_conv(self, "bt", l1.temporal_conv3d), pk_conv(self, "b3", l1.conv3)
+        if self._tail_ok(st.S.ch(64 * p, 256), st.A.ch(64 * p, 256), o):
+            ops.lf_tail(st.S.ch(64 * p, 256), st.A.ch(64 * p, 256), pct, pc3, out=o, slope=0.1)
+        else:
+            s = FM.empty(B, H, W, 256, device=dev)
+            ops.conv(st.S.ch(64 * p, 192), pct, out=s.ch(0, 64), bcast_T=4, bcast_slope=0.1, res=st.S.ch(64 * p, 64))
+            for b in range(B):
+                ops.conv(s.as_slices(b, 4, 64), pc3, out=o.as_slices(b, 4, 64), res=win(st.A, b, 0, 4))
         sums = []
         f = ops.conv(o, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
         return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
@@ -502,6 +510,12 @@ class LoopFilter(nn.Module, PackCache):
         else:
             self._slices("b1", l1.conv1, a, bf, **lr)
             self._slices("bs", l1.spatial_conv3d, bf, s)
+        if self._tail_ok(s, a, bf):
+            # inference: the temporal stage below and conv3 + residual as one launch, the map between them never reaches memory
+            ops.lf_tail(s, a, pk_conv(self, "bt", l1.temporal_conv3d), pk_conv(self, "b3", l1.conv3), out=bf, slope=0.1)
+            sums = []
+            f = ops.conv(bf, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
+            return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
         if ops.TAPE is None and LOOPFILTER_BCAST and H * W >= 8192:      # per IMAGE: conv_v5_eligible (csrc/conv_mfma_v5.hip) counts one map
             # inference: temporal (3,1,1) conv over frames 0-2 + `out + temporal` + LeakyReLU (pnet.py:304-314) as ONE pass over
             # the 4-frame buffer: a wave computes the 64 temporal channels of its pixels and rewrites their four slices in place

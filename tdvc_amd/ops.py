@@ -669,6 +669,41 @@ def conv_pair(x: FM, pp: PackedConvPair, out: FM | None = None, act1=ACT_RELU, s
     return out
 
 
+# ----------------------------------------------------------------------------- LoopFilter tail (inference)
+def _lf_tail_desc(S: FM, A: FM, out: FM, pct: PackedConv | None, pc3: PackedConv | None, slope: float):
+    d = L.LfTailDesc()
+    d.s, d.a, d.y = S.desc(), A.desc(), out.desc()
+    d.nslices, d.slice_stride = 4, 64
+    if pct is None:                               # the query: presence only, never dereferenced
+        d.wt, d.bias_t, d.w3, d.bias3 = 16, None, 16, 16
+    else:
+        d.wt, d.bias_t = pct.w.data_ptr(), (None if pct.bsrc is None else pct.bias.data_ptr())
+        d.w3, d.bias3 = pc3.w.data_ptr(), pc3.bias.data_ptr()
+    d.slope = float(slope)
+    return d
+
+
+def lf_tail_supported(S: FM, A: FM, out: FM) -> bool:
+    """inference only; S, A, out: fp16 views of 4 x 64 channels per pixel (dense buffers or ring windows), limits are the library's
+    (tdvc_lf_tail_supported)"""
+    if TAPE is not None or S.f32 or A.f32 or out.f32:
+        return False
+    return bool(L.lib().tdvc_lf_tail_supported(C.byref(_lf_tail_desc(S, A, out, None, None, 0.0))))
+
+
+def lf_tail(S: FM, A: FM, pct: PackedConv, pc3: PackedConv, out: FM, slope: float = 0.1) -> FM:
+    """out_j = conv3(lrelu(S_j + temporal(S_0 | S_1 | S_2), slope)) + A_j over the four 64-channel slices of a pixel, in one launch
+    (`tdvc_lf_tail`): byte for byte conv(bcast_T=4, res=S) followed by the conv of the four slices with residual A"""
+    if TAPE is not None:
+        raise L.TdvcHipError("lf_tail: inference only (the intermediate map is not kept for the backward pass)")
+    if (pct.cin, pct.cout, pct.kh, pct.kw, pct.ck) != (192, 64, 1, 1, 32) or (pc3.cin, pc3.cout, pc3.kh, pc3.kw, pc3.ck, pc3.stride, pc3.pad) != (64, 64, 3, 3, 32, 1, 1):
+        raise L.TdvcHipError("lf_tail: needs the 1x1 192 -> 64 temporal conv and the 3x3 64 -> 64 conv, both packed with ck = 32")
+    d = _lf_tail_desc(S, A, out, pct, pc3, slope)
+    L.check(L.lib().tdvc_lf_tail(C.byref(d), _stream()), "lf_tail")
+    _log_predicated()
+    return out
+
+
 # ----------------------------------------------------------------------------- conv backward (training path)
 def act_backward(g: FM, y: FM, act, slope=0.0, res: FM | None = None, out: FM | None = None) -> FM:
     """g * act'(z); the sign of the pre-activation comes from the stored output y (minus its residual)"""
