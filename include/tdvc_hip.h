@@ -222,7 +222,12 @@ int tdvc_lf_tail(const tdvc_lf_tail_desc* d, void* stream);
  * dcn_v2_cuda_forward (src/cuda/dcn_v2_cuda.cu:20-95) + modulated_deformable_im2col
  * (src/cuda/dcn_v2_im2col_cuda.cu:125-195).
  * om: fp16 fmap with 27*G channels = raw conv_offset_mask output [o1 | o2 | mask_logits]
- * (sigmoid applied here, dcn_v2_amp.py:220-223). Cin = Cout = 8*G, 8 channels per group. */
+ * (sigmoid applied here, dcn_v2_amp.py:220-223). Cin = Cout = 8*G, 8 channels per group.
+ * ABI 15.  fp32 maps: with x.dtype == TDVC_F32 the call runs the fp32 kernel (csrc/dcn_f32.hip) -- fp32 samples, sampling
+ * positions, mask (1 / (1 + expf(-logit)), a true division) and accumulation (v_mfma_f32_32x32x2_f32); nothing is rounded to
+ * fp16 before the epilogue (bias, one fp16 rounding if round_before_act, activation in fp32).  Then om must be fp32 too, y is
+ * fp32 or fp16 (one more rounding), x_planar must be NULL, `w` is the fp32 packing (tdvc_pack_conv_weights_indexed_f32,
+ * ck = 64, 9 taps), and the fp32 maps are 16-byte aligned with pixel / batch strides that are multiples of 4. */
 typedef struct {
   tdvc_fmap x, om, y;
   const void* w;        /* packed with tdvc_pack_conv_weights(ck = 64, 9 taps row-major) */
@@ -268,7 +273,8 @@ int tdvc_scale_act_res(const tdvc_fmap* a, const float* gate, int act, float slo
  * y3 must not alias a, r or y. */
 int tdvc_scale_act_res3(const tdvc_fmap* a, const float* gate, int act, float slope, const tdvc_fmap* r, float r_sign,
                         const tdvc_fmap* y, const tdvc_fmap* b, float b_sign, const tdvc_fmap* y3, void* stream);
-/* offset[c] += flow[c & 1] (main/model/pnet.py:163); off fp16 in place, flow fp32 2-channel fmap. */
+/* offset[c] += flow[c & 1] (main/model/pnet.py:163); off fp16 or fp32 (ABI 15) in place, C % 8 == 0; flow an fp32 fmap whose first two
+ * channels are read (C >= 2). */
 int tdvc_add_flow(const tdvc_fmap* off, const tdvc_fmap* flow, void* stream);
 /* x[:, t] = lrelu(x[:, t] + b) for the T channel-slices of width b.C (pnet.py:313-314). */
 int tdvc_bcast_add_act(const tdvc_fmap* x, const tdvc_fmap* b, int T, float slope, void* stream);
@@ -283,7 +289,7 @@ int tdvc_se_gate(const float* partial, int nblocks, float inv_count, int N, int 
                  float* gate, void* stream);
 
 /* ---------------------------------------------------------------- resampling
- * bilinear x2 upsample, align_corners=False (nn.Upsample, main/model/pnet.py:117). fp16 fmaps. */
+ * bilinear x2 upsample, align_corners=False (nn.Upsample, main/model/pnet.py:117). fp16 or fp32 (ABI 15) fmaps, C % 8 == 0. */
 int tdvc_upsample2x(const tdvc_fmap* x, const tdvc_fmap* y, void* stream);
 /* 2x2 average pooling, fp32 fmap -> fp32 fmap (F.avg_pool2d, main/model/flownet.py:103-114). */
 int tdvc_avgpool2(const tdvc_fmap* x, const tdvc_fmap* y, void* stream);
@@ -296,8 +302,8 @@ int tdvc_avgpool2_pyramid(const tdvc_fmap* xa, const tdvc_fmap* xb, const tdvc_f
  * (main/model/flownet.py:119-138 + flow_warp :8-48):
  *   flow_up = 2 * bilinear_x2(flow_lo, align_corners=True)   (zeros if flow_lo == NULL)
  *   warped  = grid_sample(supp, grid + flow_up, bilinear, border, align_corners=True)
- *   cat8    = [ref(3) | warped(3) | flow_up(2)] as fp16; flow_up is also kept in fp32.
- * ref/supp: fp32 fmaps with C>=3; flow_lo/flow_up: fp32 2-channel fmaps; cat8: fp16 C=8. */
+ *   cat8    = [ref(3) | warped(3) | flow_up(2)] in cat8's dtype; flow_up is also kept in fp32.
+ * ref/supp: fp32 fmaps with C>=3; flow_lo/flow_up: fp32 fmaps whose first two channels are used (C >= 2); cat8: fp16 or fp32 (ABI 15), C=8. */
 int tdvc_spynet_level_input(const tdvc_fmap* ref, const tdvc_fmap* supp, const tdvc_fmap* flow_lo,
                             const tdvc_fmap* flow_up, const tdvc_fmap* cat8, void* stream);
 /* generic bilinear resize, align_corners=False, fp32 fmaps, optional per-channel scale of the
@@ -306,7 +312,7 @@ int tdvc_resize_bilinear(const tdvc_fmap* x, const tdvc_fmap* y, const float* ch
 
 /* ---------------------------------------------------------------- in-loop filter matching
  * FeatureFix.forward, main/model/pnet.py:219-255. */
-/* scale x scale average pooling (floor), fp16 fmap -> fp32 [N][hp][wp][C] (nn.AvgPool2d, :224-225).
+/* scale x scale average pooling (floor), fp16 or fp32 (ABI 15) fmap -> fp32 [N][hp][wp][C] (nn.AvgPool2d, :224-225).
  * Two order-fixed stages through `work` (>= tdvc_avgpool_k_work_floats(..) floats of device memory). */
 int64_t tdvc_avgpool_k_work_floats(int N, int hp, int wp, int C, int scale);
 int tdvc_avgpool_k(const tdvc_fmap* x, int scale, float* pooled, int hp, int wp, float* work, int64_t work_floats, void* stream);
@@ -317,7 +323,7 @@ int tdvc_patch_match(const float* pin, const float* pref, int N, int hp, int wp,
                      int32_t* idx, void* stream);
 /* gather full-resolution reference blocks by idx (unfold/gather/fold with kernel 3*scale,
  * :247-254), per-pixel cosine similarity with fin over channels (:255), write
- * cat = [fin*cor | out*cor] (fp16, 128 channels) (:257). */
+ * cat = [fin*cor | out*cor] (128 channels) (:257).  fin, fref (64 channels) and cat are fp16 or fp32 (ABI 15) fmaps. */
 int tdvc_match_gather(const tdvc_fmap* fin, const tdvc_fmap* fref, const int32_t* idx, int scale,
                       int hp, int wp, const tdvc_fmap* cat, void* stream);
 

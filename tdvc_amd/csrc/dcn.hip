@@ -5,6 +5,7 @@
 //     The reference materialises `columns` in HBM (576 values / pixel = 4.8 GB at 1080p,
 //     src/cuda/dcn_v2_cuda.cu:67-92); here the modulated samples of an 8x8 pixel tile live in a
 //     25 KB LDS tile, three taps at a time, and are consumed as MFMA B fragments.
+//     On fp32 maps the same entry point runs dcn_f32_fused_kernel (csrc/dcn_f32.hip): fp32 samples, offsets, mask and MFMA.
 // (2) tdvc_dcn_v2_forward_f32: fp32 NCHW operator with `_ext.dcn_v2_forward` semantics.
 #include "common.h"
 
@@ -515,8 +516,11 @@ static int g_dcn_lds = getenv("TDVC_DCN_NO_LDS") == nullptr ? 1 : 0;
 // (2, 3: the timing-only builds MODE 1, 2 of dcn_lds_kernel)
 extern "C" void tdvc_debug_enable_dcn_lds(int enable) { g_dcn_lds = enable; }
 
+int tdvc_dcn_fused_f32(const tdvc_dcn_desc* d, void* stream);      // csrc/dcn_f32.hip
+
 extern "C" int tdvc_dcn_fused(const tdvc_dcn_desc* d, void* stream) {
   TDVC_CHECK(d, "tdvc_dcn_fused: null descriptor");
+  if (d->x.dtype == TDVC_F32) return tdvc_dcn_fused_f32(d, stream);       // fp32 maps: one kernel of its own, fp32 weight packing
   TDVC_CHECK(fmap_ok16(d->x) && fmap_ok16(d->om) && fmap_ok16(d->y), "tdvc_dcn_fused: fmaps must be fp16, C/sp %% 8, aligned");
   const int G = d->groups;
   TDVC_CHECK(G == 8, "tdvc_dcn_fused: groups=%d unsupported (the fused kernel is built for the hot-path geometry: 8 groups x 8 channels; use tdvc_dcn_v2_forward_f32 otherwise)", G);

@@ -865,16 +865,17 @@ extern "C" int tdvc_scale_act_res3(const tdvc_fmap* a, const float* gate, int ac
 }
 
 extern "C" int tdvc_add_flow(const tdvc_fmap* off, const tdvc_fmap* flow, void* stream) {
-  TDVC_CHECK(off && flow && fmap_ok16(*off) && fmap_ok32(*flow) && flow->C >= 2 && same_geom(*off, *flow), "tdvc_add_flow: bad arguments");
+  TDVC_CHECK(off && flow && fmap_any(*off) && (off->C % 8) == 0 && fmap_ok32(*flow) && flow->C >= 2 && same_geom(*off, *flow), "tdvc_add_flow: bad arguments");
   const long total = (long)off->N * off->H * off->W * (off->C / 8);
   hipLaunchKernelGGL(add_flow_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*off), to_dev(*flow));
   return tdvc_launch_status("tdvc_add_flow");
 }
 
 extern "C" int tdvc_bcast_add_act(const tdvc_fmap* x, const tdvc_fmap* b, int T, float slope, void* stream) {
-  TDVC_CHECK(x && b && fmap_ok16(*x) && fmap_ok16(*b) && same_geom(*x, *b) && x->C == T * b->C, "tdvc_bcast_add_act: bad arguments");
+  TDVC_CHECK(x && b && fmap_any(*x) && fmap_any(*b) && (b->C % 8) == 0 && same_geom(*x, *b) && x->C == T * b->C, "tdvc_bcast_add_act: bad arguments");
   const long total = (long)x->N * x->H * x->W * (x->C / 8);
-  if (T == 4 && total / 4 < (1L << 31)) {
+  const bool f16 = x->dtype == TDVC_F16 && b->dtype == TDVC_F16;      // the T-slice kernel reads raw fp16 words; fp32 maps take the generic one
+  if (f16 && T == 4 && total / 4 < (1L << 31)) {
     const long items = total / 4;
     hipLaunchKernelGGL(bcast_add_act_t_kernel<4>, grid1d(items), dim3(256), 0, ST(stream), to_dev(*x), to_dev(*b), slope, (unsigned)items,
                        (unsigned)(b->C / 8), (unsigned)((long)x->H * x->W));
@@ -898,7 +899,7 @@ extern "C" int tdvc_se_gate(const float* partial, int nblocks, float inv_count, 
 }
 
 extern "C" int tdvc_upsample2x(const tdvc_fmap* x, const tdvc_fmap* y, void* stream) {
-  TDVC_CHECK(x && y && fmap_ok16(*x) && fmap_ok16(*y) && y->H == 2 * x->H && y->W == 2 * x->W && y->C == x->C && y->N == x->N,
+  TDVC_CHECK(x && y && fmap_any(*x) && fmap_any(*y) && (x->C % 8) == 0 && y->H == 2 * x->H && y->W == 2 * x->W && y->C == x->C && y->N == x->N,
              "tdvc_upsample2x: bad arguments");
   const long total = (long)y->N * y->H * y->W * (y->C / 8);
   hipLaunchKernelGGL(upsample2x_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y));
@@ -943,7 +944,7 @@ extern "C" int tdvc_spynet_level_input(const tdvc_fmap* ref, const tdvc_fmap* su
   TDVC_CHECK(ref && supp && flow_up && cat8, "tdvc_spynet_level_input: null");
   TDVC_CHECK(fmap_ok32(*ref) && fmap_ok32(*supp) && ref->C >= 3 && supp->C >= 3 && same_geom(*ref, *supp), "tdvc_spynet_level_input: bad ref/supp");
   TDVC_CHECK(fmap_ok32(*flow_up) && flow_up->C >= 2 && same_geom(*ref, *flow_up), "tdvc_spynet_level_input: bad flow_up");
-  TDVC_CHECK(fmap_ok16(*cat8) && cat8->C == 8 && same_geom(*ref, *cat8), "tdvc_spynet_level_input: bad cat8");
+  TDVC_CHECK(fmap_any(*cat8) && cat8->C == 8 && same_geom(*ref, *cat8), "tdvc_spynet_level_input: bad cat8");
   if (flow_lo) TDVC_CHECK(fmap_ok32(*flow_lo) && flow_lo->C >= 2 && flow_lo->N == ref->N && flow_lo->H * 2 == ref->H && flow_lo->W * 2 == ref->W,
                           "tdvc_spynet_level_input: bad flow_lo");
   const long total = (long)ref->N * ref->H * ref->W;
@@ -971,7 +972,7 @@ extern "C" int64_t tdvc_avgpool_k_work_floats(int N, int hp, int wp, int C_, int
 }
 
 extern "C" int tdvc_avgpool_k(const tdvc_fmap* x, int scale, float* pooled, int hp, int wp, float* work, int64_t work_floats, void* stream) {
-  TDVC_CHECK(x && pooled && work && fmap_ok16(*x) && x->C <= 256 && scale >= 1 && hp == x->H / scale && wp == x->W / scale && hp >= 1 && wp >= 1,
+  TDVC_CHECK(x && pooled && work && fmap_any(*x) && (x->C % 8) == 0 && x->C <= 256 && scale >= 1 && hp == x->H / scale && wp == x->W / scale && hp >= 1 && wp >= 1,
              "tdvc_avgpool_k: bad arguments");
   const int nsplit = (scale + POOL_ROWS - 1) / POOL_ROWS;
   TDVC_CHECK(work_floats >= tdvc_avgpool_k_work_floats(x->N, hp, wp, x->C, scale), "tdvc_avgpool_k: workspace too small (tdvc_avgpool_k_work_floats)");
@@ -1014,7 +1015,7 @@ extern "C" int tdvc_patch_match(const float* pin, const float* pref, int N, int 
 
 extern "C" int tdvc_match_gather(const tdvc_fmap* fin, const tdvc_fmap* fref, const int32_t* idx, int scale, int hp, int wp,
                                  const tdvc_fmap* cat, void* stream) {
-  TDVC_CHECK(fin && fref && idx && cat && fmap_ok16(*fin) && fmap_ok16(*fref) && fmap_ok16(*cat), "tdvc_match_gather: bad fmaps");
+  TDVC_CHECK(fin && fref && idx && cat && fmap_any(*fin) && fmap_any(*fref) && fmap_any(*cat), "tdvc_match_gather: bad fmaps");
   TDVC_CHECK(fin->C == 64 && fref->C == 64 && cat->C == 128 && same_geom(*fin, *fref) && same_geom(*fin, *cat), "tdvc_match_gather: needs C=64 / cat C=128");
   const int ks = 3 * scale;
   const int nbh = (fin->H + ks) / ks + 1, nbw = (fin->W + ks) / ks + 1;   // fold(kernel=ks, pad=ks, stride=ks)

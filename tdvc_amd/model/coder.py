@@ -470,7 +470,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
         g[8].run(t, out=y32, out2=y16)
         return y32, y16
 
-    def run_g_s(self, y_hat: FM, out: FM | None = None, res: FM | None = None) -> FM:
+    def run_g_s(self, y_hat: FM, out: FM | None = None, res: FM | None = None, out_dtype=torch.float16) -> FM:
         g = self.g_s
         t = g[0].run(y_hat)
         for i in range(1, 5):
@@ -482,8 +482,9 @@ class Cheng2020Anchor(nn.Module, PackCache):
         # prediction + recon_res of pnet.py:76 fused into the last layer's epilogue.  Maps of < 8192 px (generic epilogue) sum in
         # fp32 and round once; the 1080p path (conv_mfma_v11, lean epilogue) rounds the conv result to fp16 and adds the
         # prediction in packed fp16 -- two roundings, <= 1 fp16 ulp of a [0,1] pixel; the 1080p trained-point parity test
-        # (tests/test_model_gpu.py::test_trained_operating_point_parity_1080p) runs through that kernel
-        return ops.conv(t, pk_conv(self, "gs9", g[9][0], shuffle=True), out=out, res=res, out_dtype=torch.float16)
+        # (tests/test_model_gpu.py::test_trained_operating_point_parity_1080p) runs through that kernel.
+        # `out_dtype` fp32 (the whole-model fp32 mode, on an fp32 island): there is no autocast region to re-enter, x_hat stays fp32
+        return ops.conv(t, pk_conv(self, "gs9", g[9][0], shuffle=True), out=out, res=res, out_dtype=out_dtype)
 
     def run_h_a(self, y16: FM) -> FM:
         h = self.h_a
@@ -530,6 +531,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
         differentiated in fp32 as well (fp32 gradient mirrors, conv_f32 data gradients, conv_wgrad_f32 weight gradients); only its
         entry cast and its fp16 reconstruction touch fp16 maps."""
         dev = x.t.device
+        xdt = torch.float32 if (f32 and x.f32) else torch.float16      # an fp32 input of an fp32 island (whole-model fp32 mode): x_hat fp32 too
         if f32:
             x = self._as_f32(x)
         adt = torch.float32 if f32 else torch.float16          # activation dtype inside the coder
@@ -553,7 +555,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
         ops.conv(y_hat, self.ctx_conv(), out=pcat.ch(2 * M, 2 * M))
         gp = self.run_entropy_parameters(pcat)
         ops.gc_forward(y32, gp, bits[0:1], noise=nl)
-        x_hat = self.run_g_s(y_hat, out=out, res=res)
+        x_hat = self.run_g_s(y_hat, out=out, res=res, out_dtype=xdt)
         if trace is not None:
             trace.update(y=y32, z=z, z_hat=z_hat, y_hat=y_hat, gp=gp)
         return x_hat, bits

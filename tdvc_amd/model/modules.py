@@ -152,9 +152,10 @@ class SPyNet(nn.Module, PackCache):
         self.register_buffer("mean", torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1))
         self.register_buffer("std", torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1))
 
-    def compute_flow(self, ref: FM, supp: FM, fused: bool = False) -> FM:
+    def compute_flow(self, ref: FM, supp: FM, fused: bool = False, f32: bool = False) -> FM:
         """ref/supp: fp32 fmaps (C=4), H, W multiples of 32 -> flow fp32 fmap (C=2).  `fused` (inference): both image pyramids in
-        one launch instead of ten (PYRAMID_FUSED); the level buffers stay separate maps, their bytes the same"""
+        one launch instead of ten (PYRAMID_FUSED); the level buffers stay separate maps, their bytes the same.  `f32` (the whole-model
+        fp32 mode): the level input and the five convs on fp32 maps; the flow map then has 8 channels, 2..7 zero"""
         if fused and PYRAMID_FUSED and ops.avgpool2_pyramid_supported(ref, supp):
             lr_, ls_ = ops.avgpool2_pyramid(ref, supp)
             refs, supps = [ref] + lr_, [supp] + ls_
@@ -169,7 +170,7 @@ class SPyNet(nn.Module, PackCache):
         for lvl in range(6):
             r, s = refs[lvl], supps[lvl]
             up = FM.empty(r.N, r.H, r.W, 2, dtype=torch.float32, device=dev)
-            x = FM.empty(r.N, r.H, r.W, 8, device=dev)
+            x = FM.empty(r.N, r.H, r.W, 8, dtype=torch.float32 if f32 else torch.float16, device=dev)
             ops.spynet_level_input(r, s, flow, up, x)
             bm = self.basic_module[lvl].basic_module
             for i in range(4):
@@ -177,16 +178,17 @@ class SPyNet(nn.Module, PackCache):
             flow = ops.conv(x, pk_conv(self, f"l{lvl}c4", bm[4].conv), res=up, out_dtype=torch.float32)
         return flow
 
-    def run(self, ref: FM, supp: FM, fused: bool = False) -> FM:
+    def run(self, ref: FM, supp: FM, fused: bool = False, f32: bool = False) -> FM:
         H, W = ref.H, ref.W
         Hu = H if H % 32 == 0 else 32 * (H // 32 + 1)
         Wu = W if W % 32 == 0 else 32 * (W // 32 + 1)
         if (Hu, Wu) != (H, W):
             ref, supp = ops.resize_bilinear(ref, Hu, Wu), ops.resize_bilinear(supp, Hu, Wu)
-        flow = self.compute_flow(ref, supp, fused)
+        flow = self.compute_flow(ref, supp, fused, f32)
         if (Hu, Wu) != (H, W):
             sc = torch.tensor([float(W) / float(Wu), float(H) / float(Hu)], dtype=torch.float32, device=flow.t.device)
-            flow = ops.resize_bilinear(flow, H, W, sc)
+            # the fp32 mode's flow map carries six zero channels more; sc has a scale for the two real ones
+            flow = ops.resize_bilinear(flow if flow.C == 2 else flow.ch(0, 2), H, W, sc)
         return flow
 
 
@@ -231,15 +233,17 @@ class OffsetGen(nn.Module, PackCache):
 
     def run(self, feats: FM, cur32: FM, ref32: FM, traced: bool = False) -> FM:
         """feats: (B,H,W,>=128) buffer with [f_cur | f_ref] in channels 0..127;
-        cur32 / ref32: fp32 RGB fmaps.  Returns estmv (B,H,W,64) fp16."""
+        cur32 / ref32: fp32 RGB fmaps.  Returns estmv (B,H,W,64) in the dtype of `feats` (fp32: the whole-model fp32 mode, every
+        layer on fp32 maps in the plain sequence of traced calls)."""
         B, H, W = feats.N, feats.H, feats.W
-        fuse = glue_fusions_allowed(self, traced)
+        f32, adt = feats.f32, feats.t.dtype
+        fuse = glue_fusions_allowed(self, traced) and not f32
         flow = None
         dev = feats.t.device
         lr = dict(act=ACT_LRELU, slope=0.1)
         cat1 = feats.ch(0, 128)
-        cat2 = FM.empty(B, H // 2, W // 2, 128, device=dev)
-        cat3 = FM.empty(B, H // 4, W // 4, 128, device=dev)
+        cat2 = FM.empty(B, H // 2, W // 2, 128, dtype=adt, device=dev)
+        cat3 = FM.empty(B, H // 4, W // 4, 128, dtype=adt, device=dev)
         for k in (0, 1):   # 0 = current frame features, 1 = reference
             t = ops.conv(cat1.ch(64 * k, 64), pk_conv(self, "l2_1", self.conv_l2_1), **lr)
             ops.conv(t, pk_conv(self, "l2_2", self.conv_l2_2), out=cat2.ch(64 * k, 64), **lr)
@@ -268,10 +272,10 @@ class OffsetGen(nn.Module, PackCache):
                 off = ops.conv(up_o1, pk_conv(self, "ff" + lv, self.feat_fusion[lv]), flow=flow if i == 1 else None, **lr)
             if i > 1:
                 up = ops.upsample2x(off)
-                up_o1 = FM.empty(B, up.H, up.W, 128, device=dev)      # [upsampled_offset | offset1]
+                up_o1 = FM.empty(B, up.H, up.W, 128, dtype=adt, device=dev)      # [upsampled_offset | offset1]
                 ops.conv(up, pk_conv(self, "upc", self.upsample_conv), out=up_o1.ch(0, 64))
         if flow is None:
-            flow = self.spynet.run(cur32, ref32, fused=fuse)
+            flow = self.spynet.run(cur32, ref32, fused=fuse, f32=f32)
             if ops.TAPE is not None:
                 off = ops.clone(off)      # keep the fusion conv's own output (LeakyReLU sign) for the backward pass
             ops.add_flow(off, flow)
@@ -296,6 +300,12 @@ class DCN(nn.Module, PackCache):
         pc = self._pk("w", lambda: ops.pack_conv(self.weight, self.bias, stride=1, pad=1, ck=8 * self.deformable_groups,
                                                  device=self.weight.device))
         # output rounded to fp16 BEFORE the activation (reference: `output.half()`, then lrelu on fp16)
+        if x.f32:
+            # whole-model fp32 mode: fp32 samples, offsets, mask and accumulation (csrc/dcn_f32.hip); the reference's output is an fp16
+            # tensor in every mode (dcn_v2_amp.py:15,67-68) that the fp32 features around it widen again
+            y16 = FM.empty(x.N, x.H, x.W, out.C, device=x.t.device)
+            ops.dcn_fused(x, om, pc, y16, groups=self.deformable_groups, act=act, slope=slope, round16=True)
+            return ops.copy_cast(y16, out)
         return ops.dcn_fused(x, om, pc, out, groups=self.deformable_groups, act=act, slope=slope, round16=True)
 
 
@@ -479,7 +489,8 @@ class LoopFilter(nn.Module, PackCache):
         dev = xt.t.device
         lr = dict(act=ACT_LRELU, slope=0.1)
         p01, p02 = pk_conv(self, "c01", self.conv01), pk_conv(self, "c02", self.conv02)
-        a = FM.empty(B, H, W, 256, device=dev)
+        adt = xt.t.dtype                   # fp32: the whole-model fp32 mode (no fused form takes fp32 maps: the plain sequence)
+        a = FM.empty(B, H, W, 256, dtype=adt, device=dev)
         fuse = LOOPFILTER_PAIR and ops.conv_pair_supported(a.as_slices(0, 4, 64).batch(0, 3))
         if fuse:
             # inference: conv02 (no activation) + conv1 (LeakyReLU) of the three reference slices in one launch -- nothing else
@@ -497,8 +508,8 @@ class LoopFilter(nn.Module, PackCache):
         if not fuse:
             self._slices("c1", self.conv1, xt, a, **lr)
         l1 = self.layer1
-        bf = FM.empty(B, H, W, 256, device=dev)
-        s = FM.empty(B, H, W, 256, device=dev)
+        bf = FM.empty(B, H, W, 256, dtype=adt, device=dev)
+        s = FM.empty(B, H, W, 256, dtype=adt, device=dev)
         if LOOPFILTER_PAIR and ops.conv_pair_supported(a.as_slices(0, 4, 64), s.as_slices(0, 4, 64)):
             # inference: layer1.conv1 (LeakyReLU) and layer1.spatial_conv3d in one launch per batch item, their intermediate
             # map stays in LDS (`bf` is then only the block's output buffer below)
@@ -516,7 +527,7 @@ class LoopFilter(nn.Module, PackCache):
             sums = []
             f = ops.conv(bf, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
             return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
-        if ops.TAPE is None and LOOPFILTER_BCAST and H * W >= 8192:      # per IMAGE: conv_v5_eligible (csrc/conv_mfma_v5.hip) counts one map
+        if ops.TAPE is None and LOOPFILTER_BCAST and H * W >= 8192 and not s.f32:      # per IMAGE: conv_v5_eligible (csrc/conv_mfma_v5.hip) counts one map
             # inference: temporal (3,1,1) conv over frames 0-2 + `out + temporal` + LeakyReLU (pnet.py:304-314) as ONE pass over
             # the 4-frame buffer: a wave computes the 64 temporal channels of its pixels and rewrites their four slices in place
             ops.conv(s.ch(0, 192), pk_conv(self, "bt", l1.temporal_conv3d), out=s.ch(0, 64), bcast_T=4, bcast_slope=0.1)
@@ -526,7 +537,7 @@ class LoopFilter(nn.Module, PackCache):
                 s = ops.clone(s)          # `s` itself is the temporal conv's input: keep it for the backward pass
             ops.bcast_add_act(s, tm, 4, 0.1)
         # inference re-uses `bf` for the block output; under the tape `bf` is still needed by the backward of `bs`
-        o = bf if ops.TAPE is None else FM.empty(B, H, W, 256, device=dev)
+        o = bf if ops.TAPE is None else FM.empty(B, H, W, 256, dtype=adt, device=dev)
         self._slices("b3", l1.conv3, s, o, res_buf=a)
         sums = []
         f = ops.conv(o, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
@@ -581,7 +592,7 @@ class FeatureFix(nn.Module, PackCache):
         self.attn = SELayer(64)
 
     def run(self, x: FM, iframe8: FM, training: bool, trace=None) -> torch.Tensor:
-        """x: reconstructed features (B,H,W,64); iframe8: I-frame (B,H,W,8) fp16.
+        """x: reconstructed features (B,H,W,64); iframe8: I-frame (B,H,W,8) fp16 (both fp32 in the whole-model fp32 mode).
         Returns the clamped RGB reconstruction as NCHW fp32."""
         B, H, W = x.N, x.H, x.W
         dev = x.t.device
@@ -595,12 +606,12 @@ class FeatureFix(nn.Module, PackCache):
             y, pref = self._iframe_features(iframe8, scale)
             fref = y.ch(64, 64)
         else:
-            y = FM.empty(B, H, W, 128, device=dev)            # [o | fref]
+            y = FM.empty(B, H, W, 128, dtype=x.t.dtype, device=dev)            # [o | fref]
             fref = self.FeatureExtract_ref.run(iframe8, out=y.ch(64, 64))
             pref = ops.avgpool_k(fref, scale)
         pin = ops.avgpool_k(fin, scale)
         idx = ops.patch_match(pin, pref)
-        cat = FM.empty(B, H, W, 128, device=dev)          # [fin*cor | out*cor]
+        cat = FM.empty(B, H, W, 128, dtype=x.t.dtype, device=dev)          # [fin*cor | out*cor]
         ops.match_gather(fin, fref, idx, scale, cat)
         ops.conv(cat, pk_conv(self, "ff", self.featfusion), out=y.ch(0, 64), **lr)
         sums = []

@@ -41,6 +41,13 @@ class VideoCompressor(nn.Module):
         # tape differentiates them in fp32 (conv_f32 dgrad, conv_wgrad_f32).  Set by TrainStep(coder_fp32=True).  Unset, a .train()
         # forward runs the fp16-in / fp32-accumulate coders whatever `enabled_amp` / `coder_fp32` say (with a warning)
         self.train_coder_fp32 = False
+        # the reference's `enable_amp: False`: an eval forward(), encode() and decode() run EVERY stage on fp32 maps with fp32 weights
+        # (conv_f32, the fp32 deformable conv of csrc/dcn_f32.hip, the streaming kernels on fp32 maps), both coders as the fp32 islands;
+        # only the deformable conv's output is rounded to fp16 and widened again, as in the reference (dcn_v2_amp.py:15,67-68).  No fused
+        # inference form and no reuse cache takes fp32 maps: this mode runs the plain sequence of traced calls.  It is the mode that is
+        # compared with the fp32 CPU oracle to fp32 accumulation error; it is bound by the fp32 matrix pipe and is no 30 fps path.
+        # Inference only: with the flag set, .train() or a recording tape raises ValueError.  `enabled_amp` keeps its meaning while unset
+        self.model_fp32 = False
         # symbol order of the y streams encode() writes and decode() expects: "raster" (compressai's, what the reference's
         # decoder reads), "wavefront" (an extension: the decoder takes an anti-diagonal per step instead of a position) or "lanes"
         # (a second extension: the wavefront sequence split over `stream_lanes` = 64 or 128 rANS sub-streams, which the decoder's
@@ -78,9 +85,11 @@ class VideoCompressor(nn.Module):
     # ----------------------------------------------------------------------------------------
     def forward(self, input_image, refer_frames, enabled_amp=True, is_compress=False, trace=None, noise=None):
         noise = noise or {}            # test hook: {"mv": {...}, "res": {...}} of fp32 FMs replaces the coders' training-mode draws
+        mf32 = self._model_fp32_checked()
         if not (input_image.is_cuda and refer_frames.is_cuda):
             raise RuntimeError("tdvc_amd.VideoCompressor runs on a HIP device only (no CPU fallback)")
-        f32 = (not enabled_amp) or self.coder_fp32
+        adt = torch.float32 if mf32 else torch.float16           # activation dtype outside the coders
+        f32 = (not enabled_amp) or self.coder_fp32 or mf32
         if self.training and self.train_coder_fp32:
             f32 = True
         elif f32 and self.training:
@@ -100,8 +109,8 @@ class VideoCompressor(nn.Module):
             x = input_image.float()
             refs = refer_frames.float().reshape(B * 4, 3, H, W)
             cur32 = ops.from_nchw(x, Cpad=4, dtype=torch.float32)
-            cur8 = ops.from_nchw(x, Cpad=8)
-            refs8 = ops.from_nchw(refs, Cpad=8)                          # (B*4,H,W,8): [I, r-3, r-2, r-1]
+            cur8 = ops.from_nchw(x, Cpad=8, dtype=adt)
+            refs8 = ops.from_nchw(refs, Cpad=8, dtype=adt)               # (B*4,H,W,8): [I, r-3, r-2, r-1]
             last = refer_frames[:, 3].float()
             ref32 = ops.from_nchw(last, Cpad=4, dtype=torch.float32)
             ref8, iframe8 = _ref_views(refs8, B)                          # frames r-1 and I: strided batch views, not second conversions
@@ -109,11 +118,11 @@ class VideoCompressor(nn.Module):
                 for t in (cur32, cur8, refs8, ref32, ref8, iframe8):
                     ops.TAPE.mark_input(t)
 
-            feats = FM.empty(B, H, W, 192, device=dev)                   # [f_cur | f_ref | dcn_out]
+            feats = FM.empty(B, H, W, 192, dtype=adt, device=dev)        # [f_cur | f_ref | dcn_out]
             npx_ = float(B * H * W)
             f_cur = self.extra_fea.run(cur8, feats.ch(0, 64))
             self.extra_fea.run(ref8, feats.ch(64, 64))
-            estmv = self.motion_est.run(feats, cur32, ref32, traced=trace is not None)
+            estmv = self.motion_est.run(feats, cur32, ref32, traced=trace is not None or mf32)
 
             tr_mv = {} if trace is not None else None
             mv_hat, mv_bits = self.mvCoder.run(estmv, training=training, trace=tr_mv, noise=noise.get("mv"), f32=f32)
@@ -122,11 +131,11 @@ class VideoCompressor(nn.Module):
                 self.mvCoder.update(force=True)
                 coded["mv"] = self.mvCoder.compress(estmv, f32=f32)
 
-            xt = FM.empty(B, H, W, 256, device=dev)                      # 4 frames x 64 ch
+            xt = FM.empty(B, H, W, 256, dtype=adt, device=dev)           # 4 frames x 64 ch
             pred1 = self.mcnet.run(mv_hat, feats, xt.ch(192, 64))
-            pred = FM.empty(B, H, W, 64, device=dev)
-            resid = FM.empty(B, H, W, 64, device=dev)
-            if modules.RESID_FUSED and modules.glue_fusions_allowed(self, trace is not None):
+            pred = FM.empty(B, H, W, 64, dtype=adt, device=dev)
+            resid = FM.empty(B, H, W, 64, dtype=adt, device=dev)
+            if modules.RESID_FUSED and modules.glue_fusions_allowed(self, trace is not None or mf32):
                 self.mcfilter.run(xt, refs8, pred, then=(f_cur, -1.0, resid))       # resid = f_cur - pred from the pass that writes pred
             else:
                 self.mcfilter.run(xt, refs8, pred)
@@ -154,15 +163,26 @@ class VideoCompressor(nn.Module):
         return recon, bpp_res, bpp_mv
 
     # ---- real encode / decode (the reference only sketches it: tools/utils/encoder.py, decoder.py) ----
+    def _model_fp32_checked(self) -> bool:
+        """`model_fp32`, refused before the first launch where the mode does not exist: training and the tape"""
+        if self.model_fp32 and (self.training or ops.TAPE is not None):
+            raise ValueError("tdvc_amd: model_fp32 is an inference / coding mode (no backward on fp32 maps outside the coders): "
+                             "unset it for .train() and under autograd.record()")
+        return bool(self.model_fp32)
+
+    def _adt(self):
+        return torch.float32 if self.model_fp32 else torch.float16
+
     def _prepare(self, refer_frames, input_image=None):
         B, _, _, H, W = refer_frames.shape
         if H % 64 or W % 64:
             raise RuntimeError(f"frames must be padded to a multiple of 64 (got {H}x{W})")
         dev = refer_frames.device
-        refs8 = ops.from_nchw(refer_frames.float().reshape(B * 4, 3, H, W), Cpad=8)
+        adt = self._adt()
+        refs8 = ops.from_nchw(refer_frames.float().reshape(B * 4, 3, H, W), Cpad=8, dtype=adt)
         last = refer_frames[:, 3].float()
         ref8, iframe8 = _ref_views(refs8, B)
-        feats = FM.empty(B, H, W, 192, device=dev)
+        feats = FM.empty(B, H, W, 192, dtype=adt, device=dev)
         self.extra_fea.run(ref8, feats.ch(64, 64))
         return B, H, W, dev, refs8, last, iframe8, feats
 
@@ -170,12 +190,13 @@ class VideoCompressor(nn.Module):
         """decoder-side reconstruction from the decoded motion latents; `res_y_hat_fn(pred)` supplies the residual latents
         (the encoder codes them against this very prediction, the decoder reads them from the stream)"""
         B, H, W, dev = feats.N, feats.H, feats.W, feats.t.device
-        mv_hat = self.mvCoder.run_g_s(mv_y_hat)
-        xt = FM.empty(B, H, W, 256, device=dev)
+        adt = feats.t.dtype
+        mv_hat = self.mvCoder.run_g_s(mv_y_hat, out_dtype=adt)
+        xt = FM.empty(B, H, W, 256, dtype=adt, device=dev)
         self.mcnet.run(mv_hat, feats, xt.ch(192, 64))
-        pred = FM.empty(B, H, W, 64, device=dev)
+        pred = FM.empty(B, H, W, 64, dtype=adt, device=dev)
         self.mcfilter.run(xt, refs8, pred)
-        recon_f = self.resCoder.run_g_s(res_y_hat_fn(pred), res=pred)
+        recon_f = self.resCoder.run_g_s(res_y_hat_fn(pred), res=pred, out_dtype=adt)
         return self.loopfilter.run(recon_f, iframe8, training=False)
 
     @torch.no_grad()
@@ -183,6 +204,7 @@ class VideoCompressor(nn.Module):
         """-> {"strings": [mv_y, mv_z, res_y, res_z] (lists over the batch), "shapes": z shapes, "recon": (B,3,H,W)}.
         The reconstruction is the DECODER's: it is built from the coded symbols, so a closed-loop encoder and the decoder
         stay bit-identical."""
+        self._model_fp32_checked()
         assert not self.training
         if self.stream_coder not in STREAM_CODERS:
             raise ValueError(f"stream_coder must be one of {STREAM_CODERS}, got {self.stream_coder!r}")
@@ -192,18 +214,19 @@ class VideoCompressor(nn.Module):
             return self._encode_batch(input_image, refer_frames)
         B, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames)
         x = input_image.float()
-        f_cur = self.extra_fea.run(ops.from_nchw(x, Cpad=8), feats.ch(0, 64))
+        adt = self._adt()
+        f_cur = self.extra_fea.run(ops.from_nchw(x, Cpad=8, dtype=adt), feats.ch(0, 64))
         estmv = self.motion_est.run(feats, ops.from_nchw(x, Cpad=4, dtype=torch.float32), ops.from_nchw(last, Cpad=4, dtype=torch.float32))
         self.mvCoder.update()
         self.resCoder.update()
-        f32 = self.coder_fp32
+        f32 = self.coder_fp32 or self.model_fp32
         mv = self.mvCoder.compress(estmv, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes,
                                     coder=self.stream_coder)                  # range coding on worker threads, or on a side stream
         cat = lambda dbg: FM(torch.cat([d["y_hat"].t for d in dbg], 0))
         out = {}
 
         def res_y_hat(pred):
-            resid = ops.scale_act_res(f_cur, FM.empty(B, H, W, 64, device=dev), res=pred, res_sign=-1.0)
+            resid = ops.scale_act_res(f_cur, FM.empty(B, H, W, 64, dtype=adt, device=dev), res=pred, res_sign=-1.0)
             out["res"] = self.resCoder.compress(resid, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes, coder=self.stream_coder)
             return cat(out["res"]["_debug"])
         recon = self._reconstruct(cat(mv["_debug"]), res_y_hat, feats, refs8, iframe8)
@@ -220,20 +243,21 @@ class VideoCompressor(nn.Module):
         im = dict(H=H, W=W, dev=dev, refs8=refs8, iframe8=iframe8, feats=feats)
         if input_image is not None:
             x = input_image[b:b + 1].float()
-            im["f_cur"] = self.extra_fea.run(ops.from_nchw(x, Cpad=8), feats.ch(0, 64))
+            im["f_cur"] = self.extra_fea.run(ops.from_nchw(x, Cpad=8, dtype=self._adt()), feats.ch(0, 64))
             im["estmv"] = self.motion_est.run(feats, ops.from_nchw(x, Cpad=4, dtype=torch.float32), ops.from_nchw(last, Cpad=4, dtype=torch.float32))
         return im
 
     def _predict(self, im, mv_y_hat: FM) -> FM:
-        mv_hat = self.mvCoder.run_g_s(mv_y_hat)
-        xt = FM.empty(1, im["H"], im["W"], 256, device=im["dev"])
+        adt = im["feats"].t.dtype
+        mv_hat = self.mvCoder.run_g_s(mv_y_hat, out_dtype=adt)
+        xt = FM.empty(1, im["H"], im["W"], 256, dtype=adt, device=im["dev"])
         self.mcnet.run(mv_hat, im["feats"], xt.ch(192, 64))
-        pred = FM.empty(1, im["H"], im["W"], 64, device=im["dev"])
+        pred = FM.empty(1, im["H"], im["W"], 64, dtype=adt, device=im["dev"])
         self.mcfilter.run(xt, im["refs8"], pred)
         return pred
 
     def _finish(self, im, res_y_hat: FM, pred: FM):
-        return self.loopfilter.run(self.resCoder.run_g_s(res_y_hat, res=pred), im["iframe8"], training=False)
+        return self.loopfilter.run(self.resCoder.run_g_s(res_y_hat, res=pred, out_dtype=pred.t.dtype), im["iframe8"], training=False)
 
     @staticmethod
     def _dense(fms) -> FM:
@@ -245,10 +269,10 @@ class VideoCompressor(nn.Module):
         ims = [self._front(refer_frames, b, input_image) for b in range(B)]
         self.mvCoder.update()
         self.resCoder.update()
-        kw = dict(f32=self.coder_fp32, order=self.stream_order, defer=True, lanes=self.stream_lanes, per_image=True, coder=self.stream_coder)
+        kw = dict(f32=self.coder_fp32 or self.model_fp32, order=self.stream_order, defer=True, lanes=self.stream_lanes, per_image=True, coder=self.stream_coder)
         mv = self.mvCoder.compress(self._dense([im["estmv"] for im in ims]), **kw)
         preds = [self._predict(im, d["y_hat"]) for im, d in zip(ims, mv["_debug"])]
-        resid = [ops.scale_act_res(im["f_cur"], FM.empty(1, im["H"], im["W"], 64, device=im["dev"]), res=p, res_sign=-1.0) for im, p in zip(ims, preds)]
+        resid = [ops.scale_act_res(im["f_cur"], FM.empty(1, im["H"], im["W"], 64, dtype=p.t.dtype, device=im["dev"]), res=p, res_sign=-1.0) for im, p in zip(ims, preds)]
         rs = self.resCoder.compress(self._dense(resid), **kw)
         recon = torch.cat([self._finish(im, d["y_hat"], p) for im, d, p in zip(ims, rs["_debug"], preds)], 0)
         mvs, rss = mv["strings"].result(), rs["strings"].result()                     # join the range coders
@@ -259,7 +283,7 @@ class VideoCompressor(nn.Module):
         ims = [self._front(refer_frames, b) for b in range(B)]
         self.mvCoder.update()
         self.resCoder.update()
-        kw = dict(synth=False, f32=self.coder_fp32, order=self.stream_order, per_image=True)
+        kw = dict(synth=False, f32=self.coder_fp32 or self.model_fp32, order=self.stream_order, per_image=True)
         mv = self.mvCoder.decompress([strings[0], strings[1]], shapes[0], **kw)["y_hat"]
         image = self.mvCoder._image
         preds = [self._predict(im, image(mv, b)) for b, im in enumerate(ims)]
@@ -269,13 +293,14 @@ class VideoCompressor(nn.Module):
     @torch.no_grad()
     def decode(self, strings, shapes, refer_frames):
         """inverse of encode(): strings [mv_y, mv_z, res_y, res_z] + z shapes + the reference list -> (B,3,H,W)"""
+        self._model_fp32_checked()
         assert not self.training
         if refer_frames.shape[0] > 1:
             return self._decode_batch(strings, shapes, refer_frames)
         B, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames)
         self.mvCoder.update()
         self.resCoder.update()
-        f32 = self.coder_fp32
+        f32 = self.coder_fp32 or self.model_fp32
         so = self.stream_order
         mv = self.mvCoder.decompress([strings[0], strings[1]], shapes[0], f32=f32, order=so)
         return self._reconstruct(mv["y_hat"], lambda pred: self.resCoder.decompress([strings[2], strings[3]], shapes[1], synth=False, f32=f32, order=so)["y_hat"],

@@ -951,13 +951,17 @@ DCN_PLANAR = __import__("os").environ.get("TDVC_DCN_PLANAR", "0") == "1"
 
 def dcn_fused(x: FM, om: FM, pc: PackedConv, out: FM, groups=8, act=ACT_NONE, slope=0.0, round16=True, planar: bool | None = None) -> FM:
     """`planar` (default: large maps): gather from a group-planar copy of x made by the same call (one extra pass over x;
-    the 288 bilinear corner gathers per pixel then share 128-byte lines between neighbouring pixels of a group)"""
+    the 288 bilinear corner gathers per pixel then share 128-byte lines between neighbouring pixels of a group).
+    An fp32 `x` selects the fp32 kernel (csrc/dcn_f32.hip: fp32 samples, offsets, mask and accumulation, the layer's fp32 weight
+    packing); `om` is then fp32 too, `out` fp32 or fp16, and there is no planar form.  Inference only."""
+    if x.f32 and TAPE is not None:
+        raise L.TdvcHipError("dcn_fused on fp32 maps is an inference form (no backward)")
     d = L.DcnDesc()
     d.x, d.om, d.y = x.desc(), om.desc(), out.desc()
-    d.w, d.bias = pc.w.data_ptr(), pc.bias.data_ptr()
+    d.w, d.bias = (pc.packed_f32() if x.f32 else pc.w).data_ptr(), pc.bias.data_ptr()
     d.groups, d.act, d.slope, d.round_before_act = groups, act, slope, int(round16)
     if planar is None:
-        planar = DCN_PLANAR and x.H * x.W >= DCN_PLANAR_MIN_PIXELS
+        planar = DCN_PLANAR and x.H * x.W >= DCN_PLANAR_MIN_PIXELS and not x.f32
     scratch = torch.empty((x.N, groups, x.H, x.W, 8), dtype=torch.float16, device=x.t.device) if planar else None
     d.x_planar = scratch.data_ptr() if scratch is not None else None
     L.check(L.lib().tdvc_dcn_fused(C.byref(d), _stream()), "dcn_fused")
@@ -1122,7 +1126,7 @@ def se_gate(x: FM, p: SEParams, partial=None) -> torch.Tensor:
 # ----------------------------------------------------------------------------- resampling
 def upsample2x(x: FM, out: FM | None = None) -> FM:
     if out is None:
-        out = FM.empty(x.N, 2 * x.H, 2 * x.W, x.C, device=x.t.device)
+        out = FM.empty(x.N, 2 * x.H, 2 * x.W, x.C, dtype=x.t.dtype, device=x.t.device)
     dx, dy = x.desc(), out.desc()
     L.check(L.lib().tdvc_upsample2x(C.byref(dx), C.byref(dy), _stream()), "upsample2x")
     _rec("upsample2x", x, out)
@@ -1166,6 +1170,8 @@ def spynet_level_input_backward(supp: FM, flow_up: FM, dcat8: FM, dflow_up: FM, 
 
 
 def resize_bilinear(x: FM, H: int, W: int, chscale: torch.Tensor | None = None) -> FM:
+    if chscale is not None and (chscale.dtype != torch.float32 or chscale.numel() < x.C):
+        raise ValueError(f"resize_bilinear: chscale needs one fp32 scale per channel ({x.C}), got {chscale.numel()} of {chscale.dtype}")
     out = FM.empty(x.N, H, W, x.C, dtype=torch.float32, device=x.t.device)
     dx, dy = x.desc(), out.desc()
     L.check(L.lib().tdvc_resize_bilinear(C.byref(dx), C.byref(dy), chscale.data_ptr() if chscale is not None else None,

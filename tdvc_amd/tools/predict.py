@@ -128,6 +128,8 @@ def main():
     ap.add_argument("--gop-batch", type=int, default=1, help="with --bitstream-dir: a rank codes this many GOPs of its shard in lockstep, frame t of all "
                                                             "of them as one batch (same files and stats as 1; a last group smaller than this runs at its own size)")
     ap.add_argument("--coder-fp32", action="store_true", help="both coders as fp32 islands (the reference's precision), also with enable_amp: True")
+    ap.add_argument("--model-fp32", action="store_true", help="every stage on fp32 maps with fp32 weights (the reference's enable_amp: False; "
+                                                              "VideoCompressor.model_fp32): the parity mode, bound by the fp32 matrix pipe")
     a = ap.parse_args()
     if a.gop_batch < 1 or (a.gop_batch > 1 and not a.bitstream_dir):
         ap.error("--gop-batch needs a value >= 1 and, above 1, --bitstream-dir (it batches the real coding)")
@@ -153,6 +155,8 @@ def main():
     # `enable_amp` says -- the reference-faithful precision for a reference checkpoint + cfg/predict.yaml (`enable_amp: True`), which
     # otherwise selects this build's fp16-in / fp32-accumulate coders
     net.coder_fp32 = bool(opt.get("coder_fp32", False)) or a.coder_fp32
+    # `model_fp32: true` (an extra yaml key, or --model-fp32): the whole model in fp32, what the reference computes with `enable_amp: False`
+    net.model_fp32 = bool(opt.get("model_fp32", False)) or a.model_fp32
     net.stream_order = a.stream_order
     net.stream_lanes = a.stream_lanes
     net.stream_coder = a.range_coder
@@ -202,6 +206,8 @@ def main():
         n = max(1, len(allstats))
         res = {"frames": len(allstats), "bpp": sum(s["bpp"] for s in allstats) / n,
                "psnr": sum(s["psnr"] for s in allstats) / n, "msssim": sum(s["msssim"] for s in allstats) / n, "seconds": time.time() - t0, "cfg": opt}
+        if net.model_fp32:
+            res["model_fp32"] = True
         timed = [s for s in allstats if "encode_s" in s]
         if timed:
             res.update(stream_order=a.stream_order, **({"stream_lanes": a.stream_lanes} if a.stream_order == "lanes" else {}),
