@@ -38,7 +38,7 @@ REVERSE_WALKERS = ["direct", "conv_mfma_v2", "conv_mfma_v3", "conv_mfma_v5", "co
 class Case:
     id: str
     kernel: str               # what tdvc_conv_select / tdvc_last_conv_kernel must name ("direct": any conv_mfma<..>)
-    form: str                 # "e4" | "generic" | "lean" | "gdn" (pool rounded to fp16 before the root) | "pair"
+    form: str                 # "e4" | "generic" | "lean" | "gdn" (pool rounded to fp16 before the root) | "gdn32" (conv_f32: fp32 pool and multiplicand) | "pair"
     cin: int
     cout: int
     win: int
@@ -59,6 +59,9 @@ class Case:
     x_f32: bool = False
     chan_sum: bool = False
     views: bool = False       # x, y, res, res2 are channel windows of wider, sentinel-filled buffers
+    res_c: int = 0            # res is a dense map of its own with only this many channels (fewer than y's): SPyNet's 2-channel flow
+    slices: str = None        # None | "all" | "last1": x, y, res are FM.as_slices(1, 4, 64) of 2 x H x W x 256 buffers (image stride 64 <
+                              # pixel stride 256, the LoopFilter's frame slices), N = 4; "last1": .batch(3, 1) of them, N = 1
     switches: tuple = ()      # ((setter, value while the case runs, value restored), ...)
     multi: bool = False       # more tiles (rows) than workgroups, with a remainder -- or, for the one-tile-per-workgroup kernels, many tiles
     ragged: bool = False      # the map is no multiple of the kernel's tile in either direction
@@ -216,6 +219,89 @@ CASES = [
     C("f32_views", "conv_f32", "e4", 64, 64, W3, 2, 33, 47, act=ACT_RELU, x_f32=True, out="f32", res="f32", views=True, ragged=True),
 ]
 
+
+def _f32(id, cin, cout, win, N, H, W, form="e4", **kw):
+    return Case(id, "conv_f32", form, cin, cout, win, N, H, W, x_f32=True, ragged=True, **{"out": "f32", **kw})
+
+
+# ---- conv_f32, whole-model fp32 mode: every instantiation <MT, NT> (f32_variant) at the smallest maps that take it.  A workgroup is 2 pixel
+# blocks of NT groups of 32 pixels, flattened over batch, rows and columns.  Output maps:
+#   1 x 129 x 131 = 16899 = 132 * 128 + 3   NT 2: the last workgroup's first block has 3 pixels, its second group and second block none
+#   2 x  91 x  93 = 16926 = 132 * 128 + 30  NT 2: image 0 ends at pixel 8463 = 264 * 32 + 15, inside a 32-pixel group
+#   1 x  33 x  47 =  1551 =  24 *  64 + 15  NT 1: the same tail; 2 x 33 x 47 = 3102 = 48 * 64 + 30 with image 0 ending inside a group
+#   1 x  19 x  37 =   703 =  10 *  64 + 63  NT 1: a full first block and a second block of 31 pixels
+#   4 x  65 x  65 = 16900 = 132 * 128 + 4   NT 2 on the four frame slices of one image
+_FIRST_NEW_F32 = len(CASES)
+CASES += [
+    # SPyNet's 7x7 layers (ck 8: 49 taps, the zero-weight padded half step); 16 -> 2 adds the 2-channel fp32 flow into an 8-channel map
+    _f32("f32_7x7_8_32", 8, 32, W7, 1, 33, 47, act=ACT_RELU),
+    _f32("f32_7x7_8_32_nt2", 8, 32, W7, 1, 129, 131, act=ACT_RELU, grade="dyadic"),
+    _f32("f32_7x7_32_64", 32, 64, W7, 2, 33, 47, act=ACT_RELU),
+    _f32("f32_7x7_32_64_nt2", 32, 64, W7, 2, 91, 93, act=ACT_RELU, density=0.5),
+    _f32("f32_7x7_64_32", 64, 32, W7, 1, 19, 37, act=ACT_RELU, grade="dyadic"),
+    _f32("f32_7x7_64_32_nt2", 64, 32, W7, 1, 129, 131, act=ACT_RELU, density=0.5),
+    _f32("f32_7x7_32_16", 32, 16, W7, 2, 33, 47, act=ACT_RELU),
+    _f32("f32_7x7_32_16_nt2", 32, 16, W7, 2, 91, 93, act=ACT_RELU, grade="dyadic"),
+    _f32("f32_7x7_16_2", 16, 2, W7, 1, 33, 47, res="f32", res_c=2),
+    _f32("f32_7x7_16_2_nt2", 16, 2, W7, 1, 129, 131, res="f32", res_c=2, grade="dyadic"),
+    # 3x3 64 -> 64, <2, 2>: the feature extractor, the residual stacks (one and two fp32 residuals), MCNet / LoopFilter windows
+    _f32("f32_c64_nt2_none", 64, 64, W3, 1, 129, 131),
+    _f32("f32_c64_nt2_none_views", 64, 64, W3, 2, 91, 93, views=True),
+    _f32("f32_c64_nt2_relu", 64, 64, W3, 1, 129, 131, act=ACT_RELU, grade="dyadic"),
+    _f32("f32_c64_nt2_lrelu", 64, 64, W3, 2, 91, 93, act=ACT_LRELU, slope=0.25),
+    _f32("f32_c64_nt2_lrelu_views", 64, 64, W3, 1, 129, 131, act=ACT_LRELU, slope=0.1, views=True, grade="dyadic"),
+    _f32("f32_c64_nt2_res", 64, 64, W3, 1, 129, 131, res="f32", grade="dyadic"),
+    _f32("f32_c64_nt2_res_views", 64, 64, W3, 2, 91, 93, res="f32", views=True),
+    _f32("f32_c64_nt2_res12", 64, 64, W3, 1, 129, 131, res="f32", res2="f32"),                               # F32MAPS: an fp32 res2
+    _f32("f32_c64_nt2_res12_views", 64, 64, W3, 2, 91, 93, res="f32", res2="f32", views=True, grade="dyadic"),
+    _f32("f32_c64_nt2_f16res_f32res2", 64, 64, W3, 1, 129, 131, act=ACT_LRELU, slope=0.1, res="f16", res2="f32", grade="dyadic"),
+    # the LoopFilter's frame slices: image stride 64 < pixel stride 256; with and without .batch(3, 1)
+    _f32("f32_slices_none", 64, 64, W3, 4, 65, 65, slices="all"),
+    _f32("f32_slices_res", 64, 64, W3, 4, 65, 65, res="f32", slices="all", grade="dyadic"),
+    _f32("f32_slices_lrelu", 64, 64, W3, 4, 65, 65, act=ACT_LRELU, slope=0.25, slices="all"),
+    _f32("f32_slices_last1_lrelu", 64, 64, W3, 1, 129, 131, act=ACT_LRELU, slope=0.1, slices="last1", grade="dyadic"),
+    # 3x3 64 -> 64, <2, 1>
+    _f32("f32_c64_none_views", 64, 64, W3, 2, 33, 47, views=True),
+    _f32("f32_c64_lrelu", 64, 64, W3, 1, 19, 37, act=ACT_LRELU, slope=0.25),
+    _f32("f32_c64_lrelu_views", 64, 64, W3, 2, 33, 47, act=ACT_LRELU, slope=0.1, views=True, grade="dyadic"),
+    # the plain stride-2 form (fp32 maps never take the space-to-depth view) on odd input maps: 65 x 93 -> 33 x 47, 257 x 261 -> 129 x 131
+    _f32("f32_s2_c64_views", 64, 64, S3, 1, 65, 93, act=ACT_LRELU, slope=0.25, views=True),
+    _f32("f32_s2_c64_views_nt2", 64, 64, S3, 1, 257, 261, act=ACT_LRELU, slope=0.1, views=True, grade="dyadic"),
+    _f32("f32_c8_64_nt2", 8, 64, W3, 1, 129, 131, act=ACT_LRELU, slope=0.25),
+    # conv_offset_mask, cout 216: rows 216..255 of the last cout tiles store nothing
+    _f32("f32_c64_216_nt2", 64, 216, W3, 1, 129, 131),
+    _f32("f32_c64_216_views", 64, 216, W3, 2, 33, 47, views=True, grade="dyadic"),
+    # the model's last layer: clamp into planar fp32
+    _f32("f32_c64_3_nchw_nt2", 64, 3, W3, 1, 129, 131, act=ACT_CLAMP01, out="nchw", grade="dyadic"),
+    # 3x3 128 -> 64 and the 1x1 layers (Cin 192 = 6 chunks of ck 32, 256 = 8)
+    _f32("f32_c128_64_lrelu", 128, 64, W3, 1, 33, 47, act=ACT_LRELU, slope=0.25, density=0.5),
+    _f32("f32_c128_64_nt2_none", 128, 64, W3, 1, 129, 131, density=0.5),
+    _f32("f32_c128_64_nt2_lrelu", 128, 64, W3, 2, 91, 93, act=ACT_LRELU, slope=0.1, grade="dyadic", density=0.5),
+    _f32("f32_c128_64_nt2_lrelu_views", 128, 64, W3, 1, 129, 131, act=ACT_LRELU, slope=0.25, views=True, density=0.5),
+    _f32("f32_1x1_192_64_nt2_views", 192, 64, W1, 1, 129, 131, views=True),
+    _f32("f32_1x1_128_64_lrelu", 128, 64, W1, 2, 33, 47, act=ACT_LRELU, slope=0.1, grade="dyadic"),
+    _f32("f32_1x1_128_64_nt2_lrelu", 128, 64, W1, 1, 129, 131, act=ACT_LRELU, slope=0.25),
+    _f32("f32_1x1_256_64_nt2_lrelu", 256, 64, W1, 2, 91, 93, act=ACT_LRELU, slope=0.1, grade="dyadic"),
+    # fp32 GDN / inverse GDN: fp32 pool, fp32 multiplicand (conv_common.h:99-102), float64 grade
+    _f32("f32_gdn_fwd_c128", 128, 128, W1, 1, 33, 47, form="gdn32", gdn=GDN_FWD, res="f32", grade="f64"),
+    _f32("f32_gdn_inv_c128", 128, 128, W1, 1, 33, 47, form="gdn32", gdn=GDN_INV, res="f32", grade="f64"),
+    _f32("f32_gdn_fwd_c64", 64, 64, W1, 1, 33, 47, form="gdn32", gdn=GDN_FWD, grade="f64"),
+    _f32("f32_gdn_inv_c64", 64, 64, W1, 1, 33, 47, form="gdn32", gdn=GDN_INV, grade="f64"),
+]
+F32_MODE_CASES = CASES[_FIRST_NEW_F32:]         # tests/test_conv_exact_cases_cpu.py checks the exactness preconditions of these on the CPU
+
+# (window (kh, kw, taps), stride, Cin, cout) of every conv that `VideoCompressor.model_fp32` runs on fp32 maps.  F32_LAYERS: everything
+# outside the two coders -- each call class of these (conv_f32_class) has a row above; F32_CODER_LAYERS: the layers of MVCoder / ResCoder,
+# whose shapes tests/test_conv_f32_gpu.py holds.  tests/test_fp32_ops_gpu.py::test_model_fp32_call_classes_have_cases holds the union to
+# what production reaches, in both directions.
+_K1, _K3, _K7, _KM = (1, 1, 1), (3, 3, 9), (7, 7, 49), (5, 5, 12)
+F32_LAYERS = {(_K7, 1, 8, 32), (_K7, 1, 32, 64), (_K7, 1, 64, 32), (_K7, 1, 32, 16), (_K7, 1, 16, 2),
+              (_K3, 1, 8, 64), (_K3, 1, 64, 64), (_K3, 2, 64, 64), (_K3, 1, 64, 216), (_K3, 1, 64, 3), (_K3, 1, 128, 64),
+              (_K1, 1, 128, 64), (_K1, 1, 192, 64), (_K1, 1, 256, 64)}
+F32_CODER_LAYERS = {(_K3, 2, 64, 128), (_K3, 2, 128, 128), (_K3, 1, 128, 128), (_K1, 2, 64, 128), (_K1, 2, 128, 128), (_K1, 1, 128, 128),
+                    (_K3, 1, 128, 192), (_K3, 1, 192, 256), (_K3, 1, 128, 256), (_K3, 1, 128, 512), (_K3, 1, 192, 768), (_KM, 1, 128, 256),
+                    (_K1, 1, 512, 426), (_K1, 1, 432, 341), (_K1, 1, 344, 256)}
+
 # conv_pair: two 3x3 64 -> 64 convs in one launch; strips of 30 or 62 columns (both run for every case)
 PAIR_CASES = [
     C("pair_w61", "conv_pair", "pair", 64, 64, W3, 1, 135, 61, act=ACT_RELU, add_input=True, ragged=True),                         # 62 k - 1
@@ -236,6 +322,38 @@ def out_map(case):
     return (case.H + 2 * pad - kh) // stride + 1, (case.W + 2 * pad - kw) // stride + 1
 
 
+def f32_variant_of(cout, npix):
+    """conv_f32's template instantiation <MT, NT> (csrc/conv_f32.hip:290-297): one 32-row cout tile up to cout 32, else two per wave;
+    two 32-pixel groups per wave from N * Ho * Wo = 16384 output pixels on"""
+    return (1 if cout <= 32 else 2, 2 if npix >= 16384 else 1)
+
+
+def f32_variant(case):
+    Ho, Wo = out_map(case)
+    return f32_variant_of(case.cout, case.N * Ho * Wo)
+
+
+def conv_f32_class(L, d):
+    """the call class of a conv_f32 launch, from its descriptor (a case's guard_desc or a production call's ops.conv_desc):
+    (window (kh, kw, taps), stride, Cin, cout, <MT, NT>, act, (dtype, C) of res and res2, (gdn, dtype of the multiplicand), output
+    kind, output dtype, layout).  Layout: "slices" when a map's image stride is smaller than its pixel stride (FM.as_slices), else
+    "window" when a map's pixel stride exceeds its channels, else "dense"."""
+    Ho = (d.x.H + 2 * d.pad - d.kh) // d.stride + 1
+    Wo = (d.x.W + 2 * d.pad - d.kw) // d.stride + 1
+    dt = lambda m: "f32" if m.dtype == L.F32 else "f16"
+    rs = lambda m: (dt(m), int(m.C)) if m.p else None
+    kind = {L.OUT_NHWC: "nhwc", L.OUT_SHUFFLE2: "shuffle", L.OUT_NCHW_F32: "nchw"}[d.out_mode]
+    maps = [d.x] + ([d.y] if kind != "nchw" else []) + [m for m in (d.res, d.res2, d.aux) if m.p]
+    layout = "slices" if any(m.sn < m.sp for m in maps) else "window" if any(m.sp != m.C for m in maps) else "dense"
+    return ((int(d.kh), int(d.kw), int(d.ntaps)), int(d.stride), int(d.x.C), int(d.cout), f32_variant_of(d.cout, d.x.N * Ho * Wo), int(d.act),
+            rs(d.res), rs(d.res2), (int(d.gdn), dt(d.aux)) if d.gdn else None, kind, "f32" if kind == "nchw" else dt(d.y), layout)
+
+
+def f32_layer(cls):
+    """(window, stride, Cin, cout) of a conv_f32 class"""
+    return cls[:4]
+
+
 def x_channels(case):
     return HD.pad8(case.cin)
 
@@ -252,7 +370,11 @@ def y_channels(case):
 def guard_desc(L, pick_ck, case):
     """the descriptor ops.conv builds for the case, over dummy pointers (helpers_conv_dispatch)"""
     kw = dict(act=case.act, slope=case.slope, res=case.res, res2=case.res2, out=case.out, narrow=case.narrow)
-    if case.gdn:
+    if case.form == "gdn32":                # the GDN call of ops.conv on fp32 maps: x, the multiplicand (aux == x), res and y all fp32
+        d = HD.desc(L, lambda *a: 32, case.cin, case.cout, window(case), case.H, case.W, case.N, res=case.res, out="f32", x_f32=True)
+        d.square_input, d.gdn = 1, case.gdn
+        d.aux = HD.fmap(L, HD.PX, case.N, case.H, case.W, case.cin, dtype=L.F32)
+    elif case.gdn:
         d = HD.gdn_desc(L, case.cin, case.H, case.W, case.N, case.gdn, res=case.res)
     elif case.bcast:
         d = HD.bcast_desc(L, case.cin, case.H, case.W, case.N)
@@ -271,6 +393,14 @@ def guard_desc(L, pick_ck, case):
                 if m.p:
                     m.C = m.sp = case.cout
                     m.sn = m.H * m.W * m.sp
+    if case.res_c:                                                       # a dense residual map of its own, narrower than y
+        d.res.C = d.res.sp = case.res_c
+        d.res.sn = d.res.H * d.res.W * case.res_c
+    if case.slices:                                                      # FM.as_slices(b, 4, 64) [.batch(3, 1)]: images interleaved inside a pixel
+        assert case.cin == case.cout == 64 and case.N == (4 if case.slices == "all" else 1) and not case.views and not case.res2, case.id
+        for m in (d.x, d.y, d.res):
+            if m.p:
+                m.sn, m.sp = 64, 256
     if case.views and not case.bcast:                                    # wider buffers: only the strides change
         for m, extra in ((d.x, 16), (d.y, 24), (d.res, 8), (d.res2, 40)):
             if m.p:
@@ -486,6 +616,16 @@ def f64_reference(case, d):
         if d.r1 is not None:
             ref, mag = ref + d.r1.double(), mag + d.r1.double().abs()
         d.ref = ref
+        if case.form == "gdn32":
+            # conv_f32, fp32 multiplicand and fp32 store (conv_common.h:99-102): a (1.0f / sqrtf(pool)) forward, a sqrtf(pool) inverse.  The
+            # library is built without fast-math and hipcc rounds fp32 sqrt and division correctly by default (no
+            # -fno-hip-fp32-correctly-rounded-divide-sqrt, csrc/Makefile), so each operation errs by at most EPS32 relative.  The pool and
+            # a are exact: forward = root, division, product (3), inverse = root, product (2) roundings of the term, one more of the sum
+            # when a residual is added, none at the fp32 store.  1 + 2^-16 covers the second-order terms.
+            assert case.out == "f32"
+            k = 3 if case.gdn == GDN_FWD else 2
+            d.tol = (k * term.abs() + (ref.abs() if d.r1 is not None else 0.0)) * EPS32 * (1 + 2.0 ** -16)
+            return d
         d.tol = (R16 * ref.abs() if d.r1 is None else EPS16 * ref.abs() + 8 * EPS32 * mag) + TINY16
         return d
     assert case.act == ACT_SIGMOID

@@ -34,7 +34,8 @@ def test_case_ids_are_unique_and_forms_known():
     ids = [c.id for c in X.CASES + X.PAIR_CASES]
     assert len(ids) == len(set(ids))
     for c in X.CASES:
-        assert c.form in ("e4", "generic", "lean", "gdn") and c.grade in ("int", "dyadic", "f64"), c.id
+        assert c.form in ("e4", "generic", "lean", "gdn", "gdn32") and c.grade in ("int", "dyadic", "f64"), c.id
+        assert (c.form == "gdn32") == bool(c.gdn and c.x_f32), c.id
         assert (c.grade == "f64") == bool(c.gdn or c.act == X.ACT_SIGMOID), c.id       # float64 only where the operation is inexact
 
 
@@ -97,3 +98,71 @@ def test_conv_row_multi_flag_is_the_arithmetic(case):
 def test_conv_row_has_long_runs():
     """the steady-state row loop: at least one case whose runs are ten rows or more"""
     assert any(rows // slots >= 10 for rows, slots, _ in map(row_runs, ROW_CASES))
+
+
+# ------------------------------------------------------------------------------------------------- conv_f32: the whole-model fp32 mode
+F32 = [c for c in X.CASES if c.kernel == "conv_f32"]
+
+
+def _npix(c):
+    Ho, Wo = X.out_map(c)
+    return c.N * Ho * Wo, Ho * Wo
+
+
+def test_f32_rows_reach_every_instantiation_and_its_tails(report):
+    """conv_f32_kernel<MT, NT> (csrc/conv_f32.hip:290-297): all four instantiations have an integer row and a dyadic row, a row whose last
+    workgroup holds a partial first pixel block and an empty second one, and a batch whose first image ends inside a 32-pixel group"""
+    by = {}
+    for c in F32:
+        assert c.x_f32 and c.ragged, c.id
+        by.setdefault(X.f32_variant(c), []).append(c)
+    report("conv_f32 rows per <MT, NT>: " + ", ".join(f"{v} {len(cs)}" for v, cs in sorted(by.items())))
+    assert set(by) == {(1, 1), (1, 2), (2, 1), (2, 2)}, sorted(by)
+    for (mt, nt), cs in by.items():
+        assert {"int", "dyadic"} <= {c.grade for c in cs}, (mt, nt)
+        assert all(_npix(c)[0] % (64 * nt) for c in cs), (mt, nt)                                     # `ragged` is the arithmetic
+        assert any(0 < _npix(c)[0] % (64 * nt) < 32 * nt for c in cs), (mt, nt)
+        assert any(32 < _npix(c)[0] % 64 < 64 for c in cs) or nt == 2, (mt, nt)                       # NT 1: a short second block as well
+        assert any(c.N > 1 and _npix(c)[1] % 32 for c in cs), (mt, nt)
+    assert any(32 < _npix(c)[0] % 64 < 64 for c in F32 if X.f32_variant(c)[1] == 1)
+
+
+def test_f32_variant_restates_the_launcher():
+    """X.f32_variant_of is a restatement: the two conditions it restates must stand in the launcher as cited (csrc/conv_f32.hip:290-297), so
+    a changed threshold or a forced branch there fails here instead of silently moving the rows off an instantiation"""
+    import os
+    import tdvc_amd
+    src = open(os.path.join(os.path.dirname(tdvc_amd.__file__), "csrc", "conv_f32.hip")).read()
+    assert "const bool big = e.total_px >= 16384;" in src
+    assert "inline int cout_tiles32(int cout) { return cout <= 32 ? 1 : 2 * ((cout + 63) / 64); }" in src
+    for inst, cond in (("<1, 2>", "if (big)"), ("<1, 1>", "else"), ("<2, 2>", "if (big)"), ("<2, 1>", "else")):
+        line = [ln for ln in src.splitlines() if "hipLaunchKernelGGL((conv_f32_kernel" + inst in ln]
+        assert len(line) == 1 and line[0].strip().startswith(cond), inst
+    assert X.f32_variant_of(32, 16383) == (1, 1) and X.f32_variant_of(33, 16384) == (2, 2)
+
+
+def test_f32_rows_have_every_layer_of_the_fp32_mode():
+    """every layer outside the coders that model_fp32 runs on fp32 maps (X.F32_LAYERS, which the GPU guard holds to production) has a row;
+    no layer is claimed twice"""
+    have = {X.f32_layer(X.conv_f32_class(L, X.guard_desc(L, ops._pick_ck, c))) for c in F32}
+    assert X.F32_LAYERS <= have, sorted(X.F32_LAYERS - have, key=str)
+    assert not (X.F32_LAYERS & X.F32_CODER_LAYERS)
+    forms = {(c.res, c.res2) for c in F32}
+    assert ("f32", "f32") in forms and ("f16", "f32") in forms                                        # the F32MAPS branch of res2
+    assert any(c.res_c == 2 and c.cout == 2 for c in F32) and any(c.cout == 216 and c.views for c in F32) and any(c.out == "nchw" for c in F32)
+    assert {(c.slices, c.act, c.res) for c in F32 if c.slices} == {("all", X.ACT_NONE, None), ("all", X.ACT_NONE, "f32"), ("all", X.ACT_LRELU, None),
+                                                                    ("last1", X.ACT_LRELU, None)}          # the LoopFilter's calls on frame slices
+    assert {(c.gdn, c.cin) for c in F32 if c.form == "gdn32"} == {(g, ch) for g in (X.GDN_FWD, X.GDN_INV) for ch in (64, 128)}
+
+
+@pytest.mark.parametrize("case", X.F32_MODE_CASES, ids=lambda c: c.id)
+def test_f32_mode_rows_meet_their_preconditions(case):
+    """X.reference asserts check_exact on the reference (sums below 2^24 in the accumulator's unit, integer stages exact fp16 values); the
+    float64 rows get a positive pool and a finite bound"""
+    d = X.reference(case, X.make_data(case))
+    _, yc = X.y_channels(case)
+    assert d.ref.shape[1] == yc and bool(d.ref.isfinite().all())
+    if case.grade == "f64":
+        assert bool((d.tol >= 0).all()) and float(d.tol.max()) < 1e-5
+    else:
+        assert float(d.ref.abs().max()) > 0

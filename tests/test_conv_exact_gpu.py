@@ -6,6 +6,9 @@ table, the three grades of data and the restated rounding sequences).
   * float64 grade (GDN, sigmoid): the bound derived in helpers_conv_exact.f64_reference, element by element;
   * the kernel that ran is the kernel the case names (tests/test_conv_exact_cases_cpu.py holds the same table to tdvc_conv_select
     without a GPU);
+  * conv_f32 in the whole-model fp32 mode: all four instantiations, the LoopFilter's frame slices (SliceWindow), a residual narrower than
+    the output, fp32 GDN; each row's call class is asserted to be the class its table entry declares (the fp32 guard of
+    tests/test_fp32_ops_gpu.py compares those classes with production's);
   * kernels that walk their tiles in both directions run three times: twice under tdvc_debug_set_conv_walk(1) -- consecutive launches
     necessarily walk in opposite directions, whatever the parity was on entry -- and once under (0); all three must give the
     reference's bits.  The walk direction must never change a bit of the output."""
@@ -84,6 +87,40 @@ class Window:
         return torch.equal(self.buf, self.start)
 
 
+class SliceWindow:
+    """the LoopFilter's frame slices: FM.as_slices(1, 4, 64) of a sentinel-filled 2 x H x W x 256 buffer -- image n of the view is channels
+    [64 n, 64 n + 64) of every pixel of image 1, image stride 64 < pixel stride 256 -- or `count` of the four from slice `first` on
+    (.batch(first, count)).  Same interface as Window."""
+
+    def __init__(self, ops, H, W, dtype, first=0, count=4, content=None):
+        self.buf = torch.full((2, H, W, 256), SENT, dtype=dtype, device="cuda")
+        self.lo, self.n = 64 * first, count
+        self.fm = ops.FM(self.buf).as_slices(1, 4, 64)
+        if (first, count) != (0, 4):
+            self.fm = self.fm.batch(first, count)
+        assert self.fm.sn == 64 and self.fm.sp == 256 and self.fm.N == count
+        if content is not None:          # (count, c <= 64, H, W) fp32 on the CPU
+            nhwc = torch.zeros(H, W, count, 64, dtype=dtype)
+            nhwc[..., :content.shape[1]] = content.permute(2, 3, 0, 1).to(dtype)
+            self.buf[1, :, :, self.lo:self.lo + 64 * count] = nhwc.reshape(H, W, 64 * count).cuda()
+        self.start = self.buf.clone()
+
+    def reset(self):
+        self.buf.copy_(self.start)
+
+    def inside(self):
+        v = self.buf[1, :, :, self.lo:self.lo + 64 * self.n].float().cpu()
+        return v.reshape(v.shape[0], v.shape[1], self.n, 64).permute(2, 3, 0, 1).contiguous()
+
+    def outside_intact(self):
+        o = self.buf.clone()
+        o[1, :, :, self.lo:self.lo + 64 * self.n] = SENT
+        return bool((o == SENT).all())
+
+    def unchanged(self):
+        return torch.equal(self.buf, self.start)
+
+
 def first_mismatch(got, want):
     """where the kernel is wrong: the failing pixel, channel or tile index usually names the line"""
     bad = (got != want).nonzero()
@@ -128,12 +165,19 @@ def test_conv_exact(case, report):
     yv, _ = X.y_channels(case)
     v = case.views
     f32 = torch.float32
-    x = Window(ops, case.N, case.H, case.W, X.x_channels(case), f32 if case.x_f32 else torch.float16, 8 * v, 8 * v, d.x)
+    sl = (3, 1) if case.slices == "last1" else (0, 4)
+    if case.slices:
+        x = SliceWindow(ops, case.H, case.W, f32, *sl, content=d.x)
+    else:
+        x = Window(ops, case.N, case.H, case.W, X.x_channels(case), f32 if case.x_f32 else torch.float16, 8 * v, 8 * v, d.x)
     pc = ops.pack_conv(d.w, d.b, stride=stride, pad=pad, taps=taps, shuffle=case.out == "shuffle")
     res = {}
     for key, kind, r, (b, a) in (("res", case.res, d.r1, (0, 8)), ("res2", case.res2, d.r2, (16, 24))):
-        if kind:
-            res[key] = Window(ops, case.N, yH, yW, yv, f32 if kind == "f32" else torch.float16, b * v, a * v, r)
+        if kind and case.slices:
+            res[key] = SliceWindow(ops, yH, yW, f32 if kind == "f32" else torch.float16, *sl, content=r)
+        elif kind:
+            rc = case.res_c if key == "res" and case.res_c else yv          # res_c: a dense residual map narrower than y
+            res[key] = Window(ops, case.N, yH, yW, rc, f32 if kind == "f32" else torch.float16, b * v, a * v, r[:, :rc])
     kwargs = dict(act=case.act, slope=case.slope, round16=case.round16, **{k: w.fm for k, w in res.items()})
     nchw = None
     if case.bcast:
@@ -146,11 +190,19 @@ def test_conv_exact(case, report):
     elif case.out == "nchw":
         nchw = torch.full((case.N, case.cout, Ho, Wo), SENT, device="cuda")
         kwargs["nchw_out"] = nchw
+    elif case.slices:
+        y = SliceWindow(ops, yH, yW, f32 if case.out == "f32" else torch.float16, *sl)
+        kwargs["out"] = y.fm
     else:
         y = Window(ops, case.N, yH, yW, yv, f32 if case.out == "f32" else torch.float16, 8 * v, case.narrow + 16 * v)
         kwargs["out"] = y.fm
     if case.gdn:
         kwargs.update(square=True, gdn=case.gdn, aux=x.fm)
+
+    if case.x_f32 and case.bias:             # the row's call class (the fp32 guard compares these with production's) is that of this very launch
+        real = X.conv_f32_class(L, ops.conv_desc(x.fm, pc, **kwargs)[0])
+        assert real == X.conv_f32_class(L, X.guard_desc(L, ops._pick_ck, case)), (case.id, real)
+        assert real[4] == X.f32_variant(case), (case.id, real[4])
 
     def launch():
         sums = [] if case.chan_sum else None

@@ -1,5 +1,6 @@
 """The fp32 conv form (conv_f32.hip, the reference's fp32 islands: pnet.py:33,57) vs torch's fp32 conv on the same
-fp32 operands: only the summation order differs, so the gate is 1e-5 of the result's scale."""
+fp32 operands: only the summation order differs, so the gate is 1e-5 of the result's scale.  Next to it, for the same cases, a float64
+reference with a bound counted per element (test_conv_f32_plain)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -9,6 +10,7 @@ from util import assert_close, fm_to_cpu, randn, to_fm
 pytestmark = pytest.mark.gpu
 
 RT, AT = 2e-5, 2e-5
+EPS32 = 2.0 ** -24
 
 
 def _ops():
@@ -32,7 +34,17 @@ CASES = [
     ("1x1_1536_256_ctx", 1, 1536, 256, 1, 1, 0, 1, 7),
     ("3x3_128_128_1x1", 1, 128, 128, 3, 1, 1, 1, 1),
     ("3x3_128_128_2x2", 2, 128, 128, 3, 1, 1, 2, 2),
+    ("3x3_128_512", 1, 128, 512, 3, 1, 1, 8, 12),          # the sub-pixel layers of g_s / h_s, as plain convs
+    ("3x3_192_768", 1, 192, 768, 3, 1, 1, 4, 6),
+    ("1x1_128_128", 1, 128, 128, 1, 1, 0, 16, 24),         # the GDN pools' geometry
 ]
+
+
+def layers():
+    """(window (kh, kw, taps), stride, padded Cin, cout) of every layer shape this module runs: the table, the masked 5x5 context conv and
+    the 3x3 128 -> 256 sub-pixel conv of the two tests below.  tests/test_fp32_ops_gpu.py holds helpers_conv_exact.F32_CODER_LAYERS to it"""
+    pad8 = lambda c: (c + 7) // 8 * 8
+    return {((k, k, k * k), s, pad8(cin), cout) for (_, _, cin, cout, k, s, _, _, _) in CASES} | {((5, 5, 12), 1, 128, 256), ((3, 3, 9), 1, 128, 256)}
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
@@ -46,7 +58,19 @@ def test_conv_f32_plain(case, report):
     pc = ops.pack_conv(w, b, stride=s, pad=p)
     y = ops.conv(to_fm(x, ops, Cpad=ops.pad8(cin), dtype=torch.float32), pc, act=ops.ACT_LRELU, slope=0.01)
     assert y.f32 and ops.L.lib().tdvc_last_conv_kernel() == b"conv_f32"
-    assert_close(fm_to_cpu(y, cout), ref, RT, AT, f"conv_f32 {name}", report)
+    got = fm_to_cpu(y, cout)
+    assert_close(got, ref, RT, AT, f"conv_f32 {name}", report)
+    # the same outputs against float64, element by element.  x, w and b are fp32 values, so the only errors are the kernel's: the K = cin k k
+    # products are exact in the fp32 MFMA's wider product or rounded once each, the K accumulations and the bias add round once each --
+    # (K + 2) EPS32 (|w| (*) |x| + |b|) in any summation order, before the activation.  LeakyReLU is 1-Lipschitz, and its product with the
+    # slope rounds once more: + EPS32 |ref|.
+    x64, w64, b64 = x.double(), w.double(), b.double()
+    v64 = F.conv2d(x64, w64, b64, stride=s, padding=p)
+    ref64 = torch.where(v64 > 0, v64, v64 * float(torch.tensor(0.01, dtype=torch.float32)))
+    bound = (cin * k * k + 2) * EPS32 * F.conv2d(x64.abs(), w64.abs(), b64.abs(), stride=s, padding=p) + EPS32 * ref64.abs()
+    err = (got.double() - ref64).abs()
+    report(f"conv_f32 {name} vs float64: max(|d|/bound) = {float((err / bound).max()):.4f}, max |d| = {float(err.max()):.3e}")
+    assert bool((err <= bound).all()), f"conv_f32 {name}: {int((err > bound).sum())} outputs outside the counted float64 bound"
     if y.C > cout:      # padded channels must be exactly zero (they feed the next layer)
         assert float(fm_to_cpu(y)[:, cout:].abs().max()) == 0.0
 

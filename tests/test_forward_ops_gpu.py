@@ -1,7 +1,9 @@
 """Op-level tests of the forward streaming kernels (csrc/pointwise.hip) against float64 references.
 
-Every launcher has a case table that reaches each of its dispatch forks and size-gated branches at the smallest size that takes
-them, plus the edge shapes (odd extents, 1-pixel rows and columns, N > 1) and feature-map views: channel slices (off != 0, pixel
+Every launcher here has a case table that reaches each of its dispatch forks and size-gated branches at the smallest size that takes
+them (the fp32-map and mixed-dtype forms of add_flow, bcast_add_act, upsample2x and spynet_level_input's cat8, and every form of avgpool_k,
+match_gather, channel_sum and cast_f32 / copy_cast live in tests/test_fp32_ops_gpu.py with tables in tests/helpers_fp32_ops.py; the call
+classes below carry the dtypes, so the guard here and the fp32 guard there use one definition), plus the edge shapes (odd extents, 1-pixel rows and columns, N > 1) and feature-map views: channel slices (off != 0, pixel
 stride > C), batch slices (FM.batch) and frame slices (FM.as_slices: images interleaved inside a pixel).  Output buffers are filled
 with a NaN sentinel first; everything outside the view must come back byte-identical.  Inputs are exactly representable in the dtype the kernel reads.
 
@@ -141,8 +143,8 @@ def cls_se_gate(C_, nblocks):
     return ("se_gate", C_, "loop4" if nblocks > 3 * se_ways(C_) else "tail")
 
 
-def cls_bcast(T):
-    return ("bcast_add_act", "t4" if T == 4 else "generic")        # :733
+def cls_bcast(T, xdt="f16", bdt="f16"):
+    return ("bcast_add_act", "t4" if T == 4 and xdt == bdt == "f16" else "generic", xdt, bdt)        # tdvc_bcast_add_act: fp32 maps take the generic kernel
 
 
 def cls_eb(numel, noise, zhat_f32):
@@ -172,7 +174,7 @@ def cls_resize(x, H, W, chscale):
 # (N, C, H, W, Cview, Cbuf, c0, dtype): nchw_to_fmap writes channels [c0, c0 + Cview) of a Cbuf-channel buffer (zeros beyond C)
 LAYOUT_CASES = [(1, 3, 5, 7, 4, 4, 0, torch.float32), (2, 3, 5, 7, 8, 8, 0, torch.float16), (2, 3, 1, 9, 3, 12, 4, torch.float32),
                 (3, 11, 6, 1, 16, 24, 8, torch.float16), (2, 64, 4, 6, 64, 128, 64, torch.float16), (1, 2, 7, 3, 2, 2, 0, torch.float32),
-                (2, 3, 4, 5, 8, 16, 8, torch.float16)]
+                (2, 3, 4, 5, 8, 16, 8, torch.float16), (1, 3, 5, 7, 8, 8, 0, torch.float32)]
 LAYOUT_CLASSES = {("nchw_to_fmap", "f32" if dt == torch.float32 else "f16", C_, Cv) for (_, C_, _, _, Cv, _, _, dt) in LAYOUT_CASES} | \
                  {("fmap_to_nchw", "f32" if dt == torch.float32 else "f16") for (*_, dt) in LAYOUT_CASES}
 
@@ -225,6 +227,7 @@ SAR_CASES = [
     ("generic_f32_res_minus", 1, 3, 9, 64, "f32", False, 0, -1.0, False, False, False),
     ("generic_f32_gate", 1, 3, 9, 64, "f32", True, 0, None, False, False, False),
     ("generic_f32_gate_lrelu", 1, 3, 9, 64, "f32", True, 2, None, False, False, False),
+    ("generic_f32_gate_res", 2, 3, 5, 64, "f32", True, 0, 1.0, False, True, False),     # the SE scaling plus identity of the fp32 mode's residual blocks
     ("generic_g_a_latent", 1, 5, 7, 128, "f32>f32>f16", True, 0, None, True, False, False),
     ("generic_g_a_latent_views", 2, 3, 4, 128, "f32>f32>f16", True, 0, None, True, True, False),
     ("generic_f16_in_f32_out", 2, 3, 4, 128, "f16>f32", True, 2, 1.0, True, True, False),
@@ -418,7 +421,7 @@ def test_se_gate(C_, nblocks, report):
 # (N, H, W, Cb, T, wide): x has T slices of Cb channels; wide = x is a channel view (64 more channels in the buffer); batch and
 # frame-slice views: test_batch_and_frame_views
 BC_CASES = [(2, 8, 16, 64, 4, False), (1, 5, 7, 64, 4, True), (2, 3, 5, 64, 3, False), (1, 1, 9, 64, 2, True), (1, 4, 4, 8, 4, False)]
-BC_CLASSES = {cls_bcast(T) for *_, T, _ in BC_CASES}
+BC_CLASSES = {cls_bcast(T) for *_, T, _ in BC_CASES}            # fp16 maps; the fp32 and mixed rows: tests/helpers_fp32_ops.py
 
 
 @pytest.mark.parametrize("N,H,W,Cb,T,wide", BC_CASES, ids=[f"{n}x{h}x{w}_T{t}x{c}{'_view' if v else ''}" for n, h, w, c, t, v in BC_CASES])
@@ -443,7 +446,7 @@ def test_bcast_add_act(N, H, W, Cb, T, wide):
 # (N, h, w, C, in view, out view)
 UP_CASES = [(2, 9, 15, 64, False, False), (1, 1, 7, 64, False, False), (1, 6, 1, 8, True, False), (3, 1, 1, 16, False, True),
             (2, 5, 4, 64, True, True)]
-UP_CLASSES = {("upsample2x", "view" if (vin or vout) else "dense") for (*_, vin, vout) in UP_CASES}
+UP_CLASSES = {("upsample2x", "view" if (vin or vout) else "dense", "f16", "f16") for (*_, vin, vout) in UP_CASES}
 
 
 def _dense(fm):
@@ -451,7 +454,7 @@ def _dense(fm):
 
 
 def cls_upsample(x, out):
-    return ("upsample2x", "dense" if _dense(x) and (out is None or _dense(out)) else "view")
+    return ("upsample2x", "dense" if _dense(x) and (out is None or _dense(out)) else "view", _dt(x), _dt(x if out is None else out))
 
 
 @pytest.mark.parametrize("N,h,w,C_,vin,vout", UP_CASES, ids=[f"{n}x{h}x{w}x{c}{'_vin' if a else ''}{'_vout' if b else ''}" for n, h, w, c, a, b in UP_CASES])
@@ -463,7 +466,7 @@ def test_upsample2x(N, h, w, C_, vin, vout, report):
     ybuf = buffer((N, 2 * h, 2 * w, C_ + (8 if vout else 0)), torch.float16)
     y = ops.FM(ybuf, 8 if vout else 0, N, C_)
     before = ybuf.clone()
-    assert cls_upsample(x, y) == ("upsample2x", "view" if (vin or vout) else "dense")
+    assert cls_upsample(x, y) == ("upsample2x", "view" if (vin or vout) else "dense", "f16", "f16")
     ops.upsample2x(x, out=y)
     torch.cuda.synchronize()
     xc = view(x).cpu().double().permute(0, 3, 1, 2)
@@ -542,11 +545,11 @@ def test_resize_bilinear(N, h, w, H, W, C_, Cb, cs, report):
 # ------------------------------------------------------------------------------------------------------------------ add_flow
 # (N, H, W, C of off, off buffer channels, flow buffer channels)
 AF_CASES = [(1, 16, 24, 64, 64, 2), (2, 5, 7, 64, 128, 4), (1, 1, 9, 8, 16, 2)]
-AF_CLASSES = {("add_flow", "dense" if Cb == C_ else "view", Cf) for (_, _, _, C_, Cb, Cf) in AF_CASES}
+AF_CLASSES = {("add_flow", "dense" if Cb == C_ else "view", Cf, "f16") for (_, _, _, C_, Cb, Cf) in AF_CASES}
 
 
 def cls_add_flow(off, flow):
-    return ("add_flow", "dense" if _dense(off) else "view", flow.sp)
+    return ("add_flow", "dense" if _dense(off) else "view", flow.sp, _dt(off))
 
 
 @pytest.mark.parametrize("N,H,W,C_,Cb,Cf", AF_CASES, ids=[f"{n}x{h}x{w}x{c}_buf{cb}_flow{cf}" for n, h, w, c, cb, cf in AF_CASES])
@@ -558,7 +561,7 @@ def test_add_flow(N, H, W, C_, Cb, Cf):
     off = ops.FM(obuf, Cb - C_, N, C_)
     flow = ops.FM(buffer((N, H, W, Cf), torch.float32, "randn", g) * 4, 0, N, 2)
     before, o0 = obuf.clone(), view(off).cpu().float()
-    assert cls_add_flow(off, flow) == ("add_flow", "dense" if Cb == C_ else "view", Cf)
+    assert cls_add_flow(off, flow) == ("add_flow", "dense" if Cb == C_ else "view", Cf, "f16")
     ops.add_flow(off, flow)
     torch.cuda.synchronize()
     want = (o0 + view(flow).cpu().repeat(1, 1, 1, C_ // 2)).half()
@@ -1041,7 +1044,7 @@ def _recorder(monkeypatch, seen):
 
     wrap("scale_act_res", cls_scale_act_res)
     wrap("se_gate", se_cls)
-    wrap("bcast_add_act", lambda x, b, T, slope: cls_bcast(T))
+    wrap("bcast_add_act", lambda x, b, T, slope: cls_bcast(T, _dt(x), _dt(b)))
     wrap("add_flow", cls_add_flow)
     wrap("upsample2x", lambda x, out=None: cls_upsample(x, out))
     wrap("avgpool2", lambda x: ("avgpool2", x.C, x.sp))
