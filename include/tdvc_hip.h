@@ -223,7 +223,7 @@ int tdvc_lf_tail(const tdvc_lf_tail_desc* d, void* stream);
  * (src/cuda/dcn_v2_im2col_cuda.cu:125-195).
  * om: fp16 fmap with 27*G channels = raw conv_offset_mask output [o1 | o2 | mask_logits]
  * (sigmoid applied here, dcn_v2_amp.py:220-223). Cin = Cout = 8*G, 8 channels per group.
- * ABI 15.  fp32 maps: with x.dtype == TDVC_F32 the call runs the fp32 kernel (csrc/dcn_f32.hip) -- fp32 samples, sampling
+ * ABI 15.  fp32 maps: with x.dtype == TDVC_F32 the call runs dcn_fused_kernel<float> (csrc/dcn_common.h) -- fp32 samples, sampling
  * positions, mask (1 / (1 + expf(-logit)), a true division) and accumulation (v_mfma_f32_32x32x2_f32); nothing is rounded to
  * fp16 before the epilogue (bias, one fp16 rounding if round_before_act, activation in fp32).  Then om must be fp32 too, y is
  * fp32 or fp16 (one more rounding), x_planar must be NULL, `w` is the fp32 packing (tdvc_pack_conv_weights_indexed_f32,

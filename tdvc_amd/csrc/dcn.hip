@@ -1,172 +1,29 @@
 // Modulated deformable convolution (DCNv2) for gfx950 — the motion-compensation operator
 // (SURVEY §8 a11/a12).
 //
-// (1) tdvc_dcn_fused: fp16 NHWC, sampling + modulation + 64x576 contraction in ONE kernel.
+// (1) tdvc_dcn_fused: NHWC maps, sampling + modulation + 64x576 contraction in ONE kernel.
 //     The reference materialises `columns` in HBM (576 values / pixel = 4.8 GB at 1080p,
 //     src/cuda/dcn_v2_cuda.cu:67-92); here the modulated samples of an 8x8 pixel tile live in a
-//     25 KB LDS tile, three taps at a time, and are consumed as MFMA B fragments.
-//     On fp32 maps the same entry point runs dcn_f32_fused_kernel (csrc/dcn_f32.hip): fp32 samples, offsets, mask and MFMA.
+//     25 KB LDS tile, three taps at a time, and are consumed as MFMA B fragments (dcn_fused_kernel, csrc/dcn_common.h), or,
+//     on maps of 8192 pixels or more, are sampled from an LDS window by the MFMA B lane itself (dcn_lds_kernel, below).
+//     fp32 maps take dcn_fused_kernel<float>, instantiated in csrc/dcn_f32.hip: fp32 samples, offsets, mask and MFMA.
 // (2) tdvc_dcn_v2_forward_f32: fp32 NCHW operator with `_ext.dcn_v2_forward` semantics.
-#include "common.h"
-
-#include <type_traits>
+#include "dcn_common.h"
 
 namespace {
 
-struct DcnParams {
-  const half_t* x; long x_sn; int x_sp; int H, W;
-  const half_t* om; long om_sn; int om_sp;
-  FMap y;
-  const half_t* w; const float* bias;
-  int G; int act; float slope; int round16;
-  long npix;   // H*W
-  const half_t* xp;   // group-planar copy of x ([N][G][H][W][8]) or null
-};
-
-// x (NHWC, 8G channels) -> [n][g][H][W][8]: 8 lanes read one pixel's 128-byte line, every group plane receives 128
+// x (NHWC, 64 channels) -> [n][g][H][W][8]: 8 lanes read one pixel's 128-byte line, every group plane receives 128
 // contiguous bytes per 8 pixels
-__global__ void dcn_planarise_kernel(const half_t* x, long x_sn, int x_sp, long npix, int G, half_t* xp) {
+__global__ void dcn_planarise_kernel(const half_t* x, long x_sn, int x_sp, long npix, half_t* xp) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int n = blockIdx.y;
-  if (i >= npix * G) return;
-  const int g = (int)(i % G);
-  const long pix = i / G;
+  if (i >= npix * DCN_G) return;
+  const int g = (int)(i % DCN_G);
+  const long pix = i / DCN_G;
   const half8 v = *reinterpret_cast<const half8*>(x + (long)n * x_sn + pix * x_sp + g * 8);
-  *reinterpret_cast<half8*>(xp + (((long)n * G + g) * npix + pix) * 8) = v;
+  *reinterpret_cast<half8*>(xp + (((long)n * DCN_G + g) * npix + pix) * 8) = v;
 }
 
-// Fused kernel, 3x3 / stride 1 / pad 1 / dilation 1, 8 channels per deformable group.
-// One 256-thread workgroup = an 8x8 pixel tile x all 8G output channels.
-//   sampling phase: thread (pixel = tid>>3 [+32], group = tid&7) -> the 8 lanes of a pixel read
-//     one full 128-byte NHWC line per bilinear corner (coalesced), branch-free (clamped address,
-//     zeroed weight) so all corner loads of a tap are in flight together; modulated samples go
-//     to an LDS column tile of 3 taps x 8G channels per pixel (stride +16 B: conflict-free).
-//   MFMA phase: wave (mt, nt) multiplies the 32-row weight tile mt with the 32-pixel half nt,
-//     B fragments = 16-byte LDS reads (lane = pixel, k-chunk = group), 3 taps per barrier pair.
-constexpr int DCN_TPX = 8, DCN_TPY = 8, DCN_TAPS_PER_CHUNK = 3;
-
-__device__ __forceinline__ half8 sample8_bf(const half_t* xg, int H, int W, int sp, float h_im, float w_im, float mask) {
-  // dcn_v2_im2col_cuda.cu:25-54 (bilinear, zero outside) and :180 (open-interval test), branch-free
-  const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-  const float hc = fminf(fmaxf(h_im, -2.f), (float)H + 1.f), wc = fminf(fmaxf(w_im, -2.f), (float)W + 1.f);
-  const float hf = floorf(hc), wf = floorf(wc);
-  const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-  const float lh = hc - hf, lw = wc - wf, hh = 1.f - lh, hw = 1.f - lw;
-  const bool hl = h_low >= 0 && h_low <= H - 1, hhg = h_high >= 0 && h_high <= H - 1;
-  const bool wl = w_low >= 0 && w_low <= W - 1, whg = w_high >= 0 && w_high <= W - 1;
-  // corner weights with the modulation mask folded in; the 8-channel combine is 4 fused multiply-adds per
-  // channel straight from the fp16 samples (v_fma_mix_f32), ~40 vector instructions instead of ~100
-  const float w1 = (inside && hl && wl) ? hh * hw * mask : 0.f, w2 = (inside && hl && whg) ? hh * lw * mask : 0.f;
-  const float w3 = (inside && hhg && wl) ? lh * hw * mask : 0.f, w4 = (inside && hhg && whg) ? lh * lw * mask : 0.f;
-  const int y0 = min(max(h_low, 0), H - 1), y1 = min(max(h_high, 0), H - 1);
-  const int x0 = min(max(w_low, 0), W - 1), x1 = min(max(w_high, 0), W - 1);
-  const int r0 = y0 * W, r1 = y1 * W;                     // pixel indices fit 32 bits (checked by the host)
-  const half8 v1 = *reinterpret_cast<const half8*>(xg + (long)(r0 + x0) * sp);
-  const half8 v2 = *reinterpret_cast<const half8*>(xg + (long)(r0 + x1) * sp);
-  const half8 v3 = *reinterpret_cast<const half8*>(xg + (long)(r1 + x0) * sp);
-  const half8 v4 = *reinterpret_cast<const half8*>(xg + (long)(r1 + x1) * sp);
-  half8 o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    o[j] = (half_t)__builtin_fmaf(w1, (float)v1[j], __builtin_fmaf(w2, (float)v2[j], __builtin_fmaf(w3, (float)v3[j], w4 * (float)v4[j])));
-  return o;
-}
-
-__global__ __launch_bounds__(256) void dcn_fused_kernel(const DcnParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char col[];
-  const int G = p.G;
-  const int PS = DCN_TAPS_PER_CHUNK * G * 16 + 16;       // LDS bytes per pixel (3 taps x 8G halves + pad)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int hh = lane >> 5, r = lane & 31;
-  const int mt = wave & 1, nt = wave >> 1;
-  const int tiles_x = (p.W + DCN_TPX - 1) / DCN_TPX;
-  const int tile_id = tdvc_xcd_tile(blockIdx.x);
-  const int tx = tile_id % tiles_x, ty = tile_id / tiles_x;
-  const int n = blockIdx.y;
-  const half_t* xn = p.x + (long)n * p.x_sn;
-
-  // ---- sampling identity: two pixels per thread (pass 0: pixels 0..31, pass 1: 32..63)
-  const int g = tid & 7;
-  const bool g_on = g < G;
-  const int gg = g_on ? g : 0;
-  // gather source of this thread's group: the NHWC map (pixel stride x_sp: every 16-byte corner of every lane is a line
-  // of its own -- the L1 takes one line per clock, profiles/r01_dcn_fused_1080p_pmc.txt) or the group-planar copy
-  // [n][g][H][W][8] (pixel stride 8: the 8 lanes of a group sample 8 neighbouring pixels, whose corners share lines)
-  const half_t* xg = p.xp ? p.xp + ((long)n * G + gg) * p.npix * 8 : xn + gg * 8;
-  const int xsp = p.xp ? 8 : p.x_sp;
-  int soy[2], sox[2];
-  half2v off[2][9];
-  float msk[2][9];
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    const int pl = (tid >> 3) + 32 * ps;
-    soy[ps] = ty * DCN_TPY + (pl >> 3);
-    sox[ps] = tx * DCN_TPX + (pl & 7);
-    const int cy = min(soy[ps], p.H - 1), cx = min(sox[ps], p.W - 1);
-    const half_t* omp = p.om + (long)n * p.om_sn + ((long)cy * p.W + cx) * p.om_sp;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      off[ps][t] = *reinterpret_cast<const half2v*>(omp + gg * 18 + 2 * t);
-      msk[ps][t] = __builtin_amdgcn_rcpf(1.f + __expf(-(float)omp[18 * G + gg * 9 + t]));    // sigmoid (dcn_v2_amp.py: mask = sigmoid(mask))
-    }
-  }
-
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  const int steps_per_tap = G / 2;
-  const half_t* wbase = p.w + ((long)mt * 9 * steps_per_tap * 64 + lane) * 8;
-  const unsigned char* bcol = col + (nt * 32 + r) * PS + hh * 16;
-
-#pragma unroll
-  for (int chunk = 0; chunk < 3; ++chunk) {             // fully unrolled: tap registers are selected at compile time
-    if (chunk > 0) __syncthreads();
-    if (g_on) {
-#pragma unroll
-      for (int ps = 0; ps < 2; ++ps) {
-#pragma unroll
-        for (int tc = 0; tc < DCN_TAPS_PER_CHUNK; ++tc) {
-          const half2v o2 = off[ps][chunk * 3 + tc];
-          const float h_im = (float)(soy[ps] - 1 + chunk) + (float)o2[0];      // tap = chunk*3 + tc: dy = chunk, dx = tc
-          const float w_im = (float)(sox[ps] - 1 + tc) + (float)o2[1];
-          const half8 v = sample8_bf(xg, p.H, p.W, xsp, h_im, w_im, msk[ps][chunk * 3 + tc]);
-          const int pl = (tid >> 3) + 32 * ps;
-          *reinterpret_cast<half8*>(col + pl * PS + tc * G * 16 + gg * 16) = v;
-        }
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int tc = 0; tc < DCN_TAPS_PER_CHUNK; ++tc) {
-      const int tap = chunk * 3 + tc;
-      for (int s2 = 0; s2 < steps_per_tap; ++s2) {
-        const half8 a = *reinterpret_cast<const half8*>(wbase + (long)(tap * steps_per_tap + s2) * 512);
-        const half8 b = *reinterpret_cast<const half8*>(bcol + tc * G * 16 + s2 * 32);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
-      }
-    }
-  }
-
-  const int pl = nt * 32 + r;
-  const int oy = ty * DCN_TPY + (pl >> 3), ox = tx * DCN_TPX + (pl & 7);
-  if (oy >= p.H || ox >= p.W) return;
-  half_t* yp = reinterpret_cast<half_t*>(p.y.p) + (long)n * p.y.sn + ((long)oy * p.W + ox) * p.y.sp;
-#pragma unroll
-  for (int gq = 0; gq < 4; ++gq) {
-    const int co = mt * 32 + 8 * gq + 4 * hh;
-    if (co >= p.y.C) continue;
-    const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.bias + co);
-    half4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float v = acc[4 * gq + i] + b4[i];
-      if (p.round16) v = (float)(half_t)v;
-      v = act_apply(v, p.act, p.slope);
-      o[i] = (half_t)v;
-    }
-    *reinterpret_cast<half4*>(yp + co) = o;
-  }
-}
 
 // ------------------------------------------------------------------------------------------
 // dcn_lds: the same operator with the bilinear corners gathered from an LDS window instead of L1.
@@ -183,8 +40,8 @@ __global__ __launch_bounds__(256) void dcn_fused_kernel(const DcnParams p) {
 //     per-pixel record), each lane keeps its 4 groups x 9 taps in registers;
 //   * a sample whose corners leave the window (more than 5 px from the tile's mean displacement) falls back to the global gather, per lane; a wave whose
 //     lanes are all inside (the common case) takes a branch without it.
-// Arithmetic and accumulation order are those of dcn_fused_kernel: the two kernels agree bit for bit
-// (tests/test_dcn_gpu.py).
+// The sampling rule (dcn_corners) and the epilogue (dcn_store) are the shared ones and the accumulation order is
+// dcn_fused_kernel's: the two kernels agree bit for bit (tests/test_dcn_gpu.py).
 // ------------------------------------------------------------------------------------------
 constexpr int DL_TY = 8, DL_TX = 16, DL_M = 6;
 constexpr int DL_WH = DL_TY + 2 * DL_M, DL_WW = DL_TX + 2 * DL_M, DL_WP = 32;      // window rows, columns, row pitch (pixels)
@@ -194,27 +51,15 @@ constexpr int DL_RED = ((DL_WH - 1) * DL_WP + DL_WW) * 128;                     
 static_assert(DL_TY * DL_TX * DL_OM_REC <= DL_RED, "the offset/mask tile is staged through the window region, below the reduction scratch");
 static_assert(DL_WP >= DL_WW + 1 && DL_WP % 16 == 0, "row pitch: a multiple of 16 pixels keeps the two rows of a wave on disjoint slots");
 
-struct DlSample {            // one (pixel, group, tap) sample in flight: corner weights, LDS addresses, image coordinates
-  float w1, w2, w3, w4;
-  int s00, s01, s10, s11;    // LDS byte offsets of the four corners (clamped into the window)
-  int y0, y1, x0, x1;        // image coordinates (for the fallback gather)
-  bool iw;                   // all four corners inside the window
+struct DlSample : DcnCorners {   // one (pixel, group, tap) sample in flight: corner weights and image coordinates (for the fallback gather),
+  int s00, s01, s10, s11;        // LDS byte offsets of the four corners (clamped into the window)
+  bool iw;                       // all four corners inside the window
 };
 
+// dcn_corners, then the window mapping and the swizzle: only the source of the four corner vectors differs from the gather kernel
 __device__ __forceinline__ DlSample dl_prepare(int wy0, int wx0, int g, int H, int W, float h_im, float w_im, float mask) {
-  // identical arithmetic to sample8_bf; only the source of the four corner vectors differs
   DlSample q;
-  const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-  const float hc = fminf(fmaxf(h_im, -2.f), (float)H + 1.f), wc = fminf(fmaxf(w_im, -2.f), (float)W + 1.f);
-  const float hf = floorf(hc), wf = floorf(wc);
-  const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-  const float lh = hc - hf, lw = wc - wf, hh = 1.f - lh, hw = 1.f - lw;
-  const bool hl = h_low >= 0 && h_low <= H - 1, hhg = h_high >= 0 && h_high <= H - 1;
-  const bool wl = w_low >= 0 && w_low <= W - 1, whg = w_high >= 0 && w_high <= W - 1;
-  q.w1 = (inside && hl && wl) ? hh * hw * mask : 0.f; q.w2 = (inside && hl && whg) ? hh * lw * mask : 0.f;
-  q.w3 = (inside && hhg && wl) ? lh * hw * mask : 0.f; q.w4 = (inside && hhg && whg) ? lh * lw * mask : 0.f;
-  q.y0 = min(max(h_low, 0), H - 1); q.y1 = min(max(h_high, 0), H - 1);
-  q.x0 = min(max(w_low, 0), W - 1); q.x1 = min(max(w_high, 0), W - 1);
+  static_cast<DcnCorners&>(q) = dcn_corners(H, W, h_im, w_im, mask);
   const int a0 = q.y0 - wy0, a1 = q.y1 - wy0, b0 = q.x0 - wx0, b1 = q.x1 - wx0;  // window coordinates (a1 >= a0, b1 >= b0)
   q.iw = a0 >= 0 && a1 < DL_WH && b0 >= 0 && b1 < DL_WW;
   const int ca0 = q.iw ? a0 : 0, ca1 = q.iw ? a1 : 0, cb0 = q.iw ? b0 : 0, cb1 = q.iw ? b1 : 0;
@@ -224,9 +69,10 @@ __device__ __forceinline__ DlSample dl_prepare(int wy0, int wx0, int g, int H, i
   return q;
 }
 
-// The same for a tile whose whole window lies inside the image: a sample inside the window needs none of the image-border
-// logic (every corner exists, the clamps are identities), so the common path is floor / fractions / four products and the
-// addresses.  The window test is done on the floats (NaN fails it); a lane that fails is recomputed by dl_prepare.
+// A deliberately shorter rule for a tile whose whole window lies inside the image.  For a sample inside the window these steps of
+// dcn_corners are identities: the open-interval test (true), the clamp before floorf (the position lies in [0, H - 1] x [0, W - 1]),
+// the four corner-exists flags (true) and the clamps of the corner coordinates.  What is left is floor / fractions / the same four
+// products and the addresses.  The window test is done on the floats (NaN fails it); a lane that fails is recomputed by dl_prepare.
 __device__ __forceinline__ DlSample dl_prepare_interior(int wy0, int wx0, int g, float h_im, float w_im, float mask) {
   DlSample q;
   const float hf = floorf(h_im), wf = floorf(w_im);
@@ -241,10 +87,7 @@ __device__ __forceinline__ DlSample dl_prepare_interior(int wy0, int wx0, int g,
   return q;
 }
 
-// MODE 0: the operator.  MODE 1 / 2: timing-only builds for tools/ab_dcn.py (1: no sampling / matrix phase, 2: no window
-// staging -- the window holds garbage, control flow and instruction stream unchanged); their output is meaningless.
-template <int MODE>
-__global__ __launch_bounds__(256, 2) void dcn_lds_kernel(const DcnParams p) {
+__global__ __launch_bounds__(256, 2) void dcn_lds_kernel(const DcnParams<half_t> p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char win[];
   const int tid0 = threadIdx.x, lane = tid0 & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
@@ -324,8 +167,7 @@ __global__ __launch_bounds__(256, 2) void dcn_lds_kernel(const DcnParams p) {
 #pragma unroll
     for (int wy = 0; wy < DL_WH; ++wy) {
       const int iy = min(max(wy0 + wy, 0), p.H - 1);                           // uniform
-      if constexpr (MODE != 2) v[wy] = *reinterpret_cast<const half8*>(xn + (long)iy * p.W * p.x_sp + lane_off);
-      else v[wy] = half8{(half_t)(float)iy, (half_t)(float)ix, 0, 0, 0, 0, 0, 0};
+      v[wy] = *reinterpret_cast<const half8*>(xn + (long)iy * p.W * p.x_sp + lane_off);
     }
     unsigned char* dst = win + (wv ? wx : 0) * 128 + ((c ^ ((wx >> 1) & 7)) << 4);
 #pragma unroll
@@ -348,8 +190,11 @@ __global__ __launch_bounds__(256, 2) void dcn_lds_kernel(const DcnParams p) {
   // step offset, the lane offset the only vector operand: no 64-bit address arithmetic per load)
   const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.w), 0, 2 * 36 * 1024, 0x00020000);
   const int lane16 = lane * 16;
-  float neg0 = -0.f;                                              // x * y == fma(x, y, -0) for every x, y: the opaque addend keeps
-  asm volatile("" : "+v"(neg0));                                  // the first product of the combine on v_fma_mix (fp16 operand)
+  // the combine of dcn_sample8 with its innermost product w4 * v4 written as fma(w4, v4, -0): x * y == fma(x, y, -0) for every x, y
+  // (NaN, infinities and signed zeros included), so the form differs and no value does; the opaque addend keeps that first product on
+  // v_fma_mix (fp16 operand converted inside the FMA) where a plain product here becomes a convert and a multiply
+  float neg0 = -0.f;
+  asm volatile("" : "+v"(neg0));
   auto issue_a = [&](int i) {
     a[i % (APF + 1)][0] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane16, i * 1024, 0));
     a[i % (APF + 1)][1] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane16, (36 + i) * 1024, 0));
@@ -400,30 +245,13 @@ __global__ __launch_bounds__(256, 2) void dcn_lds_kernel(const DcnParams p) {
       consume(i);
     }
   };
-  if constexpr (MODE != 1) {
-    if (wy0 >= 0 && wx0 >= 0 && wy0 + DL_WH <= p.H && wx0 + DL_WW <= p.W) run(std::true_type{});
-    else run(std::false_type{});
-  }
+  if (wy0 >= 0 && wx0 >= 0 && wy0 + DL_WH <= p.H && wx0 + DL_WW <= p.W) run(std::true_type{});
+  else run(std::false_type{});
 
   if (oy < p.H && ox < p.W) {
-    half_t* yp = reinterpret_cast<half_t*>(p.y.p) + (long)n * p.y.sn + ((long)oy * p.W + ox) * p.y.sp;
+    const long yoff = (long)n * p.y.sn + ((long)oy * p.W + ox) * p.y.sp;
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      const int co = mt * 32 + 8 * gq + 4 * hh;
-      if (co >= p.y.C) continue;
-      const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.bias + co);
-      half4 o;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float v = acc[mt][4 * gq + i] + b4[i];
-        if (p.round16) v = (float)(half_t)v;
-        v = act_apply(v, p.act, p.slope);
-        o[i] = (half_t)v;
-      }
-      *reinterpret_cast<half4*>(yp + co) = o;
-    }
+    for (int mt = 0; mt < 2; ++mt) dcn_store<false>(acc[mt], mt, hh, p.bias, p.round16, p.act, p.slope, p.y, yoff);
   }
 }
 
@@ -512,58 +340,54 @@ __global__ __launch_bounds__(256) void dcn_f32_forward_kernel(const DcnF32Params
 }  // namespace
 
 static int g_dcn_lds = getenv("TDVC_DCN_NO_LDS") == nullptr ? 1 : 0;
-// tests and A/B benchmarks switch the LDS-window kernel off to run the same operator on dcn_fused_kernel
-// (2, 3: the timing-only builds MODE 1, 2 of dcn_lds_kernel)
+// tests and A/B benchmarks switch the LDS-window kernel off (0) to run the same operator on dcn_fused_kernel
 extern "C" void tdvc_debug_enable_dcn_lds(int enable) { g_dcn_lds = enable; }
 
 int tdvc_dcn_fused_f32(const tdvc_dcn_desc* d, void* stream);      // csrc/dcn_f32.hip
 
-extern "C" int tdvc_dcn_fused(const tdvc_dcn_desc* d, void* stream) {
+// an fp32 map the kernel reads or writes with 16-byte accesses
+static bool dcn_map_ok32(const tdvc_fmap& f) { return fmap_ok32(f) && aligned16(f.p) && (f.sp % 4) == 0 && (f.sn % 4) == 0; }
+
+// every check of tdvc_dcn_fused, for both element types, before anything touches the device
+static int dcn_validate(const tdvc_dcn_desc* d) {
   TDVC_CHECK(d, "tdvc_dcn_fused: null descriptor");
-  if (d->x.dtype == TDVC_F32) return tdvc_dcn_fused_f32(d, stream);       // fp32 maps: one kernel of its own, fp32 weight packing
-  TDVC_CHECK(fmap_ok16(d->x) && fmap_ok16(d->om) && fmap_ok16(d->y), "tdvc_dcn_fused: fmaps must be fp16, C/sp %% 8, aligned");
-  const int G = d->groups;
-  TDVC_CHECK(G == 8, "tdvc_dcn_fused: groups=%d unsupported (the fused kernel is built for the hot-path geometry: 8 groups x 8 channels; use tdvc_dcn_v2_forward_f32 otherwise)", G);
-  TDVC_CHECK(d->x.C == 8 * G && d->y.C == 8 * G, "tdvc_dcn_fused: needs Cin = Cout = 8*groups (8 channels per group)");
-  TDVC_CHECK(d->om.C >= 27 * G, "tdvc_dcn_fused: offset/mask fmap needs >= 27*groups channels");
-  TDVC_CHECK(d->x.N == d->y.N && d->x.N == d->om.N && d->x.H == d->y.H && d->x.W == d->y.W && d->om.H == d->x.H && d->om.W == d->x.W,
-             "tdvc_dcn_fused: geometry mismatch");
-  TDVC_CHECK(d->w && aligned16(d->w) && d->bias && aligned16(d->bias), "tdvc_dcn_fused: weights/bias null or unaligned");
-  TDVC_CHECK((long)d->x.H * d->x.W < 2147483647L, "tdvc_dcn_fused: image too large (pixel indices are 32-bit)");
-  DcnParams p;
-  p.x = reinterpret_cast<const half_t*>(d->x.p); p.x_sn = d->x.sn; p.x_sp = d->x.sp; p.H = d->x.H; p.W = d->x.W;
-  p.om = reinterpret_cast<const half_t*>(d->om.p); p.om_sn = d->om.sn; p.om_sp = d->om.sp;
-  p.y = to_dev(d->y);
-  p.w = reinterpret_cast<const half_t*>(d->w); p.bias = d->bias;
-  p.G = G; p.act = d->act; p.slope = d->slope; p.round16 = d->round_before_act;
-  p.npix = (long)d->x.H * d->x.W;
-  p.xp = reinterpret_cast<const half_t*>(d->x_planar);
-  if (p.xp) {
-    TDVC_CHECK(aligned16(d->x_planar), "tdvc_dcn_fused: x_planar scratch unaligned");
-    const long items = p.npix * G;
-    hipLaunchKernelGGL(dcn_planarise_kernel, dim3((unsigned)((items + 255) / 256), d->x.N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       p.x, p.x_sn, p.x_sp, p.npix, G, reinterpret_cast<half_t*>(d->x_planar));
+  const bool f32 = d->x.dtype == TDVC_F32;
+  const char* who = f32 ? "tdvc_dcn_fused(f32)" : "tdvc_dcn_fused";
+  if (f32) {
+    TDVC_CHECK(dcn_map_ok32(d->x), "%s: x must be an fp32 fmap, 16-byte aligned, pixel and batch strides %% 4", who);
+    TDVC_CHECK(d->om.dtype == TDVC_F32 && dcn_map_ok32(d->om), "%s: with an fp32 x the offset/mask fmap must be fp32 too (16-byte aligned, strides %% 4)", who);
+    TDVC_CHECK(d->y.dtype == TDVC_F32 ? dcn_map_ok32(d->y) : fmap_ok16(d->y), "%s: y must be an fp32 (16-byte aligned, strides %% 4) or fp16 fmap", who);
+    TDVC_CHECK(!d->x_planar, "%s: x_planar is an fp16 form; it must be NULL for fp32 maps", who);
+  } else {
+    TDVC_CHECK(fmap_ok16(d->x) && fmap_ok16(d->om) && fmap_ok16(d->y), "%s: fmaps must be fp16, C/sp %% 8, aligned", who);
+    TDVC_CHECK(aligned16(d->x_planar), "%s: x_planar scratch unaligned", who);
   }
-  if (g_dcn_lds && !p.xp && (long)d->x.H * d->x.W >= 8192) {
-    static TdvcPerDeviceFlag attr_flags;
-  bool& attr_done = attr_flags.flag();
-    if (!attr_done) {
-      for (const void* k : {reinterpret_cast<const void*>(&dcn_lds_kernel<0>), reinterpret_cast<const void*>(&dcn_lds_kernel<1>),
-                            reinterpret_cast<const void*>(&dcn_lds_kernel<2>)}) {
-        const hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS);
-        TDVC_CHECK(err == hipSuccess, "tdvc_dcn_fused: cannot reserve %d bytes of LDS: %s", DL_LDS, hipGetErrorString(err));
-      }
-      attr_done = true;
-    }
-    dim3 grid_l((unsigned)(((d->x.W + DL_TX - 1) / DL_TX) * ((d->x.H + DL_TY - 1) / DL_TY)), d->x.N);
-    auto kern = g_dcn_lds == 2 ? dcn_lds_kernel<1> : g_dcn_lds == 3 ? dcn_lds_kernel<2> : dcn_lds_kernel<0>;
-    hipLaunchKernelGGL(kern, grid_l, dim3(256), DL_LDS, reinterpret_cast<hipStream_t>(stream), p);
+  const int G = d->groups;
+  TDVC_CHECK(G == DCN_G, "%s: groups=%d unsupported (the fused kernel is built for the hot-path geometry: 8 groups x 8 channels; use tdvc_dcn_v2_forward_f32 otherwise)", who, G);
+  TDVC_CHECK(d->x.C == 8 * G && d->y.C == 8 * G, "%s: needs Cin = Cout = 8*groups (8 channels per group)", who);
+  TDVC_CHECK(d->om.C >= 27 * G, "%s: offset/mask fmap needs >= 27*groups channels", who);
+  TDVC_CHECK(d->x.N == d->y.N && d->x.N == d->om.N && d->x.H == d->y.H && d->x.W == d->y.W && d->om.H == d->x.H && d->om.W == d->x.W,
+             "%s: geometry mismatch", who);
+  TDVC_CHECK(d->w && aligned16(d->w) && d->bias && aligned16(d->bias), "%s: weights/bias null or unaligned", who);
+  TDVC_CHECK((long)d->x.H * d->x.W < 2147483647L, "%s: image too large (pixel indices are 32-bit)", who);
+  TDVC_CHECK(d->x.N <= 65535, "%s: batch too large (the batch is the grid's y dimension)", who);
+  return TDVC_OK;
+}
+
+extern "C" int tdvc_dcn_fused(const tdvc_dcn_desc* d, void* stream) {
+  if (const int e = dcn_validate(d); e != TDVC_OK) return e;
+  if (d->x.dtype == TDVC_F32) return tdvc_dcn_fused_f32(d, stream);       // dcn_fused_kernel<float>, fp32 weight packing
+  const DcnParams<half_t> p = dcn_params<half_t>(d);
+  if (p.xp) {
+    hipLaunchKernelGGL(dcn_planarise_kernel, dim3((unsigned)((p.npix * DCN_G + 255) / 256), d->x.N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       p.x, p.x_sn, p.x_sp, p.npix, reinterpret_cast<half_t*>(d->x_planar));
+  } else if (g_dcn_lds && p.npix >= 8192) {
+    if (const int e = dcn_reserve_lds<&dcn_lds_kernel, DL_LDS>(); e != TDVC_OK) return e;
+    dim3 grid((unsigned)(((p.W + DL_TX - 1) / DL_TX) * ((p.H + DL_TY - 1) / DL_TY)), d->x.N);
+    hipLaunchKernelGGL(dcn_lds_kernel, grid, dim3(256), DL_LDS, reinterpret_cast<hipStream_t>(stream), p);
     return tdvc_launch_status("tdvc_dcn_fused(lds)");
   }
-  dim3 grid((unsigned)(((d->x.W + DCN_TPX - 1) / DCN_TPX) * ((d->x.H + DCN_TPY - 1) / DCN_TPY)), d->x.N);
-  const size_t lds = (size_t)64 * (DCN_TAPS_PER_CHUNK * G * 16 + 16);
-  hipLaunchKernelGGL(dcn_fused_kernel, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p);
-  return tdvc_launch_status("tdvc_dcn_fused");
+  return launch_dcn_fused<half_t>(d, stream);
 }
 
 extern "C" int tdvc_dcn_v2_forward_f32(const float* input, const float* weight, const float* bias,

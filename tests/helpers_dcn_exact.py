@@ -1,9 +1,10 @@
 """The case table, the data and the references of the exact forward-DCN tests (tests/test_dcn_exact_gpu.py launches the cases on
 the GPU, tests/test_dcn_exact_cases_cpu.py holds, without a GPU, the table to what it claims).
 
-tdvc_dcn_fused has three forward implementations behind one entry point (csrc/dcn.hip): `gather` (dcn_fused_kernel, 8x8 tiles,
-corners through L1), `planar` (the same kernel on the group-planar copy of x) and `lds` (dcn_lds_kernel<0>, 8x16 tiles, maps of
-8192 pixels or more).  Geometry is the fused kernel's own: 64 -> 64 channels, 8 groups, 3x3, stride 1, pad 1.
+tdvc_dcn_fused has three forward implementations behind one entry point (csrc/dcn.hip): `gather` (dcn_fused_kernel<half_t>,
+csrc/dcn_common.h, 8x8 tiles, corners through L1), `planar` (the same kernel on the group-planar copy of x) and `lds` (dcn_lds_kernel,
+8x16 tiles, maps of 8192 pixels or more).  All of them take the sampling rule from dcn_corners and store through dcn_store
+(csrc/dcn_common.h).  Geometry is the fused kernel's own: 64 -> 64 channels, 8 groups, 3x3, stride 1, pad 1.
 
 Three grades of data, all made here:
 

@@ -1,4 +1,4 @@
-"""Cases, bound and the genuinely-fp32 data of the exact tests of tdvc_dcn_fused on fp32 maps (csrc/dcn_f32.hip):
+"""Cases, bound and the genuinely-fp32 data of the exact tests of tdvc_dcn_fused on fp32 maps (dcn_fused_kernel<float>, csrc/dcn_common.h):
 tests/test_dcn_f32_exact_gpu.py launches them, tests/test_dcn_f32_cases_cpu.py holds the table and the fp32 case to what they claim.
 
 Cases, data and references are those of tests/helpers_dcn_exact.py (`X`).  Restated here is only what an fp32 map changes:

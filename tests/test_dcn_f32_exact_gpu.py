@@ -1,4 +1,4 @@
-"""tdvc_dcn_fused on fp32 maps (dcn_f32_fused_kernel, csrc/dcn_f32.hip) held to exact answers: the cases, data and references of
+"""tdvc_dcn_fused on fp32 maps (dcn_fused_kernel<float>, csrc/dcn_common.h) held to exact answers: the cases, data and references of
 tests/helpers_dcn_exact.py on the small maps, once with an fp32 y and once with an fp16 y (tests/helpers_dcn_f32.py: the case
 table, the epilogue rule of an fp32 output, the bound without its fp16 terms, and the genuinely-fp32 case).
 

@@ -63,6 +63,23 @@ def test_ext_errors():
         _ext.dcn_v2_forward(x, torch.zeros(4, 3, 3, 3).cuda(), b, off, m, 3, 3, 1, 1, 1, 1, 1, 1, 1)
 
 
+def test_fused_dcn_rejects_batch_beyond_grid_limit():
+    """the batch is the grid's y dimension (at most 65535): N = 65536 is an error on fp16 and on fp32 maps alike, raised before
+    anything is launched -- y keeps every bit"""
+    from tdvc_amd import _lib, ops
+    N = 65536
+    pc = ops.pack_conv(torch.zeros(64, 64, 3, 3), torch.zeros(64), stride=1, pad=1, ck=64)
+    for dt in (torch.float16, torch.float32):
+        x = ops.FM(torch.zeros(N, 1, 1, 64, dtype=dt, device="cuda"))
+        om = ops.FM(torch.zeros(N, 1, 1, 216, dtype=dt, device="cuda"))
+        sentinel = torch.full((N, 1, 1, 64), 0x5A5A, dtype=torch.int16, device="cuda")
+        y = ops.FM(sentinel.clone().view(torch.float16))
+        with pytest.raises(_lib.TdvcHipError):
+            ops.dcn_fused(x, om, pc, y, groups=8, planar=False)
+        torch.cuda.synchronize()
+        assert torch.equal(y.t.view(torch.int16), sentinel)
+
+
 @pytest.mark.parametrize("H,W", [(20, 28), (64, 96), (88, 104)])      # the last one is large enough for the LDS-window kernel
 def test_fused_dcn_vs_oracle(H, W, report):
     """fp16 fused kernel (sampling + modulation + contraction + fp16 rounding + LeakyReLU) vs the
