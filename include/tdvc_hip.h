@@ -626,11 +626,11 @@ int tdvc_se_gate_backward(const float* partial, int nblocks, float inv_count, in
                           float* dw1, float* db1, float* dw2, float* db2, void* stream);
 /* dx[n][pix][c] += v[n][c] * scale (adjoint of the global average pool). */
 int tdvc_bcast_channel_add(const tdvc_fmap* dx, const float* v, float scale, void* stream);
-/* adjoint of tdvc_add_flow: dflow[.., 0/1] += sum of the even / odd channels of doff. */
+/* adjoint of tdvc_add_flow: dflow[.., 0/1] += sum of the even / odd channels of doff (fp16, or fp32 with C % 8 == 0: ABI 16). */
 int tdvc_add_flow_backward(const tdvc_fmap* doff, const tdvc_fmap* dflow, void* stream);
-/* adjoint of tdvc_bcast_add_act: dx *= lrelu'(x) in place, db += sum over the T channel slices of dx. */
+/* adjoint of tdvc_bcast_add_act: dx *= lrelu'(x) in place, db += sum over the T channel slices of dx.  fp16 or fp32 (ABI 16) fmaps. */
 int tdvc_bcast_add_act_backward(const tdvc_fmap* dx, const tdvc_fmap* x, const tdvc_fmap* db, float slope, void* stream);
-/* adjoint of tdvc_upsample2x: dx += U^T dy. */
+/* adjoint of tdvc_upsample2x: dx += U^T dy.  fp16 or fp32 (ABI 16) fmaps, C % 8 == 0. */
 int tdvc_upsample2x_backward(const tdvc_fmap* dy, const tdvc_fmap* dx, void* stream);
 /* adjoint of tdvc_resize_bilinear (flownet.py:153-173, the flow's way back from the x32-padded size): dx += R^T (chscale * dy),
  * fp32 maps, gathered per input pixel (reproducible).  Only reached when H or W is not a multiple of 32. */
@@ -638,7 +638,7 @@ int tdvc_resize_bilinear_backward(const tdvc_fmap* dy, const tdvc_fmap* dx, cons
 
 /* backward of tdvc_spynet_level_input (flownet.py:82-140): dflow_up += flow channels of dcat8 + the warp gradient
  * (grid_sample bilinear / border / align_corners=True w.r.t. the flow), then dflow_lo += 2 * U^T dflow_up.  The images
- * need no gradient.  dflow_lo may be NULL (coarsest level). */
+ * need no gradient.  dflow_lo may be NULL (coarsest level).  dcat8: fp16 or fp32 (ABI 16), C = 8. */
 int tdvc_spynet_level_input_backward(const tdvc_fmap* supp, const tdvc_fmap* flow_up, const tdvc_fmap* dcat8, const tdvc_fmap* dflow_up,
                                      const tdvc_fmap* dflow_lo, void* stream);
 
@@ -648,7 +648,7 @@ int tdvc_sigmoid_backward_f32(float* g, const float* s, int64_t n, void* stream)
 int tdvc_axpy_f32(float* dst, const float* src, float scale, int64_t n, void* stream);
 
 /* backward of tdvc_match_gather (pnet.py:240-255): the matching indices carry no gradient; dfin += d(cat)/d(fin),
- * dfref += the gathered blocks' gradients in gather form (fixed summation order, no atomics). */
+ * dfref += the gathered blocks' gradients in gather form (fixed summation order, no atomics).  The five fmaps are fp16 or fp32 (ABI 16). */
 int tdvc_match_gather_backward(const tdvc_fmap* fin, const tdvc_fmap* fref, const int32_t* idx, int scale, int hp, int wp,
                                const tdvc_fmap* dcat, const tdvc_fmap* dfin, const tdvc_fmap* dfref, void* stream);
 
@@ -681,9 +681,14 @@ int tdvc_eb_aux(const float* params, const float* quantiles, float target, float
  * dx32 (fp32 [N][H][W][8G], zero-initialised by the caller).  The scatter is privatised: one 32x32-pixel LDS window
  * per 16x16 tile and group, stored to `work` (tdvc_dcn_col2im_work_floats floats, 16-byte aligned) and summed per
  * pixel in a fixed order; only samples displaced by more than 8 pixels use float atomics (the reference's col2im
- * uses them for every sample). */
+ * uses them for every sample).
+ * ABI 16.  x, om, col / dcol and dom may all be fp32 maps instead (the whole-model fp32 training mode): the same kernels templated on
+ * the element type, fp32 samples, offsets, columns and dom, the mask a true division of expf as in tdvc_dcn_fused on fp32 maps; fp32
+ * maps need a 16-byte aligned base and pixel / batch strides that are multiples of 4.  A mix of fp16 and fp32 maps is refused before
+ * any launch.  tdvc_dcn_col2im_tile: the side of the scatter's pixel tile (the LDS window reaches one tile further on every side). */
 int tdvc_dcn_columns(const tdvc_fmap* x, const tdvc_fmap* om, int groups, const tdvc_fmap* col, void* stream);
 int64_t tdvc_dcn_col2im_work_floats(int N, int H, int W, int groups);
+int tdvc_dcn_col2im_tile(void);
 int tdvc_dcn_col2im(const tdvc_fmap* x, const tdvc_fmap* om, const tdvc_fmap* dcol, int groups, float* dx32, const tdvc_fmap* dom,
                     float* work, int64_t work_floats, void* stream);
 /* Run-to-run reproducible form (tdvc_amd.ops.DETERMINISTIC; the reproducible training run of the parity tests): samples

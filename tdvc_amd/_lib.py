@@ -158,6 +158,7 @@ SIGNATURES = {
     "tdvc_ssim_level_backward": (_i, [_P, _P, _i, _i, _i, _i, _P, _i, _f, _f, _P, _P, _f, _P, _P, _P]),
     "tdvc_msssim_level_grads": (_i, [_P, _P, _P, _i, _i, _P, _P, _P, _P, _P]),
     "tdvc_dcn_col2im_work_floats": (_i64, [_i, _i, _i, _i]),
+    "tdvc_dcn_col2im_tile": (_i, []),
     "tdvc_dcn_col2im": (_i, [_FM, _FM, _FM, _i, _P, _FM, _P, _i64, _P]),
     "tdvc_dcn_col2im_det": (_i, [_FM, _FM, _FM, _i, _P, _FM, _P, _i64, _P, _P, _P, _i, _P]),
     "tdvc_dcn_far_apply": (_i, [_P, _P, _P, _i, _P, _P]),

@@ -138,7 +138,8 @@ class Tape:
         -> True when the add was deferred: `src` is then still to be read and must not be overwritten (in-place act_backward)"""
         key = fm.t.data_ptr()
         if not LAZY_IDENTITY or key in self.touched or key in self.pending or src.f32 or fm.f32 or src.C != fm.C:
-            accumulate(self.grad(fm), src)
+            # (a gradient wider than its target: SPyNet's fp32-mode flow map has 8 channels, the up-sampled flow it adds to has 2)
+            accumulate(self.grad(fm), src if src.C <= fm.C else src.ch(0, fm.C))
             return False
         self.pending[key] = (fm, src)
         return True                               # the caller must leave `src` untouched from here on
@@ -299,8 +300,9 @@ def record_conv(tape: Tape, x: FM, pc, y, act, slope, res, res2, gdn, aux, squar
 
     def bwd():
         if nchw_out is not None:                  # planar fp32 output (the RGB reconstruction): gradient arrives planar
-            g = ops.from_nchw(tape.grad_tensor(nchw_out), Cpad=ops.pad8(pc.cout))
-            yv = ops.from_nchw(nchw_out, Cpad=ops.pad8(pc.cout))
+            gdt = torch.float32 if x.f32 else torch.float16      # an fp32 layer's output gradient stays fp32 (whole-model fp32 training)
+            g = ops.from_nchw(tape.grad_tensor(nchw_out), Cpad=ops.pad8(pc.cout), dtype=gdt)
+            yv = ops.from_nchw(nchw_out, Cpad=ops.pad8(pc.cout), dtype=gdt)
         else:
             g, yv = tape.grad(y), y
         held = False                              # an identity gradient still to be read from g: the activation derivative goes to a new buffer
@@ -308,10 +310,8 @@ def record_conv(tape: Tape, x: FM, pc, y, act, slope, res, res2, gdn, aux, squar
             held |= tape.add_identity(res, g)
         if res2 is not None and tape.needs_grad(res2):
             held |= tape.add_identity(res2, g)
-        if x.f32:                                 # the layer ran in fp32 (fp32 coders): its backward does too -- conv_f32 on the
-            if nchw_out is not None:              # dgrad packing, conv_wgrad_f32; an fp16 gradient (x_hat is stored fp16) is cast up
-                raise NotImplementedError("autograd: planar output of an fp32 conv")
-            if not g.f32:
+        if x.f32:                                 # the layer ran in fp32 (fp32 coders, whole-model fp32): its backward does too -- conv_f32
+            if not g.f32:                         # on the dgrad packing, conv_wgrad_f32; an fp16 gradient (x_hat is stored fp16) is cast up
                 g = ops.copy_cast(g, FM.empty(g.N, g.H, g.W, g.C, dtype=torch.float32, device=g.t.device))
                 held = False
         elif g.f32:                               # fp32 outputs (flow, latents): the MFMA backward kernels take fp16
@@ -419,15 +419,20 @@ def record_spynet_level_input(tape: Tape, supp: FM, flow_lo, flow_up: FM, cat8: 
 
 
 def record_dcn_fused(tape: Tape, x: FM, om: FM, pc, out: FM, groups, act, slope):
-    """DCNv2 backward (src/cuda/dcn_v2_cuda.cu:97-216 restructured for channel-innermost fp16): the sampled columns are
+    """DCNv2 backward (src/cuda/dcn_v2_cuda.cu:97-216 restructured for channel-innermost maps): the sampled columns are
     rebuilt once (the fused forward keeps none); dW is a 1x1 weight-gradient over them, d(columns) a 1x1 conv of dY,
-    and one kernel turns d(columns) into the offset / mask gradients and the scatter to the sampled features."""
+    and one kernel turns d(columns) into the offset / mask gradients and the scatter to the sampled features.
+    fp32 `x` / `om` (whole-model fp32 training): `out` is the fp16 map the forward rounds the result to (dcn_v2_amp.py:67-68), so its
+    gradient -- and the activation's derivative -- are fp16 values, as in the reference's autograd through `.half()`; from there on
+    everything is fp32: columns, conv_wgrad_f32, conv_f32 for d(columns), the fp32 col2im and an fp32 offset / mask gradient."""
     weight, bias = pc.param_w, pc.param_b
 
     def bwd():
         g = tape.grad(out)
         if act in (ops.ACT_RELU, ops.ACT_LRELU):
             g = ops.act_backward(g, out, act, slope)
+        if x.f32 and not g.f32:
+            g = ops.copy_cast(g, FM.empty(g.N, g.H, g.W, g.C, dtype=torch.float32, device=g.t.device))
         cpc = ops.dcn_column_conv(pc, groups)
         col = ops.dcn_columns(x, om, groups)
         ops.conv_wgrad(cpc, g, col, param_grad(weight).view(-1), scale=tape.inv_scale, db=param_grad(bias))

@@ -872,22 +872,23 @@ extern "C" int tdvc_bcast_channel_add(const tdvc_fmap* dx, const float* v, float
 }
 
 extern "C" int tdvc_add_flow_backward(const tdvc_fmap* doff, const tdvc_fmap* dflow, void* stream) {
-  TDVC_CHECK(doff && dflow && fmap_ok16(*doff) && fmap_ok32(*dflow) && dflow->C >= 2 && same_geom(*doff, *dflow), "tdvc_add_flow_backward: bad arguments");
+  TDVC_CHECK(doff && dflow && fmap_any(*doff) && (doff->C % 8) == 0 && fmap_ok32(*dflow) && dflow->C >= 2 && same_geom(*doff, *dflow),
+             "tdvc_add_flow_backward: bad arguments");
   const long total = (long)doff->N * doff->H * doff->W;
   hipLaunchKernelGGL(add_flow_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*doff), to_dev(*dflow));
   return tdvc_launch_status("tdvc_add_flow_backward");
 }
 
 extern "C" int tdvc_bcast_add_act_backward(const tdvc_fmap* dx, const tdvc_fmap* x, const tdvc_fmap* db, float slope, void* stream) {
-  TDVC_CHECK(dx && x && db && fmap_ok16(*dx) && fmap_ok16(*x) && fmap_ok16(*db) && same_geom(*dx, *x) && same_geom(*dx, *db) && dx->C == x->C &&
-                 (dx->C % db->C) == 0, "tdvc_bcast_add_act_backward: bad arguments");
+  TDVC_CHECK(dx && x && db && fmap_any(*dx) && fmap_any(*x) && fmap_any(*db) && (db->C % 8) == 0 && same_geom(*dx, *x) && same_geom(*dx, *db) &&
+                 dx->C == x->C && (dx->C % db->C) == 0, "tdvc_bcast_add_act_backward: bad arguments");
   const long total = (long)dx->N * dx->H * dx->W * (db->C / 8);
   hipLaunchKernelGGL(bcast_add_act_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), to_dev(*x), to_dev(*db), slope);
   return tdvc_launch_status("tdvc_bcast_add_act_backward");
 }
 
 extern "C" int tdvc_upsample2x_backward(const tdvc_fmap* dy, const tdvc_fmap* dx, void* stream) {
-  TDVC_CHECK(dy && dx && fmap_ok16(*dy) && fmap_ok16(*dx) && dy->H == 2 * dx->H && dy->W == 2 * dx->W && dy->C == dx->C && dy->N == dx->N,
+  TDVC_CHECK(dy && dx && fmap_any(*dy) && fmap_any(*dx) && (dx->C % 8) == 0 && dy->H == 2 * dx->H && dy->W == 2 * dx->W && dy->C == dx->C && dy->N == dx->N,
              "tdvc_upsample2x_backward: bad arguments");
   const long total = (long)dx->N * dx->H * dx->W * (dx->C / 8);
   hipLaunchKernelGGL(upsample2x_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dy), to_dev(*dx));
@@ -904,7 +905,7 @@ extern "C" int tdvc_resize_bilinear_backward(const tdvc_fmap* dy, const tdvc_fma
 extern "C" int tdvc_spynet_level_input_backward(const tdvc_fmap* supp, const tdvc_fmap* flow_up, const tdvc_fmap* dcat8, const tdvc_fmap* dflow_up,
                                                 const tdvc_fmap* dflow_lo, void* stream) {
   TDVC_CHECK(supp && flow_up && dcat8 && dflow_up && fmap_ok32(*supp) && supp->C >= 3 && fmap_ok32(*flow_up) && flow_up->C >= 2 &&
-                 fmap_ok32(*dflow_up) && dflow_up->C >= 2 && fmap_ok16(*dcat8) && dcat8->C == 8 && same_geom(*supp, *flow_up) &&
+                 fmap_ok32(*dflow_up) && dflow_up->C >= 2 && fmap_any(*dcat8) && dcat8->C == 8 && same_geom(*supp, *flow_up) &&
                  same_geom(*supp, *dcat8) && same_geom(*supp, *dflow_up), "tdvc_spynet_level_input_backward: bad arguments");
   const long total = (long)supp->N * supp->H * supp->W;
   hipLaunchKernelGGL(spynet_warp_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*supp), to_dev(*flow_up), to_dev(*dcat8), to_dev(*dflow_up));
@@ -934,7 +935,7 @@ extern "C" int tdvc_axpy_f32(float* dst, const float* src, float scale, int64_t 
 
 extern "C" int tdvc_match_gather_backward(const tdvc_fmap* fin, const tdvc_fmap* fref, const int32_t* idx, int scale, int hp, int wp,
                                           const tdvc_fmap* dcat, const tdvc_fmap* dfin, const tdvc_fmap* dfref, void* stream) {
-  TDVC_CHECK(fin && fref && idx && dcat && dfin && dfref && fmap_ok16(*fin) && fmap_ok16(*fref) && fmap_ok16(*dcat) && fmap_ok16(*dfin) && fmap_ok16(*dfref),
+  TDVC_CHECK(fin && fref && idx && dcat && dfin && dfref && fmap_any(*fin) && fmap_any(*fref) && fmap_any(*dcat) && fmap_any(*dfin) && fmap_any(*dfref),
              "tdvc_match_gather_backward: bad fmaps");
   TDVC_CHECK(fin->C == 64 && fref->C == 64 && dcat->C == 128 && dfin->C == 64 && dfref->C == 64 && same_geom(*fin, *fref) && same_geom(*fin, *dcat) &&
                  same_geom(*fin, *dfin) && same_geom(*fin, *dfref), "tdvc_match_gather_backward: needs C=64 / dcat C=128");

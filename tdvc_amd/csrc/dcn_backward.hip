@@ -5,6 +5,7 @@
 // dInput is a float-atomic scatter like the reference's (summation order is not reproducible run to
 // run; everything else is deterministic).  `columns` is caller-provided scratch, reused per sample.
 #include "common.h"
+#include "dcn_common.h"      // DcnGroup<T>, dcn_vec2<T>: the 8 channels of a group and an offset pair, fp16 or fp32
 
 namespace {
 
@@ -151,13 +152,17 @@ __global__ __launch_bounds__(256) void bgrad_kernel(const float* __restrict__ gy
 }
 
 // ---------------------------------------------------------------------------------------------------
-// fp16 channel-innermost backward of the fused DCN (training path).  Column channel order k = g * 72 + t * 8 + j
-// (group-major: the 9 taps x 8 channels one (pixel, group) thread reads are 144 contiguous bytes).
+// Channel-innermost backward of the fused DCN (training path), one statement for fp16 maps (T = half_t) and fp32 maps (T = float:
+// the whole-model fp32 training mode).  Column channel order k = g * 72 + t * 8 + j (group-major: the 9 taps x 8 channels one
+// (pixel, group) thread reads are contiguous).
 //   dcn_columns_kernel : col[p][k] = mask(g,t,p) * bilinear(x[.., g*8+j], p + tap t + offset(g,t,p))      (for dW)
 //   dcn_col2im_kernel  : from dcol[p][k] = sum_co W[co][k] dY[p][co]:  d offset, d mask (raw, through the sigmoid) into
 //                        dom, and the bilinear scatter of dcol * mask into dx32 (float atomics: summation order is not
 //                        reproducible, like the reference's col2im, dcn_v2_im2col_cuda.cu:197-254)
-// One thread per (pixel, group, tap), 8 channels = one 16-byte access per bilinear corner.
+// One thread per (pixel, group, tap), 8 channels = 16 bytes (fp16) or 32 bytes (fp32) per bilinear corner.  x, om, col / dcol and dom
+// share T (the launchers refuse a mix); every sum is fp32 and a value is rounded to T only where it is stored.  Positions go through
+// dcn_pos and the mask through dcn_mask<T> of csrc/dcn_common.h, the forward's rule (the fp16 columns alone keep the division they
+// always had, so that the default mode's dW does not move by a bit).
 struct DcnBw {
   FMap x, om, col;           // col doubles as dcol
   FMap dom;
@@ -173,6 +178,22 @@ struct DcnBw {
   int far_cap;
 };
 
+// the 8 channels of one group at `p`, widened to fp32 / rounded to T and stored
+template <typename T>
+__device__ __forceinline__ void dcn_ld8(const T* p, float v[8]) {
+  const DcnGroup<T> g = DcnGroup<T>::load(p);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (float)g.v[j / DcnGroup<T>::VL][j % DcnGroup<T>::VL];
+}
+template <typename T>
+__device__ __forceinline__ void dcn_st8(T* p, const float v[8]) {
+  DcnGroup<T> g;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) g.v[j / DcnGroup<T>::VL][j % DcnGroup<T>::VL] = (T)v[j];
+  g.store(p);
+}
+
+template <typename T>
 __device__ __forceinline__ void dcn_geom(const DcnBw& p, long i, int& n, long& pix, int& g, int& t, float& h_im, float& w_im, float& mask) {
   const long npix = (long)p.x.H * p.x.W;
   t = (int)(i % 9);
@@ -182,41 +203,44 @@ __device__ __forceinline__ void dcn_geom(const DcnBw& p, long i, int& n, long& p
   pix = q % npix;
   n = (int)(q / npix);
   const int y = (int)(pix / p.x.W), xx = (int)(pix % p.x.W);
-  const half_t* omp = reinterpret_cast<const half_t*>(p.om.p) + (long)n * p.om.sn + pix * p.om.sp;
+  const T* omp = reinterpret_cast<const T*>(p.om.p) + (long)n * p.om.sn + pix * p.om.sp;
   const float oh = (float)omp[g * 18 + 2 * t], ow = (float)omp[g * 18 + 2 * t + 1];
-  mask = 1.f / (1.f + __expf(-(float)omp[18 * p.G + g * 9 + t]));
+  const float m = (float)omp[18 * p.G + g * 9 + t];
+  if constexpr (std::is_same_v<T, float>) mask = dcn_mask<float>(m);
+  else mask = 1.f / (1.f + __expf(-m));          // the fp16 columns' mask: a division of the fast exponential, as before the fp32 form
   h_im = (float)(y - 1 + t / 3) + oh;
   w_im = (float)(xx - 1 + t % 3) + ow;
 }
 
+template <typename T>
 __global__ void dcn_columns_kernel(const DcnBw p, long total) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   int n, g, t; long pix; float h_im, w_im, mask;
-  dcn_geom(p, i, n, pix, g, t, h_im, w_im, mask);
+  dcn_geom<T>(p, i, n, pix, g, t, h_im, w_im, mask);
   const int H = p.x.H, W = p.x.W;
-  half8 o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (half_t)0.f;
-  if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
-    const int hl = (int)floorf(h_im), wl = (int)floorf(w_im), hh = hl + 1, wh = wl + 1;
-    const float lh = h_im - hl, lw = w_im - wl;
-    const half_t* xg = reinterpret_cast<const half_t*>(p.x.p) + (long)n * p.x.sn + g * 8;
+  float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const DcnPos q = dcn_pos(H, W, h_im, w_im);      // the sampling rule of csrc/dcn_common.h
+  if (q.inside) {
+    const int hl = q.h_low, wl = q.w_low, hh = hl + 1, wh = wl + 1;
+    const float lh = q.lh, lw = q.lw;
+    const T* xg = reinterpret_cast<const T*>(p.x.p) + (long)n * p.x.sn + g * 8;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     auto corner = [&](int yy, int xc, float wt) {
       if (yy < 0 || yy > H - 1 || xc < 0 || xc > W - 1) return;
-      const half8 v = *reinterpret_cast<const half8*>(xg + ((long)yy * W + xc) * p.x.sp);
+      float v[8];
+      dcn_ld8<T>(xg + ((long)yy * W + xc) * p.x.sp, v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += wt * (float)v[j];
+      for (int j = 0; j < 8; ++j) acc[j] += wt * v[j];
     };
     corner(hl, wl, (1.f - lh) * (1.f - lw));
     corner(hl, wh, (1.f - lh) * lw);
     corner(hh, wl, lh * (1.f - lw));
     corner(hh, wh, lh * lw);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (half_t)(acc[j] * mask);
+    for (int j = 0; j < 8; ++j) o[j] = acc[j] * mask;
   }
-  *reinterpret_cast<half8*>(reinterpret_cast<half_t*>(p.col.p) + (long)n * p.col.sn + pix * p.col.sp + g * 72 + t * 8) = o;
+  dcn_st8<T>(reinterpret_cast<T*>(p.col.p) + (long)n * p.col.sn + pix * p.col.sp + g * 72 + t * 8, o);
 }
 
 // One single-wave workgroup = an 8x8 pixel tile of one (image, deformable group).  The bilinear scatter goes to an LDS
@@ -228,10 +252,12 @@ __global__ void dcn_columns_kernel(const DcnBw p, long total) {
 // with ds_add_f32.  One wave per workgroup, so LDS operations retire in program order and nobody else touches the
 // window.  The window is stored whole to the workgroup's slot of `wbuf` and dcn_window_gather_kernel adds the nine
 // windows that cover each pixel into dx32 in a fixed order.
+// LDS per workgroup: window 18 KB + tags 2.25 KB + the x window 9 KB (fp16) or 18 KB (fp32).
 constexpr int C2I_T = 8, C2I_R = 8, C2I_W = C2I_T + 2 * C2I_R;
+template <typename T>
 __global__ __launch_bounds__(64) void dcn_col2im_kernel(const DcnBw p) {
   __shared__ __attribute__((aligned(16))) float win[C2I_W * C2I_W * 8];
-  __shared__ half8 xw[C2I_W * C2I_W];                                // this group's 8 channels of x over the window (0 outside the image)
+  __shared__ __attribute__((aligned(16))) T xw[C2I_W * C2I_W * 8];   // this group's 8 channels of x over the window (0 outside the image)
   __shared__ int tag[C2I_W * C2I_W];
   const int H = p.x.H, W = p.x.W;
   const int tiles_x = (W + C2I_T - 1) / C2I_T;
@@ -239,15 +265,17 @@ __global__ __launch_bounds__(64) void dcn_col2im_kernel(const DcnBw p) {
   const int g = blockIdx.y % p.G, n = blockIdx.y / p.G;
   const int lane = threadIdx.x;
   const int wy0 = ty * C2I_T - C2I_R, wx0 = tx * C2I_T - C2I_R;
-  const half_t* xg = reinterpret_cast<const half_t*>(p.x.p) + (long)n * p.x.sn + g * 8;
+  const T* xg = reinterpret_cast<const T*>(p.x.p) + (long)n * p.x.sn + g * 8;
   float* dxn = p.dx32 + ((long)n * H * W) * (8 * p.G) + g * 8;
   for (int i = lane; i < C2I_W * C2I_W; i += 64) {
     const int yy = wy0 + i / C2I_W, xc = wx0 + i % C2I_W;
-    half8 v;
+    DcnGroup<T> v;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (half_t)0.f;
-    if (yy >= 0 && yy < H && xc >= 0 && xc < W) v = *reinterpret_cast<const half8*>(xg + ((long)yy * W + xc) * p.x.sp);
-    xw[i] = v;
+    for (int k = 0; k < DcnGroup<T>::NV; ++k)
+#pragma unroll
+      for (int j = 0; j < DcnGroup<T>::VL; ++j) v.v[k][j] = (T)0.f;
+    if (yy >= 0 && yy < H && xc >= 0 && xc < W) v = DcnGroup<T>::load(xg + ((long)yy * W + xc) * p.x.sp);
+    v.store(xw + i * 8);
     tag[i] = -1;
   }
   for (int i = lane; i < C2I_W * C2I_W * 2; i += 64) reinterpret_cast<float4*>(win)[i] = float4{0.f, 0.f, 0.f, 0.f};
@@ -256,29 +284,30 @@ __global__ __launch_bounds__(64) void dcn_col2im_kernel(const DcnBw p) {
   const int y = ty * C2I_T + (lane >> 3), xx = tx * C2I_T + (lane & 7);
   const bool valid = y < H && xx < W;
   const long pix = valid ? (long)y * W + xx : 0;
-  const half_t* omp = reinterpret_cast<const half_t*>(p.om.p) + (long)n * p.om.sn + pix * p.om.sp;
-  half_t* dop = reinterpret_cast<half_t*>(p.dom.p) + (long)n * p.dom.sn + pix * p.dom.sp;
-  const half_t* dcp = reinterpret_cast<const half_t*>(p.col.p) + (long)n * p.col.sn + pix * p.col.sp + g * 72;
-  half2v off[9];
+  const T* omp = reinterpret_cast<const T*>(p.om.p) + (long)n * p.om.sn + pix * p.om.sp;
+  T* dop = reinterpret_cast<T*>(p.dom.p) + (long)n * p.dom.sn + pix * p.dom.sp;
+  const T* dcp = reinterpret_cast<const T*>(p.col.p) + (long)n * p.col.sn + pix * p.col.sp + g * 72;
+  dcn_vec2<T> off[9];
   float mk[9];
-  half8 dc8[9];
+  DcnGroup<T> dc8[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
-    off[t] = *reinterpret_cast<const half2v*>(omp + g * 18 + 2 * t);
-    mk[t] = __builtin_amdgcn_rcpf(1.f + __expf(-(float)omp[18 * p.G + g * 9 + t]));
-    dc8[t] = *reinterpret_cast<const half8*>(dcp + t * 8);
+    off[t] = *reinterpret_cast<const dcn_vec2<T>*>(omp + g * 18 + 2 * t);
+    mk[t] = dcn_mask<T>((float)omp[18 * p.G + g * 9 + t]);
+    dc8[t] = DcnGroup<T>::load(dcp + t * 8);
   }
   float dof[18], dmk[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
     const float mask = mk[t];
     const float h_im = (float)(y - 1 + t / 3) + (float)off[t][0], w_im = (float)(xx - 1 + t % 3) + (float)off[t][1];
-    const bool inside = valid && h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
+    const DcnPos q = dcn_pos(H, W, h_im, w_im);              // the sampling rule of csrc/dcn_common.h: the derivative weights need its fractions
+    const bool inside = valid && q.inside;
     float dc[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) dc[j] = (float)dc8[t][j];
-    const int hl = (int)floorf(h_im), wl = (int)floorf(w_im), hh = hl + 1, wh = wl + 1;
-    const float lh = h_im - hl, lw = w_im - wl;
+    for (int j = 0; j < 8; ++j) dc[j] = (float)dc8[t].v[j / DcnGroup<T>::VL][j % DcnGroup<T>::VL];
+    const int hl = q.h_low, wl = q.w_low, hh = hl + 1, wh = wl + 1;
+    const float lh = q.lh, lw = q.lw;
     float dval = 0.f, dh = 0.f, dw = 0.f;                     // sum_c dcol_c * {val_c, dval_c/dh, dval_c/dw}
     auto corner = [&](int ci, int yy, int xc, float wt, float wth, float wtw) {
       const bool active = inside && yy >= 0 && yy <= H - 1 && xc >= 0 && xc <= W - 1;
@@ -286,12 +315,13 @@ __global__ __launch_bounds__(64) void dcn_col2im_kernel(const DcnBw p) {
       const bool inwin = active && ly >= 0 && ly < C2I_W && lx >= 0 && lx < C2I_W;
       const int tgt = inwin ? ly * C2I_W + lx : 0;
       const long off_px = active ? ((long)yy * W + xc) : 0;
-      half8 v = xw[tgt];
-      if (active && !inwin) v = *reinterpret_cast<const half8*>(xg + off_px * p.x.sp);
+      float v[8];
+      dcn_ld8<T>(xw + tgt * 8, v);
+      if (active && !inwin) dcn_ld8<T>(xg + off_px * p.x.sp, v);
       float a[8], sx = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        sx += dc[j] * (float)v[j];
+        sx += dc[j] * v[j];
         a[j] = dc[j] * mask * wt;
       }
       if (active) { dval += wt * sx; dh += wth * sx; dw += wtw * sx; }
@@ -337,11 +367,11 @@ __global__ __launch_bounds__(64) void dcn_col2im_kernel(const DcnBw p) {
   if (valid) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      half2v* d2 = reinterpret_cast<half2v*>(dop + g * 18 + 2 * t);
-      const half2v o = *d2;
-      *d2 = half2v{(half_t)((float)o[0] + dof[2 * t]), (half_t)((float)o[1] + dof[2 * t + 1])};
-      half_t* dm = dop + 18 * p.G + g * 9 + t;
-      *dm = (half_t)((float)*dm + dmk[t]);
+      dcn_vec2<T>* d2 = reinterpret_cast<dcn_vec2<T>*>(dop + g * 18 + 2 * t);
+      const dcn_vec2<T> o = *d2;
+      *d2 = dcn_vec2<T>{(T)((float)o[0] + dof[2 * t]), (T)((float)o[1] + dof[2 * t + 1])};
+      T* dm = dop + 18 * p.G + g * 9 + t;
+      *dm = (T)((float)*dm + dmk[t]);
     }
   }
   __syncthreads();
@@ -447,19 +477,33 @@ extern "C" int tdvc_dcn_v2_backward_f32(const float* input, const float* weight,
   return tdvc_launch_status("tdvc_dcn_v2_backward_f32");
 }
 
+// an fp32 map the kernels read and write 16 bytes at a time (a group's 8 channels as two float4, an offset pair as one float2)
+static inline bool dcn_ok32(const tdvc_fmap& f) {
+  return fmap_ok32(f) && (f.C % 8) == 0 && (f.sp % 4) == 0 && (f.sn % 4) == 0 && aligned16(f.p);
+}
+static inline bool dcn_map_ok(const tdvc_fmap& f) { return f.dtype == TDVC_F32 ? dcn_ok32(f) : fmap_ok16(f); }
+
 static inline bool dcn_bw_ok(const tdvc_fmap& x, const tdvc_fmap& om, const tdvc_fmap& col, int G) {
-  return fmap_ok16(x) && fmap_ok16(om) && fmap_ok16(col) && G >= 1 && x.C == 8 * G && om.C >= 27 * G && col.C == 72 * G && x.N == om.N && x.N == col.N &&
+  return dcn_map_ok(x) && dcn_map_ok(om) && dcn_map_ok(col) && G >= 1 && x.C == 8 * G && om.C >= 27 * G && col.C == 72 * G && x.N == om.N && x.N == col.N &&
          x.H == om.H && x.W == om.W && x.H == col.H && x.W == col.W && (long)x.H * x.W < 2147483647L;
 }
 
+static const char* dcn_dt(const tdvc_fmap& f) { return f.dtype == TDVC_F32 ? "fp32" : "fp16"; }
+
+extern "C" int tdvc_dcn_col2im_tile(void) { return C2I_T; }
+
 extern "C" int tdvc_dcn_columns(const tdvc_fmap* x, const tdvc_fmap* om, int groups, const tdvc_fmap* col, void* stream) {
-  TDVC_CHECK(x && om && col && dcn_bw_ok(*x, *om, *col, groups), "tdvc_dcn_columns: bad arguments (x C = 8*groups, om C >= 27*groups, col C = 72*groups)");
+  TDVC_CHECK(x && om && col, "tdvc_dcn_columns: null fmap");
+  TDVC_CHECK(x->dtype == om->dtype && x->dtype == col->dtype, "tdvc_dcn_columns: x is %s, om %s, col %s: all fmaps must be fp16 or all fp32", dcn_dt(*x), dcn_dt(*om),
+             dcn_dt(*col));
+  TDVC_CHECK(dcn_bw_ok(*x, *om, *col, groups), "tdvc_dcn_columns: bad arguments (x C = 8*groups, om C >= 27*groups, col C = 72*groups)");
   DcnBw p;
   p.wbuf = nullptr;
   p.x = to_dev(*x); p.om = to_dev(*om); p.col = to_dev(*col); p.dom = null_fmap(); p.dx32 = nullptr; p.G = groups;
   p.far_key = nullptr; p.far_val = nullptr; p.far_count = nullptr; p.far_cap = 0;
   const long total = (long)x->N * x->H * x->W * groups * 9;
-  hipLaunchKernelGGL(dcn_columns_kernel, g1(total), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, total);
+  if (x->dtype == TDVC_F32) hipLaunchKernelGGL(dcn_columns_kernel<float>, g1(total), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, total);
+  else hipLaunchKernelGGL(dcn_columns_kernel<half_t>, g1(total), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, total);
   return tdvc_launch_status("tdvc_dcn_columns");
 }
 
@@ -494,8 +538,11 @@ extern "C" int tdvc_dcn_far_apply(const int64_t* keys_sorted, const int64_t* ord
 
 static int dcn_col2im_impl(const tdvc_fmap* x, const tdvc_fmap* om, const tdvc_fmap* dcol, int groups, float* dx32, const tdvc_fmap* dom,
                            float* work, int64_t work_floats, long long* far_key, float* far_val, int* far_count, int far_cap, void* stream) {
-  TDVC_CHECK(x && om && dcol && dx32 && dom && work && dcn_bw_ok(*x, *om, *dcol, groups) && fmap_ok16(*dom) && dom->C >= 27 * groups && dom->N == x->N &&
-                 dom->H == x->H && dom->W == x->W, "tdvc_dcn_col2im: bad arguments");
+  TDVC_CHECK(x && om && dcol && dx32 && dom && work, "tdvc_dcn_col2im: null argument");
+  TDVC_CHECK(x->dtype == om->dtype && x->dtype == dcol->dtype && x->dtype == dom->dtype,
+             "tdvc_dcn_col2im: x is %s, om %s, dcol %s, dom %s: all fmaps must be fp16 or all fp32", dcn_dt(*x), dcn_dt(*om), dcn_dt(*dcol), dcn_dt(*dom));
+  TDVC_CHECK(dcn_bw_ok(*x, *om, *dcol, groups) && dcn_map_ok(*dom) && dom->C >= 27 * groups && dom->N == x->N && dom->H == x->H && dom->W == x->W,
+             "tdvc_dcn_col2im: bad arguments");
   TDVC_CHECK(work_floats >= tdvc_dcn_col2im_work_floats(x->N, x->H, x->W, groups) && (reinterpret_cast<uintptr_t>(work) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(dx32) & 15) == 0, "tdvc_dcn_col2im: workspace too small or unaligned");
   DcnBw p;
@@ -504,7 +551,8 @@ static int dcn_col2im_impl(const tdvc_fmap* x, const tdvc_fmap* om, const tdvc_f
   const int tiles_x = (x->W + C2I_T - 1) / C2I_T, tiles_y = (x->H + C2I_T - 1) / C2I_T;
   const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(x->N * groups));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(dcn_col2im_kernel, grid, dim3(64), 0, st, p);
+  if (x->dtype == TDVC_F32) hipLaunchKernelGGL(dcn_col2im_kernel<float>, grid, dim3(64), 0, st, p);
+  else hipLaunchKernelGGL(dcn_col2im_kernel<half_t>, grid, dim3(64), 0, st, p);
   hipLaunchKernelGGL(dcn_window_gather_kernel, g1((long)x->N * groups * x->H * x->W), dim3(256), 0, st, p, tiles_x, tiles_y);
   return tdvc_launch_status("tdvc_dcn_col2im");
 }

@@ -45,6 +45,32 @@ struct DcnParams {
 // weights with the modulation mask folded in, zero for a corner outside the image or a position outside (-1, H) x (-1, W), and the
 // corner coordinates clamped into the image, so that every corner can be loaded without a test.  The clamp before floorf keeps an
 // infinite or huge position finite: it lies outside and contributes zero, never NaN.
+// dcn_pos is the rule's first half, shared with the backward kernels (csrc/dcn_backward.hip), which need the fractions for the
+// derivative weights: the open-interval test, the clamped position's integer corner and its fractions.
+struct DcnPos {
+  bool inside;               // the position lies in (-1, H) x (-1, W)
+  int h_low, w_low;          // floor of the clamped position
+  float lh, lw;              // fractions: weights (1 - lh, lh) x (1 - lw, lw) on rows h_low, h_low + 1 and columns w_low, w_low + 1
+};
+
+__device__ __forceinline__ DcnPos dcn_pos(int H, int W, float h_im, float w_im) {
+  DcnPos q;
+  q.inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
+  const float hc = fminf(fmaxf(h_im, -2.f), (float)H + 1.f), wc = fminf(fmaxf(w_im, -2.f), (float)W + 1.f);
+  const float hf = floorf(hc), wf = floorf(wc);
+  q.h_low = (int)hf; q.w_low = (int)wf;
+  q.lh = hc - hf; q.lw = wc - wf;
+  return q;
+}
+
+// the modulation mask of a logit: fp16 maps rcp(1 + __expf(-m)) (the bits the exact tests' dyadic grade pins), fp32 maps a true
+// division of expf (logits +-60000 give exactly 1 and 0, logit 0 exactly 0.5)
+template <typename T>
+__device__ __forceinline__ float dcn_mask(float m) {
+  if constexpr (std::is_same_v<T, float>) return 1.f / (1.f + expf(-m));
+  else return __builtin_amdgcn_rcpf(1.f + __expf(-m));
+}
+
 struct DcnCorners {
   float w1, w2, w3, w4;      // (y0, x0), (y0, x1), (y1, x0), (y1, x1)
   int y0, y1, x0, x1;
@@ -52,11 +78,10 @@ struct DcnCorners {
 
 __device__ __forceinline__ DcnCorners dcn_corners(int H, int W, float h_im, float w_im, float mask) {
   DcnCorners c;
-  const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-  const float hc = fminf(fmaxf(h_im, -2.f), (float)H + 1.f), wc = fminf(fmaxf(w_im, -2.f), (float)W + 1.f);
-  const float hf = floorf(hc), wf = floorf(wc);
-  const int h_low = (int)hf, w_low = (int)wf, h_high = h_low + 1, w_high = w_low + 1;
-  const float lh = hc - hf, lw = wc - wf, hh = 1.f - lh, hw = 1.f - lw;
+  const DcnPos q = dcn_pos(H, W, h_im, w_im);
+  const bool inside = q.inside;
+  const int h_low = q.h_low, w_low = q.w_low, h_high = h_low + 1, w_high = w_low + 1;
+  const float lh = q.lh, lw = q.lw, hh = 1.f - lh, hw = 1.f - lw;
   const bool hl = h_low >= 0 && h_low <= H - 1, hhg = h_high >= 0 && h_high <= H - 1;
   const bool wl = w_low >= 0 && w_low <= W - 1, whg = w_high >= 0 && w_high <= W - 1;
   c.w1 = (inside && hl && wl) ? hh * hw * mask : 0.f; c.w2 = (inside && hl && whg) ? hh * lw * mask : 0.f;
@@ -167,8 +192,7 @@ __global__ __launch_bounds__(256) void dcn_fused_kernel(const DcnParams<T> p) {
       off[ps][t][0] = omp[g * 18 + 2 * t];
       off[ps][t][1] = omp[g * 18 + 2 * t + 1];
       const float m = (float)omp[18 * DCN_G + g * 9 + t];                 // sigmoid (dcn_v2_amp.py: mask = sigmoid(mask))
-      if constexpr (F32) msk[ps][t] = 1.f / (1.f + expf(-m));             // true division
-      else msk[ps][t] = __builtin_amdgcn_rcpf(1.f + __expf(-m));          // the bits the exact tests' dyadic grade pins
+      msk[ps][t] = dcn_mask<T>(m);
     }
   }
 

@@ -304,8 +304,12 @@ class DCN(nn.Module, PackCache):
             # whole-model fp32 mode: fp32 samples, offsets, mask and accumulation (csrc/dcn_f32.hip); the reference's output is an fp16
             # tensor in every mode (dcn_v2_amp.py:15,67-68) that the fp32 features around it widen again
             y16 = FM.empty(x.N, x.H, x.W, out.C, device=x.t.device)
+            # Under the tape (train_model_fp32) the widening is a recorded cast: its adjoint rounds the incoming gradient to fp16, the only
+            # fp16 value of the sweep -- what the reference's autograd does through `.half()`
             ops.dcn_fused(x, om, pc, y16, groups=self.deformable_groups, act=act, slope=slope, round16=True)
-            return ops.copy_cast(y16, out)
+            ops.copy_cast(y16, out)
+            ops._rec("cast", y16, out)
+            return out
         return ops.dcn_fused(x, om, pc, out, groups=self.deformable_groups, act=act, slope=slope, round16=True)
 
 

@@ -48,6 +48,12 @@ class VideoCompressor(nn.Module):
         # compared with the fp32 CPU oracle to fp32 accumulation error; it is bound by the fp32 matrix pipe and is no 30 fps path.
         # Inference only: with the flag set, .train() or a recording tape raises ValueError.  `enabled_amp` keeps its meaning while unset
         self.model_fp32 = False
+        # the reference's `amp: False` in TRAINING (tools/train.py:152-159): with this flag a .train() forward, or any forward under
+        # autograd.record(), runs every stage on fp32 maps exactly as the eval `model_fp32` forward does -- both coders fp32, the plain
+        # sequence of traced calls, no fused inference form -- plus the training-mode differences (noise quantisation, scale-8 matching,
+        # the 5-tuple return), and the tape differentiates all of it in fp32 (fp32 mirrors, conv_f32 dgrad, conv_wgrad_f32, the fp32
+        # deformable-conv backward).  Set by TrainStep(model_fp32=True).  `model_fp32` alone keeps refusing .train() and the tape
+        self.train_model_fp32 = False
         # symbol order of the y streams encode() writes and decode() expects: "raster" (compressai's, what the reference's
         # decoder reads), "wavefront" (an extension: the decoder takes an anti-diagonal per step instead of a position) or "lanes"
         # (a second extension: the wavefront sequence split over `stream_lanes` = 64 or 128 rANS sub-streams, which the decoder's
@@ -90,7 +96,8 @@ class VideoCompressor(nn.Module):
             raise RuntimeError("tdvc_amd.VideoCompressor runs on a HIP device only (no CPU fallback)")
         adt = torch.float32 if mf32 else torch.float16           # activation dtype outside the coders
         f32 = (not enabled_amp) or self.coder_fp32 or mf32
-        if self.training and self.train_coder_fp32:
+        tm32 = mf32 and (self.training or ops.TAPE is not None)          # whole-model fp32 TRAINING (train_model_fp32): fp32 coders implied
+        if self.training and (self.train_coder_fp32 or tm32):
             f32 = True
         elif f32 and self.training:
             if not self.__dict__.get("_warned_fp32_train"):
@@ -105,7 +112,7 @@ class VideoCompressor(nn.Module):
         if H % 64 or W % 64:
             raise RuntimeError(f"input must be padded to a multiple of 64 (got {H}x{W}); see tools/predict.py:51-53")
         dev = input_image.device
-        with torch.cuda.device(dev), torch.no_grad():
+        with torch.cuda.device(dev), torch.no_grad(), ops.train_model_fp32(tm32):
             x = input_image.float()
             refs = refer_frames.float().reshape(B * 4, 3, H, W)
             cur32 = ops.from_nchw(x, Cpad=4, dtype=torch.float32)
@@ -164,10 +171,15 @@ class VideoCompressor(nn.Module):
 
     # ---- real encode / decode (the reference only sketches it: tools/utils/encoder.py, decoder.py) ----
     def _model_fp32_checked(self) -> bool:
-        """`model_fp32`, refused before the first launch where the mode does not exist: training and the tape"""
-        if self.model_fp32 and (self.training or ops.TAPE is not None):
-            raise ValueError("tdvc_amd: model_fp32 is an inference / coding mode (no backward on fp32 maps outside the coders): "
-                             "unset it for .train() and under autograd.record()")
+        """whether this call runs every stage on fp32 maps.  Inference: `model_fp32`.  .train() and the tape: `train_model_fp32`;
+        `model_fp32` alone is refused there before the first launch (it is the inference / coding switch)"""
+        if self.training or ops.TAPE is not None:
+            if self.train_model_fp32:
+                return True
+            if self.model_fp32:
+                raise ValueError("tdvc_amd: model_fp32 is an inference / coding mode: unset it for .train() and under autograd.record(), "
+                                 "or set train_model_fp32 (TrainStep(model_fp32=True)) to train the whole model in fp32")
+            return False
         return bool(self.model_fp32)
 
     def _adt(self):

@@ -949,13 +949,35 @@ DCN_PLANAR_MIN_PIXELS = 1 << 16      # below this the map is L2-resident anyway 
 DCN_PLANAR = __import__("os").environ.get("TDVC_DCN_PLANAR", "0") == "1"
 
 
+TRAIN_MODEL_FP32 = False      # inside `with train_model_fp32(True)`: dcn_fused on fp32 maps records under a tape
+
+
+class train_model_fp32:
+    """`with ops.train_model_fp32(on):` -- VideoCompressor.forward's whole-model fp32 training mode for the calls inside the block"""
+
+    def __init__(self, on: bool):
+        self.on = bool(on)
+
+    def __enter__(self):
+        global TRAIN_MODEL_FP32
+        self.prev, TRAIN_MODEL_FP32 = TRAIN_MODEL_FP32, self.on
+        return self
+
+    def __exit__(self, *exc):
+        global TRAIN_MODEL_FP32
+        TRAIN_MODEL_FP32 = self.prev
+        return False
+
+
 def dcn_fused(x: FM, om: FM, pc: PackedConv, out: FM, groups=8, act=ACT_NONE, slope=0.0, round16=True, planar: bool | None = None) -> FM:
     """`planar` (default: large maps): gather from a group-planar copy of x made by the same call (one extra pass over x;
     the 288 bilinear corner gathers per pixel then share 128-byte lines between neighbouring pixels of a group).
     An fp32 `x` selects the fp32 kernel (csrc/dcn_f32.hip: fp32 samples, offsets, mask and accumulation, the layer's fp32 weight
-    packing); `om` is then fp32 too, `out` fp32 or fp16, and there is no planar form.  Inference only."""
-    if x.f32 and TAPE is not None:
-        raise L.TdvcHipError("dcn_fused on fp32 maps is an inference form (no backward)")
+    packing); `om` is then fp32 too, `out` fp32 or fp16, and there is no planar form.  Under a tape fp32 maps are recorded only in the
+    whole-model fp32 training mode (TRAIN_MODEL_FP32, VideoCompressor.train_model_fp32), with an fp16 `out` as the model calls it;
+    otherwise the fp32 form is inference only."""
+    if x.f32 and TAPE is not None and not (TRAIN_MODEL_FP32 and not out.f32):
+        raise L.TdvcHipError("dcn_fused on fp32 maps is an inference form (no backward) outside the whole-model fp32 training mode")
     d = L.DcnDesc()
     d.x, d.om, d.y = x.desc(), om.desc(), out.desc()
     d.w, d.bias = (pc.packed_f32() if x.f32 else pc.w).data_ptr(), pc.bias.data_ptr()
@@ -969,10 +991,29 @@ def dcn_fused(x: FM, om: FM, pc: PackedConv, out: FM, groups=8, act=ACT_NONE, sl
     return out
 
 
+def _profiled(kernel: str, shape: str, flops: float, launch):
+    """run `launch()`; under PROFILE between two events, as one row of the per-kernel table"""
+    if PROFILE is None:
+        return launch()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    r = launch()
+    e1.record()
+    PROFILE.append(dict(kernel=kernel, shape=shape, e0=e0, e1=e1, flops=flops, flops_real=flops, bytes=0.0))
+    return r
+
+
+def dcn_col2im_tile() -> int:
+    """side of the pixel tile one workgroup of dcn_col2im scatters (its LDS window reaches one tile further on every side)"""
+    return int(L.lib().tdvc_dcn_col2im_tile())
+
+
 def dcn_columns(x: FM, om: FM, groups: int) -> FM:
-    col = FM.empty(x.N, x.H, x.W, 72 * groups, device=x.t.device)
+    """the sampled, modulated columns (N, H, W, 72 groups) in the dtype of `x` (`om` must have it too)"""
+    col = FM.empty(x.N, x.H, x.W, 72 * groups, dtype=x.t.dtype, device=x.t.device)
     d1, d2, d3 = x.desc(), om.desc(), col.desc()
-    L.check(L.lib().tdvc_dcn_columns(C.byref(d1), C.byref(d2), groups, C.byref(d3), _stream()), "dcn_columns")
+    _profiled("dcn_columns_f32" if x.f32 else "dcn_columns", f"G{groups} @{x.N}x{x.H}x{x.W}", 2.0 * 4 * 72 * groups * x.N * x.H * x.W,
+              lambda: L.check(L.lib().tdvc_dcn_columns(C.byref(d1), C.byref(d2), groups, C.byref(d3), _stream()), "dcn_columns"))
     return col
 
 
@@ -983,20 +1024,23 @@ DETERMINISTIC = False
 
 
 def dcn_col2im(x: FM, om: FM, dcol: FM, groups: int, dom: FM) -> FM:
-    """-> dx as an fp32 FM (fresh; scatter through per-tile windows); offset / mask gradients accumulate into `dom`"""
+    """-> dx as an fp32 FM (fresh; scatter through per-tile windows); offset / mask gradients accumulate into `dom`.  x, om, dcol and
+    dom are all fp16 or all fp32 maps (a mix is refused before any launch)"""
     dx32 = FM.zeros(x.N, x.H, x.W, x.C, dtype=torch.float32, device=x.t.device)
     lib = L.lib()
     nwork = lib.tdvc_dcn_col2im_work_floats(x.N, x.H, x.W, groups)
     work = torch.empty((nwork,), dtype=torch.float32, device=x.t.device)
     d1, d2, d3, d4 = x.desc(), om.desc(), dcol.desc(), dom.desc()
+    name, shape, flops = "dcn_col2im_f32" if x.f32 else "dcn_col2im", f"G{groups} @{x.N}x{x.H}x{x.W}", 2.0 * 4 * 3 * 72 * groups * x.N * x.H * x.W
     if DETERMINISTIC:
         dev = x.t.device
         cap = max(1 << 16, x.N * x.H * x.W * groups * 36 // 8)          # an eighth of all samples far out of their window
         keys = torch.empty((cap,), dtype=torch.int64, device=dev)
         vals = torch.empty((cap, 8), dtype=torch.float32, device=dev)
         cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
-        L.check(lib.tdvc_dcn_col2im_det(C.byref(d1), C.byref(d2), C.byref(d3), groups, dx32.t.data_ptr(), C.byref(d4), work.data_ptr(), nwork,
-                                        keys.data_ptr(), vals.data_ptr(), cnt.data_ptr(), cap, _stream()), "dcn_col2im_det")
+        _profiled(name, shape, flops,
+                  lambda: L.check(lib.tdvc_dcn_col2im_det(C.byref(d1), C.byref(d2), C.byref(d3), groups, dx32.t.data_ptr(), C.byref(d4), work.data_ptr(), nwork,
+                                                          keys.data_ptr(), vals.data_ptr(), cnt.data_ptr(), cap, _stream()), "dcn_col2im_det"))
         n = int(cnt.item())
         if n > cap:
             raise L.TdvcHipError(f"dcn_col2im (deterministic): {n} far samples exceed the record capacity {cap}")
@@ -1004,8 +1048,9 @@ def dcn_col2im(x: FM, om: FM, dcol: FM, groups: int, dom: FM) -> FM:
             ks, order = torch.sort(keys[:n], stable=True)
             L.check(lib.tdvc_dcn_far_apply(ks.data_ptr(), order.data_ptr(), vals.data_ptr(), n, dx32.t.data_ptr(), _stream()), "dcn_far_apply")
         return dx32
-    L.check(lib.tdvc_dcn_col2im(C.byref(d1), C.byref(d2), C.byref(d3), groups, dx32.t.data_ptr(), C.byref(d4), work.data_ptr(), nwork, _stream()),
-            "dcn_col2im")
+    _profiled(name, shape, flops,
+              lambda: L.check(lib.tdvc_dcn_col2im(C.byref(d1), C.byref(d2), C.byref(d3), groups, dx32.t.data_ptr(), C.byref(d4), work.data_ptr(), nwork,
+                                                  _stream()), "dcn_col2im"))
     return dx32
 
 

@@ -12,6 +12,7 @@ by rank and the gradients averaged over RCCL (`train.GradBuckets`).
   python -m tdvc_amd.tools.train --iters 20 --batch 4 --size 256
   python -m tdvc_amd.tools.train --distortion ms-ssim --train-lambda 8     # rd_loss = lambda * (1 - MS-SSIM) + bpp (tools/train.py:133,139)
   python -m tdvc_amd.tools.train --coder-fp32                              # both coders optimised in fp32 (pnet.py:33,57)
+  python -m tdvc_amd.tools.train --model-fp32                              # the whole model in fp32: the reference's `amp: False` (tools/train.py:152-159)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m tdvc_amd.tools.train --batch 4
 """
 from __future__ import annotations
@@ -46,7 +47,7 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--train-lambda", type=float, default=2048.0)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--loss-scale", type=float, default=128.0)
+    ap.add_argument("--loss-scale", type=float, default=None, help="initial loss scale (default 128; not with --model-fp32, which trains unscaled)")
     ap.add_argument("--pretrain", default="")
     ap.add_argument("--save-dir", default="")
     ap.add_argument("--save-every", type=int, default=10000)
@@ -59,7 +60,20 @@ def make_parser() -> argparse.ArgumentParser:
                     help="what lambda multiplies: MSE (tools/train.py:136-140) or 1 - MS-SSIM (the commented line :133,139; --size >= 176)")
     ap.add_argument("--coder-fp32", action="store_true",
                     help="optimise mvCoder / resCoder in fp32, as the reference does (main/model/pnet.py:33,57): TrainStep(coder_fp32=True)")
+    ap.add_argument("--model-fp32", action="store_true",
+                    help="train the whole model in fp32, the reference's `amp: False` setting (tools/train.py:152-159: no autocast, no GradScaler, "
+                         "rd_loss.backward(), clip 2, Adam): TrainStep(model_fp32=True).  Implies --coder-fp32; no loss scaling")
     return ap
+
+
+def step_kwargs(a) -> dict:
+    """the TrainStep arguments a parsed command line selects"""
+    kw = dict(train_lambda=a.train_lambda, lr=a.lr, distortion=a.distortion, coder_fp32=a.coder_fp32, model_fp32=a.model_fp32)
+    if a.loss_scale is not None:
+        kw["loss_scale"] = a.loss_scale              # with --model-fp32 any value but 1 is refused by TrainStep
+    elif not a.model_fp32:
+        kw["loss_scale"] = 128.0
+    return kw
 
 
 def main():
@@ -81,9 +95,9 @@ def main():
     else:
         fill_parameters(net)
     net = net.to(dev)
-    step = TrainStep(net, train_lambda=a.train_lambda, lr=a.lr, loss_scale=a.loss_scale, distortion=a.distortion, coder_fp32=a.coder_fp32)
+    step = TrainStep(net, **step_kwargs(a))
     if rank == 0:
-        print(json.dumps({"distortion": a.distortion, "coder_fp32": a.coder_fp32, "train_lambda": a.train_lambda, "batch": a.batch, "size": a.size, "world": world}), flush=True)
+        print(json.dumps({"distortion": a.distortion, "coder_fp32": step.coder_fp32, "model_fp32": step.model_fp32, "train_lambda": a.train_lambda, "batch": a.batch, "size": a.size, "world": world}), flush=True)
 
     pool, cursor = [], 0
     t0 = time.time()

@@ -216,9 +216,10 @@ def msssim_distortion(recon, target):
 
 
 class TrainStep:
-    def __init__(self, model, train_lambda: float = 2048.0, lr: float = 1e-4, loss_scale: float = 1024.0, clip: float = 2.0,
-                 dynamic_scale: bool = True, growth_interval: int = 2000, graph: bool = False, graph_warmup: int = 2,
-                 side_stream: bool = True, scale_update: str = "exact", freeze_gc: bool = True, distortion="mse", coder_fp32: bool = False):
+    def __init__(self, model, train_lambda: float = 2048.0, lr: float = 1e-4, loss_scale: float | None = None, clip: float = 2.0,
+                 dynamic_scale: bool | None = None, growth_interval: int = 2000, graph: bool = False, graph_warmup: int = 2,
+                 side_stream: bool = True, scale_update: str = "exact", freeze_gc: bool = True, distortion="mse", coder_fp32: bool = False,
+                 model_fp32: bool = False):
         """distortion: what lambda multiplies in rd_loss.  "mse" (the reference's active line, tools/train.py:136-140); "ms-ssim":
         rd_loss = lambda * (1 - mean_n ms_ssim(recon, input, data_range=1.0)) + bpp_res + bpp_mv, the reference's commented line
         (:133,139), images of at least 176 pixels a side; or a callable fn(recon_fp32, target_fp32) -> (D, dD_drecon) with D a
@@ -227,6 +228,11 @@ class TrainStep:
         coder_fp32: optimise mvCoder / resCoder as the reference does, outside autocast (main/model/pnet.py:33,57): fp32 activations,
         fp32 weights and fp32 gradients through both coders, on the fp32 matrix pipe (conv_f32, conv_wgrad_f32).  The flag is written to
         `model.train_coder_fp32`; loss scaling, clipping, Adam and the gradient buckets do not change.  Not available with graph=True.
+        model_fp32: the reference's `amp: False` branch (tools/train.py:152-159: no autocast, no scaler, rd_loss.backward(), clip 2, Adam,
+        the auxiliary step): every stage of the forward on fp32 maps and the whole backward sweep in fp32, written to
+        `model.train_model_fp32`; implies fp32 coders.  The loss scale is 1 and never changes (`loss_scale` / `dynamic_scale` left at their
+        defaults -- None: 1024 and dynamic without this mode; any other value together with it raises ValueError); a step whose gradient
+        norm is not finite is still skipped.  Not available with graph=True.
         freeze_gc: after the second step (model, packed weights, descriptor caches and pools exist by then; bench.py's three warm-up steps
         include the collection) everything alive
         moves to the garbage collector's permanent generation (gc.freeze): a step allocates ~50 k short-lived containers (tape
@@ -249,13 +255,27 @@ class TrainStep:
         else:
             raise ValueError(f'distortion must be "mse", "ms-ssim" or a callable, not {distortion!r}')
         self.distortion = distortion
+        self.model_fp32 = bool(model_fp32)
+        if self.model_fp32:
+            if graph:
+                # as for coder_fp32 below: the fp32 weight twins are re-packed lazily, on first use after an optimizer step
+                raise ValueError("TrainStep: model_fp32=True is not supported with graph=True (the fp32 step runs eagerly)")
+            if loss_scale is not None and float(loss_scale) != 1.0:
+                raise ValueError(f"TrainStep: model_fp32=True trains without loss scaling (the reference's amp: False branch); loss_scale={loss_scale!r} given")
+            if dynamic_scale:
+                raise ValueError("TrainStep: model_fp32=True trains without loss scaling (the reference's amp: False branch); dynamic_scale=True given")
+            loss_scale, dynamic_scale = 1.0, False
+        else:
+            loss_scale = 1024.0 if loss_scale is None else loss_scale
+            dynamic_scale = True if dynamic_scale is None else dynamic_scale
         self.model = model
-        self.coder_fp32 = bool(coder_fp32)
+        self.coder_fp32 = bool(coder_fp32) or self.model_fp32
         if self.coder_fp32 and graph:
             # the fp32 weight twins are re-packed lazily, on first use after an optimizer step (an allocation-free launch, but one whose
             # place in the stream a captured graph would freeze together with the pre-step weights of the eager warm-up)
             raise ValueError("TrainStep: coder_fp32=True is not supported with graph=True (the fp32-coder step runs eagerly)")
         model.train_coder_fp32 = self.coder_fp32
+        model.train_model_fp32 = self.model_fp32
         # at least two eager steps: the gradient buckets are re-laid after the first one (GradBuckets.reorder), and only the second builds
         # the device pointer tables of the coders on the final layout -- a host-to-device copy, which a capture does not allow
         self.use_graph, self.graph_warmup, self._eager_steps = bool(graph), max(int(graph_warmup), 2), 0

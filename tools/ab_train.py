@@ -1,6 +1,10 @@
 """A/B inside ONE process (box-to-box and run-to-run noise is larger than the effects measured here): median step time
 of TrainStep with an attribute toggled.  python tools/ab_train.py attr value_a value_b
-or with two statements (names in scope: step, lib, torch):  python tools/ab_train.py exec "stmt_a" "stmt_b" """
+or with two or more statements (names in scope: step, m, lib, torch, TrainStep), run in turn:
+  python tools/ab_train.py exec "stmt_a" "stmt_b" ["stmt_c" ...]
+e.g. the three step modes (a TrainStep writes its mode to the model when it is built):
+  python tools/ab_train.py exec "step = TrainStep(m, loss_scale=128.0)" "step = TrainStep(m, loss_scale=128.0, coder_fp32=True)" \
+                                "step = TrainStep(m, model_fp32=True)" """
 import os
 import statistics
 import sys
@@ -14,7 +18,7 @@ from tdvc_amd.synth import fill_parameters, make_gop, ref_list  # noqa: E402
 from tdvc_amd.train import TrainStep  # noqa: E402
 
 attr = sys.argv[1]
-va, vb = (sys.argv[2], sys.argv[3]) if attr == "exec" else (eval(sys.argv[2]), eval(sys.argv[3]))
+variants = list(sys.argv[2:]) if attr == "exec" else [eval(a) for a in sys.argv[2:4]]
 from tdvc_amd import _lib  # noqa: E402
 lib = _lib.lib()
 torch.manual_seed(0)
@@ -27,9 +31,9 @@ x, refs = torch.cat(xs), torch.cat(rs)
 step = TrainStep(m, loss_scale=128.0)
 for _ in range(5):
     step(x, refs)
-res = {repr(va): [], repr(vb): []}
+res = {repr(v): [] for v in variants}
 for rnd in range(int(os.environ.get("AB_ROUNDS", "4"))):
-    for v in (va, vb):
+    for v in variants:
         if attr == "exec":
             exec(v)
         else:

@@ -1,5 +1,5 @@
-"""diagnostic: per-launch table of the conv kernels (forward, data-gradient and weight-gradient launches) of one training
-step at 4 x 256x256 (HIP events on the launch stream)"""
+"""diagnostic: per-launch table of the conv kernels (forward, data-gradient and weight-gradient launches; the DCN backward's two
+launches) of one training step at 4 x 256x256 (HIP events on the launch stream).  `--coder-fp32` / `--model-fp32`: that step mode."""
 import os
 import sys
 
@@ -21,7 +21,10 @@ for i in range(4):
     xs.append(g[3:4])
     rs.append(ref_list([g[0:1], g[1:2], g[2:3]]))
 x, refs = torch.cat(xs), torch.cat(rs)
-step = TrainStep(m, loss_scale=128.0)
+if "--model-fp32" in sys.argv:
+    step = TrainStep(m, model_fp32=True)
+else:
+    step = TrainStep(m, loss_scale=128.0, coder_fp32="--coder-fp32" in sys.argv)
 for _ in range(2):
     step(x, refs)
 torch.cuda.synchronize()
