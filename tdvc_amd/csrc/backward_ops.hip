@@ -8,14 +8,8 @@ namespace {
 // out = g * act'(z) with the sign of the pre-activation z recovered from the stored output: z > 0 <=> y - res > 0
 // (ReLU / LeakyReLU with slope >= 0).  `out` may alias `g`.
 __global__ void act_backward_kernel(FMap g, FMap y, FMap res, float slope, FMap out) {
-  const long npix = (long)g.H * g.W;
-  const int chunks = g.C / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * g.N * chunks) return;
-  const int c = (int)(i % chunks) * 8;
-  const long q = i / chunks;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, c, ok] = chunk_item(g, g.C / 8);
+  if (!ok) return;
   float gv[8], yv[8];
   load8(g, n, pix, c, gv);
   load8(y, n, pix, c, yv);
@@ -32,16 +26,10 @@ __global__ void act_backward_kernel(FMap g, FMap y, FMap res, float slope, FMap 
 
 // out[n][Y][X][(i*2+j)*C + c] = y[n][2Y+i][2X+j][c]: the sub-pixel conv's gradient in packed-row order
 __global__ void pixel_unshuffle_kernel(FMap y, FMap out) {
-  const long npix = (long)out.H * out.W;
   const int chunks = y.C / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * out.N * chunks * 4) return;
-  const int c = (int)(i % chunks) * 8;
-  long q = i / chunks;
-  const int sub = (int)(q & 3);
-  q >>= 2;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, k, ok] = sub_item(out, 4 * chunks);      // k = sub * chunks + chunk: the four sub-pixels of an output pixel
+  if (!ok) return;
+  const int sub = k / chunks, c = (k - sub * chunks) * 8;
   const int Y = (int)(pix / out.W), X = (int)(pix % out.W);
   float v[8];
   load8(y, n, (long)(2 * Y + (sub >> 1)) * y.W + 2 * X + (sub & 1), c, v);
@@ -50,38 +38,7 @@ __global__ void pixel_unshuffle_kernel(FMap y, FMap out) {
 
 // partial[(n*nblocks + blk)][c] = sum over the block's pixel range, any channel count (256 channels per blockIdx.z)
 __global__ __launch_bounds__(256) void channel_sum_wide_kernel(FMap x, float* partial, int nblocks) {
-  __shared__ float red[256][9];
-  const int c0 = blockIdx.z * 256;
-  const int cw = min(256, x.C - c0);
-  const int chunks = cw / 8;
-  const int lanes = 256 / chunks;
-  const int tid = threadIdx.x;
-  const int ck = tid % chunks, pl = tid / chunks;
-  const int n = blockIdx.y;
-  const long npix = (long)x.H * x.W;
-  const long per = (npix + nblocks - 1) / nblocks;
-  const long p0 = (long)blockIdx.x * per;
-  const long p1 = p0 + per < npix ? p0 + per : npix;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (pl < lanes) {
-    for (long pix = p0 + pl; pix < p1; pix += lanes) {
-      float v[8];
-      load8(x, n, pix, c0 + ck * 8, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += v[j];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[tid][j] = (pl < lanes) ? acc[j] : 0.f;
-  __syncthreads();
-  if (tid < cw) {
-    const int cc = tid / 8, j = tid % 8;
-    float s = 0.f;
-    for (int l = 0; l < lanes; ++l) s += red[l * chunks + cc][j];
-    partial[((long)n * nblocks + blockIdx.x) * x.C + c0 + tid] = s;
-  }
+  channel_sum_block(x, partial, nblocks, blockIdx.z * 256);
 }
 
 // out[dst[c] or c] += scale * sum_rows partial[row][c]: 64 channels x 4 row lanes per workgroup, fixed order
@@ -102,14 +59,8 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* partial, 
 
 // dst[..., c] = c < src.C ? src[..., c] : 0 (any dtypes; dst.C % 8 == 0 when fp16)
 __global__ void copy_cast_kernel(FMap src, FMap dst) {
-  const long npix = (long)dst.H * dst.W;
-  const int chunks = (dst.C + 7) / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * dst.N * chunks) return;
-  const int c = (int)(i % chunks) * 8;
-  const long q = i / chunks;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, c, ok] = chunk_item(dst, (dst.C + 7) / 8);
+  if (!ok) return;
   float v[8];
   if (src.f32) {
     const float* sp = reinterpret_cast<const float*>(src.p) + (long)n * src.sn + pix * src.sp;
@@ -126,14 +77,8 @@ __global__ void copy_cast_kernel(FMap src, FMap dst) {
 
 // g * [0 < y < 1] (the reconstruction clamp), in place
 __global__ void clamp01_backward_kernel(FMap g, FMap y) {
-  const long npix = (long)g.H * g.W;
-  const int chunks = g.C / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * g.N * chunks) return;
-  const int c = (int)(i % chunks) * 8;
-  const long q = i / chunks;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, c, ok] = chunk_item(g, g.C / 8);
+  if (!ok) return;
   float gv[8], yv[8];
   load8(g, n, pix, c, gv);
   load8(y, n, pix, c, yv);
@@ -144,21 +89,14 @@ __global__ void clamp01_backward_kernel(FMap g, FMap y) {
 
 // y = a * gate[n][c]:  da += g * gate;  partial[(n*nblocks + blk)][c] = sum_pix g * a
 __global__ __launch_bounds__(256) void gate_backward_kernel(FMap g, FMap a, const float* gate, FMap da, float* partial, int nblocks) {
-  __shared__ float red[256][9];
-  const int chunks = g.C / 8;            // <= 32
-  const int lanes = 256 / chunks;
-  const int tid = threadIdx.x;
-  const int ck = tid % chunks, pl = tid / chunks;
-  const int n = blockIdx.y;
-  const long npix = (long)g.H * g.W;
-  const long per = (npix + nblocks - 1) / nblocks;
-  const long p0 = (long)blockIdx.x * per;
-  const long p1 = p0 + per < npix ? p0 + per : npix;
+  const ChanLanes L = chan_lanes(g.C);
+  const int ck = L.ck, n = blockIdx.y;
+  const PixRange r = block_pixels(g, nblocks);
   float acc[8], gt[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { acc[j] = 0.f; gt[j] = (pl < lanes) ? gate[(long)n * g.C + ck * 8 + j] : 0.f; }
-  if (pl < lanes) {
-    for (long pix = p0 + pl; pix < p1; pix += lanes) {
+  for (int j = 0; j < 8; ++j) { acc[j] = 0.f; gt[j] = L.live ? gate[(long)n * g.C + ck * 8 + j] : 0.f; }
+  if (L.live) {
+    for (long pix = r.p0 + L.pl; pix < r.p1; pix += L.lanes) {
       float gv[8], av[8];
       load8(g, n, pix, ck * 8, gv);
       load8(a, n, pix, ck * 8, av);
@@ -173,15 +111,7 @@ __global__ __launch_bounds__(256) void gate_backward_kernel(FMap g, FMap a, cons
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[tid][j] = (pl < lanes) ? acc[j] : 0.f;
-  __syncthreads();
-  if (tid < g.C) {
-    const int cc = tid / 8, j = tid % 8;
-    float s = 0.f;
-    for (int l = 0; l < lanes; ++l) s += red[l * chunks + cc][j];
-    partial[((long)n * nblocks + blockIdx.x) * g.C + tid] = s;
-  }
+  chan_lanes_sum(L, acc, g.C, partial + ((long)n * nblocks + blockIdx.x) * g.C);
 }
 
 // out[n][c] += sum_blk partial[(n*nblocks + blk)][c]
@@ -265,14 +195,8 @@ __global__ __launch_bounds__(1024) void se_gate_backward_kernel(const float* par
 
 // dx[n][pix][c] += v[n][c] * scale
 __global__ void bcast_channel_add_kernel(FMap dx, const float* v, float scale) {
-  const long npix = (long)dx.H * dx.W;
-  const int chunks = dx.C / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * dx.N * chunks) return;
-  const int c = (int)(i % chunks) * 8;
-  const long q = i / chunks;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, c, ok] = chunk_item(dx, dx.C / 8);
+  if (!ok) return;
   float d[8];
   load8(dx, n, pix, c, d);
 #pragma unroll
@@ -282,11 +206,8 @@ __global__ void bcast_channel_add_kernel(FMap dx, const float* v, float scale) {
 
 // off += repeat(flow, C/2): dflow[.., 0/1] += sum over even / odd channels of doff
 __global__ void add_flow_backward_kernel(FMap doff, FMap dflow) {
-  const long npix = (long)doff.H * doff.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * doff.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
+  const auto [n, pix, ok] = pixel_item(doff);
+  if (!ok) return;
   float sx = 0.f, sy = 0.f;
   for (int c = 0; c < doff.C; c += 8) {
     float v[8];
@@ -301,14 +222,8 @@ __global__ void add_flow_backward_kernel(FMap doff, FMap dflow) {
 
 // x = lrelu(x_pre + b[c % b.C]) in place:  dx <- dx * lrelu'(x) (in place),  db[c'] += sum over the T slices
 __global__ void bcast_add_act_backward_kernel(FMap dx, FMap x, FMap db, float slope) {
-  const long npix = (long)dx.H * dx.W;
-  const int chunks = db.C / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * dx.N * chunks) return;
-  const int c = (int)(i % chunks) * 8;
-  const long q = i / chunks;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, c, ok] = chunk_item(dx, db.C / 8);      // one item per chunk of db: it walks the T slices of dx
+  if (!ok) return;
   float acc[8];
   load8(db, n, pix, c, acc);
   for (int t = 0; t * db.C < dx.C; ++t) {
@@ -324,33 +239,19 @@ __global__ void bcast_add_act_backward_kernel(FMap dx, FMap x, FMap db, float sl
 
 // adjoint of upsample2x_kernel (bilinear x2, align_corners = False): dx += U^T dy, gathered per input pixel
 __global__ void upsample2x_backward_kernel(FMap dy, FMap dx) {
-  const int chunks = dx.C / 8;
-  const long npix = (long)dx.H * dx.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * chunks * dx.N) return;
-  const int c = (int)(i % chunks) * 8;
-  const long t = i / chunks;
-  const long pix = t % npix;
-  const int n = (int)(t / npix);
+  const auto [n, pix, c, ok] = chunk_item(dx, dx.C / 8);
+  if (!ok) return;
   const int iy = (int)(pix / dx.W), ix = (int)(pix % dx.W);
   float acc[8];
   load8(dx, n, pix, c, acc);
-  // output row oy samples source coordinate sy = (oy + 0.5)/2 - 0.5 clamped to >= 0, rows y0 = floor(sy), y1 = min(y0+1, H-1)
+  // the output rows / columns whose two taps (tap_half2x) can include iy / ix
   for (int oy = 2 * iy - 2; oy <= 2 * iy + 2; ++oy) {
     if (oy < 0 || oy >= dy.H) continue;
-    float sy = (oy + 0.5f) * 0.5f - 0.5f;
-    if (sy < 0.f) sy = 0.f;
-    const int y0 = (int)sy, y1 = min(y0 + 1, dx.H - 1);
-    const float ly = sy - y0;
-    const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
+    const float wy = tap_weight(tap_half2x(oy, dx.H), iy);
     if (wy == 0.f) continue;
     for (int ox = 2 * ix - 2; ox <= 2 * ix + 2; ++ox) {
       if (ox < 0 || ox >= dy.W) continue;
-      float sx = (ox + 0.5f) * 0.5f - 0.5f;
-      if (sx < 0.f) sx = 0.f;
-      const int x0 = (int)sx, x1 = min(x0 + 1, dx.W - 1);
-      const float lx = sx - x0;
-      const float wx = (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f);
+      const float wx = tap_weight(tap_half2x(ox, dx.W), ix);
       if (wx == 0.f) continue;
       float g[8];
       load8(dy, n, (long)oy * dy.W + ox, c, g);
@@ -363,15 +264,11 @@ __global__ void upsample2x_backward_kernel(FMap dy, FMap dx) {
 
 // adjoint of resize_bilinear_kernel (pointwise.hip: bilinear, align_corners = False, arbitrary sizes, optional per-channel
 // scale): dx[iy][ix][c] += sum over the output pixels whose 2 x 2 source footprint contains (iy, ix) of wy * wx * chscale[c] *
-// dy[oy][ox][c], gathered per INPUT pixel (no atomics: reproducible).  Output row oy samples sy = rh (oy + 0.5) - 0.5 clamped
-// to >= 0 with rows y0 = min(floor(sy), H - 1), y1 = y0 + (y0 < H - 1): the candidates of input row iy are the oy with
-// sy in (iy - 1, iy + 1), plus the clamped borders.
+// dy[oy][ox][c], gathered per INPUT pixel (no atomics: reproducible).  Output row oy reads the rows of tap_half(oy, rh, H): the
+// candidates of input row iy are the oy with rh (oy + 0.5) - 0.5 in (iy - 1, iy + 1), plus the clamped borders.
 __global__ void resize_bilinear_backward_kernel(FMap dy, FMap dx, const float* chscale) {
-  const long npix = (long)dx.H * dx.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * dx.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
+  const auto [n, pix, ok] = pixel_item(dx);
+  if (!ok) return;
   const int iy = (int)(pix / dx.W), ix = (int)(pix % dx.W);
   const float rh = (float)dx.H / (float)dy.H, rw = (float)dx.W / (float)dy.W;
   // oy with rh (oy + 0.5) - 0.5 in [iy - 1, iy + 1]: a generous integer bracket, every candidate re-derives its exact weights
@@ -382,16 +279,10 @@ __global__ void resize_bilinear_backward_kernel(FMap dy, FMap dx, const float* c
   for (int c = 0; c < dx.C; ++c) {
     float acc = 0.f;
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      const float sy = fmaxf(rh * (oy + 0.5f) - 0.5f, 0.f);
-      const int y0 = (int)sy < dx.H - 1 ? (int)sy : dx.H - 1, y1 = y0 + (y0 < dx.H - 1);
-      const float ly1 = sy - y0;
-      const float wy = (y0 == iy ? 1.f - ly1 : 0.f) + (y1 == iy ? ly1 : 0.f);
+      const float wy = tap_weight(tap_half(oy, rh, dx.H), iy);
       if (wy == 0.f) continue;
       for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        const float sx = fmaxf(rw * (ox + 0.5f) - 0.5f, 0.f);
-        const int x0 = (int)sx < dx.W - 1 ? (int)sx : dx.W - 1, x1 = x0 + (x0 < dx.W - 1);
-        const float lx1 = sx - x0;
-        const float wx = (x0 == ix ? 1.f - lx1 : 0.f) + (x1 == ix ? lx1 : 0.f);
+        const float wx = tap_weight(tap_half(ox, rw, dx.W), ix);
         if (wx == 0.f) continue;
         acc += wy * wx * gp[((long)oy * dy.W + ox) * dy.sp + c];
       }
@@ -406,24 +297,13 @@ __global__ void resize_bilinear_backward_kernel(FMap dy, FMap dx, const float* c
 // sampling position was clamped to the border (torch's clip_coordinates_set_grad).
 __global__ void spynet_warp_backward_kernel(FMap supp, FMap flow_up, FMap dcat8, FMap dflow_up) {
   const int H = supp.H, W = supp.W;
-  const long npix = (long)H * W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * supp.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
-  const int y = (int)(pix / W), x = (int)(pix % W);
+  const auto [n, pix, ok] = pixel_item(supp);
+  if (!ok) return;
   const float* fu = reinterpret_cast<const float*>(flow_up.p) + (long)n * flow_up.sn + pix * flow_up.sp;
-  const float fx = fu[0], fy = fu[1];
-  const float gx = (float)x + fx, gy = (float)y + fy;
-  const float wm = (float)(W - 1 > 1 ? W - 1 : 1), hm = (float)(H - 1 > 1 ? H - 1 : 1);
-  const float nx = 2.0f * gx / wm - 1.0f, ny = 2.0f * gy / hm - 1.0f;
-  float ix = ((nx + 1.f) / 2.f) * (float)(W - 1), iy = ((ny + 1.f) / 2.f) * (float)(H - 1);
-  const float mx = (ix >= 0.f && ix <= (float)(W - 1)) ? (float)(W - 1) / wm : 0.f;      // d ix / d fx (0 where clamped)
-  const float my = (iy >= 0.f && iy <= (float)(H - 1)) ? (float)(H - 1) / hm : 0.f;
-  ix = fminf((float)(W - 1), fmaxf(ix, 0.f));
-  iy = fminf((float)(H - 1), fmaxf(iy, 0.f));
-  const int ix0 = (int)floorf(ix), iy0 = (int)floorf(iy), ix1 = ix0 + 1, iy1 = iy0 + 1;
-  const bool x0ok = ix0 >= 0 && ix0 < W, x1ok = ix1 >= 0 && ix1 < W, y0ok = iy0 >= 0 && iy0 < H, y1ok = iy1 >= 0 && iy1 < H;
+  const WarpAxis ax = warp_border_axis((int)(pix % W), fu[0], W), ay = warp_border_axis((int)(pix / W), fu[1], H);
+  const float ix = ax.pos, iy = ay.pos, mx = ax.dpos, my = ay.dpos;
+  const int ix0 = ax.i0, iy0 = ay.i0, ix1 = ax.i1, iy1 = ay.i1;
+  const bool x0ok = ax.ok0, x1ok = ax.ok1, y0ok = ay.ok0, y1ok = ay.ok1;
   const float* sp = reinterpret_cast<const float*>(supp.p) + (long)n * supp.sn;
   float dc[8];
   load8(dcat8, n, pix, 0, dc);
@@ -446,29 +326,19 @@ __global__ void spynet_warp_backward_kernel(FMap supp, FMap flow_up, FMap dcat8,
 // stage 2 (per half-resolution pixel): dflow_lo += 2 * U^T dflow_up, U = bilinear x2 with align_corners = True
 __global__ void upsample_ac_backward_kernel(FMap dhi, FMap dlo) {
   const int H = dhi.H, W = dhi.W, h2 = dlo.H, w2 = dlo.W;
-  const long npix = (long)h2 * w2;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * dlo.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
+  const auto [n, pix, ok] = pixel_item(dlo);
+  if (!ok) return;
   const int Y = (int)(pix / w2), X = (int)(pix % w2);
-  const float ry = (H > 1) ? (float)(h2 - 1) / (float)(H - 1) : 0.f;
-  const float rx = (W > 1) ? (float)(w2 - 1) / (float)(W - 1) : 0.f;
+  const float ry = ac_ratio(h2, H), rx = ac_ratio(w2, W);
   const int ylo = ry > 0.f ? max(0, (int)floorf((Y - 1) / ry)) : 0, yhi = ry > 0.f ? min(H - 1, (int)ceilf((Y + 1) / ry)) : H - 1;
   const int xlo = rx > 0.f ? max(0, (int)floorf((X - 1) / rx)) : 0, xhi = rx > 0.f ? min(W - 1, (int)ceilf((X + 1) / rx)) : W - 1;
   const float* hp = reinterpret_cast<const float*>(dhi.p) + (long)n * dhi.sn;
   float sx = 0.f, sy_ = 0.f;
   for (int y = ylo; y <= yhi; ++y) {
-    const float sy = ry * y;
-    const int y0 = (int)sy, y1 = y0 + (y0 < h2 - 1);
-    const float ly1 = sy - y0;
-    const float wy = (y0 == Y ? 1.f - ly1 : 0.f) + (y1 == Y ? ly1 : 0.f);
+    const float wy = tap_weight(tap_ac(y, ry, h2), Y);
     if (wy == 0.f) continue;
     for (int x = xlo; x <= xhi; ++x) {
-      const float sxx = rx * x;
-      const int x0 = (int)sxx, x1 = x0 + (x0 < w2 - 1);
-      const float lx1 = sxx - x0;
-      const float wx = (x0 == X ? 1.f - lx1 : 0.f) + (x1 == X ? lx1 : 0.f);
+      const float wx = tap_weight(tap_ac(x, rx, w2), X);
       if (wx == 0.f) continue;
       const float* g = hp + ((long)y * W + x) * dhi.sp;
       sx += wy * wx * g[0];
@@ -525,14 +395,7 @@ __device__ __forceinline__ MatchGrad match_pair_grad(const float a[8], const flo
 // dfin[p] += da(p)
 __global__ __launch_bounds__(256) void match_gather_backward_in_kernel(FMap fin, FMap fref, const int32_t* idx, int ks, int nbh, int nbw, FMap dcat, FMap dfin) {
   const int lanes = fin.C / 8;
-  const long npix = (long)fin.H * fin.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long t = i / lanes;
-  const int c = (int)(i % lanes) * 8;
-  const bool valid = t < npix * fin.N;
-  const long tc = valid ? t : 0;
-  const int n = (int)(tc / npix);
-  const long pix = tc % npix;
+  const auto [n, pix, c, valid] = chunk_item(fin, lanes);      // no early return: every lane takes part in match_pair_grad's shuffles
   const int y = (int)(pix / fin.W), x = (int)(pix % fin.W);
   const int m = idx[(long)n * nbh * nbw + (y / ks + 1) * nbw + (x / ks + 1)];
   const int sy = (m / nbw - 1) * ks + y % ks, sx = (m % nbw - 1) * ks + x % ks;
@@ -558,14 +421,7 @@ __global__ __launch_bounds__(256) void match_gather_backward_in_kernel(FMap fin,
 // dfref[q] += sum over the output blocks matched to q's block of db(p(q))   (gather form: no atomics, fixed order)
 __global__ __launch_bounds__(256) void match_gather_backward_ref_kernel(FMap fin, FMap fref, const int32_t* idx, int ks, int nbh, int nbw, FMap dcat, FMap dfref) {
   const int lanes = fin.C / 8;
-  const long npix = (long)fref.H * fref.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long t = i / lanes;
-  const int c = (int)(i % lanes) * 8;
-  const bool valid = t < npix * fref.N;
-  const long tc = valid ? t : 0;
-  const int n = (int)(tc / npix);
-  const long pix = tc % npix;
+  const auto [n, pix, c, valid] = chunk_item(fref, lanes);     // no early return, as above
   const int qy = (int)(pix / fref.W), qx = (int)(pix % fref.W);
   const int mq = (qy / ks + 1) * nbw + (qx / ks + 1);
   float b[8], acc[8];
@@ -595,14 +451,8 @@ __global__ __launch_bounds__(256) void match_gather_backward_ref_kernel(FMap fin
 }
 
 __global__ void gdn_backward_kernel(FMap g, FMap x, FMap n32, int inverse, FMap dn, FMap dx) {
-  const long npix = (long)g.H * g.W;
-  const int chunks = g.C / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * g.N * chunks) return;
-  const int c = (int)(i % chunks) * 8;
-  const long q = i / chunks;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, c, ok] = chunk_item(g, g.C / 8);
+  if (!ok) return;
   float gv[8], xv[8], nv[8], dv[8], dnv[8];
   load8(g, n, pix, c, gv);
   load8(x, n, pix, c, xv);
@@ -625,14 +475,8 @@ __global__ void gdn_backward_kernel(FMap g, FMap x, FMap n32, int inverse, FMap 
 }
 
 __global__ void mul2_accumulate_kernel(FMap dx, FMap x, FMap t) {
-  const long npix = (long)dx.H * dx.W;
-  const int chunks = dx.C / 8;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * dx.N * chunks) return;
-  const int c = (int)(i % chunks) * 8;
-  const long q = i / chunks;
-  const int n = (int)(q / npix);
-  const long pix = q % npix;
+  const auto [n, pix, c, ok] = chunk_item(dx, dx.C / 8);
+  if (!ok) return;
   float dv[8], xv[8], tv[8];
   load8(dx, n, pix, c, dv);
   load8(x, n, pix, c, xv);
@@ -703,8 +547,6 @@ __device__ __forceinline__ float eb_logits_backward(const float* P, float v, flo
   return dv;
 }
 
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
 // one workgroup per channel: dz += gscale * d bits / d z, dparams[c][:] += gscale * d bits / d params (bits = -log2 lik)
 __global__ __launch_bounds__(256) void eb_backward_kernel(FMap z, const float* params, FMap noise, float gscale, FMap dz, float* dparams) {
   __shared__ float red[4][EBP];
@@ -724,7 +566,7 @@ __global__ __launch_bounds__(256) void eb_backward_kernel(FMap z, const float* p
     const float lo = eb_logits(P, v - 0.5f), up = eb_logits(P, v + 0.5f);
     const float ssum = lo + up;
     const float sign = ssum > 0.f ? -1.f : (ssum < 0.f ? 1.f : 0.f);
-    const float su = sigm(sign * up), sl = sigm(sign * lo);
+    const float su = sigmoidf_(sign * up), sl = sigmoidf_(sign * lo);
     const float diff = su - sl;
     const float lik = fabsf(diff);
     float dv = 0.f;
@@ -744,25 +586,18 @@ __global__ __launch_bounds__(256) void eb_backward_kernel(FMap z, const float* p
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < EBP; ++i) {
-    float v = gp[i];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const float v = wave_sum(gp[i]);
     if (lane == 0) red[wave][i] = v;
   }
   __syncthreads();
-  if (threadIdx.x < EBP) dparams[(long)c * EBP + threadIdx.x] += red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  if (threadIdx.x < EBP) dparams[(long)c * EBP + threadIdx.x] += waves_sum(&red[0][threadIdx.x], 4, EBP);
 }
 
 // Gaussian conditional with additive noise: bits = -log2 max(Phi((.5 - v)/s) - Phi((-.5 - v)/s), 1e-9), v = |y + noise - mean|,
 // s = max(scale, 0.11): dy, dmean (= -dy), dscale (below the bound only a NEGATIVE gradient passes: compressai LowerBound)
 __global__ void gc_backward_kernel(FMap y, FMap gp, FMap noise, float gscale, FMap dy, FMap dgp) {
-  const long npix = (long)y.H * y.W;
-  const long total = npix * y.C * y.N;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int c = (int)(i % y.C);
-  const long t = i / y.C;
-  const long pix = t % npix;
-  const int n = (int)(t / npix);
+  const auto [n, pix, c, ok] = sub_item(y, y.C);      // one channel per thread
+  if (!ok) return;
   const float yv = reinterpret_cast<const float*>(y.p)[(long)n * y.sn + pix * y.sp + c];
   const float* g = reinterpret_cast<const float*>(gp.p) + (long)n * gp.sn + pix * gp.sp;
   const float sc = g[c], mean = g[y.C + c];
@@ -793,8 +628,7 @@ extern "C" int tdvc_act_backward(const tdvc_fmap* g, const tdvc_fmap* y, const t
              "tdvc_act_backward: bad arguments");
   if (res) TDVC_CHECK(fmap_any(*res) && same_geom(*g, *res) && res->C >= g->C, "tdvc_act_backward: bad residual");
   TDVC_CHECK(act == TDVC_ACT_RELU || act == TDVC_ACT_LRELU, "tdvc_act_backward: activation %d has no fused backward", act);
-  const long total = (long)g->N * g->H * g->W * (g->C / 8);
-  hipLaunchKernelGGL(act_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*g), to_dev(*y), res ? to_dev(*res) : null_fmap(),
+  hipLaunchKernelGGL(act_backward_kernel, grid1d(chunk_items(*g, g->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*g), to_dev(*y), res ? to_dev(*res) : null_fmap(),
                      act == TDVC_ACT_RELU ? 0.f : slope, to_dev(*out));
   return tdvc_launch_status("tdvc_act_backward");
 }
@@ -802,8 +636,7 @@ extern "C" int tdvc_act_backward(const tdvc_fmap* g, const tdvc_fmap* y, const t
 extern "C" int tdvc_pixel_unshuffle(const tdvc_fmap* y, const tdvc_fmap* out, void* stream) {
   TDVC_CHECK(y && out && fmap_any(*y) && fmap_any(*out) && (y->C % 8) == 0 && out->N == y->N && y->H == 2 * out->H && y->W == 2 * out->W && out->C == 4 * y->C,
              "tdvc_pixel_unshuffle: bad arguments");
-  const long total = (long)out->N * out->H * out->W * (y->C / 8) * 4;
-  hipLaunchKernelGGL(pixel_unshuffle_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*y), to_dev(*out));
+  hipLaunchKernelGGL(pixel_unshuffle_kernel, grid1d(chunk_items(*out, 4 * (y->C / 8))),dim3(EW_BLOCK), 0, ST(stream), to_dev(*y), to_dev(*out));
   return tdvc_launch_status("tdvc_pixel_unshuffle");
 }
 
@@ -823,15 +656,13 @@ extern "C" int tdvc_bias_grad(const tdvc_fmap* g, int nvalid, const int32_t* dst
 extern "C" int tdvc_copy_cast(const tdvc_fmap* src, const tdvc_fmap* dst, void* stream) {
   TDVC_CHECK(src && dst && fmap_any(*src) && fmap_any(*dst) && same_geom(*src, *dst) && dst->C >= src->C && (src->dtype == TDVC_F32 || (src->C % 8) == 0),
              "tdvc_copy_cast: bad arguments");
-  const long total = (long)dst->N * dst->H * dst->W * ((dst->C + 7) / 8);
-  hipLaunchKernelGGL(copy_cast_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*src), to_dev(*dst));
+  hipLaunchKernelGGL(copy_cast_kernel, grid1d(chunk_items(*dst, (dst->C + 7) / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*src), to_dev(*dst));
   return tdvc_launch_status("tdvc_copy_cast");
 }
 
 extern "C" int tdvc_clamp01_backward(const tdvc_fmap* g, const tdvc_fmap* y, void* stream) {
   TDVC_CHECK(g && y && fmap_any(*g) && fmap_any(*y) && same_geom(*g, *y) && y->C >= g->C && (g->C % 8) == 0, "tdvc_clamp01_backward: bad arguments");
-  const long total = (long)g->N * g->H * g->W * (g->C / 8);
-  hipLaunchKernelGGL(clamp01_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*g), to_dev(*y));
+  hipLaunchKernelGGL(clamp01_backward_kernel, grid1d(chunk_items(*g, g->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*g), to_dev(*y));
   return tdvc_launch_status("tdvc_clamp01_backward");
 }
 
@@ -866,39 +697,34 @@ extern "C" int tdvc_se_gate_backward(const float* partial, int nblocks, float in
 
 extern "C" int tdvc_bcast_channel_add(const tdvc_fmap* dx, const float* v, float scale, void* stream) {
   TDVC_CHECK(dx && v && fmap_any(*dx) && (dx->C % 8) == 0, "tdvc_bcast_channel_add: bad arguments");
-  const long total = (long)dx->N * dx->H * dx->W * (dx->C / 8);
-  hipLaunchKernelGGL(bcast_channel_add_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), v, scale);
+  hipLaunchKernelGGL(bcast_channel_add_kernel, grid1d(chunk_items(*dx, dx->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), v, scale);
   return tdvc_launch_status("tdvc_bcast_channel_add");
 }
 
 extern "C" int tdvc_add_flow_backward(const tdvc_fmap* doff, const tdvc_fmap* dflow, void* stream) {
   TDVC_CHECK(doff && dflow && fmap_any(*doff) && (doff->C % 8) == 0 && fmap_ok32(*dflow) && dflow->C >= 2 && same_geom(*doff, *dflow),
              "tdvc_add_flow_backward: bad arguments");
-  const long total = (long)doff->N * doff->H * doff->W;
-  hipLaunchKernelGGL(add_flow_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*doff), to_dev(*dflow));
+  hipLaunchKernelGGL(add_flow_backward_kernel, grid1d(pixel_items(*doff)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*doff), to_dev(*dflow));
   return tdvc_launch_status("tdvc_add_flow_backward");
 }
 
 extern "C" int tdvc_bcast_add_act_backward(const tdvc_fmap* dx, const tdvc_fmap* x, const tdvc_fmap* db, float slope, void* stream) {
   TDVC_CHECK(dx && x && db && fmap_any(*dx) && fmap_any(*x) && fmap_any(*db) && (db->C % 8) == 0 && same_geom(*dx, *x) && same_geom(*dx, *db) &&
                  dx->C == x->C && (dx->C % db->C) == 0, "tdvc_bcast_add_act_backward: bad arguments");
-  const long total = (long)dx->N * dx->H * dx->W * (db->C / 8);
-  hipLaunchKernelGGL(bcast_add_act_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), to_dev(*x), to_dev(*db), slope);
+  hipLaunchKernelGGL(bcast_add_act_backward_kernel, grid1d(chunk_items(*dx, db->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), to_dev(*x), to_dev(*db), slope);
   return tdvc_launch_status("tdvc_bcast_add_act_backward");
 }
 
 extern "C" int tdvc_upsample2x_backward(const tdvc_fmap* dy, const tdvc_fmap* dx, void* stream) {
   TDVC_CHECK(dy && dx && fmap_any(*dy) && fmap_any(*dx) && (dx->C % 8) == 0 && dy->H == 2 * dx->H && dy->W == 2 * dx->W && dy->C == dx->C && dy->N == dx->N,
              "tdvc_upsample2x_backward: bad arguments");
-  const long total = (long)dx->N * dx->H * dx->W * (dx->C / 8);
-  hipLaunchKernelGGL(upsample2x_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dy), to_dev(*dx));
+  hipLaunchKernelGGL(upsample2x_backward_kernel, grid1d(chunk_items(*dx, dx->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*dy), to_dev(*dx));
   return tdvc_launch_status("tdvc_upsample2x_backward");
 }
 
 extern "C" int tdvc_resize_bilinear_backward(const tdvc_fmap* dy, const tdvc_fmap* dx, const float* chscale, void* stream) {
   TDVC_CHECK(dy && dx && fmap_ok32(*dy) && fmap_ok32(*dx) && dy->N == dx->N && dy->C == dx->C, "tdvc_resize_bilinear_backward: two fp32 fmaps of equal batch and channels expected");
-  const long total = (long)dx->N * dx->H * dx->W;
-  hipLaunchKernelGGL(resize_bilinear_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dy), to_dev(*dx), chscale);
+  hipLaunchKernelGGL(resize_bilinear_backward_kernel, grid1d(pixel_items(*dx)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*dy), to_dev(*dx), chscale);
   return tdvc_launch_status("tdvc_resize_bilinear_backward");
 }
 
@@ -907,12 +733,10 @@ extern "C" int tdvc_spynet_level_input_backward(const tdvc_fmap* supp, const tdv
   TDVC_CHECK(supp && flow_up && dcat8 && dflow_up && fmap_ok32(*supp) && supp->C >= 3 && fmap_ok32(*flow_up) && flow_up->C >= 2 &&
                  fmap_ok32(*dflow_up) && dflow_up->C >= 2 && fmap_any(*dcat8) && dcat8->C == 8 && same_geom(*supp, *flow_up) &&
                  same_geom(*supp, *dcat8) && same_geom(*supp, *dflow_up), "tdvc_spynet_level_input_backward: bad arguments");
-  const long total = (long)supp->N * supp->H * supp->W;
-  hipLaunchKernelGGL(spynet_warp_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*supp), to_dev(*flow_up), to_dev(*dcat8), to_dev(*dflow_up));
+  hipLaunchKernelGGL(spynet_warp_backward_kernel, grid1d(pixel_items(*supp)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*supp), to_dev(*flow_up), to_dev(*dcat8), to_dev(*dflow_up));
   if (dflow_lo) {
     TDVC_CHECK(fmap_ok32(*dflow_lo) && dflow_lo->C >= 2 && dflow_lo->N == supp->N, "tdvc_spynet_level_input_backward: bad dflow_lo");
-    const long tl = (long)dflow_lo->N * dflow_lo->H * dflow_lo->W;
-    hipLaunchKernelGGL(upsample_ac_backward_kernel, grid1d(tl), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dflow_up), to_dev(*dflow_lo));
+    hipLaunchKernelGGL(upsample_ac_backward_kernel, grid1d(pixel_items(*dflow_lo)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*dflow_up), to_dev(*dflow_lo));
   }
   return tdvc_launch_status("tdvc_spynet_level_input_backward");
 }
@@ -942,7 +766,7 @@ extern "C" int tdvc_match_gather_backward(const tdvc_fmap* fin, const tdvc_fmap*
   const int ks = 3 * scale;
   const int nbh = (fin->H + ks) / ks + 1, nbw = (fin->W + ks) / ks + 1;
   TDVC_CHECK(nbh == (hp + 3) / 3 + 1 && nbw == (wp + 3) / 3 + 1, "tdvc_match_gather_backward: fold grid != patch grid");
-  const long total = (long)fin->N * fin->H * fin->W * 8;
+  const long total = chunk_items(*fin, fin->C / 8);
   hipLaunchKernelGGL(match_gather_backward_in_kernel, grid1d(total), dim3(256), 0, ST(stream), to_dev(*fin), to_dev(*fref), idx, ks, nbh, nbw, to_dev(*dcat), to_dev(*dfin));
   hipLaunchKernelGGL(match_gather_backward_ref_kernel, grid1d(total), dim3(256), 0, ST(stream), to_dev(*fin), to_dev(*fref), idx, ks, nbh, nbw, to_dev(*dcat), to_dev(*dfref));
   return tdvc_launch_status("tdvc_match_gather_backward");
@@ -952,8 +776,7 @@ extern "C" int tdvc_gdn_backward(const tdvc_fmap* g, const tdvc_fmap* x, const t
   TDVC_CHECK(g && x && n32 && dn && dx && fmap_any(*g) && fmap_any(*x) && fmap_ok32(*n32) && fmap_any(*dn) && fmap_any(*dx) && same_geom(*g, *x) &&
                  same_geom(*g, *n32) && same_geom(*g, *dn) && same_geom(*g, *dx) && (g->C % 8) == 0 && x->C >= g->C && n32->C >= g->C && dn->C >= g->C &&
                  dx->C >= g->C, "tdvc_gdn_backward: bad arguments");
-  const long total = (long)g->N * g->H * g->W * (g->C / 8);
-  hipLaunchKernelGGL(gdn_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*g), to_dev(*x), to_dev(*n32), inverse, to_dev(*dn), to_dev(*dx));
+  hipLaunchKernelGGL(gdn_backward_kernel, grid1d(chunk_items(*g, g->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*g), to_dev(*x), to_dev(*n32), inverse, to_dev(*dn), to_dev(*dx));
   return tdvc_launch_status("tdvc_gdn_backward");
 }
 
@@ -961,8 +784,7 @@ extern "C" int tdvc_mul2_accumulate(const tdvc_fmap* dx, const tdvc_fmap* x, con
   // the kernel moves 8 channels per thread: fp16 maps have C % 8 == 0 by construction (fmap_ok16), fp32 maps are held to it here
   TDVC_CHECK(dx && x && t && fmap_any(*dx) && fmap_any(*x) && fmap_any(*t) && (dx->C % 8) == 0 && same_geom(*dx, *x) && same_geom(*dx, *t) && x->C >= dx->C && t->C >= dx->C,
              "tdvc_mul2_accumulate: bad arguments");
-  const long total = (long)dx->N * dx->H * dx->W * (dx->C / 8);
-  hipLaunchKernelGGL(mul2_accumulate_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), to_dev(*x), to_dev(*t));
+  hipLaunchKernelGGL(mul2_accumulate_kernel, grid1d(chunk_items(*dx, dx->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*dx), to_dev(*x), to_dev(*t));
   return tdvc_launch_status("tdvc_mul2_accumulate");
 }
 
@@ -999,7 +821,7 @@ __global__ void eb_param_chain_kernel(const float* dpacked, const float* const* 
   const EbCol e = eb_col(col);
   const float x = raw[e.k][c * e.len + e.j];
   float d = 1.f;
-  if (col < 33) d = x > 20.f ? 1.f : sigm(x);
+  if (col < 33) d = x > 20.f ? 1.f : sigmoidf_(x);
   else if (col >= 46) { const float t = tanhf(x); d = 1.f - t * t; }
   grad[e.k][c * e.len + e.j] += scale * dpacked[i] * d;
 }
@@ -1023,14 +845,10 @@ __global__ __launch_bounds__(1024) void eb_aux_kernel(const float* params, const
     dq[i] = eb_logits_backward(P, v, sg, gp);
     l = fabsf(r);
   }
-  for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o);
+  l = wave_sum(l);
   if ((i & 63) == 0) sh[i >> 6] = l;
   __syncthreads();
-  if (i == 0) {
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-    loss[0] = t;
-  }
+  if (i == 0) loss[0] = waves_sum(sh, (int)(blockDim.x >> 6));      // l >= +0: the sum from sh[0] is the sum from 0.f
 }
 
 extern "C" int tdvc_eb_pack(const float* const* raw, const float* quantiles, float* packed, int C, void* stream) {
@@ -1063,7 +881,6 @@ extern "C" int tdvc_gc_backward(const tdvc_fmap* y, const tdvc_fmap* gp, const t
   TDVC_CHECK(y && gp && noise && dy && dgp && fmap_ok32(*y) && fmap_ok32(*gp) && fmap_ok32(*noise) && fmap_ok32(*dy) && fmap_ok32(*dgp) && same_geom(*y, *gp) &&
                  same_geom(*y, *noise) && same_geom(*y, *dy) && same_geom(*y, *dgp) && gp->C >= 2 * y->C && dgp->C >= 2 * y->C && dy->C >= y->C,
              "tdvc_gc_backward: bad arguments");
-  const long total = (long)y->N * y->H * y->W * y->C;
-  hipLaunchKernelGGL(gc_backward_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*y), to_dev(*gp), to_dev(*noise), gscale, to_dev(*dy), to_dev(*dgp));
+  hipLaunchKernelGGL(gc_backward_kernel, grid1d(pixel_items(*y) * y->C),dim3(EW_BLOCK), 0, ST(stream), to_dev(*y), to_dev(*gp), to_dev(*noise), gscale, to_dev(*dy), to_dev(*dgp));
   return tdvc_launch_status("tdvc_gc_backward");
 }

@@ -9,10 +9,8 @@ namespace {
 // ------------------------------------------------------------------ layout
 __global__ void nchw_to_fmap_kernel(const float* src, int C, FMap y) {
   const long npix = (long)y.H * y.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * y.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
+  const auto [n, pix, ok] = pixel_item(y);
+  if (!ok) return;
   for (int c0 = 0; c0 < y.C; c0 += 8) {
     float v[8];
 #pragma unroll
@@ -23,10 +21,8 @@ __global__ void nchw_to_fmap_kernel(const float* src, int C, FMap y) {
 
 __global__ void fmap_to_nchw_kernel(FMap x, int C, float* dst) {
   const long npix = (long)x.H * x.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * x.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
+  const auto [n, pix, ok] = pixel_item(x);
+  if (!ok) return;
   for (int c0 = 0; c0 < C; c0 += 8) {
     float v[8];
     load8(x, n, pix, c0, v);
@@ -38,14 +34,8 @@ __global__ void fmap_to_nchw_kernel(FMap x, int C, float* dst) {
 
 // ------------------------------------------------------------------ elementwise
 __global__ void scale_act_res_kernel(FMap a, const float* gate, int act, float slope, FMap r, float rs, FMap y, FMap y2) {
-  const int chunks = (a.C + 7) / 8;
-  const long npix = (long)a.H * a.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * chunks * a.N) return;
-  const int c = (int)(i % chunks) * 8;
-  const long t = i / chunks;
-  const long pix = t % npix;
-  const int n = (int)(t / npix);
+  const auto [n, pix, c, ok] = chunk_item(a, (a.C + 7) / 8);
+  if (!ok) return;
   float v[8];
   load8(a, n, pix, c, v);
   if (gate) {
@@ -153,14 +143,8 @@ __global__ __launch_bounds__(256) void scale_act_res16_y3_kernel(FMap a, const f
 }
 
 __global__ void add_flow_kernel(FMap off, FMap flow) {
-  const int chunks = off.C / 8;
-  const long npix = (long)off.H * off.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * chunks * off.N) return;
-  const int c = (int)(i % chunks) * 8;
-  const long t = i / chunks;
-  const long pix = t % npix;
-  const int n = (int)(t / npix);
+  const auto [n, pix, c, ok] = chunk_item(off, off.C / 8);
+  if (!ok) return;
   const float* fp = reinterpret_cast<const float*>(flow.p) + (long)n * flow.sn + pix * flow.sp;
   const float fx = fp[0], fy = fp[1];
   float v[8];
@@ -171,14 +155,8 @@ __global__ void add_flow_kernel(FMap off, FMap flow) {
 }
 
 __global__ void bcast_add_act_kernel(FMap x, FMap b, float slope) {
-  const int chunks = x.C / 8;
-  const long npix = (long)x.H * x.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * chunks * x.N) return;
-  const int c = (int)(i % chunks) * 8;
-  const long t = i / chunks;
-  const long pix = t % npix;
-  const int n = (int)(t / npix);
+  const auto [n, pix, c, ok] = chunk_item(x, x.C / 8);
+  if (!ok) return;
   float v[8], q[8];
   load8(x, n, pix, c, v);
   load8(b, n, pix, c % b.C, q);
@@ -212,46 +190,7 @@ __global__ __launch_bounds__(256) void bcast_add_act_t_kernel(FMap x, FMap b, fl
 // ------------------------------------------------------------------ SE attention
 // partial[n][blk][c] = sum over the block's pixel range
 __global__ __launch_bounds__(256) void channel_sum_kernel(FMap x, float* partial, int nblocks) {
-  __shared__ float red[256][9];
-  const int chunks = x.C / 8;            // <= 32
-  const int lanes = 256 / chunks;        // pixel lanes
-  const int tid = threadIdx.x;
-  const int ck = tid % chunks, pl = tid / chunks;
-  const int n = blockIdx.y;
-  const long npix = (long)x.H * x.W;
-  const long per = (npix + nblocks - 1) / nblocks;
-  const long p0 = (long)blockIdx.x * per;
-  const long p1 = p0 + per < npix ? p0 + per : npix;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (pl < lanes) {
-    long pix = p0 + pl;
-    for (; pix + 3 * lanes < p1; pix += 4 * lanes) {       // four independent 16-byte loads in flight per thread; summed in pixel order
-      float v[4][8];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) load8(x, n, pix + u * lanes, ck * 8, v[u]);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += v[u][j];
-    }
-    for (; pix < p1; pix += lanes) {
-      float v[8];
-      load8(x, n, pix, ck * 8, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += v[j];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[tid][j] = (pl < lanes) ? acc[j] : 0.f;
-  __syncthreads();
-  if (tid < x.C) {
-    const int c = tid, cc = c / 8, j = c % 8;
-    float s = 0.f;
-    for (int l = 0; l < lanes; ++l) s += red[l * chunks + cc][j];
-    partial[((long)n * nblocks + blockIdx.x) * x.C + c] = s;
-  }
+  channel_sum_block(x, partial, nblocks, 0);
 }
 
 __global__ __launch_bounds__(1024) void se_gate_kernel(const float* partial, int nblocks, float inv_count, int C, int Cmid,
@@ -293,41 +232,28 @@ __global__ __launch_bounds__(1024) void se_gate_kernel(const float* partial, int
   if (tid < C) {
     float s = b2[tid];
     for (int j = 0; j < Cmid; ++j) s += w2[tid * Cmid + j] * mid[j];
-    gate[(long)n * C + tid] = 1.f / (1.f + expf(-s));
+    gate[(long)n * C + tid] = sigmoidf_(s);
   }
 }
 
 // ------------------------------------------------------------------ resampling
 __global__ void upsample2x_kernel(FMap x, FMap y) {
-  const int chunks = x.C / 8;
-  const long npix = (long)y.H * y.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * chunks * y.N) return;
-  const int c = (int)(i % chunks) * 8;
-  const long t = i / chunks;
-  const long pix = t % npix;
-  const int n = (int)(t / npix);
-  const int oy = (int)(pix / y.W), ox = (int)(pix % y.W);
-  const float sy = fmaxf((oy + 0.5f) * 0.5f - 0.5f, 0.f), sx = fmaxf((ox + 0.5f) * 0.5f - 0.5f, 0.f);
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < x.H - 1), x1 = x0 + (x0 < x.W - 1);
-  const float ly1 = sy - y0, lx1 = sx - x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+  const auto [n, pix, c, ok] = chunk_item(y, x.C / 8);
+  if (!ok) return;
+  const Tap ty = tap_half2x((int)(pix / y.W), x.H), tx = tap_half2x((int)(pix % y.W), x.W);
   float a[8], b[8], cc[8], d[8], v[8];
-  load8(x, n, (long)y0 * x.W + x0, c, a);
-  load8(x, n, (long)y0 * x.W + x1, c, b);
-  load8(x, n, (long)y1 * x.W + x0, c, cc);
-  load8(x, n, (long)y1 * x.W + x1, c, d);
+  load8(x, n, (long)ty.i0 * x.W + tx.i0, c, a);
+  load8(x, n, (long)ty.i0 * x.W + tx.i1, c, b);
+  load8(x, n, (long)ty.i1 * x.W + tx.i0, c, cc);
+  load8(x, n, (long)ty.i1 * x.W + tx.i1, c, d);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = ly0 * (lx0 * a[j] + lx1 * b[j]) + ly1 * (lx0 * cc[j] + lx1 * d[j]);
+  for (int j = 0; j < 8; ++j) v[j] = bilerp(ty, tx, a[j], b[j], cc[j], d[j]);
   store8(y, n, pix, c, v);
 }
 
 __global__ void avgpool2_kernel(FMap x, FMap y) {
-  const long npix = (long)y.H * y.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * y.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
+  const auto [n, pix, ok] = pixel_item(y);
+  if (!ok) return;
   const int oy = (int)(pix / y.W), ox = (int)(pix % y.W);
   const float* xp = reinterpret_cast<const float*>(x.p) + (long)n * x.sn;
   float* yp = reinterpret_cast<float*>(y.p) + (long)n * y.sn + pix * y.sp;
@@ -405,17 +331,12 @@ __global__ void spynet_level_input_kernel(FMap ref, FMap supp, FMap flow_lo, FMa
   float fx = 0.f, fy = 0.f;
   if (flow_lo.p) {
     const int h2 = flow_lo.H, w2 = flow_lo.W;
-    const float ry = (H > 1) ? (float)(h2 - 1) / (float)(H - 1) : 0.f;
-    const float rx = (W > 1) ? (float)(w2 - 1) / (float)(W - 1) : 0.f;
-    const float sy = ry * y, sx = rx * x;
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = y0 + (y0 < h2 - 1), x1 = x0 + (x0 < w2 - 1);
-    const float ly1 = sy - y0, lx1 = sx - x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+    const Tap ty = tap_ac(y, ac_ratio(h2, H), h2), tx = tap_ac(x, ac_ratio(w2, W), w2);
     const float* fl = reinterpret_cast<const float*>(flow_lo.p) + (long)n * flow_lo.sn;
-    const float* pa = fl + ((long)y0 * w2 + x0) * flow_lo.sp;
-    const float* pb = fl + ((long)y0 * w2 + x1) * flow_lo.sp;
-    const float* pc = fl + ((long)y1 * w2 + x0) * flow_lo.sp;
-    const float* pd = fl + ((long)y1 * w2 + x1) * flow_lo.sp;
+    const float* pa = fl + ((long)ty.i0 * w2 + tx.i0) * flow_lo.sp;
+    const float* pb = fl + ((long)ty.i0 * w2 + tx.i1) * flow_lo.sp;
+    const float* pc = fl + ((long)ty.i1 * w2 + tx.i0) * flow_lo.sp;
+    const float* pd = fl + ((long)ty.i1 * w2 + tx.i1) * flow_lo.sp;
     f32x2 a, b, c, d;
     if constexpr (VEC) {
       a = *reinterpret_cast<const f32x2*>(pa); b = *reinterpret_cast<const f32x2*>(pb);
@@ -423,23 +344,17 @@ __global__ void spynet_level_input_kernel(FMap ref, FMap supp, FMap flow_lo, FMa
     } else {
       a = f32x2{pa[0], pa[1]}; b = f32x2{pb[0], pb[1]}; c = f32x2{pc[0], pc[1]}; d = f32x2{pd[0], pd[1]};
     }
-    fx = (ly0 * (lx0 * a[0] + lx1 * b[0]) + ly1 * (lx0 * c[0] + lx1 * d[0])) * 2.0f;
-    fy = (ly0 * (lx0 * a[1] + lx1 * b[1]) + ly1 * (lx0 * c[1] + lx1 * d[1])) * 2.0f;
+    fx = bilerp(ty, tx, a[0], b[0], c[0], d[0]) * 2.0f;
+    fy = bilerp(ty, tx, a[1], b[1], c[1], d[1]) * 2.0f;
   }
-  // grid_sample(bilinear, border, align_corners=True) through the normalise / unnormalise round trip
-  const float gx = (float)x + fx, gy = (float)y + fy;
-  const float wm = (float)(W - 1 > 1 ? W - 1 : 1), hm = (float)(H - 1 > 1 ? H - 1 : 1);
-  const float nx = 2.0f * gx / wm - 1.0f, ny = 2.0f * gy / hm - 1.0f;
-  float ix = ((nx + 1.f) / 2.f) * (float)(W - 1), iy = ((ny + 1.f) / 2.f) * (float)(H - 1);
-  ix = fminf((float)(W - 1), fmaxf(ix, 0.f));
-  iy = fminf((float)(H - 1), fmaxf(iy, 0.f));
-  const float xw = floorf(ix), yn = floorf(iy);
-  const int ix0 = (int)xw, iy0 = (int)yn, ix1 = ix0 + 1, iy1 = iy0 + 1;
+  const WarpAxis ax = warp_border_axis(x, fx, W), ay = warp_border_axis(y, fy, H);
+  const float ix = ax.pos, iy = ay.pos;
+  const int ix0 = ax.i0, iy0 = ay.i0, ix1 = ax.i1, iy1 = ay.i1;
   const float w_nw = ((float)ix1 - ix) * ((float)iy1 - iy), w_ne = (ix - (float)ix0) * ((float)iy1 - iy);
   const float w_sw = ((float)ix1 - ix) * (iy - (float)iy0), w_se = (ix - (float)ix0) * (iy - (float)iy0);
   const float* sp = reinterpret_cast<const float*>(supp.p) + (long)n * supp.sn;
   float wv[3] = {0.f, 0.f, 0.f};
-  const bool x0ok = ix0 >= 0 && ix0 < W, x1ok = ix1 >= 0 && ix1 < W, y0ok = iy0 >= 0 && iy0 < H, y1ok = iy1 >= 0 && iy1 < H;
+  const bool x0ok = ax.ok0, x1ok = ax.ok1, y0ok = ay.ok0, y1ok = ay.ok1;
   const float* rp = reinterpret_cast<const float*>(ref.p) + (long)n * ref.sn + pix * ref.sp;
   float r3[3];
   if constexpr (VEC) {
@@ -484,23 +399,15 @@ __global__ void spynet_level_input_kernel(FMap ref, FMap supp, FMap flow_lo, FMa
 }
 
 __global__ void resize_bilinear_kernel(FMap x, FMap y, const float* chscale) {
-  const long npix = (long)y.H * y.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * y.N) return;
-  const int n = (int)(i / npix);
-  const long pix = i % npix;
-  const int oy = (int)(pix / y.W), ox = (int)(pix % y.W);
-  const float rh = (float)x.H / (float)y.H, rw = (float)x.W / (float)y.W;
-  const float sy = fmaxf(rh * (oy + 0.5f) - 0.5f, 0.f), sx = fmaxf(rw * (ox + 0.5f) - 0.5f, 0.f);
-  const int y0 = (int)sy < x.H - 1 ? (int)sy : x.H - 1, x0 = (int)sx < x.W - 1 ? (int)sx : x.W - 1;
-  const int y1 = y0 + (y0 < x.H - 1), x1 = x0 + (x0 < x.W - 1);
-  const float ly1 = sy - y0, lx1 = sx - x0, ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+  const auto [n, pix, ok] = pixel_item(y);
+  if (!ok) return;
+  const Tap ty = tap_half((int)(pix / y.W), (float)x.H / (float)y.H, x.H), tx = tap_half((int)(pix % y.W), (float)x.W / (float)y.W, x.W);
   const float* xp = reinterpret_cast<const float*>(x.p) + (long)n * x.sn;
   float* yp = reinterpret_cast<float*>(y.p) + (long)n * y.sn + pix * y.sp;
   for (int c = 0; c < y.C; ++c) {
-    const float a = xp[((long)y0 * x.W + x0) * x.sp + c], b = xp[((long)y0 * x.W + x1) * x.sp + c];
-    const float cc = xp[((long)y1 * x.W + x0) * x.sp + c], d = xp[((long)y1 * x.W + x1) * x.sp + c];
-    float v = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * cc + lx1 * d);
+    const float a = xp[((long)ty.i0 * x.W + tx.i0) * x.sp + c], b = xp[((long)ty.i0 * x.W + tx.i1) * x.sp + c];
+    const float cc = xp[((long)ty.i1 * x.W + tx.i0) * x.sp + c], d = xp[((long)ty.i1 * x.W + tx.i1) * x.sp + c];
+    float v = bilerp(ty, tx, a, b, cc, d);
     if (chscale) v *= chscale[c];
     yp[c] = v;
   }
@@ -512,12 +419,9 @@ __global__ void resize_bilinear_kernel(FMap x, FMap y, const float* chscale) {
 // 136 x 136 pixels per cell and only 8 x 14 cells: one block per cell left 144 of 256 CUs idle and ran 0.8 TB/s.)
 constexpr int POOL_ROWS = 8;
 __global__ __launch_bounds__(256) void avgpool_k_strip_kernel(FMap x, int scale, float* work, int wp, int nsplit, const int* pred) {
-  __shared__ float red[256][9];
   TDVC_PREDICATE_RETURN(pred);
-  const int chunks = x.C / 8;
-  const int lanes = 256 / chunks;
-  const int tid = threadIdx.x;
-  const int ck = tid % chunks, pl = tid / chunks;
+  const ChanLanes L = chan_lanes(x.C);
+  const int lanes = L.lanes, ck = L.ck;
   const int cell = blockIdx.x / nsplit, strip = blockIdx.x - cell * nsplit, n = blockIdx.y;
   const int py = cell / wp, px = cell % wp;
   const int r0 = strip * POOL_ROWS, rows = min(POOL_ROWS, scale - r0);
@@ -525,8 +429,8 @@ __global__ __launch_bounds__(256) void avgpool_k_strip_kernel(FMap x, int scale,
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
   const int area = rows * scale;
-  if (pl < lanes) {
-    int k = pl;                          // four independent 16-byte loads in flight per thread
+  if (L.live) {
+    int k = L.pl;                        // four independent 16-byte loads in flight per thread
     for (; k + 3 * lanes < area; k += 4 * lanes) {
       float v[4][8];
 #pragma unroll
@@ -546,15 +450,7 @@ __global__ __launch_bounds__(256) void avgpool_k_strip_kernel(FMap x, int scale,
       for (int j = 0; j < 8; ++j) acc[j] += v[j];
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[tid][j] = (pl < lanes) ? acc[j] : 0.f;
-  __syncthreads();
-  if (tid < x.C) {
-    const int cc = tid / 8, j = tid % 8;
-    float s = 0.f;
-    for (int l = 0; l < lanes; ++l) s += red[l * chunks + cc][j];
-    work[(((long)n * gridDim.x) + blockIdx.x) * x.C + tid] = s;
-  }
+  chan_lanes_sum(L, acc, x.C, work + (((long)n * gridDim.x) + blockIdx.x) * x.C);
 }
 
 __global__ void avgpool_k_final_kernel(const float* work, float* pooled, long total, int C_, int nsplit, float area, const int* pred) {
@@ -611,16 +507,6 @@ __global__ __launch_bounds__(EW_BLOCK) void frames_refresh_kernel(FMap cur, FMap
   *frame_word(cache, i) = *frame_word(cur, i);
 }
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((tid & 63) == 0) sh[tid >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // patch (i,j) of a pooled map: rows 3i-3..3i-1, cols 3j-3..3j-1, zero outside (unfold k=3,s=3,p=3)
 __device__ __forceinline__ float patch_elem(const float* pm, int hp, int wp, int C, int pi, int pj, int d) {
   const int c = d / 9, k = d % 9;
@@ -668,14 +554,7 @@ __global__ __launch_bounds__(256) void patch_match_kernel(const float* pin, cons
 // 8 lanes per pixel (8 channels each, C = 64): gather matched block, cosine weight, write cat
 __global__ __launch_bounds__(256) void match_gather_kernel(FMap fin, FMap fref, const int32_t* idx, int ks, int nbh, int nbw, FMap cat) {
   const int lanes = fin.C / 8;            // 8
-  const long npix = (long)fin.H * fin.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long t = i / lanes;
-  const int c = (int)(i % lanes) * 8;
-  const bool valid = t < npix * fin.N;
-  const long tc = valid ? t : 0;
-  const int n = (int)(tc / npix);
-  const long pix = tc % npix;
+  const auto [n, pix, c, valid] = chunk_item(fin, lanes);      // no early return: every lane takes part in the shuffles below
   const int y = (int)(pix / fin.W), x = (int)(pix % fin.W);
   const int bi = y / ks + 1, bj = x / ks + 1;
   const int m = idx[(long)n * nbh * nbw + bi * nbw + bj];
@@ -705,19 +584,11 @@ __global__ __launch_bounds__(256) void match_gather_kernel(FMap fin, FMap fref, 
 }
 
 // ------------------------------------------------------------------ entropy model
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 __global__ __launch_bounds__(256) void eb_forward_kernel(FMap z, const float* params, FMap noise, FMap z_hat, float* partial) {
   __shared__ float sh[4];
-  const long npix = (long)z.H * z.W;
-  const long total = npix * z.C * z.N;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const auto [n, pix, c, ok] = sub_item(z, z.C);      // one channel per thread; every thread reaches block_sum
   float bits = 0.f;
-  if (i < total) {
-    const int c = (int)(i % z.C);
-    const long t = i / z.C;
-    const long pix = t % npix;
-    const int n = (int)(t / npix);
+  if (ok) {
     const float* P = params + (long)c * EB_NP;
     const float zv = reinterpret_cast<const float*>(z.p)[(long)n * z.sn + pix * z.sp + c];
     float v;
@@ -744,15 +615,9 @@ __global__ __launch_bounds__(256) void eb_forward_kernel(FMap z, const float* pa
 
 __global__ __launch_bounds__(256) void gc_forward_kernel(FMap y, FMap gp, FMap noise, float* partial) {
   __shared__ float sh[4];
-  const long npix = (long)y.H * y.W;
-  const long total = npix * y.C * y.N;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const auto [n, pix, c, ok] = sub_item(y, y.C);
   float bits = 0.f;
-  if (i < total) {
-    const int c = (int)(i % y.C);
-    const long t = i / y.C;
-    const long pix = t % npix;
-    const int n = (int)(t / npix);
+  if (ok) {
     const float yv = reinterpret_cast<const float*>(y.p)[(long)n * y.sn + pix * y.sp + c];
     const float* g = reinterpret_cast<const float*>(gp.p) + (long)n * gp.sn + pix * gp.sp;
     const float scale = fmaxf(g[c], 0.11f), mean = g[y.C + c];
@@ -786,14 +651,8 @@ __global__ void final_sum_kernel(const float* partial, int n, double* out) {
 }
 
 __global__ void quantize_kernel(FMap y, FMap noise, FMap y_hat) {
-  const int chunks = (y.C + 7) / 8;
-  const long npix = (long)y.H * y.W;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix * chunks * y.N) return;
-  const int c = (int)(i % chunks) * 8;
-  const long t = i / chunks;
-  const long pix = t % npix;
-  const int n = (int)(t / npix);
+  const auto [n, pix, c, ok] = chunk_item(y, (y.C + 7) / 8);
+  if (!ok) return;
   float v[8];
   load8(y, n, pix, c, v);
   if (noise.p) {
@@ -812,15 +671,13 @@ __global__ void quantize_kernel(FMap y, FMap noise, FMap y_hat) {
 
 extern "C" int tdvc_nchw_to_fmap(const float* src, int C, const tdvc_fmap* y, void* stream) {
   TDVC_CHECK(src && y && fmap_any(*y) && C >= 1 && C <= y->C, "tdvc_nchw_to_fmap: bad arguments");
-  const long total = (long)y->N * y->H * y->W;
-  hipLaunchKernelGGL(nchw_to_fmap_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), src, C, to_dev(*y));
+  hipLaunchKernelGGL(nchw_to_fmap_kernel, grid1d(pixel_items(*y)),dim3(EW_BLOCK), 0, ST(stream), src, C, to_dev(*y));
   return tdvc_launch_status("tdvc_nchw_to_fmap");
 }
 
 extern "C" int tdvc_fmap_to_nchw(const tdvc_fmap* x, int C, float* dst, void* stream) {
   TDVC_CHECK(dst && x && fmap_any(*x) && C >= 1 && C <= x->C, "tdvc_fmap_to_nchw: bad arguments");
-  const long total = (long)x->N * x->H * x->W;
-  hipLaunchKernelGGL(fmap_to_nchw_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), C, dst);
+  hipLaunchKernelGGL(fmap_to_nchw_kernel, grid1d(pixel_items(*x)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), C, dst);
   return tdvc_launch_status("tdvc_fmap_to_nchw");
 }
 
@@ -829,7 +686,7 @@ extern "C" int tdvc_scale_act_res(const tdvc_fmap* a, const float* gate, int act
   TDVC_CHECK(a && y && fmap_any(*a) && fmap_any(*y) && same_geom(*a, *y) && y->C == a->C, "tdvc_scale_act_res: bad a/y");
   if (r) TDVC_CHECK(fmap_any(*r) && same_geom(*a, *r) && r->C == a->C, "tdvc_scale_act_res: bad residual");
   if (y2) TDVC_CHECK(fmap_any(*y2) && same_geom(*a, *y2) && y2->C == a->C, "tdvc_scale_act_res: bad y2");
-  const long total = (long)a->N * a->H * a->W * ((a->C + 7) / 8);
+  const long total = chunk_items(*a, (a->C + 7) / 8);
   const bool all16 = a->dtype == TDVC_F16 && y->dtype == TDVC_F16 && (!r || r->dtype == TDVC_F16) && (!y2 || y2->dtype == TDVC_F16) &&
                      (!gate || aligned16(gate)) && total < (1L << 31) - (1L << 23);
   if (all16) {
@@ -853,7 +710,7 @@ extern "C" int tdvc_scale_act_res3(const tdvc_fmap* a, const float* gate, int ac
   TDVC_CHECK(fmap_ok16(*b) && same_geom(*a, *b) && b->C == a->C && fmap_ok16(*y3) && same_geom(*a, *y3) && y3->C == a->C,
              "tdvc_scale_act_res3: b / y3 must be fp16 maps of a's geometry");
   TDVC_CHECK(y3->p != y->p && y3->p != a->p && (!r || y3->p != r->p), "tdvc_scale_act_res3: y3 must not alias a, r or y");
-  const long total = (long)a->N * a->H * a->W * (a->C / 8);
+  const long total = chunk_items(*a, a->C / 8);
   TDVC_CHECK((!gate || aligned16(gate)) && total < (1L << 31) - (1L << 23), "tdvc_scale_act_res3: gate unaligned or map too large");
   constexpr int U = 4;
   long blocks = (total + 256 * U - 1) / (256 * U);
@@ -866,14 +723,13 @@ extern "C" int tdvc_scale_act_res3(const tdvc_fmap* a, const float* gate, int ac
 
 extern "C" int tdvc_add_flow(const tdvc_fmap* off, const tdvc_fmap* flow, void* stream) {
   TDVC_CHECK(off && flow && fmap_any(*off) && (off->C % 8) == 0 && fmap_ok32(*flow) && flow->C >= 2 && same_geom(*off, *flow), "tdvc_add_flow: bad arguments");
-  const long total = (long)off->N * off->H * off->W * (off->C / 8);
-  hipLaunchKernelGGL(add_flow_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*off), to_dev(*flow));
+  hipLaunchKernelGGL(add_flow_kernel, grid1d(chunk_items(*off, off->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*off), to_dev(*flow));
   return tdvc_launch_status("tdvc_add_flow");
 }
 
 extern "C" int tdvc_bcast_add_act(const tdvc_fmap* x, const tdvc_fmap* b, int T, float slope, void* stream) {
   TDVC_CHECK(x && b && fmap_any(*x) && fmap_any(*b) && (b->C % 8) == 0 && same_geom(*x, *b) && x->C == T * b->C, "tdvc_bcast_add_act: bad arguments");
-  const long total = (long)x->N * x->H * x->W * (x->C / 8);
+  const long total = chunk_items(*x, x->C / 8);
   const bool f16 = x->dtype == TDVC_F16 && b->dtype == TDVC_F16;      // the T-slice kernel reads raw fp16 words; fp32 maps take the generic one
   if (f16 && T == 4 && total / 4 < (1L << 31)) {
     const long items = total / 4;
@@ -901,16 +757,14 @@ extern "C" int tdvc_se_gate(const float* partial, int nblocks, float inv_count, 
 extern "C" int tdvc_upsample2x(const tdvc_fmap* x, const tdvc_fmap* y, void* stream) {
   TDVC_CHECK(x && y && fmap_any(*x) && fmap_any(*y) && (x->C % 8) == 0 && y->H == 2 * x->H && y->W == 2 * x->W && y->C == x->C && y->N == x->N,
              "tdvc_upsample2x: bad arguments");
-  const long total = (long)y->N * y->H * y->W * (y->C / 8);
-  hipLaunchKernelGGL(upsample2x_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y));
+  hipLaunchKernelGGL(upsample2x_kernel, grid1d(chunk_items(*y, x->C / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y));
   return tdvc_launch_status("tdvc_upsample2x");
 }
 
 extern "C" int tdvc_avgpool2(const tdvc_fmap* x, const tdvc_fmap* y, void* stream) {
   TDVC_CHECK(x && y && fmap_ok32(*x) && fmap_ok32(*y) && y->H == x->H / 2 && y->W == x->W / 2 && y->C <= x->C && y->N == x->N,
              "tdvc_avgpool2: bad arguments");
-  const long total = (long)y->N * y->H * y->W;
-  hipLaunchKernelGGL(avgpool2_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y));
+  hipLaunchKernelGGL(avgpool2_kernel, grid1d(pixel_items(*y)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y));
   return tdvc_launch_status("tdvc_avgpool2");
 }
 
@@ -919,8 +773,7 @@ extern "C" int tdvc_avgpool2_pyramid(const tdvc_fmap* xa, const tdvc_fmap* xb, c
   TDVC_CHECK((xa->H % 32) == 0 && (xa->W % 32) == 0, "tdvc_avgpool2_pyramid: H and W must be multiples of 32 (got %dx%d)", xa->H, xa->W);
   const int C_ = ya[0].C;
   TDVC_CHECK(C_ >= 1 && C_ <= 4 && C_ <= xa->C && C_ <= xb->C, "tdvc_avgpool2_pyramid: 1 <= C <= 4 channels, not more than the inputs have");
-  auto pix16 = [](const tdvc_fmap& f) { return f.C == 4 && (f.sp % 4) == 0 && (f.sn % 4) == 0 && aligned16(f.p); };             // whole 4-float pixels
-  bool vec = xa->C >= 4 && xb->C >= 4 && (xa->sp % 4) == 0 && (xb->sp % 4) == 0 && (xa->sn % 4) == 0 && (xb->sn % 4) == 0 && aligned16(xa->p) && aligned16(xb->p);
+  bool vec = pix16(*xa) && pix16(*xb);
   PyramidMaps a;
   a.x[0] = to_dev(*xa);
   a.x[1] = to_dev(*xb);
@@ -929,7 +782,7 @@ extern "C" int tdvc_avgpool2_pyramid(const tdvc_fmap* xa, const tdvc_fmap* xb, c
       const tdvc_fmap& y = (m ? yb : ya)[k];
       TDVC_CHECK(fmap_ok32(y) && y.N == xa->N && y.H == xa->H >> (k + 1) && y.W == xa->W >> (k + 1) && y.C == C_,
                  "tdvc_avgpool2_pyramid: level %d of map %d must be an fp32 map of %d x %d x %d", k + 1, m, xa->H >> (k + 1), xa->W >> (k + 1), C_);
-      vec = vec && pix16(y);
+      vec = vec && y.C == 4 && pix16(y);             // the levels are written as whole 4-float pixels
       a.y[m][k] = to_dev(y);
     }
   TDVC_CHECK(2L * xa->N <= 65535, "tdvc_avgpool2_pyramid: batch too large");
@@ -947,9 +800,7 @@ extern "C" int tdvc_spynet_level_input(const tdvc_fmap* ref, const tdvc_fmap* su
   TDVC_CHECK(fmap_any(*cat8) && cat8->C == 8 && same_geom(*ref, *cat8), "tdvc_spynet_level_input: bad cat8");
   if (flow_lo) TDVC_CHECK(fmap_ok32(*flow_lo) && flow_lo->C >= 2 && flow_lo->N == ref->N && flow_lo->H * 2 == ref->H && flow_lo->W * 2 == ref->W,
                           "tdvc_spynet_level_input: bad flow_lo");
-  const long total = (long)ref->N * ref->H * ref->W;
-  auto pix16 = [](const tdvc_fmap& f) { return f.C >= 4 && (f.sp % 4) == 0 && (f.sn % 4) == 0 && aligned16(f.p); };             // whole 4-float pixels
-  auto pix8 = [](const tdvc_fmap& f) { return (f.sp % 2) == 0 && (f.sn % 2) == 0 && (((uintptr_t)f.p) & 7) == 0; };             // whole 2-float pixels
+  const long total = pixel_items(*ref);
   const bool vec = pix16(*ref) && pix16(*supp) && pix8(*flow_up) && (!flow_lo || pix8(*flow_lo));
   if (vec)
     hipLaunchKernelGGL(spynet_level_input_kernel<true>, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*ref), to_dev(*supp),
@@ -962,8 +813,7 @@ extern "C" int tdvc_spynet_level_input(const tdvc_fmap* ref, const tdvc_fmap* su
 
 extern "C" int tdvc_resize_bilinear(const tdvc_fmap* x, const tdvc_fmap* y, const float* chscale, void* stream) {
   TDVC_CHECK(x && y && fmap_ok32(*x) && fmap_ok32(*y) && y->C <= x->C && y->N == x->N, "tdvc_resize_bilinear: bad arguments");
-  const long total = (long)y->N * y->H * y->W;
-  hipLaunchKernelGGL(resize_bilinear_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y), chscale);
+  hipLaunchKernelGGL(resize_bilinear_kernel, grid1d(pixel_items(*y)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*x), to_dev(*y), chscale);
   return tdvc_launch_status("tdvc_resize_bilinear");
 }
 
@@ -1021,8 +871,7 @@ extern "C" int tdvc_match_gather(const tdvc_fmap* fin, const tdvc_fmap* fref, co
   const int nbh = (fin->H + ks) / ks + 1, nbw = (fin->W + ks) / ks + 1;   // fold(kernel=ks, pad=ks, stride=ks)
   TDVC_CHECK(nbh == (hp + 3) / 3 + 1 && nbw == (wp + 3) / 3 + 1,
              "tdvc_match_gather: fold grid %dx%d != patch grid %dx%d (F.fold would raise, pnet.py:252)", nbh, nbw, (hp + 3) / 3 + 1, (wp + 3) / 3 + 1);
-  const long total = (long)fin->N * fin->H * fin->W * 8;
-  hipLaunchKernelGGL(match_gather_kernel, grid1d(total), dim3(256), 0, ST(stream), to_dev(*fin), to_dev(*fref), idx, ks, nbh, nbw, to_dev(*cat));
+  hipLaunchKernelGGL(match_gather_kernel, grid1d(chunk_items(*fin, fin->C / 8)),dim3(256), 0, ST(stream), to_dev(*fin), to_dev(*fref), idx, ks, nbh, nbw, to_dev(*cat));
   return tdvc_launch_status("tdvc_match_gather");
 }
 
@@ -1031,7 +880,7 @@ extern "C" int tdvc_eb_forward(const tdvc_fmap* z, const float* params, const td
   TDVC_CHECK(z && params && z_hat && bits_out && partial && fmap_ok32(*z) && fmap_any(*z_hat) && same_geom(*z, *z_hat) && z_hat->C >= z->C,
              "tdvc_eb_forward: bad arguments");
   if (noise) TDVC_CHECK(fmap_ok32(*noise) && same_geom(*z, *noise) && noise->C >= z->C, "tdvc_eb_forward: bad noise");
-  const long total = (long)z->N * z->H * z->W * z->C;
+  const long total = pixel_items(*z) * z->C;
   const int nb = (int)((total + 255) / 256);
   TDVC_CHECK(nb <= partial_cap, "tdvc_eb_forward: partial buffer too small (%d < %d)", partial_cap, nb);
   hipLaunchKernelGGL(eb_forward_kernel, dim3(nb), dim3(256), 0, ST(stream), to_dev(*z), params, noise ? to_dev(*noise) : null_fmap(), to_dev(*z_hat), partial);
@@ -1043,7 +892,7 @@ extern "C" int tdvc_gc_forward(const tdvc_fmap* y, const tdvc_fmap* gp, const td
                                double* bits_out, float* partial, int partial_cap, void* stream) {
   TDVC_CHECK(y && gp && bits_out && partial && fmap_ok32(*y) && fmap_ok32(*gp) && same_geom(*y, *gp) && gp->C >= 2 * y->C, "tdvc_gc_forward: bad arguments");
   if (noise) TDVC_CHECK(fmap_ok32(*noise) && same_geom(*y, *noise) && noise->C >= y->C, "tdvc_gc_forward: bad noise");
-  const long total = (long)y->N * y->H * y->W * y->C;
+  const long total = pixel_items(*y) * y->C;
   const int nb = (int)((total + 255) / 256);
   TDVC_CHECK(nb <= partial_cap, "tdvc_gc_forward: partial buffer too small (%d < %d)", partial_cap, nb);
   hipLaunchKernelGGL(gc_forward_kernel, dim3(nb), dim3(256), 0, ST(stream), to_dev(*y), to_dev(*gp), noise ? to_dev(*noise) : null_fmap(), partial);
@@ -1054,7 +903,6 @@ extern "C" int tdvc_gc_forward(const tdvc_fmap* y, const tdvc_fmap* gp, const td
 extern "C" int tdvc_quantize(const tdvc_fmap* y, const tdvc_fmap* noise, const tdvc_fmap* y_hat, void* stream) {
   TDVC_CHECK(y && y_hat && fmap_any(*y) && fmap_any(*y_hat) && same_geom(*y, *y_hat) && y_hat->C >= y->C, "tdvc_quantize: bad arguments");
   if (noise) TDVC_CHECK(fmap_any(*noise) && same_geom(*y, *noise) && noise->C >= y->C, "tdvc_quantize: bad noise");
-  const long total = (long)y->N * y->H * y->W * ((y->C + 7) / 8);
-  hipLaunchKernelGGL(quantize_kernel, grid1d(total), dim3(EW_BLOCK), 0, ST(stream), to_dev(*y), noise ? to_dev(*noise) : null_fmap(), to_dev(*y_hat));
+  hipLaunchKernelGGL(quantize_kernel, grid1d(chunk_items(*y, (y->C + 7) / 8)),dim3(EW_BLOCK), 0, ST(stream), to_dev(*y), noise ? to_dev(*noise) : null_fmap(), to_dev(*y_hat));
   return tdvc_launch_status("tdvc_quantize");
 }

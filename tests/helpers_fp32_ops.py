@@ -77,7 +77,7 @@ def cs_lanes(C_):
 
 def cls_channel_sum(dt, C_, npix, nblocks):
     per = -(-npix // nblocks)
-    return ("channel_sum", dt, C_, "loop4" if per > 3 * cs_lanes(C_) else "tail")         # pointwise.hip:230
+    return ("channel_sum", dt, C_, "loop4" if per > 3 * cs_lanes(C_) else "tail")         # channel_sum_block (pointwise_common.h): the four-loads loop
 
 
 def cls_avgpool_k(dt, C_, scale, dense):

@@ -546,3 +546,39 @@ def test_dcn_fused_record_backward(report):
 # at op level: the GDN / IGDN 1x1 over x^2, the DCN weight as a 1x1 conv over 576 sampled columns.  Read by the coverage guard
 # in test_conv_backward_gpu.py.
 WGRAD_CLASSES = {(1, 1, 1, 128, 128, False, True, False), (1, 1, 1, 9 * C_DCN, C_DCN, False, False, False)}
+
+
+# ------------------------------------------------------------------------------------------------------------------ bias gradient
+# C = 264: a last 256-channel block (blockIdx.z = 1) of 8 channels; 5 x 7: one pixel range, 40 x 52: two ranges of 1040 pixels
+# (tdvc_bias_grad cuts npix / 1024 ranges), which a 256 / (C / 8)-lane walk does not divide evenly
+BIAS_GRAD_CASES = [(C, H, W, dt) for C in (8, 216, 264) for (H, W) in ((5, 7), (40, 52)) for dt in (torch.float16, torch.float32)]
+
+
+@pytest.mark.parametrize("C,H,W,dt", BIAS_GRAD_CASES, ids=[f"C{c}_{h}x{w}_{'f16' if dt == torch.float16 else 'f32'}" for c, h, w, dt in BIAS_GRAD_CASES])
+def test_bias_grad_exact(C, H, W, dt):
+    """db[dst[c] or c] += scale * sum over batch and pixels of g[..., c], c < nvalid (channel_sum_wide_kernel + reduce_rows_kernel).
+    Inputs are small integers: every partial sum is an integer far below 2^24, so fp32 holds it exactly in any order and the result
+    is compared bit for bit with a float64 sum.  With and without a dst_index (a permutation with -1 entries, nvalid < C)."""
+    ops = _ops()
+    from tdvc_amd import _lib as L
+    N = 2
+    gen = torch.Generator().manual_seed(C * 1000 + H)
+    g = torch.randint(-4, 5, (N, H, W, C), generator=gen).to(dt).cuda()
+    gf = ops.FM(g)
+    s = g.cpu().double().sum((0, 1, 2))
+    nwork = L.lib().tdvc_bias_grad_work_floats(N, C)
+    for nvalid, indexed in ((C, False), (C - 3, True)):
+        base = torch.randint(-8, 9, (C,), generator=gen).float() * 0.25
+        dst = torch.randperm(C, generator=gen).to(torch.int32)
+        dst[torch.randperm(C, generator=gen)[:3]] = -1
+        want = base.double().clone()
+        for c in range(nvalid):
+            d = int(dst[c]) if indexed else c
+            if d >= 0:
+                want[d] += 0.5 * s[c]
+        db = base.cuda()
+        work = torch.full((nwork,), float("nan"), device="cuda")
+        idx = dst.cuda() if indexed else None
+        L.check(L.lib().tdvc_bias_grad(ops.C.byref(gf.desc()), nvalid, idx.data_ptr() if indexed else None, 0.5, db.data_ptr(), work.data_ptr(), nwork,
+                                       ops._stream()), "bias_grad")
+        assert torch.equal(db.cpu().double(), want), f"bias_grad C{C} {H}x{W} nvalid {nvalid} indexed {indexed}: {int((db.cpu().double() != want).sum())} of {C} differ"

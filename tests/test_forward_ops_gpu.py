@@ -37,8 +37,8 @@ SENT16 = 0x7E5A                 # a quiet-NaN payload no kernel writes
 SENT32 = 0x7FC0DEAD
 
 # size thresholds of the dispatch (csrc/pointwise.hip)
-SAR16_ONE_PASS = 4096 * 256 * 4     # :712 grid capped at 4096 blocks of 256 threads, U = 4 items each (:710); beyond: grid-stride passes
-FINAL_SUM_ONE = 256                 # :652 final_sum_kernel loops when there are more than 256 partials (256 elements each, :841)
+SAR16_ONE_PASS = 4096 * 256 * 4     # tdvc_scale_act_res: scale_act_res16_kernel<U>'s grid is capped at 4096 blocks of 256 threads, U = 4 items each; beyond: grid-stride passes
+FINAL_SUM_ONE = 256                 # final_sum_kernel loops when there are more than 256 partials (256 elements each: tdvc_eb_forward / tdvc_gc_forward)
 
 
 def _ops():
