@@ -32,9 +32,7 @@
 // SQ_LDS_BANK_CONFLICT = 40 % of SQ_LDS_IDX_ACTIVE).  G is one of the 720 tables (exhaustive search) that keep all three
 // windows conflict-free; it costs the few 8-byte C/D-layout accesses (t / staging writes, identity read) a second pass.
 // For the DMA-written input rows the XOR sits on the SOURCE address.
-#include <type_traits>
-
-#include "conv_dma.h"
+#include "row_pipe.h"
 
 using convk::glds16;
 using convk::raw_barrier;
@@ -70,19 +68,14 @@ template <int NCB> struct PairGeo : PairGeoBase<NCB> {
   static constexpr int X0 = 0, T0 = G::XRING * ROWB, S0 = T0 + TRING * TROWB;
   static constexpr int LDS = S0 + SRING * SROW;
   static_assert(NPX * 128 <= ROWB, "ring row holds the strip's input pixels");
-  // (1) input ring, write-after-read.  The DMA issued in step k by the fastest conv1 wave overwrites row k + PF - XRING; the
-  //     slowest wave of the interval is at step >= k - (BI - 1) and its oldest x-ring read is the identity row ID_LAG behind it:
-  //     k + PF - XRING < k - (BI - 1) - ID_LAG.
-  static_assert(G::PF - G::XRING < -(BI - 1) - ID_LAG, "input ring: a DMA would land on a row whose identity a conv2 wave BI - 1 steps behind has not read (needs PF + 2 BI + 2 <= XRING)");
-  // (2) input ring, read-after-write (landing).  A wave's own pieces of row r (issued in step r - PF) are only known to have
-  //     landed after its land_wait() of a step s >= r - PF + HD, and other waves' pieces only after a barrier behind that wait.
-  //     The last barrier before step r closes a step kb >= r - BI: r - PF + HD <= r - BI.
-  static_assert(G::PF >= G::HD + BI, "landing: row r must be past land_wait()'s history window before the last barrier in front of step r");
-  // (3) the counted wait: conv1 waves issue nothing but DMA, a fixed number per step (NCB = 2: 1 + 1 + 1 + 2 over any four consecutive
-  //     steps; NCB = 4: 2 per step, wave 0 three), so HD steps of history are a constant the hardware counter (63) holds.
-  static_assert((NCB == 2 && G::HD == 4) || (NCB == 4 && G::HD == 2), "land_wait(): constant counts for these two histories");
-  // (6) the identity row k - ID_LAG was consumed by conv1 in step k - ID_LAG (so it has landed) and is still in the ring by (1).
-  static_assert(ID_LAG >= 1 && ID_LAG <= G::XRING - G::PF - BI, "identity row inside the input ring");
+  // (1)-(3), (6): the input ring's write-after-read and landing conditions and the counted wait (row_pipe.h: RingTiming).  The oldest read
+  //     of x row r is the identity read of a conv2 wave in step r + ID_LAG (that row was consumed by conv1 in step r, so it has landed);
+  //     the first is conv1's in step r.  NCB = 2: 1 + 1 + 1 + 2 DMA instructions over any four consecutive steps; NCB = 4: 2 per step,
+  //     wave 0 three.
+  using Timing = rowk::RingTiming<G::PIECES, G::XRING, G::PF, G::HD, BI, ID_LAG, 0>;
+  using Layout = rowk::RingLayout<128, true>;
+  static_assert(rowk::row_check::dma_matches_reads<Layout>(G::PIECES, NPX), "the DMA writes every (pixel, slot) of a ring row once, where the fragment read looks for it");
+  static_assert(rowk::row_check::reads_conflict_free<Layout>(3, NCB), "a 16-lane group of a B-fragment read touches 16 distinct bank slots");
   static_assert(LDS <= 160 * 1024, "rings inside 160 KB of LDS");
 };
 // (4) t ring.  In one barrier interval [m BI, m BI + BI - 1] conv1 writes rows m BI - 1 .. m BI + BI - 2 and conv2 reads rows
@@ -111,13 +104,12 @@ constexpr int NTHR = 512;
 #endif
 
 struct PairParams {
-  const half_t* x; long x_sn; int x_sp;
-  half_t* y; long y_sn; int y_sp;
-  const half_t* res2; long r2_sn; int r2_sp;
+  rowk::MapRef<const half_t> x;
+  rowk::MapRef<half_t> y;
+  rowk::MapRef<const half_t> res2;
   const half_t* w;          // [conv 2][wave 4][tap*2 + chunk 18][lane 64][8] halves (tdvc_pack_conv_pair_weights)
   const float* bias;        // [2][64]
-  const half_t* zeros;      // >= 16 B of zeros: DMA source of out-of-image pixels
-  half_t* dump;             // 4 KB nobody reads: store target of the lanes outside a strip (keeps the store branch-free)
+  rowk::ScratchPages pg;    // zeros; dump: 4 KB
   int N, H, W;
   int strips, segs, seg_rows, jobs;
   float slope1, slope2;     // max(v, v * slope): 1 = none, 0 = ReLU, else LeakyReLU
@@ -129,26 +121,7 @@ struct PairParams {
   unsigned split[4];
 };
 
-// swizzle term of pixel q of a ring row (see the LDS image note at the top)
-__device__ __forceinline__ int swz(int q) { return (int)((0x62654210u >> (4 * ((q >> 1) & 7))) & 7u); }
-
-template <int A>
-__device__ __forceinline__ half4 actk(half4 v, half4 sl) {
-  if constexpr (A == 1) {
-    const half4 z = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
-    return __builtin_elementwise_max(v, z);
-  } else if constexpr (A == 2) {
-    return __builtin_elementwise_max(v, v * sl);
-  } else {
-    return v;
-  }
-}
-
-// ring slot of row kk: a mask for the 16-row ring, a division by a constant for the 10-row ring -- on the scalar unit (kk is wave-uniform)
-template <int XRING> __device__ __forceinline__ int pair_slot(int kk) {
-  if constexpr ((XRING & (XRING - 1)) == 0) return kk & (XRING - 1);
-  else return __builtin_amdgcn_readfirstlane(kk) % XRING;
-}
+using rowk::actk;
 
 // A1 / A2: activation after conv1 / conv2: 0 none, 1 ReLU, 2 max(v, v * slope) (LeakyReLU; slope 1 = none)
 template <int NCB, int A1, int A2, bool ADDX, bool RES2, bool STAMP = false>
@@ -165,6 +138,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
     p_jobs = act.count * p.strips * p_segs;
   }
   using G = PairGeo<NCB>;
+  using L = typename G::Layout;
   constexpr int PW = G::PW, ROWB = G::ROWB, TROWB = G::TROWB, SROW = G::SROW, XRING = G::XRING, PF = G::PF, X0 = G::X0, T0 = G::T0, S0 = G::S0;
   constexpr int NF = 6 * NCB;                  // B fragments of a row
   constexpr int NIT = NCB / 2;                 // 16-byte store items per conv2 thread and row (256 threads, 8 items per pixel)
@@ -186,33 +160,32 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
   int foff[3][2];                              // B fragment (dx, channel chunk) of column block 0: pixel dx + (l & 15); block cb sits
 #pragma unroll                                 // 16 cb pixels = 2048 cb B further (16 pixels do not change the swizzle term)
   for (int dx = 0; dx < 3; ++dx) {
-    const int q = dx + r16, sw = swz(q);
 #pragma unroll
-    for (int kc = 0; kc < 2; ++kc) foff[dx][kc] = q * 128 + (((4 * kc + kb) ^ sw) << 4);
+    for (int kc = 0; kc < 2; ++kc) foff[dx][kc] = L::slot_off(dx + r16, 4 * kc + kb);
   }
   // C/D layout (pixel l & 15, channels 16 wq + 4 kb ..+3) of column block 0: t / staging write, identity read (output column yi sits at
   // input pixel yi + 2); block cb again 2048 cb B further
   const int cdc = 2 * wq + (kb >> 1);
-  const int doff = r16 * 128 + ((cdc ^ swz(r16)) << 4) + 8 * (kb & 1);
-  const int roff = (r16 + 2) * 128 + ((cdc ^ swz(r16 + 2)) << 4) + 8 * (kb & 1);
+  const int doff = rowk::cd_off<true>(128, r16, cdc) + 8 * (kb & 1);
+  const int roff = rowk::cd_off<true>(128, r16 + 2, cdc) + 8 * (kb & 1);
   // DMA items (conv1 waves): piece j of a row covers pixels 8 j .. 8 j + 7 (lane: slot lane & 7 of pixel 8 j + (lane >> 3)).
   // NCB = 2: every step wave wq sends piece wq of the row PF steps ahead; piece 4 (pixels 32, 33) goes round the four waves.
   // NCB = 4: wave wq sends pieces wq and wq + 4, wave 0 also piece 8 (pixels 64, 65).
   constexpr int PLAST = G::PIECES - 1;         // the odd piece
   int soff_own, soff_hi = 0, soff_last;
   {
-    const int q = 8 * wq + (lane >> 3), c = (lane & 7) ^ swz(q);
-    soff_own = q * p.x_sp + c * 8;
+    const int q = 8 * wq + (lane >> 3), c = (lane & 7) ^ L::term(q);
+    soff_own = q * p.x.sp + c * 8;
     if constexpr (NCB == 4) {
-      const int qh = 32 + q, ch = (lane & 7) ^ swz(qh);
-      soff_hi = qh * p.x_sp + ch * 8;
+      const int qh = 32 + q, ch = (lane & 7) ^ L::term(qh);
+      soff_hi = qh * p.x.sp + ch * 8;
     }
-    const int ql = 8 * PLAST + (lane >> 3), cl = (lane & 7) ^ swz(ql);
-    soff_last = ql * p.x_sp + cl * 8;
+    const int ql = 8 * PLAST + (lane >> 3), cl = (lane & 7) ^ L::term(ql);
+    soff_last = ql * p.x.sp + cl * 8;
   }
   // store items (conv2 waves): item u of thread t = tid - 256 is (output column (t >> 3) + 32 u, slot t & 7)
   const int s_t = tid & 255;
-  const int s_yi = s_t >> 3, s_c = (s_t & 7) ^ swz(s_yi);
+  const int s_yi = s_t >> 3, s_c = (s_t & 7) ^ L::term(s_yi);
 
   // ---- XCD-aware job walk: workgroup b sits on XCD b % 8; an XCD takes a contiguous range of jobs (neighbouring strips
   // of one row segment share their column halo in that XCD's L2)
@@ -247,8 +220,8 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
     const int seg = rem / p.strips, strip = rem - seg * p.strips;
     const int c0 = strip * PW, ra = seg * p_seg_rows, rb = min(p.H, ra + p_seg_rows);
     const int rows = rb - ra;
-    const half_t* xn = p.x + (long)n * p.x_sn;
-    half_t* yn = p.y + (long)n * p.y_sn;
+    const half_t* xn = p.x.p + (long)n * p.x.sn;
+    half_t* yn = p.y.p + (long)n * p.y.sn;
 
     bool col_own, col_hi = false, col_last;    // this lane's pixel of its pieces is inside the image (and one of the strip's)
     {
@@ -277,14 +250,14 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
     auto issue_row = [&](int kk) __attribute__((always_inline)) -> int {
       const int row = ra - 2 + kk;
       const bool rowok = row >= 0 && row < p.H;
-      const half_t* base = xn + ((long)row * p.W + (c0 - 2)) * p.x_sp;
-      const unsigned dst = lds0 + X0 + pair_slot<XRING>(kk) * ROWB;
-      glds16((rowok && col_own) ? base + soff_own : p.zeros, dst + wq * 1024);
+      const half_t* base = xn + ((long)row * p.W + (c0 - 2)) * p.x.sp;
+      const unsigned dst = lds0 + X0 + rowk::ring_slot<XRING>(kk) * ROWB;
+      glds16((rowok && col_own) ? base + soff_own : p.pg.zeros, dst + wq * 1024);
       if constexpr (NCB == 4) {
-        glds16((rowok && col_hi) ? base + soff_hi : p.zeros, dst + (wq + 4) * 1024);
-        if (wq == 0) glds16((rowok && col_last) ? base + soff_last : p.zeros, dst + PLAST * 1024);
+        glds16((rowok && col_hi) ? base + soff_hi : p.pg.zeros, dst + (wq + 4) * 1024);
+        if (wq == 0) glds16((rowok && col_last) ? base + soff_last : p.pg.zeros, dst + PLAST * 1024);
       } else {
-        if (wq == (kk & 3)) glds16((rowok && col_last) ? base + soff_last : p.zeros, dst + PLAST * 1024);
+        if (wq == (kk & 3)) glds16((rowok && col_last) ? base + soff_last : p.pg.zeros, dst + PLAST * 1024);
       }
       return 1;
     };
@@ -360,19 +333,13 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
       for (int kk = 0; kk < PF; ++kk)
         if (kk <= rows + 3) issue_row(kk);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    rowk::wait_vmcnt<0>();
     raw_barrier();
 
     const int K = (rows + 4 + 2 * BI + BI - 1) & ~(BI - 1);      // row steps, a whole number of barrier intervals
-    // Before a step's barrier: everything this wave sent more than HD steps ago has landed (NCB = 2: row k + 4 is read from step
-    // k + 4 on); the DMA of the last HD steps -- a constant number: conv1 waves issue no other vector-memory operation -- may stay in
-    // flight.  Vector memory operations of a wave complete in order on this architecture (one counter for loads, stores and LDS-DMA).
-    auto land_wait = [&](int nvm) __attribute__((always_inline)) {
-      if (!nvm) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // issuing has stopped (segment tail)
-      else if constexpr (NCB == 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");      // 1 + 1 + 1 + 2 over any four issuing steps; shorter histories (first steps) have fewer in flight
-      else if (wq == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                  // two steps x three pieces
-      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                               // two steps x two pieces
-    };
+    // Before a step's barrier (rowk::land_wait): everything this wave sent more than HD steps ago has landed (NCB = 2: row k + 4 is read
+    // from step k + 4 on); the DMA of the last HD steps -- a constant number: conv1 waves issue no other vector-memory operation -- may
+    // stay in flight.  Vector memory operations of a wave complete in order on this architecture (one counter for loads, stores and LDS-DMA).
     // One row step k.  conv1 waves consume x row i = ra - 2 + k: t rows i + 1 (started), i, i - 1 (finished, into the t ring).
     // conv2 waves consume t row i - 1 - BI: y rows i - BI (started), i - 1 - BI, i - 2 - BI (finished, + identity, into a staging
     // row); the y row finished BI row steps ago goes to memory.  The workgroup barrier closes every BI-th row step: each group
@@ -393,7 +360,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
         // ---- conv1 wave: t row new = slot (PH + 1) % 3, mid = PH, done = (PH + 2) % 3
         int nvm = 0;
         if (FULL || k <= rows + 3) {
-          row_mfmas(X0 + pair_slot<XRING>(k) * ROWB, S1c{}, S0c{}, S2c{}, [&]() __attribute__((always_inline)) {
+          row_mfmas(X0 + rowk::ring_slot<XRING>(k) * ROWB, S1c{}, S0c{}, S2c{}, [&]() __attribute__((always_inline)) {
             // t row i - 1 -> fp16, activation, zero outside the image, into the t ring
             const int trow = i - 1;
             const unsigned rowm = (trow >= 0 && trow < p.H) ? 0xFFFFFFFFu : 0u;
@@ -417,7 +384,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           t1 = clock64();
         }
-        land_wait(nvm);
+        rowk::land_wait<typename G::Timing>(nvm, wq);
       } else {
         // ---- conv2 wave: new = (PH + 2) % 3, mid = (PH + 1) % 3, done = PH
         const int srow = ra + k - 4 - 2 * BI;  // the y row finished BI row steps ago (before the last barrier): staging row -> memory
@@ -426,7 +393,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
           for (int u = 0; u < NIT; ++u) {
             half8 yv = *reinterpret_cast<const half8*>(smem + S0 + ((k - BI) & (SRING - 1)) * SROW + (s_t + 256 * u) * 16);
             if constexpr (RES2) yv = yv + r2v[u];
-            half_t* dst = s_ok[u] ? yn + ((long)srow * p.W + c0 + s_yi + 32 * u) * p.y_sp + s_c * 8 : p.dump + (s_t + 256 * u) * 8;
+            half_t* dst = s_ok[u] ? yn + ((long)srow * p.W + c0 + s_yi + 32 * u) * p.y.sp + s_c * 8 : p.pg.dump + (s_t + 256 * u) * 8;
             *reinterpret_cast<half8*>(dst) = yv;
           }
         }
@@ -435,7 +402,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
 #pragma unroll
           for (int u = 0; u < NIT; ++u) {
             const bool ok = s_ok[u] && (FULL || (nrow >= ra && nrow < rb));
-            const half_t* src = ok ? p.res2 + (long)n * p.r2_sn + ((long)nrow * p.W + c0 + s_yi + 32 * u) * p.r2_sp + s_c * 8 : p.zeros;
+            const half_t* src = ok ? p.res2.p + (long)n * p.res2.sn + ((long)nrow * p.W + c0 + s_yi + 32 * u) * p.res2.sp + s_c * 8 : p.pg.zeros;
             r2v[u] = *reinterpret_cast<const half8*>(src);
           }
         }
@@ -444,7 +411,7 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
           row_mfmas(T0 + ((k - T_LAG) & (TRING - 1)) * TROWB, S2c{}, S1c{}, S0c{}, [&]() __attribute__((always_inline)) {
             // y row i - 2 - BI -> fp16, activation, + identity (that x row is still in the ring), into the staging row
             unsigned char* sb = smem + S0 + (k & (SRING - 1)) * SROW + doff;
-            const unsigned char* xb = smem + X0 + pair_slot<XRING>(k - ID_LAG) * ROWB + roff;
+            const unsigned char* xb = smem + X0 + rowk::ring_slot<XRING>(k - ID_LAG) * ROWB + roff;
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
               const f32x4 v = acc[PH][cb];
@@ -467,24 +434,13 @@ __global__ __launch_bounds__(NTHR, 1) void conv_pair_kernel(const PairParams p, 
         st_busy += t1 - t0; st_vm += t2 - t1; st_bar += t3 - t2; st_n += 1;
       }
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
     auto edge_steps = [&](int k, int kend) __attribute__((always_inline)) {   // k % 3 == 0
-      for (; k < kend; k += 3) {
-        step(I0{}, std::false_type{}, k);
-        if (k + 1 < kend) step(I1{}, std::false_type{}, k + 1);
-        if (k + 2 < kend) step(I2{}, std::false_type{}, k + 2);
-      }
+      for (; k < kend; k += 3) rowk::steps_of<3>(step, std::false_type{}, k, kend);
     };
     constexpr int KF = ((4 + 2 * BI + 2) / 3) * 3;      // first steady-state step: a multiple of 3 (accumulator rotation) >= 4 + 2 BI
     edge_steps(0, KF);
     int k = KF;
-    for (; k + 2 <= rows + 2; k += 3) {
-      step(I0{}, std::true_type{}, k);
-      step(I1{}, std::true_type{}, k + 1);
-      step(I2{}, std::true_type{}, k + 2);
-    }
+    for (; k + 2 <= rows + 2; k += 3) rowk::steps_of<3>(step, std::true_type{}, k, k + 3);
     edge_steps(k, K);
   }
   };
@@ -570,18 +526,14 @@ extern "C" int tdvc_conv_pair(const tdvc_conv_pair_desc* d, void* stream) {
   auto slope_of = [](int act, float slope) { return act == TDVC_ACT_NONE ? 1.f : (act == TDVC_ACT_RELU ? 0.f : slope); };
   TDVC_CHECK((d->act1 == TDVC_ACT_NONE || d->act1 == TDVC_ACT_RELU || d->act1 == TDVC_ACT_LRELU) &&
              (d->act2 == TDVC_ACT_NONE || d->act2 == TDVC_ACT_RELU || d->act2 == TDVC_ACT_LRELU), "tdvc_conv_pair: activations are none / ReLU / LeakyReLU");
-  const void* zeros = nullptr;
-  void* dump = nullptr;
-  if (const int zrc = tdvc_scratch_pages(&zeros, &dump)) return zrc;
   PairParams p;
-  p.x = reinterpret_cast<const half_t*>(d->x.p); p.x_sn = d->x.sn; p.x_sp = d->x.sp;
-  p.y = reinterpret_cast<half_t*>(d->y.p); p.y_sn = d->y.sn; p.y_sp = d->y.sp;
-  p.res2 = reinterpret_cast<const half_t*>(d->res2.p); p.r2_sn = d->res2.p ? d->res2.sn : 0; p.r2_sp = d->res2.p ? d->res2.sp : 0;
+  if (const int zrc = rowk::scratch_pages(p.pg)) return zrc;
+  p.x = rowk::map_ref<const half_t>(d->x.p, d->x.sn, d->x.sp);
+  p.y = rowk::map_ref<half_t>(d->y.p, d->y.sn, d->y.sp);
+  p.res2 = rowk::map_ref<const half_t>(d->res2.p, d->res2.sn, d->res2.sp);
   p.w = reinterpret_cast<const half_t*>(d->w);
   p.bias = d->bias;
-  p.zeros = reinterpret_cast<const half_t*>(zeros);
   p.experiment = g_pair_experiment;
-  p.dump = reinterpret_cast<half_t*>(dump);
   p.N = d->x.N; p.H = d->x.H; p.W = d->x.W;
   p.slope1 = slope_of(d->act1, d->slope1);
   p.slope2 = slope_of(d->act2, d->slope2);

@@ -26,7 +26,7 @@
 // instruction is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, ...), i.e. eight pixels with slot s and the other eight
 // with slot s ^ 1.  With SIGMA sending lanes {0-3, 12-15} to the even and lanes {4-11} to the odd pixels of the 16-pixel block the
 // two sets are the parity classes of the window, F pairs q with q ^ 2 (same parity), and every group reads 16 different 16-byte
-// bank slots for all three windows dx = 0, 1, 2 (exhaustive check: tools/check_row_swizzle.py).  For the DMA-written rows the XOR
+// bank slots for all three windows dx = 0, 1, 2 (static_asserts of row_pipe.h, for every geometry below).  For the DMA-written rows the XOR
 // sits on the SOURCE address.  The accumulators' columns follow SIGMA, so the pack writes pixel 16 cb + SIGMA(r).
 //
 // Geometries (RowGeo): the same code runs the Cin = 128 -> 128 k layers (32-column strips), the single Cin = 64 -> 64 k layers (64-column
@@ -34,9 +34,10 @@
 // ring) and the space-to-depth form of the 3x3 STRIDE-2 convs with 64 input channels (a 2x2 conv over (H/2, W/2, 256): 512-byte ring
 // pixels whose four 128-byte parity blocks the DMA gathers from two image rows; the 7 of 16 (tap, parity) blocks outside the 3x3 window
 // hold zero weights and are skipped at compile time: 18 fragments per wave, two live output rows).
-#include <type_traits>
-
-#include "conv_dma.h"
+// The pieces this kernel shares with lf_tail and conv_pair are in row_pipe.h.  Four stay here although lf_tail has the same code ("The
+// shared row pipeline"): the weight gather, the dense loader (soff / colok / issue_row), the store phase and the three step loops.  Moved
+// into the header each of them reordered this file's weight loads or stores and with them the compiler's own s_waitcnt vmcnt.
+#include "row_pipe.h"
 
 using convk::ConvParams;
 using convk::glds16;
@@ -54,6 +55,9 @@ template <> struct RowGeo<GEO_C128> { static constexpr int NKC = 4, KH = 3, KW =
 template <> struct RowGeo<GEO_C64> { static constexpr int NKC = 2, KH = 3, KW = 3, SW = 64, NCG = 4, PIECES = 9, XRING = 8, PF = 6, HD = 4, DMA_POS = 2, CORIG = 64; static constexpr bool S2D = false; };
 template <> struct RowGeo<GEO_C128W> { static constexpr int NKC = 4, KH = 3, KW = 3, SW = 64, NCG = 4, PIECES = 17, XRING = 6, PF = 4, HD = 2, DMA_POS = 2, CORIG = 128; static constexpr bool S2D = false; };
 template <> struct RowGeo<GEO_S2D64> { static constexpr int NKC = 8, KH = 2, KW = 2, SW = 32, NCG = 8, PIECES = 17, XRING = 6, PF = 4, HD = 2, DMA_POS = 1, CORIG = 64; static constexpr bool S2D = true; };
+// ---- synchronisation geometry (step k consumes input row k; a workgroup barrier closes every BI-th step; between two barriers
+// two waves are at most BI - 1 steps apart and always in the same barrier interval).
+constexpr int RW_BI = 2;
 template <int GID> struct RowDerived : RowGeo<GID> {
   using G = RowGeo<GID>;
   static constexpr int CO = 16 * G::NCG;                 // output channels per pass
@@ -67,17 +71,13 @@ template <int GID> struct RowDerived : RowGeo<GID> {
   static_assert(G::SW * CO * 2 == 8192, "a staging row is 8 KB = 512 items of 16 bytes");
   static_assert((G::SW + G::KW - 1) * PXB <= ROWB && (G::PIECES % 4) == 1, "ring row");
   static_assert(G::SW / 16 == 2 * (8 / G::NCG), "a wave computes two column blocks");
-  // (1) input ring, write-after-read: the DMA issued in step k by the fastest loader overwrites row k + PF - XRING; the slowest wave
-  //     of the interval is at step >= k - (BI - 1) and reads exactly that step's row: k + PF - XRING < k - (BI - 1).
-  // (2) landing: a loader's own pieces of row r (issued in step r - PF) are known to have landed after its land_wait() of a step
-  //     s >= r - PF + HD, the other waves learn it at the next barrier; the last barrier before step r closes a step >= r - BI.
-  static_assert(G::PF + 2 <= G::XRING && G::PF >= G::HD + 2, "ring conditions (BI = 2)");
-  static_assert(G::HD == 4 || G::HD == 2, "land_wait(): four-step history with the odd piece going round the loaders, or two steps with a fixed owner");
+  // the ring conditions and the counted wait (row_pipe.h): every wave reads row k in step k and in no other
+  using Timing = rowk::RingTiming<G::PIECES, G::XRING, G::PF, G::HD, RW_BI, 0, 0>;
+  using Layout = rowk::RingLayout<PXB>;
+  static_assert(rowk::row_check::dma_matches_reads<Layout>(G::PIECES, G::SW + G::KW - 1), "the DMA writes every (pixel, slot) of a ring row once, where the fragment read looks for it");
+  static_assert(rowk::row_check::reads_conflict_free<Layout>(G::KW, G::SW / 16), "a 16-lane group of a B-fragment read touches 16 distinct bank slots");
   static_assert(LDS <= 160 * 1024, "LDS");
 };
-// ---- synchronisation geometry (step k consumes input row k; a workgroup barrier closes every BI-th step; between two barriers
-// two waves are at most BI - 1 steps apart and always in the same barrier interval).
-constexpr int RW_BI = 2;
 constexpr int RW_SRING = 2 * RW_BI;             // staging rows: written in step k, stored in step k + BI (the next barrier interval), overwritten in step k + SRING
 constexpr int RW_SROW = 8192;
 constexpr int RW_NTHR = 512;
@@ -86,13 +86,12 @@ constexpr int RW_NTHR = 512;
 #endif
 
 struct RowParams {
-  const half_t* x; long x_sn; int x_sp;
-  half_t* y; long y_sn; int y_sp;
-  const half_t* res; long r1_sn; int r1_sp;
+  rowk::MapRef<const half_t> x;
+  rowk::MapRef<half_t> y;
+  rowk::MapRef<const half_t> res;
   const half_t* w;          // the layer's standard blob: [cout tile 32][chunk NKC][k-step STEPS][lane 64][8 halves]
   const float* bias;
-  const half_t* zeros;      // >= 16 B of zeros: DMA source of out-of-image pixels
-  half_t* dump;             // >= 8 KB nobody reads: store target of items outside the image
+  rowk::ScratchPages pg;
   int N, H, W;              // OUTPUT rows / columns (= the input's, or half of them in the space-to-depth geometry)
   int Win;                  // input image row pitch in pixels (W, or 2 W)
   int ncb;                  // cout blocks of CO channels
@@ -102,19 +101,6 @@ struct RowParams {
   int reverse;
   const int* pred;          // launch predicate (tdvc_set_predicate) or null: the kernel returns at once when *pred == 0
 };
-
-template <int PXB> __device__ __forceinline__ int rw_f(int q) {                                          // ring-row swizzle term
-  return PXB == 128 ? ((q >> 1) & 7) : ((q & 12) | ((q & 1) << 1) | ((q >> 1) & 1));
-}
-__device__ __forceinline__ int rw_sigma(int r) { return r < 4 ? 2 * r : (r >= 12 ? 2 * r - 16 : 2 * r - 7); }   // fragment lane -> pixel of its 16-px block
-__device__ __forceinline__ int rw_g(int q) { return (q >> 1) & 7; }                                      // staging-row swizzle term
-
-// ring slot of row kk: a mask for the 8-row rings; the 6-row rings divide by a constant -- on the scalar unit (kk is wave-uniform; left to
-// itself hipcc did the multiply-high in vector registers, three more live registers in kernels at the 256-register limit)
-template <int XRING> __device__ __forceinline__ int rw_slot(int kk) {
-  if constexpr ((XRING & (XRING - 1)) == 0) return kk & (XRING - 1);
-  else return __builtin_amdgcn_readfirstlane(kk) % XRING;
-}
 
 // which (tap row dy, tap column dx, chunk kc) fragments exist: all of them for a dense window; in the space-to-depth geometry chunk kc
 // belongs to parity block (py, px) = bits of kc / (CORIG / 32), and virtual tap (dy, dx) of that block is the original tap
@@ -160,6 +146,8 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
   using G = RowDerived<GID>;
   constexpr int NKC = G::NKC, KH = G::KH, KW = G::KW, SW = G::SW, CO = G::CO, PXB = G::PXB, XRING = G::XRING, PF = G::PF, NP = G::NP;
   constexpr int NG = rw_ngroups<GID>(), G0 = rw_first_group_of_row0<GID>();
+  using L = typename G::Layout;
+  using T = typename G::Timing;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(smem));
   const int tid = threadIdx.x, lane = tid & 63;
@@ -169,24 +157,10 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
   const int cg = wave % G::NCG, cbp = wave / G::NCG;        // block of 16 output channels; pair of column blocks (2 cbp, 2 cbp + 1) of the strip
   const int r16 = lane & 15, kb = lane >> 4;
 
-  // ---- workgroup -> (cout block, run of rows).  The launch's work is the flat sequence of (image, strip, row) = N * strips * H
-  // rows of SW output columns; a cout block's S workgroup slots cut it into S equal runs (a run that crosses a strip end is two
-  // segments), so every workgroup gets the same number of rows whatever H and the strip count are (a segment pays KH - 1 + BI extra
-  // steps).  Workgroup b sits on XCD b % 8: an XCD's slots take consecutive runs (neighbouring strips share their column halo in
-  // that XCD's L2); the cout block is fixed per workgroup (its weights are loaded once)
-  const int nwg = (int)gridDim.x, b = (int)blockIdx.x;
-  int cbk, pos_slot, nslots;
-  if ((nwg & 7) == 0 && ((nwg >> 3) % p.ncb) == 0) {
-    const int slot = b >> 3, per_xcd = (nwg >> 3) / p.ncb;
-    cbk = slot % p.ncb;
-    pos_slot = (b & 7) * per_xcd + slot / p.ncb;
-    nslots = 8 * per_xcd;
-  } else {
-    cbk = b % p.ncb; pos_slot = b / p.ncb; nslots = nwg / p.ncb;
-  }
-  if (p.reverse) pos_slot = nslots - 1 - pos_slot;
-  const long allrows = (long)p.N * p.strips * p.H;
-  const long run_begin = allrows * pos_slot / nslots, run_end = allrows * (pos_slot + 1) / nslots;
+  // ---- workgroup -> (cout block, run of rows of SW output columns): rowk::run_range; a segment of the run pays KH - 1 + BI extra steps
+  const rowk::RunRange rr = rowk::run_range(p.ncb, p.reverse, p.N, p.strips, p.H);
+  const int cbk = rr.cbk;
+  const long run_begin = rr.begin, run_end = rr.end;
 
   // ---- this wave's 16 output channels: its A fragments (tap, chunk) in registers for the whole launch.  Lane (r16, kb) of
   // fragment (tap, kc) holds w[cout][cin = 32 kc + 8 kb .. + 7][tap]: in the standard blob that is k-step tap * 2 + (kb >> 1),
@@ -210,14 +184,14 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
   int foff[KW];                                // B fragment (dx), chunk 0, column block 0; chunk kc: ^ (kc << 6); block 1: + 16 pixels
 #pragma unroll
   for (int dx = 0; dx < KW; ++dx) {
-    const int q = 32 * cbp + dx + rw_sigma(r16), f = rw_f<PXB>(q);
-    foff[dx] = q * PXB + ((kb ^ f) << 4);              // (4 kc + kb) ^ f = (kb ^ f) ^ (kc << 2)
+    const int q = 32 * cbp + dx + rowk::sigma(r16);
+    foff[dx] = L::slot_off(q, kb);              // (4 kc + kb) ^ f = (kb ^ f) ^ (kc << 2)
   }
   int doff[2];                                 // pack: pixel 16 cb + SIGMA(r16), channels 16 cg + 4 kb .. + 3 of the block
 #pragma unroll
   for (int cb = 0; cb < 2; ++cb) {
-    const int q = 32 * cbp + 16 * cb + rw_sigma(r16), c = 2 * cg + (kb >> 1);
-    doff[cb] = q * (CO * 2) + ((c ^ rw_g(q)) << 4) + 8 * (kb & 1);
+    const int q = 32 * cbp + 16 * cb + rowk::sigma(r16);
+    doff[cb] = rowk::cd_off(CO * 2, q, 2 * cg + (kb >> 1)) + 8 * (kb & 1);
   }
   // ---- everything below is instantiated once per ROLE (waves 0-3: loaders, waves 4-7: storers) inside one wave-uniform branch, so that a
   // role's private registers (DMA offsets and masks / output offsets and the prefetched residual row) share physical registers with
@@ -237,13 +211,13 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
 #pragma unroll
   for (int j = 0; j < SRC; ++j) {
     const int piece = j == SRC - 1 ? G::PIECES - 1 : wq + 4 * j;
-    const int q = (64 / G::LPP) * piece + lane / G::LPP, c = (lane % G::LPP) ^ rw_f<PXB>(q);
+    const int q = L::dma_px(piece, lane), c = (lane % G::LPP) ^ L::term(q);      // = L::dma_slot(piece, lane)
     sq[j] = q;
     if constexpr (G::S2D) {
       const int par = c / (G::CORIG / 8), within = c % (G::CORIG / 8);
-      soff[j] = (2 * q + (par & 1)) * p.x_sp + (par >> 1) * p.Win * p.x_sp + within * 8;
+      soff[j] = (2 * q + (par & 1)) * p.x.sp + (par >> 1) * p.Win * p.x.sp + within * 8;
     } else {
-      soff[j] = q * p.x_sp + c * 8;
+      soff[j] = q * p.x.sp + c * 8;
     }
   }
   // store items (storer waves): item it = (tid - 256) + 256 j: pixel it / SLOTS, position it % SLOTS of the staging row
@@ -253,7 +227,7 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
   for (int j = 0; j < 2; ++j) {
     const int it = s_t + 256 * j;
     s_px[j] = it / G::SLOTS;
-    s_co[j] = cbk * CO + (((it % G::SLOTS) ^ rw_g(it / G::SLOTS)) << 3);
+    s_co[j] = cbk * CO + (((it % G::SLOTS) ^ rowk::stage_g(it / G::SLOTS)) << 3);
   }
   int s_pc[2], s_sub[2];
 #pragma unroll
@@ -269,13 +243,10 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
   half8 r1v[2] = {};
 
   for (long pos = run_begin; pos < run_end;) {
-    const int sid = (int)(pos / p.H);          // (image, strip)
-    const int ra = (int)(pos - (long)sid * p.H), rb = (int)min((long)p.H, ra + (run_end - pos));
-    const int rows = rb - ra;
-    pos += rows;
-    const int n = sid / p.strips, strip = sid - n * p.strips;
+    const rowk::Segment sg = rowk::next_segment(pos, run_end, p.H, p.strips);
+    const int ra = sg.ra, rb = sg.rb, rows = sg.rows, n = sg.n, strip = sg.strip;
     const int c0 = strip * SW;
-    const half_t* xn = p.x + (long)n * p.x_sn;
+    const half_t* xn = p.x.p + (long)n * p.x.sn;
     const int last_in = rows + KH - 2;         // the last step that consumes an input row
 
     unsigned colok = 0;                        // bit j: this lane's pixel of its j-th piece is one of the row's SW + KW - 1 and inside the image
@@ -295,14 +266,14 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
       s_ok[j] = col < p.W;
       const int off = SHUF ? (s_sub[j] >> 1) * OW + 2 * col + (s_sub[j] & 1) : col;       // pixel indices fit 32 bits (checked by the host)
       const int offc = SHUF ? (s_sub[j] >> 1) * OW + 2 * colc + (s_sub[j] & 1) : colc;
-      y_lo[j] = off * p.y_sp + s_pc[j];
-      r_lo[j] = offc * p.r1_sp + s_pc[j];
+      y_lo[j] = off * p.y.sp + s_pc[j];
+      r_lo[j] = offc * p.res.sp + s_pc[j];
     }
-    const half_t* const yimg = p.y + (long)n * p.y_sn;
-    const half_t* const rimg = NRES >= 1 ? p.res + (long)n * p.r1_sn : nullptr;
-    const long yrow_stride = (long)(SHUF ? 2 : 1) * OW * p.y_sp, rrow_stride = (long)(SHUF ? 2 : 1) * OW * p.r1_sp;
-    const long xrow_stride = (long)(G::S2D ? 2 : 1) * p.Win * p.x_sp;       // one ring row = one image row (two in the space-to-depth geometry)
-    const half_t* const xcol = xn + (long)(G::S2D ? 2 : 1) * (c0 - 1) * p.x_sp;
+    const half_t* const yimg = p.y.p + (long)n * p.y.sn;
+    const half_t* const rimg = NRES >= 1 ? p.res.p + (long)n * p.res.sn : nullptr;
+    const long yrow_stride = (long)(SHUF ? 2 : 1) * OW * p.y.sp, rrow_stride = (long)(SHUF ? 2 : 1) * OW * p.res.sp;
+    const long xrow_stride = (long)(G::S2D ? 2 : 1) * p.Win * p.x.sp;       // one ring row = one image row (two in the space-to-depth geometry)
+    const half_t* const xcol = xn + (long)(G::S2D ? 2 : 1) * (c0 - 1) * p.x.sp;
 #pragma unroll
     for (int s3 = 0; s3 < KH; ++s3)
 #pragma unroll
@@ -313,25 +284,25 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
       const int row = ra - 1 + kk;
       const bool rowok = row >= 0 && row < p.H;
       const half_t* base = xcol + row * xrow_stride;
-      const unsigned dst = lds0 + G::X0 + rw_slot<XRING>(kk) * G::ROWB;
+      const unsigned dst = lds0 + G::X0 + rowk::ring_slot<XRING>(kk) * G::ROWB;
       const unsigned okb = rowok ? colok : 0u;
       if constexpr (G::S2D || NP <= 3) {
 #pragma unroll
         for (int j = 0; j < NP - 1; ++j) {
-          const half_t* src = G::S2D ? base + soff[j] : base + (long)(QSTEP * j) * p.x_sp + soff[0];
-          glds16(((okb >> j) & 1u) ? src : p.zeros, dst + (wq + 4 * j) * 1024);
+          const half_t* src = G::S2D ? base + soff[j] : base + (long)(QSTEP * j) * p.x.sp + soff[0];
+          glds16(((okb >> j) & 1u) ? src : p.pg.zeros, dst + (wq + 4 * j) * 1024);
         }
       } else {
         // four regular pieces per loader (the 17-piece rows): a rolled loop, so that the four source addresses are formed one at a time
         // (unrolled, hipcc forms them all up front: 10 more live registers in a kernel that sits at the 256-register limit)
 #pragma nounroll
         for (int j = 0; j < NP - 1; ++j) {
-          const half_t* src = base + (long)(QSTEP * j) * p.x_sp + soff[0];
-          glds16(((okb >> j) & 1u) ? src : p.zeros, dst + (wq + 4 * j) * 1024);
+          const half_t* src = base + (long)(QSTEP * j) * p.x.sp + soff[0];
+          glds16(((okb >> j) & 1u) ? src : p.pg.zeros, dst + (wq + 4 * j) * 1024);
         }
       }
       if (G::HD == 4 ? wq == (kk & 3) : wq == 0) {
-        glds16(((okb >> (NP - 1)) & 1u) ? base + soff[SRC - 1] : p.zeros, dst + (G::PIECES - 1) * 1024);
+        glds16(((okb >> (NP - 1)) & 1u) ? base + soff[SRC - 1] : p.pg.zeros, dst + (G::PIECES - 1) * 1024);
         return NP;
       }
       return NP - 1;
@@ -343,24 +314,13 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
       for (int kk = 0; kk < PF; ++kk)
         if (kk <= last_in) issue_row(kk);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    rowk::wait_vmcnt<0>();
     raw_barrier();
 
     const int K = (rows + KH - 1 + RW_BI + RW_BI - 1) & ~(RW_BI - 1);     // steps, a whole number of barrier intervals
     // A loader's count of instructions left in flight is a constant while rows are being issued: HD = 4: the odd piece goes round the four
     // loaders, 4 (NP - 1) + 1 over any four consecutive steps; HD = 2: loader 0 owns it, 2 NP, the others 2 (NP - 1).  Shorter histories
     // (the first steps of a segment) have fewer outstanding than that and pass without waiting; once issuing has stopped the wait is vmcnt(0).
-    auto land_wait = [&](int nvm) __attribute__((always_inline)) {
-      if (!nvm) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
-      if constexpr (G::HD == 4) {
-        static_assert(G::HD != 4 || NP == 3, "vmcnt(9)");
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-      } else {
-        static_assert(G::HD != 2 || NP == 5, "vmcnt(10) / vmcnt(8)");
-        if (wq == 0) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      }
-    };
 
     // One step k: every wave consumes ring row i = ra - 1 + k: tap row dy of it belongs to output row i + 1 - dy (started: dy = 0, finished:
     // dy = KH - 1 -> staging row k); storer waves first send the row finished BI steps ago (staging row k - BI, image row
@@ -380,7 +340,7 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
             if constexpr (NRES >= 1) yv = yv + r1v[j];
             // no branch around the store: behind a branch hipcc drains vmcnt(0) at the join, i.e. in front of the residual loads below
             // (measured: 128 -> 128 + residual @544x960 145 -> 175 us); lanes outside the image store into the dump page instead
-            *reinterpret_cast<half8*>(s_ok[j] ? yrow + y_lo[j] : p.dump + (s_t + 256 * j) * 8) = yv;
+            *reinterpret_cast<half8*>(s_ok[j] ? yrow + y_lo[j] : p.pg.dump + (s_t + 256 * j) * 8) = yv;
           }
         }
         if constexpr (NRES >= 1) {
@@ -393,7 +353,7 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
       }
       int nvm = 0;
       if (FULL || k <= last_in) {
-        const unsigned char* xb = smem + G::X0 + rw_slot<XRING>(k) * G::ROWB;
+        const unsigned char* xb = smem + G::X0 + rowk::ring_slot<XRING>(k) * G::ROWB;
         // NG groups (kc, dx) of up to 2 KH MFMAs (KH output rows x 2 column blocks) on two B fragments; the fragments of group g + FBN - 1
         // are requested before group g's MFMAs (FBN fragment pairs in flight)
         constexpr int FBN = (PXB == 256 && (NRES == 1 || GID == GEO_C128W)) ? 2 : 3;      // the 128-channel geometries sit at the 256-register limit
@@ -435,33 +395,19 @@ __global__ __launch_bounds__(RW_NTHR, 1) void conv_row_kernel(const RowParams p)
           unsigned char* sb = smem + G::S0 + (k & (RW_SRING - 1)) * RW_SROW;
 #pragma unroll
           for (int cb = 0; cb < 2; ++cb) {
-            const f32x4 v = acc[SD][cb];
-            half4 h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-            if constexpr (ACT == 1) {
-              const half4 z = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
-              h = __builtin_elementwise_max(h, z);
-            } else if constexpr (ACT == 2) {
-              h = __builtin_elementwise_max(h, h * sl4);
-            }
+            const half4 h = rowk::pack_act<ACT>(acc[SD][cb], sl4);
             *reinterpret_cast<half4*>(sb + doff[cb]) = h;
           }
         }
       }
-      if constexpr (LOADER) land_wait(nvm);
+      if constexpr (LOADER) rowk::land_wait<T>(nvm, wq);
       raw_barrier((k & (RW_BI - 1)) != RW_BI - 1);
-    };
-    auto steps_of = [&](auto FULLc, int k0, int kend) __attribute__((always_inline)) {    // up to KH steps from k0 (k0 % KH == 0), while < kend
-      step(std::integral_constant<int, 0>{}, FULLc, k0);
-      if (k0 + 1 < kend) step(std::integral_constant<int, 1 % KH>{}, FULLc, k0 + 1);
-      if constexpr (KH == 3) {
-        if (k0 + 2 < kend) step(std::integral_constant<int, 2 % KH>{}, FULLc, k0 + 2);
-      }
     };
     constexpr int KF = ((RW_BI + KH - 1 + KH - 1) / KH) * KH;       // first steady-state step: a multiple of KH >= BI + KH - 1
     int k = 0;
-    for (; k < KF; k += KH) steps_of(std::false_type{}, k, KF);
-    for (; k + KH - 1 <= last_in; k += KH) steps_of(std::true_type{}, k, k + KH);
-    for (; k < K; k += KH) steps_of(std::false_type{}, k, K);
+    for (; k < KF; k += KH) rowk::steps_of<KH>(step, std::false_type{}, k, KF);
+    for (; k + KH - 1 <= last_in; k += KH) rowk::steps_of<KH>(step, std::true_type{}, k, k + KH);
+    for (; k < K; k += KH) rowk::steps_of<KH>(step, std::false_type{}, k, K);
     raw_barrier();                              // the next job's prologue overwrites ring rows the slowest wave may still read
   }
   };
@@ -495,16 +441,12 @@ int conv_row_geometry(const tdvc_conv_desc* d, const ConvParams& p, int Ho, int 
 template <int GID>
 static int launch_conv_row_t(const ConvParams& p, int N, hipStream_t st) {
   using G = RowDerived<GID>;
-  const void* zeros = nullptr;
-  void* dump = nullptr;
-  if (const int zrc = tdvc_scratch_pages(&zeros, &dump)) return zrc;
   RowParams q;
-  q.x = p.x; q.x_sn = p.x_sn; q.x_sp = p.x_sp;
-  q.y = reinterpret_cast<half_t*>(p.y.p); q.y_sn = p.y.sn; q.y_sp = p.y.sp;
-  q.res = reinterpret_cast<const half_t*>(p.res.p); q.r1_sn = p.res.p ? p.res.sn : 0; q.r1_sp = p.res.p ? p.res.sp : 0;
+  if (const int zrc = rowk::scratch_pages(q.pg)) return zrc;
+  q.x = {p.x, p.x_sn, p.x_sp};
+  q.y = rowk::map_ref<half_t>(p.y.p, p.y.sn, p.y.sp);
+  q.res = rowk::map_ref<const half_t>(p.res.p, p.res.sn, p.res.sp);
   q.w = p.w; q.bias = p.bias;
-  q.zeros = reinterpret_cast<const half_t*>(zeros);
-  q.dump = reinterpret_cast<half_t*>(dump);
   q.N = N; q.H = p.Ho; q.W = p.Wo; q.Win = p.W;
   q.ncb = p.cout / G::CO;
   const bool shuf = p.out_mode == TDVC_OUT_SHUFFLE2;
@@ -519,9 +461,9 @@ static int launch_conv_row_t(const ConvParams& p, int N, hipStream_t st) {
   if (allrows < per) per = (int)allrows;
   const int grid = per * q.ncb;
   if (!p.res.p && p.res2.p) {                  // a single residual always travels as `res`
-    q.res = reinterpret_cast<const half_t*>(p.res2.p); q.r1_sn = p.res2.sn; q.r1_sp = p.res2.sp;
+    q.res = rowk::map_ref<const half_t>(p.res2.p, p.res2.sn, p.res2.sp);
   }
-  const bool has1 = q.res != nullptr;
+  const bool has1 = q.res.p != nullptr;
   const int act = q.slope == 1.f ? 0 : (q.slope == 0.f ? 1 : 2);
   const int nres = has1 ? 1 : 0;
   q.pred = tdvc_launch_predicate();

@@ -24,9 +24,7 @@
 // row r is raw until the barrier that closes step r - 3, read by A1 in step r - 2, rewritten by A2 in step r - 1, read by B in step r and
 // overwritten by the DMA of step r + XRING - PF = r + 1.
 // Zero padding belongs to s, the conv's input: out-of-image ring pixels are DMA'd zeros; their T is +0 (no bias) and lrelu(0 + 0) = +0.
-#include <type_traits>
-
-#include "conv_dma.h"
+#include "row_pipe.h"
 
 using convk::glds16;
 using convk::raw_barrier;
@@ -34,35 +32,36 @@ using convk::raw_barrier;
 namespace {
 
 constexpr int LT_SW = 32, LT_RPX = LT_SW + 2, LT_PXB = 512, LT_PIECES = 17, LT_ROWB = LT_PIECES * 1024;
-constexpr int LT_XRING = 6, LT_PF = 5;           // ring rows; rows the DMA runs ahead (land_wait leaves two steps of DMA in flight)
+constexpr int LT_XRING = 6, LT_PF = 5, LT_HD = 2;      // ring rows; rows the DMA runs ahead; land_wait leaves two steps of DMA in flight
 constexpr int LT_SROW = LT_SW * LT_PXB;          // a staging row: 32 px x 4 images x 64 channels
 constexpr int LT_TPS = 144, LT_TROW = LT_RPX * LT_TPS;      // a T row: 34 px x 64 channels fp16, 144-byte pixel pitch
 constexpr int LT_X0 = 0, LT_S0 = LT_XRING * LT_ROWB, LT_T0 = LT_S0 + 2 * LT_SROW, LT_B0 = LT_T0 + 2 * LT_TROW, LT_LDS = LT_B0 + 256;
 constexpr int LT_NTHR = 512;
 static_assert(LT_RPX * LT_PXB == LT_ROWB, "a ring row is exactly 17 pieces");
-// landing: row r is issued in step r - PF; a loader knows its pieces landed after land_wait() of a step >= r - PF + 2, the others at that
-// step's barrier; A1 reads the row in step r - 2, behind the barrier of step r - 3: r - 3 >= r - PF + 2.  Write-after-read: the DMA of step
-// k overwrites row k + PF - XRING, last read in step k + PF - XRING < k.
-static_assert(LT_PF >= 5 && LT_PF < LT_XRING, "ring conditions");
+// One barrier per step (BI = 1).  Ring row r is read by A1 in step r - LT_A1 (raw), rewritten in place by A2 in step r - LT_A2 and read by
+// B in step r: the first read is LT_A1 steps before the row's own step, the last is in it.  The write-after-read and landing inequalities
+// and the counted wait are RingTiming's (row_pipe.h); the three phases of one row lie in three different steps, so a barrier separates
+// A1's read from A2's rewrite and A2's rewrite from B's read.
+constexpr int LT_A1 = 2, LT_A2 = 1, LT_B = 0;
+using LtTiming = rowk::RingTiming<LT_PIECES, LT_XRING, LT_PF, LT_HD, 1, LT_B, LT_A1>;
+using LtLayout = rowk::RingLayout<LT_PXB>;
+static_assert(LT_A1 > LT_A2 && LT_A2 > LT_B && LT_B == 0, "A1, A2 and B of a row in three consecutive steps: one barrier between each pair");
+static_assert(rowk::row_check::dma_matches_reads<LtLayout>(LT_PIECES, LT_RPX), "the DMA writes every (pixel, slot) of a ring row once, where the fragment read looks for it");
+static_assert(rowk::row_check::reads_conflict_free<LtLayout>(3, 2), "a 16-lane group of a B-fragment read touches 16 distinct bank slots");
 static_assert((LT_T0 % 16) == 0 && LT_LDS <= 160 * 1024, "LDS");
 
 struct TailParams {
-  const half_t* s; long s_sn; int s_sp;
-  const half_t* a; long a_sn; int a_sp;
-  half_t* y; long y_sn; int y_sp;
+  rowk::MapRef<const half_t> s;
+  rowk::MapRef<const half_t> a;
+  rowk::MapRef<half_t> y;
   const half_t* wt;         // temporal conv, standard blob (ck = 32, one tap): [cout tile 32][chunk 6][k-step 2][lane 64][8 halves]
   const half_t* w3;         // conv3, standard blob: [cout tile 32][chunk 2][k-step 18][lane 64][8 halves]
   const float* bias3;
-  const half_t* zeros;      // >= 16 B of zeros: DMA source of out-of-image pixels
-  half_t* dump;             // >= 16 KB nobody reads: store target of items outside the image
+  rowk::ScratchPages pg;    // zeros; dump: >= 16 KB
   int N, H, W, strips;
   float slope;
   float tzero;              // 0.f: the temporal conv's (absent) bias, added in fp32 as conv_mfma_v5 does
 };
-
-__device__ __forceinline__ int lt_f(int q) { return (q & 12) | ((q & 1) << 1) | ((q >> 1) & 1); }           // ring-row swizzle term (conv_row: rw_f)
-__device__ __forceinline__ int lt_sigma(int r) { return r < 4 ? 2 * r : (r >= 12 ? 2 * r - 16 : 2 * r - 7); }  // fragment lane -> pixel of its 16-px block
-__device__ __forceinline__ int lt_g(int q) { return (q >> 1) & 7; }                                         // staging-row swizzle term
 
 __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -75,11 +74,8 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
   const int r16 = lane & 15, kb = lane >> 4;
 
   // ---- workgroup -> run of rows of the flat sequence (batch item, strip, row), as conv_row does with one cout block
-  const int nwg = (int)gridDim.x, b = (int)blockIdx.x;
-  int pos_slot = b;
-  if ((nwg & 7) == 0) pos_slot = (b & 7) * (nwg >> 3) + (b >> 3);
-  const long allrows = (long)p.N * p.strips * p.H;
-  const long run_begin = allrows * pos_slot / nwg, run_end = allrows * (pos_slot + 1) / nwg;
+  const rowk::RunRange rr = rowk::run_range(1, 0, p.N, p.strips, p.H);
+  const long run_begin = rr.begin, run_end = rr.end;
 
   // ---- conv3: this wave's 16 output channels as 18 A fragments (tap, chunk), exactly conv_row's gather from the standard blob
   half8 wf[18];
@@ -98,22 +94,21 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
   int foff[3];                                 // B fragment (dx), logical slot kb of column block 0; slot 8 j + 4 kc + kb: ^ ((8 j + 4 kc) << 4)
 #pragma unroll
   for (int dx = 0; dx < 3; ++dx) {
-    const int q = dx + lt_sigma(r16);
-    foff[dx] = q * LT_PXB + ((kb ^ lt_f(q)) << 4);
+    foff[dx] = LtLayout::slot_off(dx + rowk::sigma(r16), kb);
   }
   int doff[2];                                 // pack: pixel 16 cb + SIGMA(r16), image 2 ip, channels 16 cg + 4 kb .. + 3; image + 1: + 128
 #pragma unroll
   for (int cb = 0; cb < 2; ++cb) {
-    const int q = 16 * cb + lt_sigma(r16), c = 16 * ip + 2 * cg + (kb >> 1);
-    doff[cb] = q * LT_PXB + ((c ^ lt_g(q)) << 4) + 8 * (kb & 1);
+    const int q = 16 * cb + rowk::sigma(r16), c = 16 * ip + 2 * cg + (kb >> 1);
+    doff[cb] = rowk::cd_off(LT_PXB, q, c) + 8 * (kb & 1);
   }
   // A2 items: 34 px x 32 positions of 16 bytes; thread t owns position t & 31 of pixels (t >> 5) and (t >> 5) + 16, wave 7 also pixels 32, 33
   // (the swizzle term depends on q & 15 only: one logical slot per thread)
   const int a2_pos = tid & 31, a2_q = tid >> 5;
-  const int a2_slot = a2_pos ^ lt_f(a2_q);     // image a2_slot >> 3, channels 8 (a2_slot & 7) .. + 7
+  const int a2_slot = a2_pos ^ LtLayout::term(a2_q);     // image a2_slot >> 3, channels 8 (a2_slot & 7) .. + 7
   const int a2_x = a2_q * LT_PXB + a2_pos * 16, a2_t = a2_q * LT_TPS + (a2_slot & 7) * 16;
   const bool a2_third = tid >= LT_NTHR - 64;   // wave 7: threads 448 .. 511 (a2_q = 14, 15) also own pixels 32, 33, whose swizzle term is that of pixels 0, 1
-  const int a2_t3 = (a2_q + 18) * LT_TPS + ((a2_pos ^ lt_f(a2_q - 14)) & 7) * 16;
+  const int a2_t3 = (a2_q + 18) * LT_TPS + ((a2_pos ^ LtLayout::term(a2_q - 14)) & 7) * 16;
 
   auto run = [&](auto LOADERc) __attribute__((always_inline)) {
   constexpr bool LOADER = decltype(LOADERc)::value;
@@ -124,14 +119,14 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int q = dq + 8 * j;
-    soff[j] = q * p.s_sp + (((lane & 31) ^ lt_f(q)) << 3);
+    soff[j] = q * p.s.sp + (((lane & 31) ^ LtLayout::term(q)) << 3);
   }
   // ---- loader waves: the temporal conv.  Wave (mt, nt): channels [32 mt, +32) of ring pixels 32 nt + (lane & 31) (nt = 1: pixels 32, 33 only;
   // the other lanes re-read pixel 33 and write nothing).  Lane (r, hh) of k-step m holds channels 16 m + 8 hh .. + 7: logical slot 2 m + hh.
   const int mt = wq & 1, nt = wq >> 1;
   const int a1_q = min(32 * nt + (lane & 31), LT_RPX - 1), a1_hh = lane >> 5;
   const bool a1_ok = 32 * nt + (lane & 31) < LT_RPX;
-  const int a1_x = a1_q * LT_PXB + ((a1_hh ^ lt_f(a1_q)) << 4);
+  const int a1_x = a1_q * LT_PXB + ((a1_hh ^ LtLayout::term(a1_q)) << 4);
   const int a1_t = a1_q * LT_TPS + (32 * mt + 4 * a1_hh) * 2;
   half8 tw[LOADER ? 12 : 1];
   if constexpr (LOADER) {
@@ -145,19 +140,16 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
   for (int j = 0; j < 4; ++j) {
     const int it = s_t + 256 * j;
     s_px[j] = it >> 5;
-    s_co[j] = ((it & 31) ^ lt_g(it >> 5)) << 3;
+    s_co[j] = ((it & 31) ^ rowk::stage_g(it >> 5)) << 3;
   }
 
   f32x4 acc[3][2][2];                          // [rotating output row][column block][image of the pair]
   half8 r1v[4] = {};
 
   for (long pos = run_begin; pos < run_end;) {
-    const int sid = (int)(pos / p.H);          // (batch item, strip)
-    const int ra = (int)(pos - (long)sid * p.H), rb = (int)min((long)p.H, ra + (run_end - pos));
-    const int rows = rb - ra;
-    pos += rows;
-    const int n = sid / p.strips, strip = sid - n * p.strips;
-    const int c0 = strip * LT_SW;
+    const rowk::Segment sg = rowk::next_segment(pos, run_end, p.H, p.strips);      // of (batch item, strip)
+    const int ra = sg.ra, rb = sg.rb, rows = sg.rows, n = sg.n;
+    const int c0 = sg.strip * LT_SW;
     const int last_in = rows + 1;              // the last step that consumes an input row
 
     unsigned colok = 0;                        // bit j: this lane's pixel of its j-th piece is inside the image
@@ -172,13 +164,13 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
     for (int j = 0; j < 4; ++j) {
       const int col = c0 + s_px[j], colc = min(col, p.W - 1);
       s_ok[j] = col < p.W;
-      y_lo[j] = col * p.y_sp + s_co[j];        // element offsets fit 32 bits (checked by the host)
-      r_lo[j] = colc * p.a_sp + s_co[j];
+      y_lo[j] = col * p.y.sp + s_co[j];        // element offsets fit 32 bits (checked by the host)
+      r_lo[j] = colc * p.a.sp + s_co[j];
     }
-    const half_t* const yimg = p.y + (long)n * p.y_sn;
-    const half_t* const rimg = p.a + (long)n * p.a_sn;
-    const long yrow_stride = (long)p.W * p.y_sp, rrow_stride = (long)p.W * p.a_sp, xrow_stride = (long)p.W * p.s_sp;
-    const half_t* const xcol = p.s + (long)n * p.s_sn + (long)(c0 - 1) * p.s_sp;
+    const half_t* const yimg = p.y.p + (long)n * p.y.sn;
+    const half_t* const rimg = p.a.p + (long)n * p.a.sn;
+    const long yrow_stride = (long)p.W * p.y.sp, rrow_stride = (long)p.W * p.a.sp, xrow_stride = (long)p.W * p.s.sp;
+    const half_t* const xcol = p.s.p + (long)n * p.s.sn + (long)(c0 - 1) * p.s.sp;
 #pragma unroll
     for (int s3 = 0; s3 < 3; ++s3)
 #pragma unroll
@@ -191,29 +183,23 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
       const int row = ra - 1 + kk;
       const bool rowok = row >= 0 && row < p.H;
       const half_t* base = xcol + row * xrow_stride;
-      const unsigned dst = lds0 + LT_X0 + (__builtin_amdgcn_readfirstlane(kk) % LT_XRING) * LT_ROWB;
+      const unsigned dst = lds0 + LT_X0 + rowk::ring_slot<LT_XRING>(kk) * LT_ROWB;
       const unsigned okb = rowok ? colok : 0u;
 #pragma nounroll
       for (int j = 0; j < 4; ++j) {
-        const half_t* src = base + (long)(16 * (j >> 1)) * p.s_sp + soff[j & 1];
-        glds16(((okb >> j) & 1u) ? src : p.zeros, dst + (wq + 4 * j) * 1024);
+        const half_t* src = base + (long)(16 * (j >> 1)) * p.s.sp + soff[j & 1];
+        glds16(((okb >> j) & 1u) ? src : p.pg.zeros, dst + (wq + 4 * j) * 1024);
       }
       if (wq == 0) {
-        glds16(((okb >> 4) & 1u) ? base + (long)32 * p.s_sp + soff[0] : p.zeros, dst + (LT_PIECES - 1) * 1024);
+        glds16(((okb >> 4) & 1u) ? base + (long)32 * p.s.sp + soff[0] : p.pg.zeros, dst + (LT_PIECES - 1) * 1024);
         return 5;
       }
       return 4;
     };
-    // two steps of DMA stay in flight (loader 0: 2 x 5 instructions, the others 2 x 4); once issuing has stopped: everything
-    auto land_wait = [&](int nvm) __attribute__((always_inline)) {
-      if (!nvm) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
-      if (wq == 0) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    };
     // A1: T of ring row kk (raw) -> T row kk & 1
     auto phase_a1 = [&](int kk) __attribute__((always_inline)) {
       if constexpr (LOADER) {
-        const unsigned char* xb = smem + LT_X0 + (__builtin_amdgcn_readfirstlane(kk) % LT_XRING) * LT_ROWB;
+        const unsigned char* xb = smem + LT_X0 + rowk::ring_slot<LT_XRING>(kk) * LT_ROWB;
         unsigned char* tb = smem + LT_T0 + (kk & 1) * LT_TROW;
         f32x16 t;
 #pragma unroll
@@ -236,7 +222,7 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
     };
     // A2: ring row kk in place: s_j = lrelu(S_j + T) with T row kk & 1
     auto phase_a2 = [&](int kk) __attribute__((always_inline)) {
-      unsigned char* xb = smem + LT_X0 + (__builtin_amdgcn_readfirstlane(kk) % LT_XRING) * LT_ROWB;
+      unsigned char* xb = smem + LT_X0 + rowk::ring_slot<LT_XRING>(kk) * LT_ROWB;
       const unsigned char* tb = smem + LT_T0 + (kk & 1) * LT_TROW;
       auto item = [&](int qadd, int toff) __attribute__((always_inline)) {
         unsigned char* xp = xb + a2_x + qadd * LT_PXB;
@@ -261,7 +247,7 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
       for (int kk = 0; kk < LT_PF; ++kk)
         if (kk <= last_in) issue_row(kk);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    rowk::wait_vmcnt<0>();
     raw_barrier();
     phase_a1(0);
     raw_barrier();
@@ -284,7 +270,7 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
             half8 yv = *reinterpret_cast<const half8*>(sb + (s_t + 256 * j) * 16);
             yv = yv + r1v[j];
             // no branch around the store (conv_row): lanes outside the image store into the dump page
-            *reinterpret_cast<half8*>(s_ok[j] ? yrow + y_lo[j] : p.dump + (s_t + 256 * j) * 8) = yv;
+            *reinterpret_cast<half8*>(s_ok[j] ? yrow + y_lo[j] : p.pg.dump + (s_t + 256 * j) * 8) = yv;
           }
         }
         const int nrow = srow + 1;
@@ -292,13 +278,13 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
         const half_t* const rrow = rimg + (rok ? nrow : ra) * rrow_stride;          // wave-uniform; a row outside the segment reads a valid one
 #pragma unroll
         for (int j = 0; j < 4; ++j) r1v[j] = *reinterpret_cast<const half8*>(rrow + r_lo[j]);
-        if (FULL || k + 1 <= last_in) phase_a2(k + 1);       // storers: elementwise work first, under the loaders' MFMAs
+        if (FULL || k + LT_A2 <= last_in) phase_a2(k + LT_A2);       // storers: elementwise work first, under the loaders' MFMAs
       } else {
-        if (FULL || k + 2 <= last_in) phase_a1(k + 2);
+        if (FULL || k + LT_A1 <= last_in) phase_a1(k + LT_A1);
       }
       int nvm = 0;
       if (FULL || k <= last_in) {
-        const unsigned char* xb = smem + LT_X0 + (__builtin_amdgcn_readfirstlane(k) % LT_XRING) * LT_ROWB;
+        const unsigned char* xb = smem + LT_X0 + rowk::ring_slot<LT_XRING>(k) * LT_ROWB;
         // 12 groups (image of the pair, chunk, dx) of 6 MFMAs (3 output rows x 2 column blocks) on two B fragments, the next group's
         // fragments requested before this group's MFMAs
         half8 fb[2][2];
@@ -341,20 +327,15 @@ __global__ __launch_bounds__(LT_NTHR, 1) void lf_tail_kernel(const TailParams p)
         }
       }
       if constexpr (LOADER) {
-        if (FULL || k + 1 <= last_in) phase_a2(k + 1);       // loaders: behind their MFMAs, under the storers'
-        land_wait(nvm);
+        if (FULL || k + LT_A2 <= last_in) phase_a2(k + LT_A2);       // loaders: behind their MFMAs, under the storers'
+        rowk::land_wait<LtTiming>(nvm, wq);       // two steps of DMA stay in flight (loader 0: 2 x 5 instructions, the others 2 x 4)
       }
       raw_barrier();
     };
-    auto steps_of = [&](auto FULLc, int k0, int kend) __attribute__((always_inline)) {     // up to 3 steps from k0 (k0 % 3 == 0), while < kend
-      step(std::integral_constant<int, 0>{}, FULLc, k0);
-      if (k0 + 1 < kend) step(std::integral_constant<int, 1>{}, FULLc, k0 + 1);
-      if (k0 + 2 < kend) step(std::integral_constant<int, 2>{}, FULLc, k0 + 2);
-    };
     int k = 0;
-    for (; k < 3; k += 3) steps_of(std::false_type{}, k, min(3, K));
-    for (; k + 2 + 2 <= last_in; k += 3) steps_of(std::true_type{}, k, k + 3);        // full: rows k - 3 .. stored, rows .. k + 4 consumed
-    for (; k < K; k += 3) steps_of(std::false_type{}, k, K);
+    for (; k < 3; k += 3) rowk::steps_of<3>(step, std::false_type{}, k, min(3, K));
+    for (; k + 2 + 2 <= last_in; k += 3) rowk::steps_of<3>(step, std::true_type{}, k, k + 3);        // full: rows k - 3 .. stored, rows .. k + 4 consumed
+    for (; k < K; k += 3) rowk::steps_of<3>(step, std::false_type{}, k, K);
   }
   };
   if (loader) run(std::true_type{});
@@ -396,18 +377,14 @@ extern "C" int tdvc_lf_tail(const tdvc_lf_tail_desc* d, void* stream) {
     tdvc_set_error("tdvc_lf_tail: %s", why);
     return TDVC_EINVAL;
   }
-  const void* zeros = nullptr;
-  void* dump = nullptr;
-  if (const int zrc = tdvc_scratch_pages(&zeros, &dump)) return zrc;
   TailParams q;
-  q.s = reinterpret_cast<const half_t*>(d->s.p); q.s_sn = d->s.sn; q.s_sp = d->s.sp;
-  q.a = reinterpret_cast<const half_t*>(d->a.p); q.a_sn = d->a.sn; q.a_sp = d->a.sp;
-  q.y = reinterpret_cast<half_t*>(d->y.p); q.y_sn = d->y.sn; q.y_sp = d->y.sp;
+  if (const int zrc = rowk::scratch_pages(q.pg)) return zrc;
+  q.s = rowk::map_ref<const half_t>(d->s.p, d->s.sn, d->s.sp);
+  q.a = rowk::map_ref<const half_t>(d->a.p, d->a.sn, d->a.sp);
+  q.y = rowk::map_ref<half_t>(d->y.p, d->y.sn, d->y.sp);
   q.wt = reinterpret_cast<const half_t*>(d->wt);
   q.w3 = reinterpret_cast<const half_t*>(d->w3);
   q.bias3 = d->bias3;
-  q.zeros = reinterpret_cast<const half_t*>(zeros);
-  q.dump = reinterpret_cast<half_t*>(dump);
   q.N = d->s.N; q.H = d->s.H; q.W = d->s.W;
   q.strips = (q.W + LT_SW - 1) / LT_SW;
   q.slope = d->slope;

@@ -119,6 +119,20 @@ CASES = [
     C("row_dy_shuffle", "conv_row", "lean", 128, 256, W3, 1, 65, 131, act=ACT_LRELU, slope=0.1, out="shuffle", res="f16", grade="dyadic", multi=True, ragged=True),
     C("row_s2d", "conv_row(s2d)", "lean", 64, 128, S3, 1, 130, 262, act=ACT_RELU, s2d=True, res="f16", multi=True, ragged=True),  # 65 x 131 output
     C("row_s2d_dy", "conv_row(s2d)", "lean", 64, 128, S3, 1, 130, 262, act=ACT_LRELU, slope=0.1, s2d=True, grade="dyadic", multi=True, ragged=True),
+    # the instantiations <geometry, activation, residual, shuffle> that a 1080p P-frame launches and no case above reaches: no activation
+    # without a residual, the sub-pixel store without a residual (the 128 -> 512 layers), the 128 -> 64 geometry without a residual
+    C("row_c128_plain", "conv_row", "lean", 128, 128, W3, 1, 65, 131, multi=True, ragged=True),
+    C("row_c128_plain_shuffle", "conv_row", "lean", 128, 256, W3, 1, 65, 131, out="shuffle", multi=True, ragged=True),
+    C("row_c128_none_res", "conv_row", "lean", 128, 128, W3, 1, 65, 131, res="f16", multi=True, ragged=True),
+    C("row_c128_none_res_shuffle", "conv_row", "lean", 128, 256, W3, 1, 65, 131, out="shuffle", res="f16", multi=True, ragged=True),
+    C("row_c128_relu", "conv_row", "lean", 128, 128, W3, 1, 65, 131, act=ACT_RELU, multi=True, ragged=True),
+    C("row_c128_lrelu", "conv_row", "lean", 128, 128, W3, 1, 65, 131, act=ACT_LRELU, slope=0.25, multi=True, ragged=True),
+    C("row_c128_lrelu_shuffle512", "conv_row", "lean", 128, 512, W3, 1, 65, 131, act=ACT_LRELU, slope=0.25, out="shuffle", multi=True, ragged=True),
+    C("row_c64_plain", "conv_row", "lean", 64, 64, W3, 1, 65, 131, ragged=True),
+    C("row_c64_relu", "conv_row", "lean", 64, 64, W3, 1, 65, 131, act=ACT_RELU, ragged=True),
+    C("row_c128w_plain", "conv_row", "lean", 128, 64, W3, 1, 65, 131, ragged=True),
+    C("row_c128w_relu", "conv_row", "lean", 128, 64, W3, 1, 65, 131, act=ACT_RELU, ragged=True),
+    C("row_c128w_lrelu", "conv_row", "lean", 128, 64, W3, 1, 65, 131, act=ACT_LRELU, slope=0.25, ragged=True),
     # ---- conv_mfma_v3: 8x32 tiles on 512 slots; every epilogue form
     C("v3_multi", "conv_mfma_v3", "lean", 128, 256, W3, 4, 75, 100, act=ACT_RELU, res="f16", multi=True, ragged=True),            # 40 tiles on 32 workgroups, H % 8 = 3, W % 32 = 4, below the streaming floor, above v9's
     C("v3_ragged", "conv_mfma_v3", "lean", 64, 64, W3, 2, 67, 69, act=ACT_LRELU, slope=0.25, res="f16", res2="f16", ragged=True), # 9246 px over the batch: H % 8 = 3, W % 32 = 5
