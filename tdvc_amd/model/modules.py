@@ -11,6 +11,8 @@ slices of a shared buffer, never copies.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -20,13 +22,64 @@ from .ring import SlotRing
 
 
 class PackCache:
-    """mixin: lazily packed weights keyed by name"""
+    """mixin: lazily packed weights keyed by name, and the reuse states computed from them"""
 
     def _pk(self, key, fn):
         c = self.__dict__.setdefault("_packed", {})
         if key not in c:
             c[key] = fn()
         return c[key]
+
+    def _state(self, name, key, make):
+        """the `ReuseState` kept under `name`: the cached one while its key is `key`, else make(key) in its place"""
+        c = self.__dict__.setdefault("_packed", {})
+        st = c.get(name)
+        if st is None or st.key != key:
+            st = c[name] = make(key)
+        return st
+
+    @contextlib.contextmanager
+    def _state_trusted(self, name):
+        """around the launches that write the state's buffers: an exception may leave them half written, the state is never trusted again"""
+        try:
+            yield
+        except BaseException:
+            self.__dict__.get("_packed", {}).pop(name, None)
+            raise
+
+
+class ReuseState:
+    """What a block keeps from one call to the next (FeatureFix: the I-frame's features; LoopFilter: the per-reference-frame maps), held
+    in the packed-weight cache (`PackCache._state`), so that `clear_packed()` and `train.refresh_packed` drop it with the weights it was
+    computed from.  `key`: what the buffers were made for.  `usable` is None until the first call has shown whether every launch of the
+    chain carries the predicate; then True, or False for good: the buffers are dropped and every call computes in full, unpredicated.
+    `log`: the last call's per-kernel answers (ops.predicate).  A subclass names its buffers in `BUFFERS`."""
+
+    __slots__ = ("key", "usable", "log")
+    BUFFERS = ()
+
+    def __init__(self, key):
+        self.key, self.usable, self.log = key, None, []
+        self.drop()
+
+    def drop(self):
+        for name in self.BUFFERS:
+            setattr(self, name, None)
+
+    def refuse(self):
+        """stop caching for this key"""
+        self.drop()
+        self.usable = False
+
+    def took(self, log) -> bool:
+        """the log of the call just enqueued -> usable.  An entry that is not true is a kernel outside the predicated set: it ran in
+        full behind producers that may have skipped"""
+        self.log = list(log)
+        if all(self.log):
+            self.usable = True
+        else:
+            self.refuse()
+        return self.usable
 
 
 def _dev(m: nn.Module):
@@ -352,17 +405,47 @@ LOOPFILTER_TAIL = True          # A/B switch: temporal conv + broadcast add + Le
 LOOPFILTER_RING = 9             # slots of per-frame maps; a call's window is four of them and slides by one per call (model/ring.py)
 
 
-class LoopFilterReuse:
-    """LoopFilter's state for one (device, stream, B, H, W): per batch item a ring of slots, each holding what the head of the block makes
-    of ONE frame -- `A` (conv01 + conv02 + conv1) and `S` (layer1.conv1 + spatial_conv3d), 64 channels per slot -- and the frame it was
-    made from (`F`).  `flags[b]` are the device flags of the last call (1 = slice computed; flags[b, 3], prediction1's, stays 1).
-    `usable` as in IFrameReuse; `log`: the last call's per-kernel answers."""
+class LoopFilterReuse(ReuseState):
+    """LoopFilter's state for one (device, stream, B, H, W, ring size): per batch item a ring of slots, each holding what the head of the
+    block makes of ONE frame -- `A` (conv01 + conv02 + conv1) and `S` (layer1.conv1 + spatial_conv3d), 64 channels per slot -- and the
+    frame it was made from (`F`).  `flags[b]` are the device flags of the last call (1 = slice computed; flags[b, 3], prediction1's,
+    stays 1)."""
 
-    __slots__ = ("key", "ring", "A", "S", "F", "flags", "usable", "log")
+    __slots__ = ("ring", "A", "S", "F", "flags")
+    BUFFERS = ("A", "S", "F", "flags")
 
     def __init__(self, key, slots):
-        self.key, self.ring, self.usable, self.log = key, SlotRing(slots), None, []
-        self.A = self.S = self.F = self.flags = None
+        super().__init__(key)
+        self.ring = SlotRing(slots)
+
+
+class _LfPlace:
+    """Where the per-frame maps of one LoopFilter call live.  `A4`, `S4`: the four slices of every batch item as (B,H,W,256) views --
+    two dense buffers, or (`st` given) the window of four slots at position `p` of a LoopFilterReuse state's rings, whose launches run
+    under the per-image flags (`force`: the ring's mask of slots that hold nothing comparable)."""
+
+    __slots__ = ("A4", "S4", "st", "p", "force")
+
+    def __init__(self, a: FM, s: FM, st: LoopFilterReuse | None = None, p: int = 0, force: int = 0):
+        self.st, self.p, self.force = st, p, force
+        self.A4, self.S4 = (a, s) if st is None else (a.ch(64 * p, 256), s.ch(64 * p, 256))
+
+    @property
+    def keep_S(self) -> bool:
+        """the slots are the next call's inputs: the temporal stage, which rewrites all four slices, must run out of place"""
+        return self.st is not None
+
+    def A(self, b, j0=0, n=4) -> FM:
+        """slices j0 .. j0 + n - 1 of batch item b as a batch of n 64-channel images: image stride 64 channels, pixel stride the
+        buffer's (256 channels, or the whole ring's)"""
+        return self.A4.as_slices(b, 4, 64).batch(j0, n)
+
+    def S(self, b, j0=0, n=4) -> FM:
+        return self.S4.as_slices(b, 4, 64).batch(j0, n)
+
+    def flags(self, b, n):
+        """`with place.flags(b, n) as log:` -- the launches inside run under the flags of the first n slices of batch item b"""
+        return contextlib.nullcontext([]) if self.st is None else ops.predicate_images(self.st.flags[b, :n])
 
 
 class LoopFilter(nn.Module, PackCache):
@@ -379,172 +462,136 @@ class LoopFilter(nn.Module, PackCache):
         self.attn = SELayer(64)
         self.feat_fusion = nn.Conv2d(256, 64, 1, 1)
 
-    def _slices(self, name, conv, src: FM, dst: FM, res_buf: FM | None = None, **kw):
+    def _slices(self, name, conv, src: FM, dst: FM, **kw):
         pc = pk_conv(self, name, conv)
         for b in range(src.N):
-            ops.conv(src.as_slices(b, 4, 64), pc, out=dst.as_slices(b, 4, 64),
-                     res=res_buf.as_slices(b, 4, 64) if res_buf is not None else None, **kw)
+            ops.conv(src.as_slices(b, 4, 64), pc, out=dst.as_slices(b, 4, 64), **kw)
 
     def run(self, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM:
         """xt: (B,H,W,256) with prediction1 already in slice 3; refs8: (B*4,H,W,8) fp16 frames
         [I, r-3, r-2, r-1] per batch item; writes the fused prediction into `out`.  `then` = (b, sign, out3), inference only: the last
         pass also writes out3 = b + sign * out (the residual `f_cur - pred`, RESID_FUSED) instead of a launch that reads `out` back."""
+        B, H, W = xt.N, xt.H, xt.W
+        dev, adt = xt.t.device, xt.t.dtype
         # conv01, conv02 + conv1 and layer1.conv1 + spatial_conv3d do not mix frames, and by the reference-list rule (synth.ref_list) this
-        # call's r-3 and r-2 are the previous call's r-2 and r-1: their maps are kept (`_run_reuse`).  Training, the tape, the per-kernel
-        # profile (a table of real work), fp32 inputs and shapes the fused kernels do not take compute everything afresh
-        if (LOOPFILTER_REUSE and LOOPFILTER_PAIR and LOOPFILTER_BCAST and not self.training and ops.TAPE is None and ops.PROFILE is None
-                and not xt.f32 and not refs8.f32 and xt.H * xt.W >= 8192 and ops.conv_pair_supported(xt.as_slices(0, 4, 64))):
-            r = self._run_reuse(xt, refs8, out, then)
-            if r is not None:
-                return r
-        return self._run_plain(xt, refs8, out, then)
-
-    def _tail_ok(self, S: FM, A: FM, o: FM) -> bool:
-        """the fused tail (ops.lf_tail) takes these views: inference without tape or per-kernel profile, fp16, no temporal bias"""
-        return (LOOPFILTER_TAIL and LOOPFILTER_BCAST and not self.training and ops.TAPE is None and ops.PROFILE is None
-                and self.layer1.temporal_conv3d.bias is None and ops.lf_tail_supported(S, A, o))
+        # call's r-3 and r-2 are the previous call's r-2 and r-1: their maps are kept in ring slots (`_ring_place`).  Training, the tape, the
+        # per-kernel profile (a table of real work), fp32 inputs and shapes the fused kernels do not take compute everything afresh
+        if (LOOPFILTER_REUSE and LOOPFILTER_PAIR and LOOPFILTER_BCAST and glue_fusions_allowed(self) and not xt.f32 and not refs8.f32
+                and H * W >= 8192 and ops.conv_pair_supported(xt.as_slices(0, 4, 64))):
+            key = (dev.index, ops._stream().value, B, H, W, LOOPFILTER_RING)
+            st = self._state("lf_reuse", key, lambda key: LoopFilterReuse(key, LOOPFILTER_RING))
+            if st.usable is not False:                    # False: some launch of the head does not test the flags at this shape
+                with self._state_trusted("lf_reuse"):
+                    place = self._ring_place(st, refs8)
+                    if place is not None and st.took(self._head(place, xt, refs8)):
+                        st.ring.commit()
+                        return self._finish(self._tail(place), xt, out, then)
+            # the skipping cannot be relied on: the state's buffers are gone, and the plain form below computes everything
+        place = _LfPlace(FM.empty(B, H, W, 256, dtype=adt, device=dev), FM.empty(B, H, W, 256, dtype=adt, device=dev))
+        if LOOPFILTER_PAIR and ops.conv_pair_supported(place.A(0), place.S(0)):
+            self._head(place, xt, refs8)
+            bf = None
+        else:
+            bf = self._head_unfused(place, xt, refs8)
+        return self._finish(self._tail(place, bf), xt, out, then)
 
     def reuse_state(self) -> LoopFilterReuse | None:
         return self.__dict__.get("_packed", {}).get("lf_reuse")
 
-    def _run_reuse(self, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM | None:
-        """The head of the block on persistent per-frame slots.  Per batch item `ops.frames_changed` compares the three reference frames
-        with the frames the window's slots were computed from (exact, on the device; slots that hold nothing comparable are forced) and
-        the head's launches run under the per-image flags: conv_c8 and conv_pair compute the images whose flag is set, their workgroups
-        sharing that work, and leave the other slots as they are.  No host wait, no dependence on tensor identity, bit-identical results.
-        The state lives in the packed-weight cache: `clear_packed()` and `train.refresh_packed` drop it with the weights it was computed
-        from.  -> None when the skipping cannot be relied on (the caller then runs the plain form)."""
-        B, H, W = xt.N, xt.H, xt.W
-        dev = xt.t.device
-        key = (dev.index, ops._stream().value, B, H, W)
-        cache = self.__dict__.setdefault("_packed", {})
-        st = cache.get("lf_reuse")
-        if st is None or st.key != key or st.ring.slots != LOOPFILTER_RING:
-            st = cache["lf_reuse"] = LoopFilterReuse(key, LOOPFILTER_RING)
-        if st.usable is False:                            # some launch of the head does not test the flags at this shape
-            return None
-        try:
-            return self._reuse_call(st, xt, refs8, out, then)
-        except BaseException:
-            cache.pop("lf_reuse", None)                   # slots may be half written: nothing of this state is trusted again
-            raise
-
-    def _reuse_call(self, st: LoopFilterReuse, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM | None:
-        B, H, W = xt.N, xt.H, xt.W
-        dev = xt.t.device
-        lr = dict(act=ACT_LRELU, slope=0.1)
-        R = st.ring.slots
-        if st.A is None:
+    def _ring_place(self, st: LoopFilterReuse, refs8: FM) -> _LfPlace | None:
+        """The window of this call on the persistent per-frame slots of `st`.  Per batch item `ops.frames_changed` compares the three
+        reference frames with the frames the window's slots were computed from (exact, on the device; slots that hold nothing comparable
+        are forced) and the head's launches run under the per-image flags: conv_c8 and conv_pair compute the images whose flag is set,
+        their workgroups sharing that work, and leave the other slots as they are.  No host wait, no dependence on tensor identity,
+        bit-identical results.  -> None when the launcher does not take the windows (nothing has been launched then)."""
+        first = st.A is None
+        if first:
+            _, _, B, H, W, R = st.key
+            dev = refs8.t.device
             st.A, st.S = FM.empty(B, H, W, 64 * R, device=dev), FM.empty(B, H, W, 64 * R, device=dev)
             st.F = FM.empty(B * R, H, W, refs8.C, device=dev)
             st.flags = torch.ones((B, 4), dtype=torch.int32, device=dev)
-            # the launcher must take the views the head really runs on: slot windows of pixel stride 64 R (not the dense slices that
-            # `run` asked about).  If it does not, nothing has been launched yet: no state, the plain form
-            a3, a4, s4 = FM(st.A.t, st.A.off, 3, 64, 64), FM(st.A.t, st.A.off, 4, 64, 64), FM(st.S.t, st.S.off, 4, 64, 64)
-            if not (ops.conv_pair_supported(a3) and ops.conv_pair_supported(a4, s4)):      # a3: as the first pair's output (geometry query)
-                st.usable = False
-                st.A = st.S = st.F = st.flags = None
-                return None
         p, force = st.ring.begin()                        # first call and first call behind a wrap: every slot forced
-        # slots p + j0 .. of batch item b as a batch of n 64-channel images: image stride 64 channels, pixel stride the whole ring's
-        win = lambda buf, b, j0, n: FM(buf.t, buf.off + b * buf.sn + 64 * (p + j0), n, 64, 64)
-        l1 = self.layer1
+        place = _LfPlace(st.A, st.S, st, p, force)
+        # the launcher must take the views the head really runs on: slot windows of pixel stride 64 R (not the dense slices that `run`
+        # asked about); A(0, 0, 3) as the first pair's output (geometry query)
+        if first and not (ops.conv_pair_supported(place.A(0, 0, 3)) and ops.conv_pair_supported(place.A(0), place.S(0))):
+            st.refuse()
+            return None
+        return place
+
+    def _head(self, place: _LfPlace, xt: FM, refs8: FM) -> list:
+        """The fused head (inference), batch item by batch item: conv01, then conv02 (no activation) + conv1 (LeakyReLU) of the three
+        reference slices in one launch -- nothing else reads conv02's output; slice 3 (prediction1, already in xt) takes conv1 alone;
+        then layer1.conv1 (LeakyReLU) + layer1.spatial_conv3d of the four slices in one launch, their intermediate map stays in LDS.
+        -> the launches' answers under the per-image flags: three per batch item on ring slots, none on dense buffers"""
+        lr = dict(act=ACT_LRELU, slope=0.1)
+        l1, st = self.layer1, place.st
         p01, pc1 = pk_conv(self, "c01", self.conv01), pk_conv(self, "c1", self.conv1)
         pp_a = self._pk("pair_c02_c1", lambda: ops.pack_conv_pair(self.conv02.weight, self.conv02.bias,
                                                                    self.conv1.weight.view(64, 64, 3, 3), self.conv1.bias))
         pp_b = self._pk("pair_b1_bs", lambda: ops.pack_conv_pair(l1.conv1.weight.view(64, 64, 3, 3), l1.conv1.bias,
                                                                   l1.spatial_conv3d.weight.view(64, 64, 3, 3), l1.spatial_conv3d.bias))
         log = []
-        for b in range(B):
+        for b in range(xt.N):
             frames = refs8.batch(4 * b + 1, 3)
-            ops.frames_changed(frames, st.F.batch(b * R + p, 3), st.flags[b, :3], force)
-            with ops.predicate_images(st.flags[b, :3]) as lg:
+            if st is not None:
+                ops.frames_changed(frames, st.F.batch(b * st.ring.slots + place.p, 3), st.flags[b, :3], place.force)
+            with place.flags(b, 3) as lg:
                 t = ops.conv(frames, p01, **lr)           # a skipped image's slice of `t` is never written, and never read
-                ops.conv_pair(t, pp_a, out=win(st.A, b, 0, 3), act1=ACT_NONE, act2=ACT_LRELU, slope2=0.1, add_input=False)
+                ops.conv_pair(t, pp_a, out=place.A(b, 0, 3), act1=ACT_NONE, act2=ACT_LRELU, slope2=0.1, add_input=False)
             log += lg
-            ops.conv(xt.as_slices(b, 4, 64).batch(3, 1), pc1, out=win(st.A, b, 3, 1), **lr)
-            with ops.predicate_images(st.flags[b, :4]) as lg:
-                ops.conv_pair(win(st.A, b, 0, 4), pp_b, out=win(st.S, b, 0, 4), act1=ACT_LRELU, slope1=0.1, act2=ACT_NONE, add_input=False)
+            ops.conv(xt.as_slices(b, 4, 64).batch(3, 1), pc1, out=place.A(b, 3, 1), **lr)
+            with place.flags(b, 4) as lg:
+                ops.conv_pair(place.A(b), pp_b, out=place.S(b), act1=ACT_LRELU, slope1=0.1, act2=ACT_NONE, add_input=False)
             log += lg
-        st.log = list(log)
-        if not all(log):
-            # a kernel outside the per-image set ran in full behind producers that may have skipped: stop caching for this key
-            st.usable = False
-            st.A = st.S = st.F = st.flags = None
-            return None
-        st.usable = True
-        st.ring.commit()
-        # the temporal conv reads slots p .. p + 2 and rewrites all four slices: out of place, the slots keep what the next call reuses
-        o = FM.empty(B, H, W, 256, device=dev)
-        pct, pc3 = pk_conv(self, "bt", l1.temporal_conv3d), pk_conv(self, "b3", l1.conv3)
-        if self._tail_ok(st.S.ch(64 * p, 256), st.A.ch(64 * p, 256), o):
-            ops.lf_tail(st.S.ch(64 * p, 256), st.A.ch(64 * p, 256), pct, pc3, out=o, slope=0.1)
-        else:
-            s = FM.empty(B, H, W, 256, device=dev)
-            ops.conv(st.S.ch(64 * p, 192), pct, out=s.ch(0, 64), bcast_T=4, bcast_slope=0.1, res=st.S.ch(64 * p, 64))
-            for b in range(B):
-                ops.conv(s.as_slices(b, 4, 64), pc3, out=o.as_slices(b, 4, 64), res=win(st.A, b, 0, 4))
-        sums = []
-        f = ops.conv(o, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
-        return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
+        return log
 
-    def _run_plain(self, xt: FM, refs8: FM, out: FM, then: tuple | None = None) -> FM:
-        B, H, W = xt.N, xt.H, xt.W
-        dev = xt.t.device
+    def _head_unfused(self, place: _LfPlace, xt: FM, refs8: FM) -> FM:
+        """The head layer by layer over the whole batch, on dense buffers: under the tape (this is the order training records), on fp32
+        maps, with LOOPFILTER_PAIR off and at shapes conv_pair does not take.  -> `bf`, layer1.conv1's output: the backward pass of
+        spatial_conv3d needs it; in inference it is free again"""
         lr = dict(act=ACT_LRELU, slope=0.1)
         p01, p02 = pk_conv(self, "c01", self.conv01), pk_conv(self, "c02", self.conv02)
-        adt = xt.t.dtype                   # fp32: the whole-model fp32 mode (no fused form takes fp32 maps: the plain sequence)
-        a = FM.empty(B, H, W, 256, dtype=adt, device=dev)
-        fuse = LOOPFILTER_PAIR and ops.conv_pair_supported(a.as_slices(0, 4, 64).batch(0, 3))
-        if fuse:
-            # inference: conv02 (no activation) + conv1 (LeakyReLU) of the three reference slices in one launch -- nothing else
-            # reads conv02's output; slice 3 (prediction1, already in xt) takes conv1 alone
-            pp = self._pk("pair_c02_c1", lambda: ops.pack_conv_pair(self.conv02.weight, self.conv02.bias,
-                                                                     self.conv1.weight.view(64, 64, 3, 3), self.conv1.bias))
-            pc1 = pk_conv(self, "c1", self.conv1)
-        for b in range(B):
+        for b in range(xt.N):
             t = ops.conv(refs8.batch(4 * b + 1, 3), p01, **lr)                 # (3,H,W,64)
-            if fuse:
-                ops.conv_pair(t, pp, out=a.as_slices(b, 4, 64).batch(0, 3), act1=ACT_NONE, act2=ACT_LRELU, slope2=0.1, add_input=False)
-                ops.conv(xt.as_slices(b, 4, 64).batch(3, 1), pc1, out=a.as_slices(b, 4, 64).batch(3, 1), **lr)
-            else:
-                ops.conv(t, p02, out=xt.as_slices(b, 4, 64).batch(0, 3))
-        if not fuse:
-            self._slices("c1", self.conv1, xt, a, **lr)
+            ops.conv(t, p02, out=xt.as_slices(b, 4, 64).batch(0, 3))
+        self._slices("c1", self.conv1, xt, place.A4, **lr)
+        bf = FM.empty(xt.N, xt.H, xt.W, 256, dtype=xt.t.dtype, device=xt.t.device)
+        self._slices("b1", self.layer1.conv1, place.A4, bf, **lr)
+        self._slices("bs", self.layer1.spatial_conv3d, bf, place.S4)
+        return bf
+
+    def _tail(self, place: _LfPlace, bf: FM | None = None) -> FM:
+        """The temporal (3,1,1) conv over slices 0-2, `S + temporal` + LeakyReLU over the four slices (pnet.py:304-314), conv3 and the
+        residual A -> the block's output `o` (B,H,W,256).  `bf`: the unfused head's spare buffer, which inference re-uses for `o`; under
+        the tape the backward pass of spatial_conv3d still needs it"""
         l1 = self.layer1
-        bf = FM.empty(B, H, W, 256, dtype=adt, device=dev)
-        s = FM.empty(B, H, W, 256, dtype=adt, device=dev)
-        if LOOPFILTER_PAIR and ops.conv_pair_supported(a.as_slices(0, 4, 64), s.as_slices(0, 4, 64)):
-            # inference: layer1.conv1 (LeakyReLU) and layer1.spatial_conv3d in one launch per batch item, their intermediate
-            # map stays in LDS (`bf` is then only the block's output buffer below)
-            pp = self._pk("pair_b1_bs", lambda: ops.pack_conv_pair(l1.conv1.weight.view(64, 64, 3, 3), l1.conv1.bias,
-                                                                    l1.spatial_conv3d.weight.view(64, 64, 3, 3), l1.spatial_conv3d.bias))
-            for b in range(B):
-                ops.conv_pair(a.as_slices(b, 4, 64), pp, out=s.as_slices(b, 4, 64), act1=ACT_LRELU, slope1=0.1, act2=ACT_NONE,
-                              add_input=False)
+        A4, S4 = place.A4, place.S4
+        fresh = lambda: FM.empty(A4.N, A4.H, A4.W, 256, dtype=A4.t.dtype, device=A4.t.device)
+        pct, pc3 = pk_conv(self, "bt", l1.temporal_conv3d), pk_conv(self, "b3", l1.conv3)
+        o = bf if bf is not None and ops.TAPE is None else fresh()
+        if (LOOPFILTER_TAIL and LOOPFILTER_BCAST and glue_fusions_allowed(self) and l1.temporal_conv3d.bias is None
+                and ops.lf_tail_supported(S4, A4, o)):
+            # all of it as one launch, the map between the temporal stage and conv3 never reaches memory
+            return ops.lf_tail(S4, A4, pct, pc3, out=o, slope=0.1)
+        if ops.TAPE is None and LOOPFILTER_BCAST and A4.H * A4.W >= 8192 and not S4.f32:      # per IMAGE: conv_v5_eligible (csrc/conv_mfma_v5.hip) counts one map
+            # the temporal stage as ONE pass: a wave computes the 64 temporal channels of its pixels and rewrites their four slices, in
+            # place on dense buffers; ring slots keep what the next call reuses, so from them the pass writes a buffer of its own
+            s = fresh() if place.keep_S else S4
+            ops.conv(S4.ch(0, 192), pct, out=s.ch(0, 64), bcast_T=4, bcast_slope=0.1, res=S4.ch(0, 64) if place.keep_S else None)
         else:
-            self._slices("b1", l1.conv1, a, bf, **lr)
-            self._slices("bs", l1.spatial_conv3d, bf, s)
-        if self._tail_ok(s, a, bf):
-            # inference: the temporal stage below and conv3 + residual as one launch, the map between them never reaches memory
-            ops.lf_tail(s, a, pk_conv(self, "bt", l1.temporal_conv3d), pk_conv(self, "b3", l1.conv3), out=bf, slope=0.1)
-            sums = []
-            f = ops.conv(bf, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
-            return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
-        if ops.TAPE is None and LOOPFILTER_BCAST and H * W >= 8192 and not s.f32:      # per IMAGE: conv_v5_eligible (csrc/conv_mfma_v5.hip) counts one map
-            # inference: temporal (3,1,1) conv over frames 0-2 + `out + temporal` + LeakyReLU (pnet.py:304-314) as ONE pass over
-            # the 4-frame buffer: a wave computes the 64 temporal channels of its pixels and rewrites their four slices in place
-            ops.conv(s.ch(0, 192), pk_conv(self, "bt", l1.temporal_conv3d), out=s.ch(0, 64), bcast_T=4, bcast_slope=0.1)
-        else:
-            tm = ops.conv(s.ch(0, 192), pk_conv(self, "bt", l1.temporal_conv3d))
-            if ops.TAPE is not None:
-                s = ops.clone(s)          # `s` itself is the temporal conv's input: keep it for the backward pass
+            assert not place.keep_S, "the reuse form is entered only where the one-pass temporal stage runs"
+            tm = ops.conv(S4.ch(0, 192), pct)
+            s = ops.clone(S4) if ops.TAPE is not None else S4          # S is the temporal conv's input: kept for the backward pass
             ops.bcast_add_act(s, tm, 4, 0.1)
-        # inference re-uses `bf` for the block output; under the tape `bf` is still needed by the backward of `bs`
-        o = bf if ops.TAPE is None else FM.empty(B, H, W, 256, dtype=adt, device=dev)
-        self._slices("b3", l1.conv3, s, o, res_buf=a)
+        for b in range(A4.N):
+            ops.conv(s.as_slices(b, 4, 64), pc3, out=o.as_slices(b, 4, 64), res=place.A(b))
+        return o
+
+    def _finish(self, o: FM, xt: FM, out: FM, then: tuple | None) -> FM:
         sums = []
-        f = ops.conv(o, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, **lr)
+        f = ops.conv(o, pk_conv(self, "ff", self.feat_fusion), chan_sum=sums, act=ACT_LRELU, slope=0.1)
         return self.attn.run(f, out=out, res=xt.ch(192, 64), sums=sums, then=then)
 
 
@@ -566,16 +613,12 @@ class FeatureExtract(nn.Module, PackCache):
 FEATUREFIX_REUSE = True         # A/B switch: FeatureFix keeps the I-frame's feature maps across the P-frames of a GOP (device-predicated)
 
 
-class IFrameReuse:
-    """FeatureFix's state for one (device, stream, B, H, W, scale): what `FeatureExtract_ref` + `avgpool_k` make of the I-frame, and the
-    frame they were made from.  `usable` is None until the first call has shown whether every launch of the chain carries the predicate
-    (False: the buffers are dropped and the chain runs in full, unpredicated, on every call).  `log`: the last call's per-kernel answers."""
+class IFrameReuse(ReuseState):
+    """FeatureFix's state for one (device, stream, B, H, W, scale): what `FeatureExtract_ref` + `avgpool_k` make of the I-frame (`y`,
+    `pref`), the frame they were made from (`iframe`) and the device flag of the last call (`flag`: 1 = the frame had changed)."""
 
-    __slots__ = ("key", "y", "iframe", "pref", "flag", "usable", "log")
-
-    def __init__(self, key):
-        self.key, self.usable, self.log = key, None, []
-        self.y = self.iframe = self.pref = self.flag = None
+    __slots__ = ("y", "iframe", "pref", "flag")
+    BUFFERS = __slots__
 
 
 class FeatureFix(nn.Module, PackCache):
@@ -640,11 +683,7 @@ class FeatureFix(nn.Module, PackCache):
         cache: `clear_packed()` (load_state_dict, .to()) and `train.refresh_packed` drop it with the weights it was computed from."""
         B, H, W = iframe8.N, iframe8.H, iframe8.W
         dev = iframe8.t.device
-        key = (dev.index, ops._stream().value, B, H, W, scale)
-        cache = self.__dict__.setdefault("_packed", {})
-        st = cache.get("iframe_reuse")
-        if st is None or st.key != key:
-            st = cache["iframe_reuse"] = IFrameReuse(key)
+        st = self._state("iframe_reuse", (dev.index, ops._stream().value, B, H, W, scale), IFrameReuse)
 
         def chain(y, pref):
             fref = self.FeatureExtract_ref.run(iframe8, out=y.ch(64, 64))
@@ -658,24 +697,18 @@ class FeatureFix(nn.Module, PackCache):
             y, pref = fresh()
             chain(y, pref)
             return y, pref
-        if st.usable is None:                             # first call: fill the cache, computing under a flag of 1 to learn who tests it
-            st.y, st.pref = fresh()
-            st.iframe = FM.empty(B, H, W, iframe8.C, device=dev)
-            st.flag = torch.ones(1, dtype=torch.int32, device=dev)
-            ops.copy_cast(iframe8, st.iframe)
-        else:
-            ops.frame_changed(iframe8, st.iframe, st.flag)
-        with ops.predicate(st.flag) as log:
-            chain(st.y, st.pref)
-        st.log = list(log)
-        y, pref = st.y, st.pref
-        if not all(log):
-            # a kernel outside the predicated set ran in full behind producers that may have skipped: compute again without the flag and
-            # stop caching for this key
-            if st.usable is not None:
-                chain(y, pref)
-            st.usable = False
-            st.y = st.iframe = st.pref = st.flag = None
-        else:
-            st.usable = True
+        with self._state_trusted("iframe_reuse"):
+            first = st.usable is None
+            if first:                                     # fill the cache, computing under a flag of 1 to learn who tests it
+                st.y, st.pref = fresh()
+                st.iframe = FM.empty(B, H, W, iframe8.C, device=dev)
+                st.flag = torch.ones(1, dtype=torch.int32, device=dev)
+                ops.copy_cast(iframe8, st.iframe)
+            else:
+                ops.frame_changed(iframe8, st.iframe, st.flag)
+            with ops.predicate(st.flag) as log:
+                chain(st.y, st.pref)
+            y, pref = st.y, st.pref
+            if not st.took(log) and not first:
+                chain(y, pref)                            # producers may have skipped in front of a kernel that ran: again, without the flag
         return y, pref

@@ -185,81 +185,31 @@ class VideoCompressor(nn.Module):
     def _adt(self):
         return torch.float32 if self.model_fp32 else torch.float16
 
-    def _prepare(self, refer_frames, input_image=None):
-        B, _, _, H, W = refer_frames.shape
+    # ---- a call codes a batch of frames, a single frame as a batch of one: the networks run image by image, each coder's context loop
+    # once for all images.  The forward conv dispatch counts pixels over the batch, so a layer can land on another kernel (other last
+    # bits) in a batch than alone; run this way, frame b's strings and reconstruction are those of a call with frame b alone, whatever
+    # the batch size (tools/predict --gop-batch writes the files of --gop-batch 1), and the loops -- launch-latency bound, the part a
+    # batch speeds up -- are shared
+    def _front(self, refer_frames, b, input_image=None):
+        """image b in front of the motion coder, on N = 1 maps: the reference features and, with the frame given (the encoder), the
+        frame's features and the motion features `estmv`"""
+        _, _, _, H, W = refer_frames.shape
         if H % 64 or W % 64:
             raise RuntimeError(f"frames must be padded to a multiple of 64 (got {H}x{W})")
-        dev = refer_frames.device
-        adt = self._adt()
-        refs8 = ops.from_nchw(refer_frames.float().reshape(B * 4, 3, H, W), Cpad=8, dtype=adt)
-        last = refer_frames[:, 3].float()
-        ref8, iframe8 = _ref_views(refs8, B)
-        feats = FM.empty(B, H, W, 192, dtype=adt, device=dev)
+        dev, adt = refer_frames.device, self._adt()
+        refs8 = ops.from_nchw(refer_frames[b:b + 1].float().reshape(4, 3, H, W), Cpad=8, dtype=adt)
+        ref8, iframe8 = _ref_views(refs8, 1)
+        feats = FM.empty(1, H, W, 192, dtype=adt, device=dev)
         self.extra_fea.run(ref8, feats.ch(64, 64))
-        return B, H, W, dev, refs8, last, iframe8, feats
-
-    def _reconstruct(self, mv_y_hat: FM, res_y_hat_fn, feats: FM, refs8: FM, iframe8: FM):
-        """decoder-side reconstruction from the decoded motion latents; `res_y_hat_fn(pred)` supplies the residual latents
-        (the encoder codes them against this very prediction, the decoder reads them from the stream)"""
-        B, H, W, dev = feats.N, feats.H, feats.W, feats.t.device
-        adt = feats.t.dtype
-        mv_hat = self.mvCoder.run_g_s(mv_y_hat, out_dtype=adt)
-        xt = FM.empty(B, H, W, 256, dtype=adt, device=dev)
-        self.mcnet.run(mv_hat, feats, xt.ch(192, 64))
-        pred = FM.empty(B, H, W, 64, dtype=adt, device=dev)
-        self.mcfilter.run(xt, refs8, pred)
-        recon_f = self.resCoder.run_g_s(res_y_hat_fn(pred), res=pred, out_dtype=adt)
-        return self.loopfilter.run(recon_f, iframe8, training=False)
-
-    @torch.no_grad()
-    def encode(self, input_image, refer_frames):
-        """-> {"strings": [mv_y, mv_z, res_y, res_z] (lists over the batch), "shapes": z shapes, "recon": (B,3,H,W)}.
-        The reconstruction is the DECODER's: it is built from the coded symbols, so a closed-loop encoder and the decoder
-        stay bit-identical."""
-        self._model_fp32_checked()
-        assert not self.training
-        if self.stream_coder not in STREAM_CODERS:
-            raise ValueError(f"stream_coder must be one of {STREAM_CODERS}, got {self.stream_coder!r}")
-        if self.stream_coder == "device" and self.stream_order != "lanes":
-            raise ValueError(f"stream_coder=\"device\" needs stream_order=\"lanes\", got {self.stream_order!r}")
-        if refer_frames.shape[0] > 1:
-            return self._encode_batch(input_image, refer_frames)
-        B, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames)
-        x = input_image.float()
-        adt = self._adt()
-        f_cur = self.extra_fea.run(ops.from_nchw(x, Cpad=8, dtype=adt), feats.ch(0, 64))
-        estmv = self.motion_est.run(feats, ops.from_nchw(x, Cpad=4, dtype=torch.float32), ops.from_nchw(last, Cpad=4, dtype=torch.float32))
-        self.mvCoder.update()
-        self.resCoder.update()
-        f32 = self.coder_fp32 or self.model_fp32
-        mv = self.mvCoder.compress(estmv, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes,
-                                    coder=self.stream_coder)                  # range coding on worker threads, or on a side stream
-        cat = lambda dbg: FM(torch.cat([d["y_hat"].t for d in dbg], 0))
-        out = {}
-
-        def res_y_hat(pred):
-            resid = ops.scale_act_res(f_cur, FM.empty(B, H, W, 64, dtype=adt, device=dev), res=pred, res_sign=-1.0)
-            out["res"] = self.resCoder.compress(resid, f32=f32, order=self.stream_order, defer=True, lanes=self.stream_lanes, coder=self.stream_coder)
-            return cat(out["res"]["_debug"])
-        recon = self._reconstruct(cat(mv["_debug"]), res_y_hat, feats, refs8, iframe8)
-        rs = out["res"]
-        mvs, rss = mv["strings"].result(), rs["strings"].result()                     # join the range coders
-        return {"strings": [mvs[0], mvs[1], rss[0], rss[1]], "shapes": [mv["shape"], rs["shape"]], "recon": recon}
-
-    # ---- a batch of frames: the networks run image by image, each coder's context loop once for all images.  The forward conv
-    # dispatch counts pixels over the batch, so a layer can land on another kernel (other last bits) in a batch than alone; run this
-    # way, frame b's strings and reconstruction are those of a call with frame b alone, whatever the batch size (tools/predict
-    # --gop-batch writes the files of --gop-batch 1), and the loops -- launch-latency bound, the part a batch speeds up -- are shared
-    def _front(self, refer_frames, b, input_image=None):
-        _, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames[b:b + 1])
         im = dict(H=H, W=W, dev=dev, refs8=refs8, iframe8=iframe8, feats=feats)
         if input_image is not None:
-            x = input_image[b:b + 1].float()
-            im["f_cur"] = self.extra_fea.run(ops.from_nchw(x, Cpad=8, dtype=self._adt()), feats.ch(0, 64))
+            x, last = input_image[b:b + 1].float(), refer_frames[b:b + 1, 3].float()
+            im["f_cur"] = self.extra_fea.run(ops.from_nchw(x, Cpad=8, dtype=adt), feats.ch(0, 64))
             im["estmv"] = self.motion_est.run(feats, ops.from_nchw(x, Cpad=4, dtype=torch.float32), ops.from_nchw(last, Cpad=4, dtype=torch.float32))
         return im
 
     def _predict(self, im, mv_y_hat: FM) -> FM:
+        """decoder-side prediction from the decoded motion latents"""
         adt = im["feats"].t.dtype
         mv_hat = self.mvCoder.run_g_s(mv_y_hat, out_dtype=adt)
         xt = FM.empty(1, im["H"], im["W"], 256, dtype=adt, device=im["dev"])
@@ -273,47 +223,49 @@ class VideoCompressor(nn.Module):
 
     @staticmethod
     def _dense(fms) -> FM:
-        """images given as FMs of N = 1 -> one dense batch FM"""
+        """images given as FMs of N = 1 -> one dense batch FM (a single image that is dense already: itself, not a copy)"""
+        f = fms[0]
+        if len(fms) == 1 and f.off == 0 and f.C == f.t.shape[3] and f.N == f.t.shape[0] and f.t.is_contiguous():
+            return f
         return FM(torch.cat([f.t[..., f.off:f.off + f.C] if (f.off or f.C != f.t.shape[3]) else f.t for f in fms], 0).contiguous())
 
-    def _encode_batch(self, input_image, refer_frames):
-        B = refer_frames.shape[0]
-        ims = [self._front(refer_frames, b, input_image) for b in range(B)]
+    @torch.no_grad()
+    def encode(self, input_image, refer_frames):
+        """-> {"strings": [mv_y, mv_z, res_y, res_z] (lists over the batch), "shapes": z shapes, "recon": (B,3,H,W)}.
+        The reconstruction is the DECODER's: it is built from the coded symbols (the residual is coded against the prediction the
+        decoder will make), so a closed-loop encoder and the decoder stay bit-identical."""
+        self._model_fp32_checked()
+        assert not self.training
+        if self.stream_coder not in STREAM_CODERS:
+            raise ValueError(f"stream_coder must be one of {STREAM_CODERS}, got {self.stream_coder!r}")
+        if self.stream_coder == "device" and self.stream_order != "lanes":
+            raise ValueError(f"stream_coder=\"device\" needs stream_order=\"lanes\", got {self.stream_order!r}")
+        ims = [self._front(refer_frames, b, input_image) for b in range(refer_frames.shape[0])]
         self.mvCoder.update()
         self.resCoder.update()
+        # defer: range coding on worker threads, or on a side stream
         kw = dict(f32=self.coder_fp32 or self.model_fp32, order=self.stream_order, defer=True, lanes=self.stream_lanes, per_image=True, coder=self.stream_coder)
         mv = self.mvCoder.compress(self._dense([im["estmv"] for im in ims]), **kw)
         preds = [self._predict(im, d["y_hat"]) for im, d in zip(ims, mv["_debug"])]
         resid = [ops.scale_act_res(im["f_cur"], FM.empty(1, im["H"], im["W"], 64, dtype=p.t.dtype, device=im["dev"]), res=p, res_sign=-1.0) for im, p in zip(ims, preds)]
         rs = self.resCoder.compress(self._dense(resid), **kw)
-        recon = torch.cat([self._finish(im, d["y_hat"], p) for im, d, p in zip(ims, rs["_debug"], preds)], 0)
+        recon = [self._finish(im, d["y_hat"], p) for im, d, p in zip(ims, rs["_debug"], preds)]
         mvs, rss = mv["strings"].result(), rs["strings"].result()                     # join the range coders
-        return {"strings": [mvs[0], mvs[1], rss[0], rss[1]], "shapes": [mv["shape"], rs["shape"]], "recon": recon}
-
-    def _decode_batch(self, strings, shapes, refer_frames):
-        B = refer_frames.shape[0]
-        ims = [self._front(refer_frames, b) for b in range(B)]
-        self.mvCoder.update()
-        self.resCoder.update()
-        kw = dict(synth=False, f32=self.coder_fp32 or self.model_fp32, order=self.stream_order, per_image=True)
-        mv = self.mvCoder.decompress([strings[0], strings[1]], shapes[0], **kw)["y_hat"]
-        image = self.mvCoder._image
-        preds = [self._predict(im, image(mv, b)) for b, im in enumerate(ims)]
-        res = self.resCoder.decompress([strings[2], strings[3]], shapes[1], **kw)["y_hat"]
-        return torch.cat([self._finish(im, image(res, b), preds[b]) for b, im in enumerate(ims)], 0)
+        return {"strings": [mvs[0], mvs[1], rss[0], rss[1]], "shapes": [mv["shape"], rs["shape"]], "recon": recon[0] if len(recon) == 1 else torch.cat(recon, 0)}
 
     @torch.no_grad()
     def decode(self, strings, shapes, refer_frames):
         """inverse of encode(): strings [mv_y, mv_z, res_y, res_z] + z shapes + the reference list -> (B,3,H,W)"""
         self._model_fp32_checked()
         assert not self.training
-        if refer_frames.shape[0] > 1:
-            return self._decode_batch(strings, shapes, refer_frames)
-        B, H, W, dev, refs8, last, iframe8, feats = self._prepare(refer_frames)
+        ims = [self._front(refer_frames, b) for b in range(refer_frames.shape[0])]
         self.mvCoder.update()
         self.resCoder.update()
-        f32 = self.coder_fp32 or self.model_fp32
-        so = self.stream_order
-        mv = self.mvCoder.decompress([strings[0], strings[1]], shapes[0], f32=f32, order=so)
-        return self._reconstruct(mv["y_hat"], lambda pred: self.resCoder.decompress([strings[2], strings[3]], shapes[1], synth=False, f32=f32, order=so)["y_hat"],
-                                 feats, refs8, iframe8)
+        # synth=False: the coders hand out the latents only, `_predict` and `_finish` run the synthesis
+        kw = dict(synth=False, f32=self.coder_fp32 or self.model_fp32, order=self.stream_order, per_image=True)
+        mv = self.mvCoder.decompress([strings[0], strings[1]], shapes[0], **kw)["y_hat"]
+        image = self.mvCoder._image
+        preds = [self._predict(im, image(mv, b)) for b, im in enumerate(ims)]
+        res = self.resCoder.decompress([strings[2], strings[3]], shapes[1], **kw)["y_hat"]
+        recon = [self._finish(im, image(res, b), preds[b]) for b, im in enumerate(ims)]
+        return recon[0] if len(recon) == 1 else torch.cat(recon, 0)

@@ -417,3 +417,79 @@ def test_tape_lazy_identity_gradients(monkeypatch):
         autograd.LAZY_IDENTITY = prev
     tape.release()
     assert not tape.pending and not tape.touched
+
+
+def test_reuse_state_rule():
+    """the one state rule of FeatureFix and LoopFilter (modules.ReuseState, PackCache._state)"""
+    from tdvc_amd.model.modules import IFrameReuse, LoopFilterReuse, PackCache, ReuseState
+    owner = PackCache()
+    made = []
+
+    def make(key):
+        made.append(key)
+        return LoopFilterReuse(key, 9)
+    st = owner._state("lf", ("k", 1), make)
+    assert isinstance(st, ReuseState) and st.key == ("k", 1) and st.usable is None and st.log == [] and st.ring.slots == 9
+    assert owner._state("lf", ("k", 1), make) is st and made == [("k", 1)], "the same key returns the cached state"
+    other = owner._state("lf", ("k", 2), make)
+    assert other is not st and other.key == ("k", 2) and owner._state("lf", ("k", 2), make) is other, "a new key replaces the state"
+    assert owner._state("if", ("k", 2), IFrameReuse).key == ("k", 2) and owner._state("lf", ("k", 2), make) is other, "states are kept by name"
+    assert made == [("k", 1), ("k", 2)]
+    for cls, args in ((LoopFilterReuse, (("k",), 5)), (IFrameReuse, (("k",),))):
+        slots = [n for n in cls.__slots__ if n != "ring"]
+        assert sorted(slots) == sorted(cls.BUFFERS) and sorted(ReuseState.__slots__) == ["key", "log", "usable"]
+        st = cls(*args)
+        assert all(getattr(st, n) is None for n in slots)
+        for n in slots:
+            setattr(st, n, object())
+        assert st.took([True, True, True]) is True and st.usable is True and st.log == [True] * 3
+        assert all(getattr(st, n) is not None for n in slots), "an all-true log keeps the buffers"
+        st.drop()
+        assert all(getattr(st, n) is None for n in slots) and st.usable is True, "drop() clears every buffer slot, nothing else"
+        for n in slots:
+            setattr(st, n, object())
+        assert st.took([True, False, True]) is False and st.usable is False and st.log == [True, False, True]
+        assert all(getattr(st, n) is None for n in slots), "a log with a False drops the buffers"
+        assert st.usable is False and st.key == ("k",)
+    # a failed call drops the state by name, and the exception goes on
+    owner._state("lf", ("k", 3), make)
+    with pytest.raises(KeyError):
+        with owner._state_trusted("lf"):
+            raise KeyError("boom")
+    assert "lf" not in owner._packed and "if" in owner._packed
+    with owner._state_trusted("if"):
+        pass
+    assert "if" in owner._packed
+
+
+def test_loopfilter_placement_views():
+    """modules._LfPlace: the dense form is as_slices(b, 4, 64).batch(j0, n), the ring form the slot window at p"""
+    from tdvc_amd.model.modules import LoopFilterReuse, _LfPlace
+    B, H, W, R = 2, 4, 6, 9
+    geo = lambda f: (f.t.data_ptr(), f.off, f.N, f.C, f.H, f.W, f.sn, f.sp)
+    a, s = ops.FM(torch.zeros(B, H, W, 256, dtype=torch.float16)), ops.FM(torch.zeros(B, H, W, 256, dtype=torch.float16))
+    dense = _LfPlace(a, s)
+    assert not dense.keep_S and dense.A4 is a and dense.S4 is s
+    with dense.flags(1, 3) as log:
+        assert log == []
+    st = LoopFilterReuse(("k",), R)
+    st.A, st.S = ops.FM(torch.zeros(B, H, W, 64 * R, dtype=torch.float16)), ops.FM(torch.zeros(B, H, W, 64 * R, dtype=torch.float16))
+    for b in range(B):
+        for j0, n in ((0, 3), (3, 1), (0, 4), (1, 2)):
+            assert geo(dense.A(b, j0, n)) == geo(a.as_slices(b, 4, 64).batch(j0, n))
+            assert geo(dense.S(b, j0, n)) == geo(s.as_slices(b, 4, 64).batch(j0, n))
+        assert geo(dense.A(b)) == geo(a.as_slices(b, 4, 64)) and dense.A(b).desc().p == a.t.data_ptr() + 2 * b * H * W * 256
+    for p in (0, 5):
+        ring = _LfPlace(st.A, st.S, st, p, 0b101)
+        assert ring.keep_S and ring.force == 0b101
+        for name, buf, view, view4 in (("A", st.A, ring.A, ring.A4), ("S", st.S, ring.S, ring.S4)):
+            for b in range(B):
+                for j0, n in ((0, 3), (3, 1), (0, 4), (1, 2)):
+                    want = ops.FM(buf.t, buf.off + b * buf.sn + 64 * (p + j0), n, 64, 64)      # the slot window, spelled out
+                    got = view(b, j0, n)
+                    assert geo(got) == geo(want), (name, p, b, j0, n)
+                    assert (got.off, got.N, got.C, got.sn, got.sp) == (b * H * W * 64 * R + 64 * (p + j0), n, 64, 64, 64 * R)
+                assert geo(view(b)) == geo(view(b, 0, 4))
+            assert geo(view4) == geo(buf.ch(64 * p, 256)) and (view4.off, view4.N, view4.C, view4.sn, view4.sp) == (64 * p, B, 256, H * W * 64 * R, 64 * R)
+            # slice j of the 256-channel view is image j of the window
+            assert all(view4.as_slices(b, 4, 64).batch(j, 1).desc().p == view(b, j, 1).desc().p for b in range(B) for j in range(4))
