@@ -3,8 +3,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib as L
-from .ops import _stream
+from .ops import launch
 
 
 def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group):
@@ -25,11 +24,8 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, 
     gw, gb = torch.empty_like(weight), torch.empty_like(bias)
     cols = torch.empty(C * kh * kw * Ho * Wo, dtype=torch.float32, device=input.device)
     with torch.cuda.device(input.device):
-        L.check(L.lib().tdvc_dcn_v2_backward_f32(
-            input.data_ptr(), weight.data_ptr(), bias.data_ptr(), offset.data_ptr(), mask.data_ptr(),
-            grad_output.data_ptr(), gi.data_ptr(), go.data_ptr(), gm.data_ptr(), gw.data_ptr(), gb.data_ptr(),
-            cols.data_ptr(), B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, _stream()),
-            "dcn_v2_backward")
+        launch("tdvc_dcn_v2_backward_f32", input, weight, bias, offset, mask, grad_output, gi, go, gm, gw, gb, cols,
+               B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, what="dcn_v2_backward")
     return [gi, go, gm, gw, gb]
 
 

@@ -16,6 +16,7 @@ import math
 import torch
 
 from . import _lib as L
+from .ops import launch
 
 _WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
@@ -40,23 +41,17 @@ def _check(X, Y, win_size):
         raise RuntimeError("tdvc_amd.metrics runs on the GPU only (no CPU fallback)")
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _level(X, Y, taps, data_range):
     """-> (ssim, cs) per image, already through the reference's (v + 1) / 2 (ms_ssim_torch.py:79-81)"""
-    lib = L.lib()
     N, Cc, H, W = X.shape
-    n = lib.tdvc_ssim_level_work_floats(N, Cc, H, W, len(taps))
+    n = L.lib().tdvc_ssim_level_work_floats(N, Cc, H, W, len(taps))
     if n <= 0:
         raise ValueError(f"ms_ssim: image {H}x{W} smaller than the {len(taps)}-tap window (or window > 15 taps)")
     work = torch.empty(n, dtype=torch.float32, device=X.device)
     out = torch.empty(2, N, dtype=torch.float32, device=X.device)
     win = (C.c_float * len(taps))(*taps)
     c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
-    L.check(lib.tdvc_ssim_level(X.data_ptr(), Y.data_ptr(), N, Cc, H, W, win, len(taps), c1, c2, out[0].data_ptr(), out[1].data_ptr(),
-                                work.data_ptr(), n, _stream()), "ssim_level")
+    launch("tdvc_ssim_level", X, Y, N, Cc, H, W, win, len(taps), c1, c2, out[0], out[1], work, n)
     return (out[0] + 1) / 2, (out[1] + 1) / 2
 
 
@@ -64,7 +59,7 @@ def _pool(X):
     N, Cc, H, W = X.shape
     Ho, Wo = (H + 2 * (H % 2) - 2) // 2 + 1, (W + 2 * (W % 2) - 2) // 2 + 1
     out = torch.empty(N, Cc, Ho, Wo, dtype=torch.float32, device=X.device)
-    L.check(L.lib().tdvc_avgpool2_pad_f32(X.data_ptr(), N * Cc, H, W, out.data_ptr(), _stream()), "avgpool2_pad_f32")
+    launch("tdvc_avgpool2_pad_f32", X, N * Cc, H, W, out)
     return out
 
 
@@ -99,9 +94,7 @@ def _level_backward(X, Y, taps, data_range, g_ssim, g_cs, g_pool=None, scale=1.0
     dx = torch.empty_like(X)
     win = (C.c_float * len(taps))(*taps)
     c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
-    L.check(L.lib().tdvc_ssim_level_backward(X.data_ptr(), Y.data_ptr(), N, Cc, H, W, win, len(taps), c1, c2, g_ssim.data_ptr(), g_cs.data_ptr(),
-                                             float(scale), None if g_pool is None else g_pool.data_ptr(), dx.data_ptr(), _stream()),
-            "ssim_level_backward")
+    launch("tdvc_ssim_level_backward", X, Y, N, Cc, H, W, win, len(taps), c1, c2, g_ssim, g_cs, float(scale), g_pool, dx)
     return dx
 
 
@@ -179,8 +172,7 @@ def _pyramid_backward(xs, ys, taps, data_range, mcs, s, weights, grad_out, wrt_x
     out = torch.empty(2 * levels + 1, N, dtype=torch.float32, device=mcs.device)
     g_ssim, g_cs = out[:levels], out[levels:2 * levels]
     w = (C.c_float * levels)(*weights)
-    L.check(L.lib().tdvc_msssim_level_grads(mcs.data_ptr(), s.data_ptr(), w, levels, N, None if grad_out is None else grad_out.data_ptr(),
-                                            out[2 * levels].data_ptr(), g_ssim.data_ptr(), g_cs.data_ptr(), _stream()), "msssim_level_grads")
+    launch("tdvc_msssim_level_grads", mcs, s, w, levels, N, grad_out, out[2 * levels], g_ssim, g_cs)
     dX = dY = None
     for lv in reversed(range(levels)):
         if wrt_x:

@@ -7,7 +7,7 @@ Every function enqueues on torch's current HIP stream and returns immediately.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 import torch
@@ -42,59 +42,71 @@ TAPE = None
 _IN_BACKWARD = False      # set by Tape.backward(): ops called from backward closures are not recorded
 
 
+def _profiled(kernel, shape: str, flops: float, run, flops_real: float | None = None, bytes: float = 0.0, **more):
+    """`run()`; under PROFILE between two events, as one row of the per-kernel table.  `kernel`: the row's name, or a callable that
+    gives it behind the launch; `flops_real`: the algorithmic count where padding makes it differ from `flops`; `more`: further columns"""
+    if PROFILE is None:
+        return run()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    r = run()
+    e1.record()
+    PROFILE.append(dict(kernel=kernel() if callable(kernel) else kernel, shape=shape, e0=e0, e1=e1, flops=flops,
+                        flops_real=flops if flops_real is None else flops_real, bytes=bytes, **more))
+    return r
+
+
 # ----------------------------------------------------------------------------- launch predicate
 _PRED_LOG = None          # inside `with predicate(flag)`: one tdvc_last_launch_predicated() answer per kernel conv / conv_pair / avgpool_k launched
 
 
-class predicate:
+class _predicate_block:
+    """enter / exit of the two predicate forms: `_SET` is the library's setter, `_on()` its arguments inside the block, `_OFF` behind it"""
+
+    def __enter__(self):
+        global _PRED_LOG
+        if _PRED_LOG is not None:
+            raise L.TdvcHipError(f"ops.{type(self).__name__} does not nest")
+        launch(self._SET, *self._on(), host=True)
+        _PRED_LOG = []
+        return _PRED_LOG
+
+    def __exit__(self, *exc):
+        global _PRED_LOG
+        _PRED_LOG = None
+        getattr(L.lib(), self._SET)(*self._OFF)
+        return False
+
+
+class predicate(_predicate_block):
     """`with ops.predicate(flag) as log:` -- the launches inside carry the device flag (int32 tensor of one element, written on
     this stream by `frame_changed`) wherever their kernel tests it (tdvc_set_predicate): conv_c8, conv_pair, conv_row and both
     kernels of avgpool_k return at once, outputs untouched, when the flag is 0; any other kernel runs in full.  `log` collects,
     per kernel launched by conv / conv_pair / avgpool_k, whether it carried the flag: a chain may only rely on the skipping
     when every entry is true (a skipped producer in front of a consumer that ran would feed it stale memory)."""
+    _SET, _OFF = "tdvc_set_predicate", (None,)
 
     def __init__(self, flag: torch.Tensor):
         assert flag.dtype == torch.int32 and flag.is_cuda and flag.numel() >= 1
         self.flag = flag
 
-    def __enter__(self):
-        global _PRED_LOG
-        if _PRED_LOG is not None:
-            raise L.TdvcHipError("ops.predicate does not nest")
-        L.check(L.lib().tdvc_set_predicate(self.flag.data_ptr()), "set_predicate")
-        _PRED_LOG = []
-        return _PRED_LOG
-
-    def __exit__(self, *exc):
-        global _PRED_LOG
-        _PRED_LOG = None
-        L.lib().tdvc_set_predicate(None)
-        return False
+    def _on(self):
+        return (self.flag,)
 
 
-class predicate_images:
+class predicate_images(_predicate_block):
     """`with ops.predicate_images(flags) as log:` -- the per-image form (tdvc_set_predicate_images): `flags` is a contiguous int32 device
     tensor of n <= 4 elements (written on this stream by `frames_changed`); a conv_c8 or conv_pair launch over exactly n images computes
     image i only when flags[i] != 0 and leaves the others' outputs as they were, its workgroups sharing the active images' work.  Any
     other launch runs in full.  `log` as for `predicate`; the two forms do not nest, in themselves or in each other."""
+    _SET, _OFF = "tdvc_set_predicate_images", (None, 0)
 
     def __init__(self, flags: torch.Tensor):
         assert flags.dtype == torch.int32 and flags.is_cuda and flags.dim() == 1 and flags.is_contiguous() and 1 <= flags.numel() <= 4
         self.flags = flags
 
-    def __enter__(self):
-        global _PRED_LOG
-        if _PRED_LOG is not None:
-            raise L.TdvcHipError("ops.predicate_images does not nest")
-        L.check(L.lib().tdvc_set_predicate_images(self.flags.data_ptr(), self.flags.numel()), "set_predicate_images")
-        _PRED_LOG = []
-        return _PRED_LOG
-
-    def __exit__(self, *exc):
-        global _PRED_LOG
-        _PRED_LOG = None
-        L.lib().tdvc_set_predicate_images(None, 0)
-        return False
+    def _on(self):
+        return (self.flags, self.flags.numel())
 
 
 def _log_predicated(kernels=1):
@@ -104,16 +116,14 @@ def _log_predicated(kernels=1):
 
 def frame_changed(cur: FM, cache: FM, flag: torch.Tensor) -> None:
     """flag[0] = (cur != cache) as exact 16-byte words, and cache = cur when they differ; all on the stream, no host wait"""
-    dc, dk = cur.desc(), cache.desc()
-    L.check(L.lib().tdvc_frame_changed(C.byref(dc), C.byref(dk), flag.data_ptr(), _stream()), "frame_changed")
+    launch("tdvc_frame_changed", cur, cache, flag)
 
 
 def frames_changed(cur: FM, cache: FM, flags: torch.Tensor, force_mask: int = 0) -> None:
     """per image n of at most four: flags[n] = bit n of force_mask | (cur[n] != cache[n]) as exact 16-byte words, and cache[n] = cur[n]
     where the flag is set; all on the stream, no host wait"""
     assert flags.dtype == torch.int32 and flags.is_cuda and flags.is_contiguous() and flags.numel() >= cur.N
-    dc, dk = cur.desc(), cache.desc()
-    L.check(L.lib().tdvc_frames_changed(C.byref(dc), C.byref(dk), flags.data_ptr(), int(force_mask) & 0xF, _stream()), "frames_changed")
+    launch("tdvc_frames_changed", cur, cache, flags, int(force_mask) & 0xF)
 
 
 def _rec(name, *args):
@@ -186,12 +196,51 @@ class FM:
     def to_nchw(self, C_=None) -> torch.Tensor:
         C_ = self.C if C_ is None else C_
         out = torch.empty((self.N, C_, self.H, self.W), dtype=torch.float32, device=self.t.device)
-        d = self.desc()
-        L.check(L.lib().tdvc_fmap_to_nchw(C.byref(d), C_, out.data_ptr(), _stream()), "fmap_to_nchw")
+        launch("tdvc_fmap_to_nchw", self, C_, out)
         return out
 
 
 _NULL_FM = L.FMapDesc(None, 0, 0, 0, 0, 0, 0, 0)
+
+
+# ----------------------------------------------------------------------------- the launch rule
+class _Marshal(dict):
+    """argument type -> how a wrapper's argument of that type becomes the C argument, resolved once per type: a map is its cached
+    descriptor and a tensor its address; anything else (None, descriptor structures, ctypes arrays, raw addresses) passes as it is.
+    `_lib.SIGNATURES` declares every argument, so ctypes itself passes a structure by reference, None as NULL, an int as a pointer"""
+    __slots__ = ()
+
+    def __missing__(self, t):
+        rule = self[t] = FM.desc if issubclass(t, FM) else torch.Tensor.data_ptr if issubclass(t, torch.Tensor) else None
+        return rule
+
+
+_marshal = _Marshal()
+_LAUNCHERS = {}           # entry point -> its launcher
+
+
+def _launcher(name: str, host: bool):
+    """the launcher of one entry point, written once from its declared argument types: an argument declared as a pointer goes through
+    `_marshal`, a scalar passes untouched, and the launch stream (`_stream()`'s choice, as a raw handle) follows unless the entry point
+    is a host one.  One expression per entry point instead of a loop over the arguments per call: the training step is bound by host time"""
+    types = L.SIGNATURES[name][1]
+    names = [f"a{i}" for i in range(len(types) - (not host))]
+    call = [f"({a} if (f := _marshal[{a}.__class__]) is None else f({a}))" if (t is C.c_void_p or issubclass(t, C._Pointer)) else a
+            for a, t in zip(names, types)]
+    if not host:
+        call.append("FORCE_STREAM if FORCE_STREAM is not None else _raw_stream(_cur_dev())")
+    fn = _LAUNCHERS[name] = eval(f"lambda {', '.join(names)}: L.lib().{name}({', '.join(call)})", globals())
+    return fn
+
+
+def launch(name: str, *args, what: str | None = None, check: bool = True, host: bool = False) -> int:
+    """call the library's entry point `name` with the wrapper's arguments, marshalled as `_launcher` says, and check its return code;
+    `what` names the call in the error message (default: `name` without its prefix).  `host=True`: an entry point without a stream
+    argument.  `check=False`: -> the return code, for the caller to read"""
+    rc = (_LAUNCHERS.get(name) or _launcher(name, host))(*args)
+    if rc and check:
+        L.check(rc, what or name[5:])
+    return rc
 
 
 def from_nchw(x: torch.Tensor, Cpad: int | None = None, dtype=torch.float16, out: FM | None = None) -> FM:
@@ -201,13 +250,23 @@ def from_nchw(x: torch.Tensor, Cpad: int | None = None, dtype=torch.float16, out
     N, Cc, H, W = x.shape
     if out is None:
         out = FM.empty(N, H, W, pad8(Cc) if Cpad is None else Cpad, dtype=dtype, device=x.device)
-    d = out.desc()
-    L.check(L.lib().tdvc_nchw_to_fmap(x.data_ptr(), Cc, C.byref(d), _stream()), "nchw_to_fmap")
+    launch("tdvc_nchw_to_fmap", x, Cc, out)
     return out
 
 
 # ----------------------------------------------------------------------------- conv
 FORMS_CREATED = 0            # PackedConv objects built so far (train.refresh_packed: has a form appeared since the PackBatch was built?)
+
+
+class _Keyed(dict):
+    """slot -> (key, value): what was built for a slot is kept with the key it was built for and built again under another key"""
+    __slots__ = ()
+
+    def of(self, slot, key, build, *args):
+        e = self.get(slot)
+        if e is None or e[0] != key:
+            e = self[slot] = (key, build(*args))
+        return e[1]
 
 
 @dataclass
@@ -238,10 +297,26 @@ class PackedConv:
     owner: object | None = None            # module that maps this layer's weight gradient to its own parameters (GDN)
     w32: torch.Tensor | None = None        # fp32 twin of `w` for the fp32 islands (conv_f32.hip), packed on first use
     w32_buf: torch.Tensor | None = None    # the buffer of a twin that a re-pack of `w` made stale: the next packed_f32() fills it again
+    column: "PackedConv | None" = None     # lazily built: the DCN weight as a 1x1 conv over sampled columns (ops.dcn_column_conv)
+    plain: "PackedConv | None" = None      # lazily built: the plain stride-2 3x3 packing of a space-to-depth layer (ops._plain_form)
+    # --- what is derived from the layer without being a packed form: nothing to re-pack
+    bias_index: torch.Tensor | None = field(default=None, init=False, repr=False, compare=False)    # sub-pixel row order (ops._bias_index)
+    tmpl: _Keyed = field(default_factory=_Keyed, init=False, repr=False, compare=False)    # weight dtype -> descriptor template
+    wgrad: _Keyed = field(default_factory=_Keyed, init=False, repr=False, compare=False)   # weight-gradient tables and workspace size
 
     def __post_init__(self):
         global FORMS_CREATED
         FORMS_CREATED += 1                 # a layer or a derived form (dgrad, plain, column) is new: PackBatch tables are incomplete
+
+    def forms(self, seen: set | None = None):
+        """the packed forms derived from this layer (data gradient, column, plain) and from those, each once; `seen`: ids of forms
+        met earlier in a walk over several layers.  The one list of what a re-pack has to follow"""
+        seen = set() if seen is None else seen
+        for f in (self.dgrad, self.column, self.plain):
+            if f is not None and id(f) not in seen:
+                seen.add(id(f))
+                yield f
+                yield from f.forms(seen)
 
     def packed_f32(self) -> torch.Tensor:
         """the same fragment order as `w`, as floats (tdvc_pack_conv_weights_indexed_f32).  Packed on first use and again on the first
@@ -257,18 +332,13 @@ class PackedConv:
             self.w32_buf, self.w32 = self.w32, None
 
     def repack(self):
-        """re-pack from the (updated) fp32 parameters: one kernel launch, plus the bias gather"""
-        _pack_from_tables(self.wsrc, self.tables, self.w)
-        self.stale_f32()
-        if self.bsrc is not None:
-            b = self.bsrc.detach().float()
-            self.bias[:self.cout] = b[torch.from_numpy(convpack.shuffle_perm(self.cout)).to(b.device)] if self.shuffle else b
-        if self.dgrad is not None:
-            self.dgrad.repack()
-        for key in ("_colpc", "_plain"):           # the DCN weight as a 1x1 conv over sampled columns; the plain stride-2 form
-            aux = self.__dict__.get(key)
-            if aux is not None:
-                aux.repack()
+        """re-pack from the (updated) fp32 parameters, the derived forms too: per form one kernel launch, plus the bias gather"""
+        for pc in (self, *self.forms()):
+            _pack_from_tables(pc.wsrc, pc.tables, pc.w)
+            pc.stale_f32()
+            if pc.bsrc is not None:
+                b = pc.bsrc.detach().float()
+                pc.bias[:pc.cout] = b[torch.from_numpy(convpack.shuffle_perm(pc.cout)).to(b.device)] if pc.shuffle else b
 
 
 def _cout_pad(cout):
@@ -294,33 +364,30 @@ def _s2d_weights(w: torch.Tensor) -> torch.Tensor:
     return w2
 
 
-def _pack_from_tables(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None = None) -> torch.Tensor:
-    lib = L.lib()
-    nbytes = lib.tdvc_conv_packed_bytes(tb.cout, tb.cin, len(tb.taps), tb.ck)
+def _pack(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None, f32: bool) -> torch.Tensor:
+    """the weight in the tables' fragment order, as halves in a byte blob or (`f32`) as floats; into `dst` when one is given"""
+    nbytes = L.lib().tdvc_conv_packed_bytes(tb.cout, tb.cin, len(tb.taps), tb.ck)
     assert nbytes > 0
     w = wsrc.detach()
     assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
-    if dst is None:
-        dst = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    assert dst.numel() == nbytes
-    L.check(lib.tdvc_pack_conv_weights_indexed(w.data_ptr(), tb.row_off.data_ptr(), tb.chan_off.data_ptr(), tb.tap_off.data_ptr(),
-                                               tb.row_mask.data_ptr(), tb.chan_mask.data_ptr(), tb.tap_mask.data_ptr(),
-                                               tb.cout, tb.cin, len(tb.taps), tb.ck, dst.data_ptr(), _stream()), "pack_conv_weights_indexed")
+    if f32:                                       # a passed buffer is reused only when it fits
+        if dst is None or dst.numel() != nbytes // 2 or dst.device != w.device:
+            dst = torch.empty(nbytes // 2, dtype=torch.float32, device=w.device)      # 8 floats where the fp16 blob has 8 halves
+    else:
+        if dst is None:
+            dst = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        assert dst.numel() == nbytes
+    launch("tdvc_pack_conv_weights_indexed_f32" if f32 else "tdvc_pack_conv_weights_indexed", w, tb.row_off, tb.chan_off, tb.tap_off,
+           tb.row_mask, tb.chan_mask, tb.tap_mask, tb.cout, tb.cin, len(tb.taps), tb.ck, dst)
     return dst
+
+
+def _pack_from_tables(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None = None) -> torch.Tensor:
+    return _pack(wsrc, tb, dst, False)
 
 
 def _pack_from_tables_f32(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None = None) -> torch.Tensor:
-    lib = L.lib()
-    nbytes = lib.tdvc_conv_packed_bytes(tb.cout, tb.cin, len(tb.taps), tb.ck)
-    assert nbytes > 0
-    w = wsrc.detach()
-    assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
-    if dst is None or dst.numel() != nbytes // 2 or dst.device != w.device:
-        dst = torch.empty(nbytes // 2, dtype=torch.float32, device=w.device)      # 8 floats where the fp16 blob has 8 halves
-    L.check(lib.tdvc_pack_conv_weights_indexed_f32(w.data_ptr(), tb.row_off.data_ptr(), tb.chan_off.data_ptr(), tb.tap_off.data_ptr(),
-                                                   tb.row_mask.data_ptr(), tb.chan_mask.data_ptr(), tb.tap_mask.data_ptr(),
-                                                   tb.cout, tb.cin, len(tb.taps), tb.ck, dst.data_ptr(), _stream()), "pack_conv_weights_indexed_f32")
-    return dst
+    return _pack(wsrc, tb, dst, True)
 
 
 class _PackJob(C.Structure):
@@ -338,18 +405,12 @@ class PackBatch:
     def __init__(self, pcs):
         self.pcs = []
         seen = set()
-
-        def walk(pc):
-            if pc is None or id(pc) in seen:
-                return
-            seen.add(id(pc))
-            self.pcs.append(pc)
-            walk(pc.dgrad)
-            walk(pc.__dict__.get("_colpc"))
-            walk(pc.__dict__.get("_plain"))
         self.forms = FORMS_CREATED                 # forms built after this walk (a layer's first dgrad, the plain form of an s2d layer the
         for pc in pcs:                             # first time it sees a small or an fp32 map) are not members: refresh_packed rebuilds
-            walk(pc)
+            if pc is not None and id(pc) not in seen:
+                seen.add(id(pc))
+                self.pcs.append(pc)
+                self.pcs.extend(pc.forms(seen))
         self._build()
 
     def _tensors(self, pc):
@@ -398,8 +459,7 @@ class PackBatch:
             if (([t.data_ptr() for t in self._tensors(pc)] != ptrs) if full else (pc.wsrc.data_ptr() != ptrs[0] or pc.w.data_ptr() != ptrs[7])):
                 self._build()
                 break
-        L.check(L.lib().tdvc_pack_conv_weights_batch(self.jobs.data_ptr(), self.starts.data_ptr(), len(self.pcs), self.total_blocks, _stream()),
-                "pack_conv_weights_batch")
+        launch("tdvc_pack_conv_weights_batch", self.jobs, self.starts, len(self.pcs), self.total_blocks)
         for pc in self.pcs:
             pc.stale_f32()               # fp32 twins (fp32 islands, fp32-coder training) are re-packed from the parameters on next use
 
@@ -464,11 +524,22 @@ SMALL_MAP_PIXELS = 8192      # conv_mfma_v9's range: LARGE_MAP_PIXELS of csrc/co
 
 def _plain_form(pc: PackedConv) -> PackedConv:
     """the un-transformed stride-2 3x3 packing of a layer whose main form is the space-to-depth view (built on first use)"""
-    alt = pc.__dict__.get("_plain")
-    if alt is None:
-        alt = pack_conv(pc.wsrc, pc.bsrc, stride=2, pad=1, allow_s2d=False, layout=pc.layout, param_w=pc.param_w, param_b=pc.param_b)
-        pc.__dict__["_plain"] = alt
-    return alt
+    if pc.plain is None:
+        pc.plain = pack_conv(pc.wsrc, pc.bsrc, stride=2, pad=1, allow_s2d=False, layout=pc.layout, param_w=pc.param_w, param_b=pc.param_b)
+    return pc.plain
+
+
+def _conv_template(pc: PackedConv, wt: torch.Tensor) -> L.ConvDesc:
+    """the layer's part of a `tdvc_conv_desc` (weights `wt`, bias, window, taps)"""
+    t_ = L.ConvDesc()
+    t_.w = wt.data_ptr()
+    t_.bias = pc.bias.data_ptr()
+    t_.cout, t_.ntaps = pc.cout, len(pc.taps)
+    for i, (dy, dx) in enumerate(pc.taps):
+        t_.tap_dy[i], t_.tap_dx[i] = dy, dx
+    t_.kh, t_.kw, t_.stride, t_.pad, t_.ck = pc.kh, pc.kw, pc.stride, pc.pad, pc.ck
+    t_.s2d = int(pc.s2d)
+    return t_
 
 
 def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None,
@@ -495,19 +566,7 @@ def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=
     # the layer's part of the descriptor (weights, bias, window, taps) is built once per layer and weight form and copied per call
     # (re-packing writes the same buffers in place; a re-allocated blob is caught by the pointer check)
     wt = pc.packed_f32() if x.f32 else pc.w
-    key = "_tmpl32" if x.f32 else "_tmpl16"
-    tm = pc.__dict__.get(key)
-    if tm is None or tm[1] != wt.data_ptr():
-        t_ = L.ConvDesc()
-        t_.w = wt.data_ptr()
-        t_.bias = pc.bias.data_ptr()
-        t_.cout, t_.ntaps = pc.cout, len(pc.taps)
-        for i, (dy, dx) in enumerate(pc.taps):
-            t_.tap_dy[i], t_.tap_dx[i] = dy, dx
-        t_.kh, t_.kw, t_.stride, t_.pad, t_.ck = pc.kh, pc.kw, pc.stride, pc.pad, pc.ck
-        t_.s2d = int(pc.s2d)
-        tm = pc.__dict__[key] = (t_, wt.data_ptr())
-    d = L.ConvDesc.from_buffer_copy(tm[0])
+    d = L.ConvDesc.from_buffer_copy(pc.tmpl.of(wt.dtype, wt.data_ptr(), _conv_template, pc, wt))
     d.x = x.desc()
     d.square_input, d.gdn = int(square), gdn
     d.aux = aux.desc() if aux is not None else _NULL_FM
@@ -550,7 +609,7 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
     left empty otherwise (the caller then sums with tdvc_channel_sum)."""
     d, ret, Ho, Wo, pc, rec_pc = conv_desc(x, pc, out, act, slope, res, res2, gdn, aux, square, out_dtype, round16, nchw_out, bcast_T, bcast_slope)
     if chan_sum is not None and TAPE is None and FUSE_CHAN_SUM:
-        rows = L.lib().tdvc_conv_chan_sum_rows(C.byref(d))
+        rows = L.lib().tdvc_conv_chan_sum_rows(d)
         if rows > 0:
             part = torch.empty((x.N, rows, pc.cout), dtype=torch.float32, device=x.t.device)
             d.chan_sum = part.data_ptr()
@@ -561,27 +620,21 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
         if (TAPE is not None and not _IN_BACKWARD) or chan_sum is not None or nchw_out is not None:
             raise L.TdvcHipError("conv: flow is an inference-only fusion of an fmap output, not combined with chan_sum (use conv + add_flow)")
         d.flow = flow.desc()
-        if L.lib().tdvc_conv_flow_supported(C.byref(d)) != 1:       # another kernel: the conv as it is, then one pass over its output
+        if L.lib().tdvc_conv_flow_supported(d) != 1:       # another kernel: the conv as it is, then one pass over its output
             d.flow = _NULL_FM
-            L.check(L.lib().tdvc_conv2d(C.byref(d), _stream()), "conv2d")
+            launch("tdvc_conv2d", d)
             _log_predicated()
             add_flow(ret, flow)
             return ret
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(L.lib().tdvc_conv2d(C.byref(d), _stream()), "conv2d")
-        e1.record()
-        PROFILE.append(dict(kernel=L.lib().tdvc_last_conv_kernel().decode(),
-                            shape=f"{pc.kh}x{pc.kw} s{pc.stride} {x.C}->{pc.cout} @{x.H}x{x.W}" + (" f32out" if out_dtype == torch.float32 else "") + (" nchw" if nchw_out is not None else ""),
-                            e0=e0, e1=e1,
-                            flops=2.0 * x.N * Ho * Wo * pc.cout * x.C * len(pc.taps),
-                            flops_real=(x.N * Ho * Wo * pc.flops_per_px) if pc.s2d else 2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(pc.taps),
-                            bytes=2.0 * x.N * (x.H * x.W * x.C + Ho * Wo * pc.cout * (4 if pc.shuffle else 1) / (4 if pc.shuffle else 1))))
-        _rec("conv", x, rec_pc, None if nchw_out is not None else ret, act, slope, res, res2, gdn, aux, square, nchw_out)
-        return ret
-    L.check(L.lib().tdvc_conv2d(C.byref(d), _stream()), "conv2d")
-    _log_predicated()
+    if PROFILE is None:
+        launch("tdvc_conv2d", d)
+        _log_predicated()
+    else:                                         # the kernel's name is known behind the launch; a profiled call does not log its predicate
+        _profiled(lambda: L.lib().tdvc_last_conv_kernel().decode(),
+                  f"{pc.kh}x{pc.kw} s{pc.stride} {x.C}->{pc.cout} @{x.H}x{x.W}" + (" f32out" if out_dtype == torch.float32 else "") + (" nchw" if nchw_out is not None else ""),
+                  2.0 * x.N * Ho * Wo * pc.cout * x.C * len(pc.taps), lambda: launch("tdvc_conv2d", d),
+                  flops_real=(x.N * Ho * Wo * pc.flops_per_px) if pc.s2d else 2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(pc.taps),
+                  bytes=2.0 * x.N * (x.H * x.W * x.C + Ho * Wo * pc.cout * (4 if pc.shuffle else 1) / (4 if pc.shuffle else 1)))
     _rec("conv", x, rec_pc, None if nchw_out is not None else ret, act, slope, res, res2, gdn, aux, square, nchw_out)
     return ret
 
@@ -644,7 +697,7 @@ def conv_pair_supported(x: FM, out: FM | None = None, res2: FM | None = None) ->
     d.y = out.desc() if out is not None else x.desc()
     d.res2 = res2.desc() if res2 is not None else L.FMapDesc()
     d.w = d.bias = 1            # presence only; never dereferenced by the query
-    return bool(L.lib().tdvc_conv_pair_supported(C.byref(d)))
+    return bool(L.lib().tdvc_conv_pair_supported(d))
 
 
 def conv_pair(x: FM, pp: PackedConvPair, out: FM | None = None, act1=ACT_RELU, slope1=0.0, act2=ACT_NONE, slope2=0.0,
@@ -655,17 +708,12 @@ def conv_pair(x: FM, pp: PackedConvPair, out: FM | None = None, act1=ACT_RELU, s
     if out is None:
         out = FM.empty(x.N, x.H, x.W, 64, device=x.t.device)
     d = _pair_desc(x, pp, out, act1, slope1, act2, slope2, add_input, res2)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(L.lib().tdvc_conv_pair(C.byref(d), _stream()), "conv_pair")
-        e1.record()
-        fl = 2 * 2.0 * x.N * x.H * x.W * 64 * 64 * 9
-        PROFILE.append(dict(kernel="conv_pair", shape=f"2x(3x3 s1 64->64) @{x.H}x{x.W}", e0=e0, e1=e1, flops=fl, flops_real=fl,
-                            bytes=2.0 * x.N * x.H * x.W * 128))
-        return out
-    L.check(L.lib().tdvc_conv_pair(C.byref(d), _stream()), "conv_pair")
-    _log_predicated()
+    if PROFILE is None:
+        launch("tdvc_conv_pair", d)
+        _log_predicated()
+    else:                                         # as in conv: a profiled call does not log its predicate
+        _profiled("conv_pair", f"2x(3x3 s1 64->64) @{x.H}x{x.W}", 2 * 2.0 * x.N * x.H * x.W * 64 * 64 * 9, lambda: launch("tdvc_conv_pair", d),
+                  bytes=2.0 * x.N * x.H * x.W * 128)
     return out
 
 
@@ -688,7 +736,7 @@ def lf_tail_supported(S: FM, A: FM, out: FM) -> bool:
     (tdvc_lf_tail_supported)"""
     if TAPE is not None or S.f32 or A.f32 or out.f32:
         return False
-    return bool(L.lib().tdvc_lf_tail_supported(C.byref(_lf_tail_desc(S, A, out, None, None, 0.0))))
+    return bool(L.lib().tdvc_lf_tail_supported(_lf_tail_desc(S, A, out, None, None, 0.0)))
 
 
 def lf_tail(S: FM, A: FM, pct: PackedConv, pc3: PackedConv, out: FM, slope: float = 0.1) -> FM:
@@ -698,8 +746,7 @@ def lf_tail(S: FM, A: FM, pct: PackedConv, pc3: PackedConv, out: FM, slope: floa
         raise L.TdvcHipError("lf_tail: inference only (the intermediate map is not kept for the backward pass)")
     if (pct.cin, pct.cout, pct.kh, pct.kw, pct.ck) != (192, 64, 1, 1, 32) or (pc3.cin, pc3.cout, pc3.kh, pc3.kw, pc3.ck, pc3.stride, pc3.pad) != (64, 64, 3, 3, 32, 1, 1):
         raise L.TdvcHipError("lf_tail: needs the 1x1 192 -> 64 temporal conv and the 3x3 64 -> 64 conv, both packed with ck = 32")
-    d = _lf_tail_desc(S, A, out, pct, pc3, slope)
-    L.check(L.lib().tdvc_lf_tail(C.byref(d), _stream()), "lf_tail")
+    launch("tdvc_lf_tail", _lf_tail_desc(S, A, out, pct, pc3, slope))
     _log_predicated()
     return out
 
@@ -708,10 +755,7 @@ def lf_tail(S: FM, A: FM, pct: PackedConv, pc3: PackedConv, out: FM, slope: floa
 def act_backward(g: FM, y: FM, act, slope=0.0, res: FM | None = None, out: FM | None = None) -> FM:
     """g * act'(z); the sign of the pre-activation comes from the stored output y (minus its residual)"""
     out = g if out is None else out
-    dg, dy, do = g.desc(), y.desc(), out.desc()
-    dr = res.desc() if res is not None else None
-    L.check(L.lib().tdvc_act_backward(C.byref(dg), C.byref(dy), C.byref(dr) if dr is not None else None, act, slope, C.byref(do), _stream()),
-            "act_backward")
+    launch("tdvc_act_backward", g, y, res, act, slope, out)
     return out
 
 
@@ -719,8 +763,7 @@ def pixel_unshuffle(y: FM, out: FM | None = None) -> FM:
     """(N, 2H, 2W, C) -> (N, H, W, 4C), channel (i*2+j)*C + c: the gradient of a sub-pixel conv in packed-row order"""
     if out is None:
         out = FM.empty(y.N, y.H // 2, y.W // 2, 4 * y.C, dtype=y.t.dtype, device=y.t.device)
-    dy, do = y.desc(), out.desc()
-    L.check(L.lib().tdvc_pixel_unshuffle(C.byref(dy), C.byref(do), _stream()), "pixel_unshuffle")
+    launch("tdvc_pixel_unshuffle", y, out)
     return out
 
 
@@ -774,7 +817,6 @@ class WgradBatch:
             if len(rounds) <= r:
                 rounds.append([])
             rounds[r].append(job)
-        lib = L.lib()
         for jobs in rounds:
             n = len(jobs)
             arr = (L.WgradReduceJob * n)(*jobs)
@@ -788,7 +830,7 @@ class WgradBatch:
             dev = host.to(jobs_device(jobs), non_blocking=True)
             if torch.cuda.is_current_stream_capturing():
                 _GRAPH_KEEP.append((host, dev))          # a captured copy node re-reads the pinned table at every replay
-            L.check(lib.tdvc_wgrad_reduce_batch(dev.data_ptr(), dev.data_ptr() + nb_j, n, int(starts[n]), _stream()), "wgrad_reduce_batch")
+            launch("tdvc_wgrad_reduce_batch", dev, dev.data_ptr() + nb_j, n, int(starts[n]))
         self.items.clear()
 
 
@@ -799,6 +841,22 @@ def jobs_device(jobs):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _wgrad_tables(pc: PackedConv, cin: int, taps):
+    """plain-geometry tables (also for layers that RUN in space-to-depth form) for an input of `cin` channels, and the tap arrays"""
+    o = pc.orig
+    return (convpack.forward_tables(pc.layout, cin_pad=cin, taps=taps, pad=o["pad"], ck=8, shuffle=pc.shuffle, cin_perm=o["cin_perm"], device=pc.w.device),
+            (C.c_int8 * len(taps))(*[t[0] for t in taps]), (C.c_int8 * len(taps))(*[t[1] for t in taps]))
+
+
+def _wgrad_static(pc: PackedConv, cin: int, N: int, Ho: int, Wo: int, taps):
+    """what the weight-gradient launches of a layer at one geometry share -> (tables, the launch's arguments between its maps and
+    `square_x`, workspace floats).  The tables are the layer's for `cin` input channels: another channel count builds them again"""
+    o = pc.orig
+    tb, dy, dxs = pc.wgrad.of("tables", cin, _wgrad_tables, pc, cin, taps)
+    return (tb, (pc.cout, o["kh"], o["kw"], o["stride"], o["pad"], len(taps), dy, dxs, tb.row_off, tb.chan_off, tb.tap_off),
+            L.lib().tdvc_conv_wgrad_work_floats(pc.cout, cin, len(taps), N, Ho, Wo))
+
+
 def conv_wgrad(pc: PackedConv, g: FM, x: FM, dw: torch.Tensor, scale=1.0, square_x=False, db: torch.Tensor | None = None,
                defer: WgradBatch | None = None) -> None:
     """dW += scale * dL/dW (fp32, the parameter's own layout); `g` as in conv_dgrad.  With `db` the bias gradient
@@ -806,86 +864,55 @@ def conv_wgrad(pc: PackedConv, g: FM, x: FM, dw: torch.Tensor, scale=1.0, square
     the tap list beyond the forward's (masked convs: the reference's autograd also fills the masked taps)."""
     o = pc.orig
     taps = o.get("wgrad_taps") or o["taps"]
-    tb = pc.__dict__.get("_wg_tables")
-    if tb is None:                               # plain-geometry tables (also for layers that RUN in space-to-depth form)
-        tb = convpack.forward_tables(pc.layout, cin_pad=x.C, taps=taps, pad=o["pad"], ck=8, shuffle=pc.shuffle, cin_perm=o["cin_perm"],
-                                     device=pc.w.device)
-        pc.__dict__["_wg_tables"] = tb
     assert dw.is_cuda and dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == pc.wsrc.numel()
-    lib = L.lib()
     Ho, Wo = g.H, g.W
-    wk = pc.__dict__.get("_wg_static")          # per layer and geometry: workspace size, tap arrays (built once)
-    if wk is None or wk[0] != (x.C, x.N, Ho, Wo):
-        wk = pc.__dict__["_wg_static"] = ((x.C, x.N, Ho, Wo), lib.tdvc_conv_wgrad_work_floats(pc.cout, x.C, len(taps), x.N, Ho, Wo),
-                                          (C.c_int8 * len(taps))(*[t[0] for t in taps]), (C.c_int8 * len(taps))(*[t[1] for t in taps]))
-    _, nwork, dy, dxs = wk
+    tb, static, nwork = pc.wgrad.of("launch", (x.C, x.N, Ho, Wo), _wgrad_static, pc, x.C, x.N, Ho, Wo, taps)
     work = torch.empty((nwork,), dtype=torch.float32, device=dw.device)
     if FORCE_KEEP is not None:
         FORCE_KEEP.append(work)
-    dg, dxd = g.desc(), x.desc()
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     bidx = None
     if db is not None:
         assert db.is_cuda and db.dtype == torch.float32 and db.is_contiguous() and db.numel() >= pc.cout
         bidx = _bias_index(pc, db.device)
+    args = (g, x, *static, int(square_x), scale, dw, bidx, db, work, nwork)
     if defer is not None and PROFILE is None:
         job = L.WgradReduceJob()
-        L.check(lib.tdvc_conv_wgrad_partials(C.byref(dg), C.byref(dxd), pc.cout, o["kh"], o["kw"], o["stride"], o["pad"], len(taps), dy, dxs,
-                                             tb.row_off.data_ptr(), tb.chan_off.data_ptr(), tb.tap_off.data_ptr(), int(square_x), scale, dw.data_ptr(),
-                                             bidx.data_ptr() if bidx is not None else None, db.data_ptr() if db is not None else None,
-                                             work.data_ptr(), nwork, C.byref(job), _stream()), "conv_wgrad_partials")
+        launch("tdvc_conv_wgrad_partials", *args, job)
         defer.add(job, (work, dw, db, tb, bidx))             # the workspace and the tables live until the flush
         return
-    L.check(lib.tdvc_conv_wgrad_bias(C.byref(dg), C.byref(dxd), pc.cout, o["kh"], o["kw"], o["stride"], o["pad"], len(taps), dy, dxs,
-                                tb.row_off.data_ptr(), tb.chan_off.data_ptr(), tb.tap_off.data_ptr(), int(square_x), scale, dw.data_ptr(),
-                                bidx.data_ptr() if bidx is not None else None, db.data_ptr() if db is not None else None,
-                                work.data_ptr(), nwork, _stream()), "conv_wgrad")
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(dict(kernel="conv_wgrad_f32" if x.f32 else "conv_wgrad", shape=f"{o['kh']}x{o['kw']} s{o['stride']} {x.C}->{pc.cout} @{x.N}x{x.H}x{x.W}", e0=e0, e1=e1,
-                            flops=2.0 * x.N * Ho * Wo * pc.cout * x.C * len(taps), flops_real=2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(taps),
-                            bytes=0.0,
-                            # geometry class (kh, kw, stride, cin, cout, shuffle, square_x, masked): the op-level test coverage guard
-                            geo=(o["kh"], o["kw"], o["stride"], pc.cin_real, pc.cout, bool(pc.shuffle), bool(square_x), "wgrad_taps" in o)))
+    _profiled("conv_wgrad_f32" if x.f32 else "conv_wgrad", f"{o['kh']}x{o['kw']} s{o['stride']} {x.C}->{pc.cout} @{x.N}x{x.H}x{x.W}",
+              2.0 * x.N * Ho * Wo * pc.cout * x.C * len(taps), lambda: launch("tdvc_conv_wgrad_bias", *args, what="conv_wgrad"),
+              flops_real=2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(taps),
+              # geometry class (kh, kw, stride, cin, cout, shuffle, square_x, masked): the op-level test coverage guard
+              geo=(o["kh"], o["kw"], o["stride"], pc.cin_real, pc.cout, bool(pc.shuffle), bool(square_x), "wgrad_taps" in o))
 
 
 def _bias_index(pc: PackedConv, device):
-    idx = pc.__dict__.get("_bg_index")
-    if idx is None and pc.shuffle:
-        idx = torch.from_numpy(convpack.shuffle_perm(pc.cout)).to(torch.int32).to(device)
-        pc.__dict__["_bg_index"] = idx
-    return idx
+    if pc.bias_index is None and pc.shuffle:
+        pc.bias_index = torch.from_numpy(convpack.shuffle_perm(pc.cout)).to(torch.int32).to(device)
+    return pc.bias_index
 
 
 def conv_bgrad(pc: PackedConv, g: FM, db: torch.Tensor, scale=1.0) -> None:
     """db += scale * sum over batch and pixels of g (rows un-permuted for sub-pixel layers)"""
-    lib = L.lib()
-    idx = _bias_index(pc, db.device)
-    nwork = lib.tdvc_bias_grad_work_floats(g.N, g.C)
+    nwork = L.lib().tdvc_bias_grad_work_floats(g.N, g.C)
     work = torch.empty((nwork,), dtype=torch.float32, device=db.device)
-    dg = g.desc()
-    L.check(lib.tdvc_bias_grad(C.byref(dg), pc.cout, idx.data_ptr() if idx is not None else None, scale, db.data_ptr(), work.data_ptr(), nwork,
-                               _stream()), "bias_grad")
+    launch("tdvc_bias_grad", g, pc.cout, _bias_index(pc, db.device), scale, db, work, nwork)
 
 
 def gdn_backward(g: FM, x: FM, n32: FM, inverse: bool, dx: FM) -> FM:
     """-> dn (x's dtype); dx += g * n^(-+1/2)"""
     dn = FM.empty(g.N, g.H, g.W, g.C, dtype=x.t.dtype, device=g.t.device)
-    d1, d2, d3, d4, d5 = g.desc(), x.desc(), n32.desc(), dn.desc(), dx.desc()
-    L.check(L.lib().tdvc_gdn_backward(C.byref(d1), C.byref(d2), C.byref(d3), int(inverse), C.byref(d4), C.byref(d5), _stream()), "gdn_backward")
+    launch("tdvc_gdn_backward", g, x, n32, int(inverse), dn, dx)
     return dn
 
 
 def mul2_accumulate(dx: FM, x: FM, t: FM) -> None:
-    d1, d2, d3 = dx.desc(), x.desc(), t.desc()
-    L.check(L.lib().tdvc_mul2_accumulate(C.byref(d1), C.byref(d2), C.byref(d3), _stream()), "mul2_accumulate")
+    launch("tdvc_mul2_accumulate", dx, x, t)
 
 
 def copy_cast(src: FM, dst: FM) -> FM:
-    ds, dd = src.desc(), dst.desc()
-    L.check(L.lib().tdvc_copy_cast(C.byref(ds), C.byref(dd), _stream()), "copy_cast")
+    launch("tdvc_copy_cast", src, dst)
     return dst
 
 
@@ -898,19 +925,14 @@ def cast_f32(x: FM) -> FM:
 
 
 def clamp01_backward(g: FM, y: FM) -> FM:
-    dg, dy = g.desc(), y.desc()
-    L.check(L.lib().tdvc_clamp01_backward(C.byref(dg), C.byref(dy), _stream()), "clamp01_backward")
+    launch("tdvc_clamp01_backward", g, y)
     return g
 
 
 def gate_backward(g: FM, a: FM, gate: torch.Tensor, da: FM | None, dgate: torch.Tensor) -> None:
-    lib = L.lib()
-    nwork = lib.tdvc_gate_backward_work_floats(g.N, g.C)
+    nwork = L.lib().tdvc_gate_backward_work_floats(g.N, g.C)
     work = torch.empty((nwork,), dtype=torch.float32, device=gate.device)
-    dg, dad = g.desc(), a.desc()
-    dda = da.desc() if da is not None else None
-    L.check(lib.tdvc_gate_backward(C.byref(dg), C.byref(dad), gate.data_ptr(), C.byref(dda) if dda is not None else None, dgate.data_ptr(),
-                                   work.data_ptr(), nwork, _stream()), "gate_backward")
+    launch("tdvc_gate_backward", g, a, gate, da, dgate, work, nwork)
 
 
 def se_gate_backward(p: "SEParams", partial: torch.Tensor, nblocks: int, npix: int, gate: torch.Tensor, dgate: torch.Tensor, scale: float,
@@ -918,31 +940,24 @@ def se_gate_backward(p: "SEParams", partial: torch.Tensor, nblocks: int, npix: i
     """-> dmean [N][C]; parameter gradients accumulate into `grads` = (dw1, db1, dw2, db2)"""
     N = gate.shape[0]
     dmean = torch.empty_like(gate)
-    L.check(L.lib().tdvc_se_gate_backward(partial.data_ptr(), nblocks, 1.0 / npix, N, p.C, p.Cmid, p.w1.data_ptr(), p.b1.data_ptr(),
-                                          p.w2.data_ptr(), p.b2.data_ptr(), gate.data_ptr(), dgate.data_ptr(), scale, dmean.data_ptr(),
-                                          grads[0].data_ptr(), grads[1].data_ptr(), grads[2].data_ptr(), grads[3].data_ptr(), _stream()),
-            "se_gate_backward")
+    launch("tdvc_se_gate_backward", partial, nblocks, 1.0 / npix, N, p.C, p.Cmid, p.w1, p.b1, p.w2, p.b2, gate, dgate, scale, dmean, *grads[:4])
     return dmean
 
 
 def bcast_channel_add(dx: FM, v: torch.Tensor, scale: float) -> None:
-    d = dx.desc()
-    L.check(L.lib().tdvc_bcast_channel_add(C.byref(d), v.data_ptr(), scale, _stream()), "bcast_channel_add")
+    launch("tdvc_bcast_channel_add", dx, v, scale)
 
 
 def add_flow_backward(doff: FM, dflow: FM) -> None:
-    do, df = doff.desc(), dflow.desc()
-    L.check(L.lib().tdvc_add_flow_backward(C.byref(do), C.byref(df), _stream()), "add_flow_backward")
+    launch("tdvc_add_flow_backward", doff, dflow)
 
 
 def bcast_add_act_backward(dx: FM, x: FM, db: FM, slope: float) -> None:
-    d1, d2, d3 = dx.desc(), x.desc(), db.desc()
-    L.check(L.lib().tdvc_bcast_add_act_backward(C.byref(d1), C.byref(d2), C.byref(d3), slope, _stream()), "bcast_add_act_backward")
+    launch("tdvc_bcast_add_act_backward", dx, x, db, slope)
 
 
 def upsample2x_backward(dy: FM, dx: FM) -> None:
-    d1, d2 = dy.desc(), dx.desc()
-    L.check(L.lib().tdvc_upsample2x_backward(C.byref(d1), C.byref(d2), _stream()), "upsample2x_backward")
+    launch("tdvc_upsample2x_backward", dy, dx)
 
 
 DCN_PLANAR_MIN_PIXELS = 1 << 16      # below this the map is L2-resident anyway and the extra pass does not pay
@@ -986,21 +1001,9 @@ def dcn_fused(x: FM, om: FM, pc: PackedConv, out: FM, groups=8, act=ACT_NONE, sl
         planar = DCN_PLANAR and x.H * x.W >= DCN_PLANAR_MIN_PIXELS and not x.f32
     scratch = torch.empty((x.N, groups, x.H, x.W, 8), dtype=torch.float16, device=x.t.device) if planar else None
     d.x_planar = scratch.data_ptr() if scratch is not None else None
-    L.check(L.lib().tdvc_dcn_fused(C.byref(d), _stream()), "dcn_fused")
+    launch("tdvc_dcn_fused", d)
     _rec("dcn_fused", x, om, pc, out, groups, act, slope)
     return out
-
-
-def _profiled(kernel: str, shape: str, flops: float, launch):
-    """run `launch()`; under PROFILE between two events, as one row of the per-kernel table"""
-    if PROFILE is None:
-        return launch()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    r = launch()
-    e1.record()
-    PROFILE.append(dict(kernel=kernel, shape=shape, e0=e0, e1=e1, flops=flops, flops_real=flops, bytes=0.0))
-    return r
 
 
 def dcn_col2im_tile() -> int:
@@ -1011,9 +1014,8 @@ def dcn_col2im_tile() -> int:
 def dcn_columns(x: FM, om: FM, groups: int) -> FM:
     """the sampled, modulated columns (N, H, W, 72 groups) in the dtype of `x` (`om` must have it too)"""
     col = FM.empty(x.N, x.H, x.W, 72 * groups, dtype=x.t.dtype, device=x.t.device)
-    d1, d2, d3 = x.desc(), om.desc(), col.desc()
     _profiled("dcn_columns_f32" if x.f32 else "dcn_columns", f"G{groups} @{x.N}x{x.H}x{x.W}", 2.0 * 4 * 72 * groups * x.N * x.H * x.W,
-              lambda: L.check(L.lib().tdvc_dcn_columns(C.byref(d1), C.byref(d2), groups, C.byref(d3), _stream()), "dcn_columns"))
+              lambda: launch("tdvc_dcn_columns", x, om, groups, col))
     return col
 
 
@@ -1027,60 +1029,53 @@ def dcn_col2im(x: FM, om: FM, dcol: FM, groups: int, dom: FM) -> FM:
     """-> dx as an fp32 FM (fresh; scatter through per-tile windows); offset / mask gradients accumulate into `dom`.  x, om, dcol and
     dom are all fp16 or all fp32 maps (a mix is refused before any launch)"""
     dx32 = FM.zeros(x.N, x.H, x.W, x.C, dtype=torch.float32, device=x.t.device)
-    lib = L.lib()
-    nwork = lib.tdvc_dcn_col2im_work_floats(x.N, x.H, x.W, groups)
+    nwork = L.lib().tdvc_dcn_col2im_work_floats(x.N, x.H, x.W, groups)
     work = torch.empty((nwork,), dtype=torch.float32, device=x.t.device)
-    d1, d2, d3, d4 = x.desc(), om.desc(), dcol.desc(), dom.desc()
-    name, shape, flops = "dcn_col2im_f32" if x.f32 else "dcn_col2im", f"G{groups} @{x.N}x{x.H}x{x.W}", 2.0 * 4 * 3 * 72 * groups * x.N * x.H * x.W
+    entry, args = "tdvc_dcn_col2im", (x, om, dcol, groups, dx32.t, dom, work, nwork)
     if DETERMINISTIC:
         dev = x.t.device
         cap = max(1 << 16, x.N * x.H * x.W * groups * 36 // 8)          # an eighth of all samples far out of their window
         keys = torch.empty((cap,), dtype=torch.int64, device=dev)
         vals = torch.empty((cap, 8), dtype=torch.float32, device=dev)
         cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
-        _profiled(name, shape, flops,
-                  lambda: L.check(lib.tdvc_dcn_col2im_det(C.byref(d1), C.byref(d2), C.byref(d3), groups, dx32.t.data_ptr(), C.byref(d4), work.data_ptr(), nwork,
-                                                          keys.data_ptr(), vals.data_ptr(), cnt.data_ptr(), cap, _stream()), "dcn_col2im_det"))
+        entry, args = "tdvc_dcn_col2im_det", args + (keys, vals, cnt, cap)
+    _profiled("dcn_col2im_f32" if x.f32 else "dcn_col2im", f"G{groups} @{x.N}x{x.H}x{x.W}", 2.0 * 4 * 3 * 72 * groups * x.N * x.H * x.W,
+              lambda: launch(entry, *args))
+    if DETERMINISTIC:
         n = int(cnt.item())
         if n > cap:
             raise L.TdvcHipError(f"dcn_col2im (deterministic): {n} far samples exceed the record capacity {cap}")
         if n:
             ks, order = torch.sort(keys[:n], stable=True)
-            L.check(lib.tdvc_dcn_far_apply(ks.data_ptr(), order.data_ptr(), vals.data_ptr(), n, dx32.t.data_ptr(), _stream()), "dcn_far_apply")
-        return dx32
-    _profiled(name, shape, flops,
-              lambda: L.check(lib.tdvc_dcn_col2im(C.byref(d1), C.byref(d2), C.byref(d3), groups, dx32.t.data_ptr(), C.byref(d4), work.data_ptr(), nwork,
-                                                  _stream()), "dcn_col2im"))
+            launch("tdvc_dcn_far_apply", ks, order, vals, n, dx32.t)
     return dx32
 
 
 def dcn_column_conv(pc: PackedConv, groups: int) -> PackedConv:
     """the DCN weight (cout, 8G, 3, 3) as a 1x1 conv over the 72G column channels k = g*72 + t*8 + j, input channel
     c = g*8 + j (weight offset c*9 + t)"""
-    cp = pc.__dict__.get("_colpc")
-    if cp is None:
+    if pc.column is None:
         cin = 8 * groups
         chan = np.array([(g * 8 + j) * 9 + t for g in range(groups) for t in range(9) for j in range(8)], dtype=np.int64)
         lay = convpack.WeightLayout(pc.cout, 9 * cin, 1, 1, np.arange(pc.cout, dtype=np.int64) * cin * 9, chan, np.zeros(1, dtype=np.int64))
-        cp = pack_conv(pc.wsrc, None, stride=1, pad=0, layout=lay, param_w=pc.param_w)
-        pc.__dict__["_colpc"] = cp
-    return cp
+        pc.column = pack_conv(pc.wsrc, None, stride=1, pad=0, layout=lay, param_w=pc.param_w)
+    return pc.column
 
 
 def sigmoid_f32(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(x)
-    L.check(L.lib().tdvc_sigmoid_f32(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "sigmoid_f32")
+    launch("tdvc_sigmoid_f32", x, out, x.numel())
     return out
 
 
 def sigmoid_backward_f32(g: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    L.check(L.lib().tdvc_sigmoid_backward_f32(g.data_ptr(), s.data_ptr(), g.numel(), _stream()), "sigmoid_backward_f32")
+    launch("tdvc_sigmoid_backward_f32", g, s, g.numel())
     return g
 
 
 def axpy_f32(dst: torch.Tensor, src: torch.Tensor, scale: float) -> None:
     assert dst.numel() == src.numel() and dst.dtype == src.dtype == torch.float32 and dst.is_contiguous() and src.is_contiguous()
-    L.check(L.lib().tdvc_axpy_f32(dst.data_ptr(), src.data_ptr(), scale, dst.numel(), _stream()), "axpy_f32")
+    launch("tdvc_axpy_f32", dst, src, scale, dst.numel())
 
 
 # ----------------------------------------------------------------------------- elementwise / SE
@@ -1091,11 +1086,7 @@ def scale_act_res3(a: FM, out: FM, b: FM, out3: FM, b_sign=-1.0, gate: torch.Ten
     if TAPE is not None and not _IN_BACKWARD:
         raise L.TdvcHipError("scale_act_res3 is an inference-only fusion (under the tape: two scale_act_res calls)")
     if not (a.f32 or out.f32 or b.f32 or out3.f32 or (res is not None and res.f32)):
-        da, dy, db, d3 = a.desc(), out.desc(), b.desc(), out3.desc()
-        dr = res.desc() if res is not None else None
-        L.check(L.lib().tdvc_scale_act_res3(C.byref(da), gate.data_ptr() if gate is not None else None, act, slope,
-                                            C.byref(dr) if dr is not None else None, res_sign, C.byref(dy), C.byref(db), b_sign,
-                                            C.byref(d3), _stream()), "scale_act_res3")
+        launch("tdvc_scale_act_res3", a, gate, act, slope, res, res_sign, out, b, b_sign, out3)
         return out
     scale_act_res(a, out, gate=gate, act=act, slope=slope, res=res, res_sign=res_sign)
     scale_act_res(b, out3, res=out, res_sign=b_sign)
@@ -1104,12 +1095,7 @@ def scale_act_res3(a: FM, out: FM, b: FM, out3: FM, b_sign=-1.0, gate: torch.Ten
 
 def scale_act_res(a: FM, out: FM, gate: torch.Tensor | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None,
                   res_sign=1.0, out2: FM | None = None) -> FM:
-    da, dy = a.desc(), out.desc()
-    dr = res.desc() if res is not None else None
-    d2 = out2.desc() if out2 is not None else None
-    L.check(L.lib().tdvc_scale_act_res(C.byref(da), gate.data_ptr() if gate is not None else None, act, slope,
-                                       C.byref(dr) if dr is not None else None, res_sign, C.byref(dy),
-                                       C.byref(d2) if d2 is not None else None, _stream()), "scale_act_res")
+    launch("tdvc_scale_act_res", a, gate, act, slope, res, res_sign, out, out2)
     _rec("scale_act_res", a, out, gate, act, slope, res, res_sign, out2)
     return out
 
@@ -1123,14 +1109,12 @@ def clone(x: FM) -> FM:
 
 
 def add_flow(off: FM, flow: FM):
-    do, df = off.desc(), flow.desc()
-    L.check(L.lib().tdvc_add_flow(C.byref(do), C.byref(df), _stream()), "add_flow")
+    launch("tdvc_add_flow", off, flow)
     _rec("add_flow", off, flow)
 
 
 def bcast_add_act(x: FM, b: FM, T: int, slope: float):
-    dx, db = x.desc(), b.desc()
-    L.check(L.lib().tdvc_bcast_add_act(C.byref(dx), C.byref(db), T, slope, _stream()), "bcast_add_act")
+    launch("tdvc_bcast_add_act", x, b, T, slope)
     _rec("bcast_add_act", x, b, slope)
 
 
@@ -1153,17 +1137,14 @@ def se_gate(x: FM, p: SEParams, partial=None) -> torch.Tensor:
     channel sums of `x` that its producer already wrote (conv(..., chan_sum=)); otherwise one pass over x (tdvc_channel_sum)."""
     npix = x.H * x.W
     gate = torch.empty((x.N, x.C), dtype=torch.float32, device=x.t.device)
-    lib = L.lib()
     if partial is not None:
         partial, nblocks = partial
         assert tuple(partial.shape) == (x.N, nblocks, x.C) and partial.dtype == torch.float32
     else:
         nblocks = max(1, min(1024, npix // 256))      # 4 workgroups per CU at full resolution: 64 KB of loads in flight per CU
         partial = torch.empty((x.N, nblocks, x.C), dtype=torch.float32, device=x.t.device)
-        dx = x.desc()
-        L.check(lib.tdvc_channel_sum(C.byref(dx), partial.data_ptr(), nblocks, _stream()), "channel_sum")
-    L.check(lib.tdvc_se_gate(partial.data_ptr(), nblocks, 1.0 / npix, x.N, p.C, p.Cmid, p.w1.data_ptr(),
-                             p.b1.data_ptr(), p.w2.data_ptr(), p.b2.data_ptr(), gate.data_ptr(), _stream()), "se_gate")
+        launch("tdvc_channel_sum", x, partial, nblocks)
+    launch("tdvc_se_gate", partial, nblocks, 1.0 / npix, x.N, p.C, p.Cmid, p.w1, p.b1, p.w2, p.b2, gate)
     _rec("se_gate", x, p, partial, nblocks, gate)
     return gate
 
@@ -1172,16 +1153,14 @@ def se_gate(x: FM, p: SEParams, partial=None) -> torch.Tensor:
 def upsample2x(x: FM, out: FM | None = None) -> FM:
     if out is None:
         out = FM.empty(x.N, 2 * x.H, 2 * x.W, x.C, dtype=x.t.dtype, device=x.t.device)
-    dx, dy = x.desc(), out.desc()
-    L.check(L.lib().tdvc_upsample2x(C.byref(dx), C.byref(dy), _stream()), "upsample2x")
+    launch("tdvc_upsample2x", x, out)
     _rec("upsample2x", x, out)
     return out
 
 
 def avgpool2(x: FM) -> FM:
     out = FM.empty(x.N, x.H // 2, x.W // 2, x.C, dtype=torch.float32, device=x.t.device)
-    dx, dy = x.desc(), out.desc()
-    L.check(L.lib().tdvc_avgpool2(C.byref(dx), C.byref(dy), _stream()), "avgpool2")
+    launch("tdvc_avgpool2", x, out)
     return out
 
 
@@ -1193,42 +1172,30 @@ def avgpool2_pyramid(a: FM, b: FM) -> tuple:
     """five chained avgpool2 levels of both maps in one launch -> ([a/2, a/4, ..., a/32], [b/2, ..., b/32]), separate buffers"""
     lv = lambda x: [FM.empty(x.N, x.H >> k, x.W >> k, x.C, dtype=torch.float32, device=x.t.device) for k in range(1, 6)]
     la, lb = lv(a), lv(b)
-    da, db = a.desc(), b.desc()
-    ya, yb = (L.FMapDesc * 5)(*[f.desc() for f in la]), (L.FMapDesc * 5)(*[f.desc() for f in lb])
-    L.check(L.lib().tdvc_avgpool2_pyramid(C.byref(da), C.byref(db), ya, yb, _stream()), "avgpool2_pyramid")
+    launch("tdvc_avgpool2_pyramid", a, b, (L.FMapDesc * 5)(*[f.desc() for f in la]), (L.FMapDesc * 5)(*[f.desc() for f in lb]))
     return la, lb
 
 
 def spynet_level_input(ref: FM, supp: FM, flow_lo: FM | None, flow_up: FM, cat8: FM):
-    dr, ds, du, dc = ref.desc(), supp.desc(), flow_up.desc(), cat8.desc()
-    dl = flow_lo.desc() if flow_lo is not None else None
-    L.check(L.lib().tdvc_spynet_level_input(C.byref(dr), C.byref(ds), C.byref(dl) if dl is not None else None,
-                                            C.byref(du), C.byref(dc), _stream()), "spynet_level_input")
+    launch("tdvc_spynet_level_input", ref, supp, flow_lo, flow_up, cat8)
     _rec("spynet_level_input", supp, flow_lo, flow_up, cat8)
 
 
 def spynet_level_input_backward(supp: FM, flow_up: FM, dcat8: FM, dflow_up: FM, dflow_lo: FM | None) -> None:
-    d1, d2, d3, d4 = supp.desc(), flow_up.desc(), dcat8.desc(), dflow_up.desc()
-    d5 = dflow_lo.desc() if dflow_lo is not None else None
-    L.check(L.lib().tdvc_spynet_level_input_backward(C.byref(d1), C.byref(d2), C.byref(d3), C.byref(d4),
-                                                     C.byref(d5) if d5 is not None else None, _stream()), "spynet_level_input_backward")
+    launch("tdvc_spynet_level_input_backward", supp, flow_up, dcat8, dflow_up, dflow_lo)
 
 
 def resize_bilinear(x: FM, H: int, W: int, chscale: torch.Tensor | None = None) -> FM:
     if chscale is not None and (chscale.dtype != torch.float32 or chscale.numel() < x.C):
         raise ValueError(f"resize_bilinear: chscale needs one fp32 scale per channel ({x.C}), got {chscale.numel()} of {chscale.dtype}")
     out = FM.empty(x.N, H, W, x.C, dtype=torch.float32, device=x.t.device)
-    dx, dy = x.desc(), out.desc()
-    L.check(L.lib().tdvc_resize_bilinear(C.byref(dx), C.byref(dy), chscale.data_ptr() if chscale is not None else None,
-                                         _stream()), "resize_bilinear")
+    launch("tdvc_resize_bilinear", x, out, chscale)
     _rec("resize_bilinear", x, out, chscale)
     return out
 
 
 def resize_bilinear_backward(dy: FM, dx: FM, chscale: torch.Tensor | None = None) -> None:
-    d1, d2 = dy.desc(), dx.desc()
-    L.check(L.lib().tdvc_resize_bilinear_backward(C.byref(d1), C.byref(d2), chscale.data_ptr() if chscale is not None else None, _stream()),
-            "resize_bilinear_backward")
+    launch("tdvc_resize_bilinear_backward", dy, dx, chscale)
 
 
 # ----------------------------------------------------------------------------- in-loop filter matching
@@ -1238,8 +1205,7 @@ def avgpool_k(x: FM, scale: int, out: torch.Tensor | None = None) -> torch.Tenso
     assert pooled.shape == (x.N, hp, wp, x.C) and pooled.dtype == torch.float32 and pooled.is_contiguous()
     nwork = L.lib().tdvc_avgpool_k_work_floats(x.N, hp, wp, x.C, scale)
     work = torch.empty((nwork,), dtype=torch.float32, device=x.t.device)
-    dx = x.desc()
-    L.check(L.lib().tdvc_avgpool_k(C.byref(dx), scale, pooled.data_ptr(), hp, wp, work.data_ptr(), nwork, _stream()), "avgpool_k")
+    launch("tdvc_avgpool_k", x, scale, pooled, hp, wp, work, nwork)
     _log_predicated(2)               # strip pass + final pass
     return pooled
 
@@ -1248,22 +1214,17 @@ def patch_match(pin: torch.Tensor, pref: torch.Tensor) -> torch.Tensor:
     N, hp, wp, Cc = pin.shape
     Lp = ((hp + 3) // 3 + 1) * ((wp + 3) // 3 + 1)
     idx = torch.empty((N, Lp), dtype=torch.int32, device=pin.device)
-    L.check(L.lib().tdvc_patch_match(pin.data_ptr(), pref.data_ptr(), N, hp, wp, Cc, idx.data_ptr(), _stream()),
-            "patch_match")
+    launch("tdvc_patch_match", pin, pref, N, hp, wp, Cc, idx)
     return idx
 
 
 def match_gather(fin: FM, fref: FM, idx: torch.Tensor, scale: int, cat: FM):
-    df, dr, dc = fin.desc(), fref.desc(), cat.desc()
-    L.check(L.lib().tdvc_match_gather(C.byref(df), C.byref(dr), idx.data_ptr(), scale, fin.H // scale, fin.W // scale,
-                                      C.byref(dc), _stream()), "match_gather")
+    launch("tdvc_match_gather", fin, fref, idx, scale, fin.H // scale, fin.W // scale, cat)
     _rec("match_gather", fin, fref, idx, scale, cat)
 
 
 def match_gather_backward(fin: FM, fref: FM, idx: torch.Tensor, scale: int, dcat: FM, dfin: FM, dfref: FM) -> None:
-    d1, d2, d3, d4, d5 = fin.desc(), fref.desc(), dcat.desc(), dfin.desc(), dfref.desc()
-    L.check(L.lib().tdvc_match_gather_backward(C.byref(d1), C.byref(d2), idx.data_ptr(), scale, fin.H // scale, fin.W // scale,
-                                               C.byref(d3), C.byref(d4), C.byref(d5), _stream()), "match_gather_backward")
+    launch("tdvc_match_gather_backward", fin, fref, idx, scale, fin.H // scale, fin.W // scale, dcat, dfin, dfref)
 
 
 # ----------------------------------------------------------------------------- entropy model
@@ -1271,52 +1232,42 @@ def eb_forward(z: FM, params: torch.Tensor, z_hat: FM, bits_out: torch.Tensor, n
     numel = z.N * z.H * z.W * z.C
     cap = (numel + 255) // 256
     partial = torch.empty(cap, dtype=torch.float32, device=z.t.device)
-    dz, dh = z.desc(), z_hat.desc()
-    dn = noise.desc() if noise is not None else None
-    L.check(L.lib().tdvc_eb_forward(C.byref(dz), params.data_ptr(), C.byref(dn) if dn is not None else None, C.byref(dh),
-                                    bits_out.data_ptr(), partial.data_ptr(), cap, _stream()), "eb_forward")
+    launch("tdvc_eb_forward", z, params, noise, z_hat, bits_out, partial, cap)
     _rec("eb_forward", z, params, z_hat, noise)
 
 
 def eb_pack(raw_table: torch.Tensor, quantiles: torch.Tensor, packed: torch.Tensor, Cn: int) -> None:
-    L.check(L.lib().tdvc_eb_pack(raw_table.data_ptr(), quantiles.data_ptr(), packed.data_ptr(), Cn, _stream()), "eb_pack")
+    launch("tdvc_eb_pack", raw_table, quantiles, packed, Cn)
 
 
 def eb_param_chain(dpacked: torch.Tensor, raw_table: torch.Tensor, grad_table: torch.Tensor, scale: float, Cn: int) -> None:
     assert dpacked.is_contiguous() and dpacked.dtype == torch.float32 and tuple(dpacked.shape) == (Cn, 59)
-    L.check(L.lib().tdvc_eb_param_chain(dpacked.data_ptr(), raw_table.data_ptr(), grad_table.data_ptr(), scale, Cn, _stream()), "eb_param_chain")
+    launch("tdvc_eb_param_chain", dpacked, raw_table, grad_table, scale, Cn)
 
 
 def eb_aux(params: torch.Tensor, quantiles: torch.Tensor, target: float, dq: torch.Tensor, loss: torch.Tensor, Cn: int) -> None:
     assert quantiles.is_contiguous() and dq.is_contiguous() and quantiles.numel() == 3 * Cn == dq.numel() and dq.dtype == torch.float32
-    L.check(L.lib().tdvc_eb_aux(params.data_ptr(), quantiles.data_ptr(), target, dq.data_ptr(), loss.data_ptr(), Cn, _stream()), "eb_aux")
+    launch("tdvc_eb_aux", params, quantiles, target, dq, loss, Cn)
 
 
 def eb_backward(z: FM, params: torch.Tensor, noise: FM, gscale: float, dz: FM, dparams: torch.Tensor) -> None:
-    d1, d2, d3 = z.desc(), noise.desc(), dz.desc()
-    L.check(L.lib().tdvc_eb_backward(C.byref(d1), params.data_ptr(), C.byref(d2), gscale, C.byref(d3), dparams.data_ptr(), _stream()), "eb_backward")
+    launch("tdvc_eb_backward", z, params, noise, gscale, dz, dparams)
 
 
 def gc_backward(y: FM, gp: FM, noise: FM, gscale: float, dy: FM, dgp: FM) -> None:
-    d1, d2, d3, d4, d5 = y.desc(), gp.desc(), noise.desc(), dy.desc(), dgp.desc()
-    L.check(L.lib().tdvc_gc_backward(C.byref(d1), C.byref(d2), C.byref(d3), gscale, C.byref(d4), C.byref(d5), _stream()), "gc_backward")
+    launch("tdvc_gc_backward", y, gp, noise, gscale, dy, dgp)
 
 
 def gc_forward(y: FM, gp: FM, bits_out: torch.Tensor, noise: FM | None = None):
     numel = y.N * y.H * y.W * y.C
     cap = (numel + 255) // 256
     partial = torch.empty(cap, dtype=torch.float32, device=y.t.device)
-    dy, dg = y.desc(), gp.desc()
-    dn = noise.desc() if noise is not None else None
-    L.check(L.lib().tdvc_gc_forward(C.byref(dy), C.byref(dg), C.byref(dn) if dn is not None else None,
-                                    bits_out.data_ptr(), partial.data_ptr(), cap, _stream()), "gc_forward")
+    launch("tdvc_gc_forward", y, gp, noise, bits_out, partial, cap)
     _rec("gc_forward", y, gp, noise)
 
 
 def quantize(y: FM, out: FM, noise: FM | None = None) -> FM:
-    dy, do = y.desc(), out.desc()
-    dn = noise.desc() if noise is not None else None
-    L.check(L.lib().tdvc_quantize(C.byref(dy), C.byref(dn) if dn is not None else None, C.byref(do), _stream()), "quantize")
+    launch("tdvc_quantize", y, noise, out)
     _rec("quantize", y, out, noise)
     return out
 
@@ -1325,7 +1276,7 @@ def quantize(y: FM, out: FM, noise: FM | None = None) -> FM:
 def pmf_to_quantized_cdf(pmf: np.ndarray, precision: int = 16) -> np.ndarray:
     p = np.ascontiguousarray(pmf, dtype=np.float32)
     out = np.zeros(p.size + 1, dtype=np.int32)
-    L.check(L.lib().tdvc_pmf_to_quantized_cdf(p.ctypes.data, p.size, precision, out.ctypes.data), "pmf_to_quantized_cdf")
+    launch("tdvc_pmf_to_quantized_cdf", p.ctypes.data, p.size, precision, out.ctypes.data, host=True)
     return out
 
 
@@ -1382,8 +1333,8 @@ class RansDecoder:
     def decode(self, indexes: np.ndarray, t: CdfTables) -> np.ndarray:
         i = np.ascontiguousarray(indexes.reshape(-1), dtype=np.int32)
         out = np.empty(i.size, dtype=np.int32)
-        L.check(L.lib().tdvc_rans_decoder_decode(self._h, i.ctypes.data, i.size, t.cdf.ctypes.data, t.stride,
-                                                 t.sizes.ctypes.data, t.offsets.ctypes.data, out.ctypes.data), "rans_decode")
+        launch("tdvc_rans_decoder_decode", self._h, i.ctypes.data, i.size, t.cdf.ctypes.data, t.stride, t.sizes.ctypes.data, t.offsets.ctypes.data,
+               out.ctypes.data, what="rans_decode", host=True)
         return out
 
     def close(self):
@@ -1421,8 +1372,8 @@ def rans_decode_lanes(data: bytes, indexes: np.ndarray, t: CdfTables) -> np.ndar
     if i.ndim != 2:
         raise ValueError("rans_decode_lanes: indexes must be [npos][M]")
     out = np.empty(i.shape, dtype=np.int32)
-    L.check(L.lib().tdvc_rans_decode_lanes(buf.ctypes.data if buf.size else None, buf.size, i.ctypes.data, i.shape[0], i.shape[1], t.cdf.ctypes.data,
-                                           t.stride, t.sizes.ctypes.data, t.offsets.ctypes.data, out.ctypes.data), "rans_decode_lanes")
+    launch("tdvc_rans_decode_lanes", buf.ctypes.data if buf.size else None, buf.size, i.ctypes.data, i.shape[0], i.shape[1], t.cdf.ctypes.data,
+           t.stride, t.sizes.ctypes.data, t.offsets.ctypes.data, out.ctypes.data, host=True)
     return out
 
 
@@ -1485,7 +1436,7 @@ def rans_encode_lanes_dev_ref(symbols: np.ndarray, indexes: np.ndarray, pos: np.
     enc = L.LanesEncDesc(s.ctypes.data, i.ctypes.data, B, H, W, M, p.ctypes.data, p.shape[0], int(lanes), scratch.ctypes.data, int(lane_words), scratch.size,
                          out.ctypes.data, stride, out.size, info.ctypes.data)
     tabs = L.CdfTablesDesc(t.cdf.ctypes.data, t.sizes.ctypes.data, t.offsets.ctypes.data, t.stride, len(t.sizes))      # `t`: a CdfTables or anything with its four fields
-    L.check(L.lib().tdvc_rans_encode_lanes_dev_ref(C.byref(enc), C.byref(tabs)), "rans_encode_lanes_dev_ref")
+    launch("tdvc_rans_encode_lanes_dev_ref", enc, tabs, host=True)
     if raw:
         return out, info, scratch
     return lanes_strings(out, info, "rans_encode_lanes_dev_ref")
@@ -1522,7 +1473,7 @@ def ar_encode_lanes_batch(symbols: torch.Tensor, indexes: torch.Tensor, pos: tor
     td = t.device(dev)
     enc = L.LanesEncDesc(symbols.data_ptr(), indexes.data_ptr(), B, H, W, M, pos.data_ptr(), pos.shape[0], int(lanes), scratch.data_ptr(), int(lane_words),
                          scratch.numel(), out.data_ptr(), stride, out.numel(), info.data_ptr())
-    L.check(L.lib().tdvc_ar_encode_lanes_batch(C.byref(enc), C.byref(td), _stream()), "ar_encode_lanes_batch")
+    launch("tdvc_ar_encode_lanes_batch", enc, td)
     return LanesEncoding(out, info, scratch, (symbols, indexes, pos, td))
 
 
@@ -1547,7 +1498,7 @@ def ar_chain_kernels(descs: list, rows: int) -> tuple:
     for d0 in descs:
         d = L.ConvDesc.from_buffer_copy(d0)
         d.x.W = d.y.W = rows
-        name = L.lib().tdvc_conv_select(C.byref(d))
+        name = L.lib().tdvc_conv_select(d)
         out.append(name.decode() if name else None)
     return tuple(out)
 
@@ -1574,8 +1525,7 @@ def ar_batch_groups(descs: list, B: int, nmax: int) -> list:
 
 def ar_gather_batch(y_hat: FM, params: FM, pos: torch.Tensor, npos: int, x1: FM, pc: FM):
     assert pos.numel() >= 2 * npos
-    dy, dp, dx, dc = y_hat.desc(), params.desc(), x1.desc(), pc.desc()
-    L.check(L.lib().tdvc_ar_gather_batch(C.byref(dy), C.byref(dp), pos.data_ptr(), npos, C.byref(dx), C.byref(dc), _stream()), "ar_gather_batch")
+    launch("tdvc_ar_gather_batch", y_hat, params, pos, npos, x1, pc)
 
 
 def _ar_rows_ok(a: torch.Tensor, y_hat: FM, cbase: int, npos: int) -> bool:
@@ -1586,18 +1536,12 @@ def ar_quantize_batch(y: FM | None, gp: FM, pos: torch.Tensor, npos: int, table:
                       indexes: torch.Tensor, symbols_in: torch.Tensor | None = None, cbase: int = -1):
     """`cbase` < 0: the arrays are raster [B][H][W][M]; else compact [B][H * W][M], this call's position k at row cbase + k of a block"""
     assert pos.numel() >= 2 * npos and all(_ar_rows_ok(a, y_hat, cbase, npos) for a in (symbols, indexes) + ((symbols_in,) if symbols_in is not None else ()))
-    dg, dh = gp.desc(), y_hat.desc()
-    dy = y.desc() if y is not None else None
-    L.check(L.lib().tdvc_ar_quantize_batch(C.byref(dy) if dy is not None else None, C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(),
-                                           symbols_in.data_ptr() if symbols_in is not None else None, C.byref(dh), symbols.data_ptr(), indexes.data_ptr(),
-                                           cbase, _stream()), "ar_quantize_batch")
+    launch("tdvc_ar_quantize_batch", y, gp, pos, npos, table, table.numel(), symbols_in, y_hat, symbols, indexes, cbase)
 
 
 def ar_indexes_batch(gp: FM, pos: torch.Tensor, npos: int, B: int, table: torch.Tensor, M: int, H: int, W: int, indexes: torch.Tensor, cbase: int = -1):
     assert pos.numel() >= 2 * npos and indexes.dtype == torch.int32 and indexes.numel() >= B * H * W * M and cbase + npos <= H * W
-    dg = gp.desc()
-    L.check(L.lib().tdvc_ar_indexes_batch(C.byref(dg), pos.data_ptr(), npos, B, table.data_ptr(), table.numel(), M, H, W, indexes.data_ptr(), cbase,
-                                          _stream()), "ar_indexes_batch")
+    launch("tdvc_ar_indexes_batch", gp, pos, npos, B, table, table.numel(), M, H, W, indexes, cbase)
 
 
 def _host_strings(strings):
@@ -1638,10 +1582,7 @@ def ar_wavefront_batch(loop: ArLoop, strings, t: CdfTables | None, y: FM | None,
     raster [B][H][W][M]), decoder with `strings` (B byte strings) + `t` (idx / sym [B][H * W][M] in step order)"""
     assert strings is None or len(strings) == y_hat.N
     keep, ptrs, sizes = _host_strings(strings) if strings is not None else (None, None, None)
-    d = loop.desc(y_hat, params, scale_table, idx, sym)
-    dy = y.desc() if y is not None else None
-    L.check(L.lib().tdvc_ar_wavefront_batch(C.byref(d), C.byref(dy) if dy is not None else None, ptrs, sizes, C.byref(t.desc) if t else None, _stream()),
-            "ar_wavefront_batch")
+    launch("tdvc_ar_wavefront_batch", loop.desc(y_hat, params, scale_table, idx, sym), y, ptrs, sizes, t.desc if t else None)
 
 
 def ar_decode_serial_batch(loop: ArLoop, strings, t: CdfTables, y_hat: FM, params: FM, scale_table: torch.Tensor, idx: torch.Tensor, sym: torch.Tensor) -> None:
@@ -1649,8 +1590,7 @@ def ar_decode_serial_batch(loop: ArLoop, strings, t: CdfTables, y_hat: FM, param
     (`tdvc_ar_decode_serial_batch`; `loop`: a raster position list, no step sizes); fills y_hat, idx / sym [B][H][W][M]"""
     assert len(strings) == y_hat.N and loop.step_sizes is None
     keep, ptrs, sizes = _host_strings(strings)
-    d = loop.desc(y_hat, params, scale_table, idx, sym)
-    L.check(L.lib().tdvc_ar_decode_serial_batch(C.byref(d), ptrs, sizes, C.byref(t.desc), _stream()), "ar_decode_serial_batch")
+    launch("tdvc_ar_decode_serial_batch", loop.desc(y_hat, params, scale_table, idx, sym), ptrs, sizes, t.desc)
 
 
 def ar_lanes_batch_layout(sizes, lanes: int):
@@ -1682,8 +1622,7 @@ def ar_lanes_state_batch(lanes: int, B: int, device) -> torch.Tensor:
 def ar_lanes_init_batch(streams_dev: torch.Tensor, B: int, lanes: int, state: torch.Tensor) -> None:
     """lane states of B containers from their length tables; `streams_dev` as `ar_lanes_pack_batch` lays it out (table at its head)"""
     assert streams_dev.dtype == torch.uint8 and streams_dev.numel() >= 16 and state.numel() * 4 >= B * L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
-    L.check(L.lib().tdvc_ar_lanes_init_batch(streams_dev.data_ptr(), streams_dev.numel(), streams_dev.data_ptr(), B, int(lanes), state.data_ptr(), _stream()),
-            "ar_lanes_init_batch")
+    launch("tdvc_ar_lanes_init_batch", streams_dev, streams_dev.numel(), streams_dev, B, int(lanes), state)
 
 
 def ar_decode_lanes_step_batch(gp: FM, pos: torch.Tensor, npos: int, table: torch.Tensor, streams_dev: torch.Tensor, lanes: int, t: CdfTables,
@@ -1694,10 +1633,8 @@ def ar_decode_lanes_step_batch(gp: FM, pos: torch.Tensor, npos: int, table: torc
     td = t.device(y_hat.t.device)
     assert streams_dev.dtype == torch.uint8 and state.numel() * 4 >= y_hat.N * L.lib().tdvc_ar_lanes_state_bytes(int(lanes))
     assert pos.numel() >= 2 * npos and _ar_rows_ok(symbols, y_hat, cbase, npos) and _ar_rows_ok(indexes, y_hat, cbase, npos)
-    dg, dh = gp.desc(), y_hat.desc()
-    L.check(L.lib().tdvc_ar_decode_lanes_step_batch(C.byref(dg), pos.data_ptr(), npos, table.data_ptr(), table.numel(), streams_dev.data_ptr(),
-                                                    streams_dev.numel(), streams_dev.data_ptr(), int(lanes), C.byref(td), state.data_ptr(), C.byref(dh),
-                                                    symbols.data_ptr(), indexes.data_ptr(), cbase, _stream()), "ar_decode_lanes_step_batch")
+    launch("tdvc_ar_decode_lanes_step_batch", gp, pos, npos, table, table.numel(), streams_dev, streams_dev.numel(), streams_dev, int(lanes), td, state,
+           y_hat, symbols, indexes, cbase)
 
 
 def ar_wavefront_lanes_batch(loop: ArLoop, strings, t: CdfTables, stream_dev: torch.Tensor, state: torch.Tensor, y_hat: FM, params: FM, scale_table: torch.Tensor,
@@ -1707,10 +1644,9 @@ def ar_wavefront_lanes_batch(loop: ArLoop, strings, t: CdfTables, stream_dev: to
     a damaged stream raises TdvcStreamError (a ValueError) whose `image` is the first image of the call whose error word is set"""
     assert len(strings) == y_hat.N and stream_dev.dtype == torch.uint8 and state.numel() * 4 >= y_hat.N * L.lib().tdvc_ar_lanes_state_bytes(lanes_of(strings[0]))
     keep, ptrs, nbytes = _host_strings(strings)
-    d = loop.desc(y_hat, params, scale_table, idx, sym)
     bad = C.c_int32(-1)
-    rc = L.lib().tdvc_ar_wavefront_lanes_batch(C.byref(d), ptrs, nbytes, stream_dev.data_ptr(), stream_dev.numel(), state.data_ptr(),
-                                               C.byref(t.device(y_hat.t.device)), C.byref(bad), _stream())
+    rc = launch("tdvc_ar_wavefront_lanes_batch", loop.desc(y_hat, params, scale_table, idx, sym), ptrs, nbytes, stream_dev, stream_dev.numel(), state,
+                t.device(y_hat.t.device), bad, check=False)
     if rc != 0 and bad.value >= 0:
         e = L.TdvcStreamError(L.lib().tdvc_last_error().decode("utf-8", "replace"))
         e.image = bad.value
@@ -1720,8 +1656,7 @@ def ar_wavefront_lanes_batch(loop: ArLoop, strings, t: CdfTables, stream_dev: to
 
 def round_symbols(z: FM, median: torch.Tensor) -> torch.Tensor:
     out = torch.empty((z.N, z.H, z.W, z.C), dtype=torch.int32, device=z.t.device)
-    dz = z.desc()
-    L.check(L.lib().tdvc_round_symbols(C.byref(dz), median.data_ptr(), out.data_ptr(), _stream()), "round_symbols")
+    launch("tdvc_round_symbols", z, median, out)
     return out
 
 
@@ -1749,7 +1684,6 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh
         raise RuntimeError("dcn_v2_forward: offset/mask shape mismatch")
     out = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=input.device)
     with torch.cuda.device(input.device):
-        L.check(L.lib().tdvc_dcn_v2_forward_f32(input.data_ptr(), weight.data_ptr(), bias.data_ptr(), offset.data_ptr(),
-                                                mask.data_ptr(), out.data_ptr(), B, Cc, H, W, Cout, kh, kw, sh, sw, ph, pw,
-                                                dh, dw, deformable_group, _stream()), "dcn_v2_forward")
+        launch("tdvc_dcn_v2_forward_f32", input, weight, bias, offset, mask, out, B, Cc, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
+               what="dcn_v2_forward")
     return out

@@ -217,8 +217,8 @@ def _forms(net):
         seen.add(id(pc))
         out.append((name, pc))
         walk(name + " dgrad", pc.dgrad)
-        walk(name + " plain", pc.__dict__.get("_plain"))
-        walk(name + " column", pc.__dict__.get("_colpc"))
+        walk(name + " plain", pc.plain)
+        walk(name + " column", pc.column)
     for mname, m in net.named_modules():
         for key, pc in m.__dict__.get("_packed", {}).items():
             if isinstance(pc, ops.PackedConv):
@@ -296,7 +296,7 @@ def test_switching_a_trained_model_to_fp32_coders(report):
     batch = net.__dict__["_pack_batch"]
     assert not step(x, refs)["skipped"]
     assert net.__dict__["_pack_batch"] is batch, "a default-mode step rebuilt the batched re-pack although no layer form was new"
-    late = [n for n, pc in _forms(net.mvCoder) + _forms(net.resCoder) if pc.s2d and "_plain" not in pc.__dict__]
+    late = [n for n, pc in _forms(net.mvCoder) + _forms(net.resCoder) if pc.s2d and pc.plain is None]
     assert late, "no coder layer is in space-to-depth form only: the case this test is about does not occur at this size"
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
