@@ -169,6 +169,14 @@ const char* tdvc_conv_select(const tdvc_conv_desc* d);
  * accumulation on v_mfma_f32_32x32x2_f32; aux / residual / output fmaps fp32 or fp16.  tdvc_conv2d forwards here
  * when d->x.dtype == TDVC_F32, so fixed descriptor chains (tdvc_ar_decode_serial_batch) run in either precision. */
 int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream);
+/* ABI 17.  tdvc_conv2d_f32's contract on the bf16 matrix pipe (csrc/conv_split.hip): the same descriptors are accepted and rejected, the
+ * same epilogue runs, `w` = the three-plane bf16 packing (tdvc_pack_conv_weights_indexed_bf16x3).  Every fp32 operand is split exactly
+ * into three bf16 parts (v == h + m + l for every normal fp32 value below bf16's overflow threshold of about 3.39e38; the l part of values below about 2^-110
+ * underflows; an operand that is Inf, or finite above that threshold, yields NaN where tdvc_conv2d_f32 yields Inf or a finite sum) and a MAC is the
+ * fp32 sum of six exact products on v_mfma_f32_32x32x16_bf16; the three dropped cross terms are below (2 u^3 + u^4) |x| |w| per product,
+ * u = 2^-8.  Results are fp32-grade but NOT bit-equal to tdvc_conv2d_f32's.  Strictly opt-in: tdvc_conv2d and tdvc_conv_select never
+ * choose it.  tdvc_last_conv_kernel() reports "conv_split". */
+int tdvc_conv2d_split(const tdvc_conv_desc* d, void* stream);
 
 /* ---------------------------------------------------------------- fused conv pair
  * y = act2(conv2(act1(conv1(x)))) [+ x] [+ res2] for two 3x3 / stride 1 / pad 1 / 64 -> 64 convs in one launch, the
@@ -550,6 +558,13 @@ int tdvc_pack_conv_weights_indexed(const float* w, const int32_t* row_off, const
 int tdvc_pack_conv_weights_indexed_f32(const float* w, const int32_t* row_off, const int32_t* chan_off, const int32_t* tap_off,
                                        const uint8_t* row_mask, const uint8_t* chan_mask, const uint8_t* tap_mask,
                                        int cout, int cin, int ntaps, int ck, float* dst, void* stream);
+/* ABI 17.  Split twin of the packing for tdvc_conv2d_split: same arguments and item order; per item (the 8 values of one lane) three 16-byte
+ * bf16 fragments h = bf16(w), m = bf16(w - h), l = bf16((w - h) - m), round-to-nearest-even each, stored as
+ * [cout tile][k-step = chunk * steps + step][plane h, m, l][lane 64][8 bf16]: 3 x tdvc_conv_packed_bytes bytes, every plane of a k-step one
+ * contiguous 1 KB line. */
+int tdvc_pack_conv_weights_indexed_bf16x3(const float* w, const int32_t* row_off, const int32_t* chan_off, const int32_t* tap_off,
+                                          const uint8_t* row_mask, const uint8_t* chan_mask, const uint8_t* tap_mask,
+                                          int cout, int cin, int ntaps, int ck, void* dst, void* stream);
 /* The same for many layers in one launch (after an optimizer step every packed layer follows its parameters).  `jobs`
  * and `block_start` (njobs + 1 prefix sums of tdvc_pack_job_blocks) are DEVICE arrays; a job with bias_src also
  * gathers its bias: bias_dst[i] = bias_src[bias_perm ? bias_perm[i] : i], i < cout. */

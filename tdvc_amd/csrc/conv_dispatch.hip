@@ -301,6 +301,8 @@ int conv2d_impl(const tdvc_conv_desc* d, void* stream, int query) {
 // A fused launch outside tdvc_conv2d that stands for `launches` of its launches (tdvc_lf_tail): the launches behind it walk in the
 // direction they had behind the unfused sequence, so results that depend on the walk (tdvc_conv_desc::chan_sum partials) keep their bytes.
 void tdvc_conv_walk_advance(int launches) { g_walk_parity += (unsigned)launches; }
+// a conv entry point outside tdvc_conv2d (tdvc_conv2d_split) names its kernel for tdvc_last_conv_kernel()
+void tdvc_set_last_conv_kernel(const char* name) { snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", name); }
 
 extern "C" void tdvc_debug_set_conv_walk(int mode) { g_walk_mode = mode; }
 extern "C" int tdvc_conv2d(const tdvc_conv_desc* d, void* stream) { return conv2d_impl(d, stream, LAUNCH); }

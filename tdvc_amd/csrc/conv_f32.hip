@@ -256,12 +256,9 @@ int conv_f32_validate(const tdvc_conv_desc* d, int& Ho, int& Wo) {
   return TDVC_OK;
 }
 
-// tdvc_conv2d forwards here when the input fmap is fp32 (`d->w` then points at the fp32 packing).
-extern "C" int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream) {
-  int Ho, Wo;
-  if (const int rc = conv_f32_validate(d, Ho, Wo)) return rc;
-
-  ConvParams p;
+// launch parameters of a validated fp32-input descriptor (conv_f32 and conv_split.hip): ConvParams without x / w, which are typed half_t*
+// there, the tile count of the padded cout and the flattened pixel count
+void conv_f32_params(const tdvc_conv_desc* d, int Ho, int Wo, ConvParams& p, int& cout_tiles, int& total_px) {
   memset(&p, 0, sizeof(p));
   p.x = nullptr; p.x_sn = d->x.sn; p.x_sp = d->x.sp;
   p.H = d->x.H; p.W = d->x.W; p.Cin = d->x.C;
@@ -272,19 +269,27 @@ extern "C" int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream) {
   p.res2 = d->res2.p ? to_dev(d->res2) : null_fmap();
   p.ntaps = d->ntaps; p.kh = d->kh; p.kw = d->kw; p.pad = d->pad;
   p.in_stride = d->stride;
-  const int ck8 = d->ck / 8;
   p.nchunks = (d->x.C + d->ck - 1) / d->ck;
-  p.steps = (d->ntaps * ck8 + 1) / 2;
+  p.steps = (d->ntaps * (d->ck / 8) + 1) / 2;
   p.square = d->square_input; p.gdn = d->gdn; p.act = d->act; p.slope = d->slope;
   p.round16 = 0; p.out_mode = d->out_mode;
   memcpy(p.tap_dy, d->tap_dy, sizeof(p.tap_dy));
   memcpy(p.tap_dx, d->tap_dx, sizeof(p.tap_dx));
+  cout_tiles = cout_tiles32(d->cout);
+  total_px = d->x.N * Ho * Wo;
+}
+
+// tdvc_conv2d forwards here when the input fmap is fp32 (`d->w` then points at the fp32 packing).
+extern "C" int tdvc_conv2d_f32(const tdvc_conv_desc* d, void* stream) {
+  int Ho, Wo;
+  if (const int rc = conv_f32_validate(d, Ho, Wo)) return rc;
+
+  ConvParams p;
   F32Extra e;
+  conv_f32_params(d, Ho, Wo, p, e.cout_tiles, e.total_px);
   e.x = reinterpret_cast<const float*>(d->x.p);
   e.w = reinterpret_cast<const float*>(d->w);
-  e.ck8 = ck8;
-  e.cout_tiles = cout_tiles32(d->cout);
-  e.total_px = d->x.N * Ho * Wo;
+  e.ck8 = d->ck / 8;
   // workgroup = 2 x (NT * 32) pixels by 2 x MT cout tiles; small maps keep NT = 1 so that the few pixels still spread over the CUs
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool big = e.total_px >= 16384;

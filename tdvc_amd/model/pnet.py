@@ -10,6 +10,8 @@ matching and rate terms.  There is no PyTorch/CPU fallback: tensors must live on
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 import torch.nn as nn
 
@@ -25,6 +27,16 @@ def _ref_views(refs8: FM, B: int):
     return (FM(refs8.t, refs8.off + 3 * refs8.sn, B, refs8.C, 4 * refs8.sn), FM(refs8.t, refs8.off, B, refs8.C, 4 * refs8.sn))
 
 
+def _under_f32_split(fn):
+    """forward / encode / decode run their convs of fp32 maps as `VideoCompressor.f32_split` says (or an enclosing ops.f32_split block).
+    The model's flag is an inference / coding switch: a .train() forward ignores it, with or without a recording tape"""
+    @functools.wraps(fn)
+    def run(self, *a, **kw):
+        with ops.f32_split((self.f32_split and not self.training) or ops.F32_SPLIT):
+            return fn(self, *a, **kw)
+    return run
+
+
 class VideoCompressor(nn.Module):
     fp32_islands_supported = True
 
@@ -37,6 +49,13 @@ class VideoCompressor(nn.Module):
         # `enable_amp: True` (cfg/predict.yaml) keeps fp32 coders; here that value selects the fp16-in coders, so the reference-faithful
         # setting is coder_fp32 = True (tools/predict: yaml key `coder_fp32: true` or --coder-fp32), independent of `enabled_amp`
         self.coder_fp32 = False
+        # the convs of fp32 maps (wherever `enabled_amp=False`, `coder_fp32` or `model_fp32` make some) on conv_split instead of conv_f32:
+        # every fp32 operand split exactly into three bf16 parts, six exact products per MAC on the bf16 matrix pipe (csrc/conv_split.hip,
+        # DESIGN.md section 4c).  fp32-grade results, not bit-equal to conv_f32's: the strings are NOT promised byte-equal to the default
+        # fp32 islands' or the oracle's beyond rounding ties, and, like `coder_fp32`, the ENCODER AND THE DECODER MUST AGREE on the flag.
+        # Inference / coding only (under the tape nothing changes); the context loop's native chains stay on conv_f32.  No effect
+        # without fp32 maps.  tools/predict: yaml key `f32_split: true` or --f32-split
+        self.f32_split = False
         # training with fp32 coders (what the reference's tools/train.py optimises): a .train() forward keeps both coders in fp32 and the
         # tape differentiates them in fp32 (conv_f32 dgrad, conv_wgrad_f32).  Set by TrainStep(coder_fp32=True).  Unset, a .train()
         # forward runs the fp16-in / fp32-accumulate coders whatever `enabled_amp` / `coder_fp32` say (with a warning)
@@ -89,6 +108,7 @@ class VideoCompressor(nn.Module):
         return super()._apply(fn, *a, **kw)
 
     # ----------------------------------------------------------------------------------------
+    @_under_f32_split
     def forward(self, input_image, refer_frames, enabled_amp=True, is_compress=False, trace=None, noise=None):
         noise = noise or {}            # test hook: {"mv": {...}, "res": {...}} of fp32 FMs replaces the coders' training-mode draws
         mf32 = self._model_fp32_checked()
@@ -229,6 +249,7 @@ class VideoCompressor(nn.Module):
             return f
         return FM(torch.cat([f.t[..., f.off:f.off + f.C] if (f.off or f.C != f.t.shape[3]) else f.t for f in fms], 0).contiguous())
 
+    @_under_f32_split
     @torch.no_grad()
     def encode(self, input_image, refer_frames):
         """-> {"strings": [mv_y, mv_z, res_y, res_z] (lists over the batch), "shapes": z shapes, "recon": (B,3,H,W)}.
@@ -253,6 +274,7 @@ class VideoCompressor(nn.Module):
         mvs, rss = mv["strings"].result(), rs["strings"].result()                     # join the range coders
         return {"strings": [mvs[0], mvs[1], rss[0], rss[1]], "shapes": [mv["shape"], rs["shape"]], "recon": recon[0] if len(recon) == 1 else torch.cat(recon, 0)}
 
+    @_under_f32_split
     @torch.no_grad()
     def decode(self, strings, shapes, refer_frames):
         """inverse of encode(): strings [mv_y, mv_z, res_y, res_z] + z shapes + the reference list -> (B,3,H,W)"""

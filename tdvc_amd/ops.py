@@ -297,6 +297,8 @@ class PackedConv:
     owner: object | None = None            # module that maps this layer's weight gradient to its own parameters (GDN)
     w32: torch.Tensor | None = None        # fp32 twin of `w` for the fp32 islands (conv_f32.hip), packed on first use
     w32_buf: torch.Tensor | None = None    # the buffer of a twin that a re-pack of `w` made stale: the next packed_f32() fills it again
+    wsplit: torch.Tensor | None = None     # three-plane bf16 twin of `w` for ops.f32_split (conv_split.hip), packed on first use
+    wsplit_buf: torch.Tensor | None = None  # as w32_buf
     column: "PackedConv | None" = None     # lazily built: the DCN weight as a 1x1 conv over sampled columns (ops.dcn_column_conv)
     plain: "PackedConv | None" = None      # lazily built: the plain stride-2 3x3 packing of a space-to-depth layer (ops._plain_form)
     # --- what is derived from the layer without being a packed form: nothing to re-pack
@@ -325,11 +327,20 @@ class PackedConv:
             self.w32, self.w32_buf = _pack_from_tables_f32(self.wsrc, self.tables, self.w32_buf), None
         return self.w32
 
+    def packed_split(self) -> torch.Tensor:
+        """the same item order as `w`, every value split exactly into three bf16 parts (tdvc_pack_conv_weights_indexed_bf16x3: per k-step
+        the h, m and l planes).  Built and made stale exactly as `packed_f32()`"""
+        if self.wsplit is None:
+            self.wsplit, self.wsplit_buf = _pack(self.wsrc, self.tables, self.wsplit_buf, "bf16x3"), None
+        return self.wsplit
+
     def stale_f32(self):
-        """`w` was re-packed from updated parameters: the fp32 twin (if one was ever built) follows on its next use.  No launch here: a
-        default-mode training step never pays for twins it does not use"""
+        """`w` was re-packed from updated parameters: the fp32 twins (the float and the split one, if ever built) follow on their next use.
+        No launch here: a default-mode training step never pays for twins it does not use"""
         if self.w32 is not None:
             self.w32_buf, self.w32 = self.w32, None
+        if self.wsplit is not None:
+            self.wsplit_buf, self.wsplit = self.wsplit, None
 
     def repack(self):
         """re-pack from the (updated) fp32 parameters, the derived forms too: per form one kernel launch, plus the bias gather"""
@@ -364,30 +375,35 @@ def _s2d_weights(w: torch.Tensor) -> torch.Tensor:
     return w2
 
 
-def _pack(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None, f32: bool) -> torch.Tensor:
-    """the weight in the tables' fragment order, as halves in a byte blob or (`f32`) as floats; into `dst` when one is given"""
+_PACK_FORMS = {"f16": "tdvc_pack_conv_weights_indexed", "f32": "tdvc_pack_conv_weights_indexed_f32", "bf16x3": "tdvc_pack_conv_weights_indexed_bf16x3"}
+
+
+def _pack(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None, form: str) -> torch.Tensor:
+    """the weight in the tables' fragment order: as halves in a byte blob ("f16"), as floats ("f32") or as three bf16 planes per k-step
+    ("bf16x3"); into `dst` when one is given"""
     nbytes = L.lib().tdvc_conv_packed_bytes(tb.cout, tb.cin, len(tb.taps), tb.ck)
     assert nbytes > 0
     w = wsrc.detach()
     assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
-    if f32:                                       # a passed buffer is reused only when it fits
-        if dst is None or dst.numel() != nbytes // 2 or dst.device != w.device:
-            dst = torch.empty(nbytes // 2, dtype=torch.float32, device=w.device)      # 8 floats where the fp16 blob has 8 halves
+    if form != "f16":                             # a passed buffer is reused only when it fits
+        n, dt = (nbytes // 2, torch.float32) if form == "f32" else (3 * nbytes // 2, torch.bfloat16)      # per 8 halves: 8 floats / 3 x 8 bf16
+        if dst is None or dst.numel() != n or dst.device != w.device:
+            dst = torch.empty(n, dtype=dt, device=w.device)
     else:
         if dst is None:
             dst = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
         assert dst.numel() == nbytes
-    launch("tdvc_pack_conv_weights_indexed_f32" if f32 else "tdvc_pack_conv_weights_indexed", w, tb.row_off, tb.chan_off, tb.tap_off,
+    launch(_PACK_FORMS[form], w, tb.row_off, tb.chan_off, tb.tap_off,
            tb.row_mask, tb.chan_mask, tb.tap_mask, tb.cout, tb.cin, len(tb.taps), tb.ck, dst)
     return dst
 
 
 def _pack_from_tables(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None = None) -> torch.Tensor:
-    return _pack(wsrc, tb, dst, False)
+    return _pack(wsrc, tb, dst, "f16")
 
 
 def _pack_from_tables_f32(wsrc: torch.Tensor, tb: convpack.PackTables, dst: torch.Tensor | None = None) -> torch.Tensor:
-    return _pack(wsrc, tb, dst, True)
+    return _pack(wsrc, tb, dst, "f32")
 
 
 class _PackJob(C.Structure):
@@ -542,6 +558,30 @@ def _conv_template(pc: PackedConv, wt: torch.Tensor) -> L.ConvDesc:
     return t_
 
 
+F32_SPLIT = False         # inside `with f32_split(True)`: conv() runs fp32 maps on conv_split (six bf16 MFMA products) instead of conv_f32
+
+
+class f32_split:
+    """`with ops.f32_split(True):` -- every conv() of an fp32 map inside the block that no tape records launches `tdvc_conv2d_split`
+    (csrc/conv_split.hip: each fp32 operand split exactly into three bf16 parts, a MAC the fp32 sum of six exact products on the bf16
+    matrix pipe) with the layer's `packed_split()` weights instead of conv_f32.  fp32-grade, not bit-equal to conv_f32: an encoder and its
+    decoder must run under the same setting.  fp16 maps, recorded (training) convs, `conv_desc()` and the native descriptor chains built
+    from it are not affected.  Nests; `f32_split(False)` switches it off inside an enabled block."""
+
+    def __init__(self, enable: bool):
+        self.enable = bool(enable)
+
+    def __enter__(self):
+        global F32_SPLIT
+        self.prev, F32_SPLIT = F32_SPLIT, self.enable
+        return self
+
+    def __exit__(self, *exc):
+        global F32_SPLIT
+        F32_SPLIT = self.prev
+        return False
+
+
 def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None,
               res2: FM | None = None, gdn=GDN_NONE, aux: FM | None = None, square=False, out_dtype=None,
               round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0):
@@ -607,7 +647,11 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
     `chan_sum` (inference only): a list; when the kernel this conv dispatches to can sum the values it stores per channel
     (tdvc_conv_desc::chan_sum), (partial [N][rows][cout] fp32, rows) is appended -- the input of `se_gate(..., partial=)`;
     left empty otherwise (the caller then sums with tdvc_channel_sum)."""
+    split = x.f32 and F32_SPLIT and TAPE is None       # ops.f32_split: inference convs of fp32 maps on the bf16 matrix pipe
+    entry = "tdvc_conv2d_split" if split else "tdvc_conv2d"
     d, ret, Ho, Wo, pc, rec_pc = conv_desc(x, pc, out, act, slope, res, res2, gdn, aux, square, out_dtype, round16, nchw_out, bcast_T, bcast_slope)
+    if split:                                     # conv_desc() never selects the split form: the descriptor it built is conv_f32's, and
+        d.w = pc.packed_split().data_ptr()        # only this launch swaps the weights (the layer's form `pc`, as conv_desc chose it)
     if chan_sum is not None and TAPE is None and FUSE_CHAN_SUM:
         rows = L.lib().tdvc_conv_chan_sum_rows(d)
         if rows > 0:
@@ -622,17 +666,17 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
         d.flow = flow.desc()
         if L.lib().tdvc_conv_flow_supported(d) != 1:       # another kernel: the conv as it is, then one pass over its output
             d.flow = _NULL_FM
-            launch("tdvc_conv2d", d)
+            launch(entry, d)
             _log_predicated()
             add_flow(ret, flow)
             return ret
     if PROFILE is None:
-        launch("tdvc_conv2d", d)
+        launch(entry, d)
         _log_predicated()
     else:                                         # the kernel's name is known behind the launch; a profiled call does not log its predicate
         _profiled(lambda: L.lib().tdvc_last_conv_kernel().decode(),
                   f"{pc.kh}x{pc.kw} s{pc.stride} {x.C}->{pc.cout} @{x.H}x{x.W}" + (" f32out" if out_dtype == torch.float32 else "") + (" nchw" if nchw_out is not None else ""),
-                  2.0 * x.N * Ho * Wo * pc.cout * x.C * len(pc.taps), lambda: launch("tdvc_conv2d", d),
+                  2.0 * x.N * Ho * Wo * pc.cout * x.C * len(pc.taps), lambda: launch(entry, d),
                   flops_real=(x.N * Ho * Wo * pc.flops_per_px) if pc.s2d else 2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(pc.taps),
                   bytes=2.0 * x.N * (x.H * x.W * x.C + Ho * Wo * pc.cout * (4 if pc.shuffle else 1) / (4 if pc.shuffle else 1)))
     _rec("conv", x, rec_pc, None if nchw_out is not None else ret, act, slope, res, res2, gdn, aux, square, nchw_out)

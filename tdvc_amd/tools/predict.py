@@ -130,6 +130,9 @@ def main():
     ap.add_argument("--coder-fp32", action="store_true", help="both coders as fp32 islands (the reference's precision), also with enable_amp: True")
     ap.add_argument("--model-fp32", action="store_true", help="every stage on fp32 maps with fp32 weights (the reference's enable_amp: False; "
                                                               "VideoCompressor.model_fp32): the parity mode, bound by the fp32 matrix pipe")
+    ap.add_argument("--f32-split", action="store_true", help="the convs of fp32 maps (--coder-fp32, --model-fp32, enable_amp: False) as six bf16 MFMA "
+                                                             "products (VideoCompressor.f32_split): fp32-grade, strings not promised byte-equal "
+                                                             "to the default fp32 islands'; encoder and decoder must agree")
     a = ap.parse_args()
     if a.gop_batch < 1 or (a.gop_batch > 1 and not a.bitstream_dir):
         ap.error("--gop-batch needs a value >= 1 and, above 1, --bitstream-dir (it batches the real coding)")
@@ -157,6 +160,8 @@ def main():
     net.coder_fp32 = bool(opt.get("coder_fp32", False)) or a.coder_fp32
     # `model_fp32: true` (an extra yaml key, or --model-fp32): the whole model in fp32, what the reference computes with `enable_amp: False`
     net.model_fp32 = bool(opt.get("model_fp32", False)) or a.model_fp32
+    # `f32_split: true` (an extra yaml key, or --f32-split): those fp32 convs on the bf16 matrix pipe
+    net.f32_split = bool(opt.get("f32_split", False)) or a.f32_split
     net.stream_order = a.stream_order
     net.stream_lanes = a.stream_lanes
     net.stream_coder = a.range_coder
@@ -208,6 +213,8 @@ def main():
                "psnr": sum(s["psnr"] for s in allstats) / n, "msssim": sum(s["msssim"] for s in allstats) / n, "seconds": time.time() - t0, "cfg": opt}
         if net.model_fp32:
             res["model_fp32"] = True
+        if net.f32_split:
+            res["f32_split"] = True
         timed = [s for s in allstats if "encode_s" in s]
         if timed:
             res.update(stream_order=a.stream_order, **({"stream_lanes": a.stream_lanes} if a.stream_order == "lanes" else {}),
