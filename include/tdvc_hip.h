@@ -616,6 +616,19 @@ int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, int cout, i
                              const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
                              float* work, int64_t work_floats, tdvc_wgrad_reduce_job* job, void* stream);
 int tdvc_wgrad_reduce_batch(const tdvc_wgrad_reduce_job* jobs, const int32_t* block_start, int njobs, int total_blocks, void* stream);
+/* The split forms of tdvc_conv_wgrad_bias / tdvc_conv_wgrad_partials (csrc/conv_backward.hip, conv_wgrad_split_kernel): fp32 g and x (both;
+ * C % 8 == 0, 16-byte aligned pixels; anything else is an error before any launch), every value split exactly into three bf16 parts and a MAC
+ * the fp32 sum of six products on the bf16 matrix pipe (tdvc_conv2d_split's arithmetic; db is the plain fp32 sum of g).  fp32-grade, not
+ * bit-equal to the fp32 kernel.  Same workspace (tdvc_conv_wgrad_work_floats), same job, same second stage; a window / stride whose
+ * three-plane tiles do not fit the LDS is refused. */
+int tdvc_conv_wgrad_bias_split(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
+                               int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
+                               const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
+                               float* work, int64_t work_floats, void* stream);
+int tdvc_conv_wgrad_partials_split(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
+                                   int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
+                                   const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
+                                   float* work, int64_t work_floats, tdvc_wgrad_reduce_job* job, void* stream);
 
 /* out = g * act'(z), ReLU / LeakyReLU, the sign of z taken from the stored output (y - res); out may alias g. */
 int tdvc_act_backward(const tdvc_fmap* g, const tdvc_fmap* y, const tdvc_fmap* res, int act, float slope, const tdvc_fmap* out, void* stream);

@@ -168,6 +168,8 @@ SIGNATURES = {
     "tdvc_conv_wgrad": (_i, [_FM, _FM] + [_i] * 6 + [_P] * 5 + [_i, _f, _P, _P, _i64, _P]),
     "tdvc_conv_wgrad_bias": (_i, [_FM, _FM] + [_i] * 6 + [_P] * 5 + [_i, _f, _P, _P, _P, _P, _i64, _P]),
     "tdvc_conv_wgrad_partials": (_i, [_FM, _FM] + [_i] * 6 + [_P] * 5 + [_i, _f, _P, _P, _P, _P, _i64, C.POINTER(WgradReduceJob), _P]),
+    "tdvc_conv_wgrad_bias_split": (_i, [_FM, _FM] + [_i] * 6 + [_P] * 5 + [_i, _f, _P, _P, _P, _P, _i64, _P]),
+    "tdvc_conv_wgrad_partials_split": (_i, [_FM, _FM] + [_i] * 6 + [_P] * 5 + [_i, _f, _P, _P, _P, _P, _i64, C.POINTER(WgradReduceJob), _P]),
     "tdvc_wgrad_reduce_batch": (_i, [_P, _P, _i, _i, _P]),
     "tdvc_gdn_backward": (_i, [_FM, _FM, _FM, _i, _FM, _FM, _P]),
     "tdvc_mul2_accumulate": (_i, [_FM, _FM, _FM, _P]),

@@ -101,6 +101,7 @@ class Tape:
         # executed after the sweep AND after join(), when no MFMA kernel runs on the side stream any more -- torch's own device code is
         # built WITH packed-FP32 instructions, and its softplus kernels contain the `v_pk_*_f32 ... op_sel:[0,1]` form that returned
         # wrong values next to a concurrent MFMA stream (profiles/r04_torch_packed_fp32_scan.txt)
+        self.f32_split_train = False              # set by a forward under VideoCompressor.train_f32_split: backward() sweeps under ops.f32_split_train
         self.fused_aux = False                    # the owner takes the auxiliary loss's gradient from EntropyBottleneck.loss_fused (coder.aux_loss)
         self.touched: set = set()                 # activation buffers whose gradient mirror has been handed out
         self.pending: dict = {}                   # buffer -> (view, identity gradient) not yet added to its mirror (add_identity)
@@ -243,6 +244,11 @@ class Tape:
 
     # ------------------------------------------------------------------ the backward sweep
     def backward(self):
+        # a tape whose forward ran under VideoCompressor.train_f32_split sweeps under the same switch (ops.f32_split_train)
+        with ops.f32_split_train(self.f32_split_train or ops.F32_SPLIT_TRAIN):
+            self._sweep()
+
+    def _sweep(self):
         prev, ops._IN_BACKWARD = ops._IN_BACKWARD, True
         try:
             self.n_backward_nodes = len(self.nodes)

@@ -13,6 +13,16 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// The split rule of conv_split.hip and conv_wgrad_split_kernel: v == h + m + l, each part the round-to-nearest-even bf16 of what the parts
+// before it left (v_cvt_pk_bf16_f32); both subtractions are exact in fp32 (the library is built with -ffp-contract=off)
+__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
+  h = (__bf16)v;
+  const float r1 = v - (float)h;
+  m = (__bf16)r1;
+  l = (__bf16)(r1 - (float)m);
+}
 
 void tdvc_set_error(const char* fmt, ...);
 // per-device scratch (lib.cpp): >= 4 KB of zeros nobody writes, >= 16 KB dump page nobody reads; 0 or a HIP error code

@@ -12,6 +12,8 @@
 //     column-major), two reads per 32x16 operand fragment.  One workgroup owns a (64 co x 32 ci x <= 12 taps)
 //     block of dW in registers and walks a strided set of 8x32-pixel blocks; partial results go to a
 //     workspace and are reduced in a fixed order (bitwise reproducible, no float atomics).
+//     fp32 maps: conv_wgrad_f32_kernel (the fp32 matrix pipe, operands straight from global memory), or, through the entry points
+//     tdvc_conv_wgrad_*_split, conv_wgrad_split_kernel (six bf16 MFMA products per MAC, three-plane LDS tiles).
 #include "common.h"
 
 namespace {
@@ -490,6 +492,253 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const WgradParams p
   }
 }
 
+// The split form (fp32 training on the bf16 matrix pipe): fp32 dY and X maps as conv_wgrad_f32_kernel takes them,
+// the contraction on v_mfma_f32_32x32x16_bf16 with conv_split.hip's arithmetic.  Every value is split exactly into three bf16 parts
+// (split3: h + m + l == v) and a MAC g * x is the fp32 sum of the six products  gh xh + gh xm + gm xh + gm xm + gh xl + gl xh;  the three
+// dropped terms are below (2 u^3 + u^4) |g| |x|, u = 2^-8.  gh xh goes to one accumulator set, the five small products to a second one,
+// and the two are added once in front of the store (conv_split.hip: a small product added to the large running sum would be rounded at
+// the sum's ulp).
+// The contraction index is the pixel, so the bf16 fragments need conv_wgrad_kernel's transpose: tiles travel global -> registers -> LDS,
+// the border / padding-channel mask (a select: a clamped address that holds Inf contributes exact zeros), the fp32 square of `square_x`
+// (one rounding, as conv_f32's GDN pool) and the split are applied ONCE per workgroup at the LDS write, into three planes per tile with
+// conv_wgrad_kernel's pixel strides, and fragments are read with ds_read_b64_tr_b16 (any 16-bit element).  Three planes of an 8 x 32
+// block do not fit the LDS, so the host's 8 x 32 block walk (worker counts, workspace) is kept and a block is processed in sub-tiles
+// of 4 x SW output pixels, SW = 32 or 16 by geometry (the launcher's plan); sub-tiles without a pixel inside the map are skipped.
+// The bias gradient is the fp32 sum of the dY values as loaded (masked), not of their parts.  Same decomposition, grid, workspace and
+// second stage as the two kernels above; waves without a tap (1-tap layers: three of four) stage tiles and skip the contraction.
+constexpr int WS_TH = 4;                        // output rows of a sub-tile
+
+__device__ __forceinline__ short4v tr_read16(const unsigned char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(p));
+}
+
+// SW = sub-tile width; XL = 32-byte X-tile pieces (8 channels of a pixel) per thread, rounded up
+template <int SW, int XL>
+__global__ __launch_bounds__(256) void conv_wgrad_split_kernel(const WgradParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int GPIX = WS_TH * SW, GPLANE = GPIX * PSG;             // dY tile: three planes (h, m, l) of GPIX pixels x PSG
+  constexpr int NSX = WG_TW / SW, NSUB = (WG_TH / WS_TH) * NSX;     // sub-tiles of a block
+  constexpr int GL = GPIX * (WG_CO / 8) / 256;                      // dY pieces per thread (4 or 2)
+  const int xplane = p.tih * p.tiw * PSX;                           // X tile (p.tih x p.tiw: the SUB-tile's extent): three planes
+  unsigned char* gt = smem;
+  unsigned char* xt = smem + 3 * GPLANE;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: the tap tests are s_cbranch
+  const int T = p.co_tiles * p.ci_tiles * p.ngroups;                // grid mapping of conv_wgrad_kernel
+  const int jx = (int)blockIdx.x >> 3;
+  const int worker = ((int)blockIdx.x & 7) + 8 * (jx / T), nworkers = p.nworkers;
+  if (worker >= nworkers) return;                                   // padding workgroups (whole workgroup, before any barrier)
+  const int item = jx % T, tile = item % (p.co_tiles * p.ci_tiles), zgroup = item / (p.co_tiles * p.ci_tiles);
+  const int cit = tile % p.ci_tiles, cot = tile / p.ci_tiles;
+  const int tap0 = zgroup * WG_MAXT, ntaps_g = min(WG_MAXT, p.ntaps_all - tap0);
+  const int co0 = cot * WG_CO, ci0 = cit * WG_CI;
+
+  f32x16 acc[3][2], lo[3][2];                                       // gh xh / the five small products
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { acc[a][m][i] = 0.f; lo[a][m][i] = 0.f; }
+
+  // transposing-read lane geometry of conv_wgrad_kernel
+  const int gq = lane >> 4, li = lane & 15, rq = li >> 2, cp = li & 3;
+  const int khalf = gq >> 1;
+  const int colbase = 16 * (gq & 1) + 4 * cp;
+
+  // piece geometry (sub-tile-invariant): dY piece j = pixel (tid >> 3) + 32 j of the sub-tile, channels 8 * (tid & 7); X piece j = tile
+  // pixel (tid >> 2) + 64 j, channels 8 * (tid & 3).  A piece is two 16-byte loads.
+  f32x4 gr[GL][2], xr[XL][2];
+  const int x_items = p.tih * p.tiw * (WG_CI / 8);
+  const bool g_cok = co0 + (tid & 7) * 8 < p.g.C;
+  const int g_c = g_cok ? co0 + (tid & 7) * 8 : 0;
+  unsigned gmask = 0, xmask = 0;                                    // validity bits of the pieces in flight
+  int x_yx[XL];                                                     // (row << 8 | column) of the piece's tile pixel: tiles are < 256 wide
+#pragma unroll
+  for (int j = 0; j < XL; ++j) {
+    const int px = min((tid >> 2) + 64 * j, p.tih * p.tiw - 1);     // a piece beyond the tile is never valid (prefetch) nor written
+    const int yy = px / p.tiw;
+    x_yx[j] = (yy << 8) | (px - yy * p.tiw);
+  }
+  const bool x_cok = ci0 + (tid & 3) * 8 < p.x.C;
+  const int x_c = x_cok ? ci0 + (tid & 3) * 8 : 0;
+
+  // the walk: blocks worker, worker + nworkers, ... and the sub-tiles of each; settle() moves (blk, sub) forward to the next sub-tile
+  // with a pixel inside the map (workgroup-uniform)
+  const int per_img = p.blocks_x * p.blocks_y;
+  int blk = worker, sub = 0, oy0 = 0, ox0 = 0, img = 0;
+  auto settle = [&]() -> bool {
+    while (blk < p.nblocks) {
+      img = blk / per_img;
+      const int rem = blk - img * per_img;
+      const int by = rem / p.blocks_x, bx = rem - by * p.blocks_x;
+      oy0 = by * WG_TH + (sub / NSX) * WS_TH;
+      ox0 = bx * WG_TW + (sub % NSX) * SW;
+      if (oy0 < p.Ho && ox0 < p.Wo) return true;
+      if (++sub == NSUB) { sub = 0; blk += nworkers; }
+    }
+    return false;
+  };
+  // loads are unconditional at clamped addresses; the out-of-range pieces are zeroed when they are written to LDS
+  auto prefetch = [&]() {
+    const float* gbase = reinterpret_cast<const float*>(p.g.p) + (long)img * p.g.sn + g_c;
+    const float* xbase = reinterpret_cast<const float*>(p.x.p) + (long)img * p.x.sn + x_c;
+    const int iy0 = oy0 * p.stride - p.pad, ix0 = ox0 * p.stride - p.pad;
+    gmask = 0; xmask = 0;
+#pragma unroll
+    for (int j = 0; j < GL; ++j) {
+      const int pix = (tid >> 3) + 32 * j;
+      const int oy = oy0 + pix / SW, ox = ox0 + pix % SW;
+      const bool ok = oy < p.Ho && ox < p.Wo && g_cok;
+      const float* q = gbase + (min(oy, p.Ho - 1) * p.Wo + min(ox, p.Wo - 1)) * p.g.sp;
+      gr[j][0] = *reinterpret_cast<const f32x4*>(q);
+      gr[j][1] = *reinterpret_cast<const f32x4*>(q + 4);
+      gmask |= (ok ? 1u : 0u) << j;
+    }
+#pragma unroll
+    for (int j = 0; j < XL; ++j) {
+      const int iy = iy0 + (x_yx[j] >> 8), ix = ix0 + (x_yx[j] & 255);
+      const bool ok = iy >= 0 && iy < p.x.H && ix >= 0 && ix < p.x.W && x_cok && tid + j * 256 < x_items;
+      const float* q = xbase + (min(max(iy, 0), p.x.H - 1) * p.x.W + min(max(ix, 0), p.x.W - 1)) * p.x.sp;
+      xr[j][0] = *reinterpret_cast<const f32x4*>(q);
+      xr[j][1] = *reinterpret_cast<const f32x4*>(q + 4);
+      xmask |= (ok ? 1u : 0u) << j;
+    }
+  };
+  // bias gradient rides along as in conv_wgrad_kernel: the fp32 sum of the dY values as loaded
+  const bool do_bias = p.bwork != nullptr && cit == 0 && zgroup == 0;
+  float bs[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) bs[q] = 0.f;
+
+  // one piece -> its 16 bytes in each of the three planes
+  auto put = [&](const f32x4 (&v)[2], bool ok, bool square, unsigned char* dst, int plane, bool to_bias) {
+    bf16x8 ph, pm, pl;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      float f = ok ? v[q >> 2][q & 3] : 0.f;                          // a select, before the split: exact zeros for any bit pattern
+      if (to_bias) bs[q] += f;                                        // wave-uniform
+      if (square) f *= f;
+      __bf16 h, m, l;
+      split3(f, h, m, l);
+      ph[q] = h; pm[q] = m; pl[q] = l;
+    }
+    *reinterpret_cast<bf16x8*>(dst) = ph;
+    *reinterpret_cast<bf16x8*>(dst + plane) = pm;
+    *reinterpret_cast<bf16x8*>(dst + 2 * plane) = pl;
+  };
+
+  // this wave's taps: wave, wave + 4, wave + 8 of the group; an absent tap reads tap 0's window and skips its MFMAs
+  int xoff[3];
+  bool tv[3];
+#pragma unroll
+  for (int ai = 0; ai < 3; ++ai) {
+    const int t = wave + 4 * ai;
+    tv[ai] = t < ntaps_g;
+    const int tt = tap0 + (tv[ai] ? t : 0);
+    xoff[ai] = (p.tap_dy[tt] * p.tiw + p.tap_dx[tt]) * PSX;
+  }
+  const unsigned char* abase = gt + (8 * khalf + rq) * PSG + colbase * 2;
+  const unsigned char* bbase = xt + (8 * khalf + rq) * p.stride * PSX + colbase * 2;
+  bool have = settle();
+  if (have) prefetch();
+  while (have) {
+    __syncthreads();                                                // the previous sub-tile's reads are done
+#pragma unroll
+    for (int j = 0; j < GL; ++j) {
+      const int it = tid + j * 256;
+      put(gr[j], (gmask >> j) & 1u, false, gt + (it >> 3) * PSG + (it & 7) * 16, GPLANE, do_bias);
+    }
+#pragma unroll
+    for (int j = 0; j < XL; ++j) {
+      const int it = tid + j * 256;
+      if (it < x_items) put(xr[j], (xmask >> j) & 1u, p.square_x != 0, xt + (it >> 2) * PSX + (it & 3) * 16, xplane, false);
+    }
+    __syncthreads();
+    if (++sub == NSUB) { sub = 0; blk += nworkers; }
+    have = settle();
+    if (have) prefetch();                                           // the next sub-tile's loads land under this one's contraction
+    if (!tv[0]) continue;                                           // a wave without a tap (wave-uniform)
+    // ---- contraction: k-steps of 16 consecutive output pixels of one row, tap by tap.  The X fragments of the NEXT tap (three planes) are
+    // read under the 12 MFMAs of this one, the dY fragments of the next k-step under the first tap's: two dY sets and two X sets live
+    // (72 registers; whole k-steps double-buffered are 120, and spill next to the 192 accumulator registers and the pieces in flight).
+    constexpr int KS = WS_TH * (SW / 16);
+    auto frag = [&](const unsigned char* q, int half) {
+      const short4v l4 = tr_read16(q), h4 = tr_read16(q + half);
+      return __builtin_bit_cast(bf16x8, __builtin_shufflevector(l4, h4, 0, 1, 2, 3, 4, 5, 6, 7));
+    };
+    auto load_a = [&](int ks, bf16x8 (&a)[2][3]) {
+      const unsigned char* ap = abase + ks * 16 * PSG;              // pixel yy * SW + kh * 16 of the sub-tile
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) a[m][pl] = frag(ap + pl * GPLANE + m * 64, 4 * PSG);
+    };
+    auto load_b = [&](int ks, int ai, bf16x8 (&b)[3]) {
+      const int yy = ks / (SW / 16), kh = ks % (SW / 16);
+      const unsigned char* bp = bbase + ((yy * p.stride) * p.tiw + kh * 16 * p.stride) * PSX + xoff[ai];
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) b[pl] = frag(bp + pl * xplane, 4 * p.stride * PSX);
+    };
+    auto fma = [&](int ai, const bf16x8 (&a)[2][3], const bf16x8 (&b)[3]) {
+      if (tv[ai]) {                                                  // wave-uniform
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {                                // the small products, smallest first, then gh xh
+          lo[ai][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b[1], lo[ai][m], 0, 0, 0);
+          lo[ai][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b[0], lo[ai][m], 0, 0, 0);
+          lo[ai][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b[2], lo[ai][m], 0, 0, 0);
+          lo[ai][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b[0], lo[ai][m], 0, 0, 0);
+          lo[ai][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b[1], lo[ai][m], 0, 0, 0);
+          acc[ai][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b[0], acc[ai][m], 0, 0, 0);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);                             // pins the order read / matrix / read / matrix
+    };
+    bf16x8 a0[2][3], a1[2][3], b0[3], b1[3];
+    load_a(0, a0);
+    load_b(0, 0, b0);
+    // A rolled loop: unrolled, every k-step's read addresses (run-time strides) are hoisted out of the sub-tile loop and spill.  The last
+    // pass reads step 0 again instead of branching.
+#pragma unroll 1
+    for (int ks = 0; ks < KS; ks += 2) {
+      const int nx = ks + 2 < KS ? ks + 2 : 0;
+      load_b(ks, 1, b1); load_a(ks + 1, a1); __builtin_amdgcn_sched_barrier(0); fma(0, a0, b0);
+      load_b(ks, 2, b0);                     __builtin_amdgcn_sched_barrier(0); fma(1, a0, b1);
+      load_b(ks + 1, 0, b1);                 __builtin_amdgcn_sched_barrier(0); fma(2, a0, b0);
+      load_b(ks + 1, 1, b0); load_a(nx, a0); __builtin_amdgcn_sched_barrier(0); fma(0, a1, b1);
+      load_b(ks + 1, 2, b1);                 __builtin_amdgcn_sched_barrier(0); fma(1, a1, b0);
+      load_b(nx, 0, b0);                     __builtin_amdgcn_sched_barrier(0); fma(2, a1, b1);
+    }
+  }
+  if (do_bias) {
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(smem);                    // [32 pixel lanes][64 channels]
+#pragma unroll
+    for (int q = 0; q < 8; ++q) red[(tid >> 3) * 64 + (tid & 7) * 8 + q] = bs[q];
+    __syncthreads();
+    if (tid < 64) {
+      float t = 0.f;
+      for (int r = 0; r < 32; ++r) t += red[r * 64 + tid];
+      p.bwork[(long)worker * p.co_tiles * WG_CO + co0 + tid] = t;
+    }
+  }
+  const int CIW = p.ci_tiles * WG_CI, COW = p.co_tiles * WG_CO;
+  float* wk = p.work + (long)worker * p.ntaps_all * COW * CIW;
+  const int col = lane & 31, hh = lane >> 5;
+#pragma unroll
+  for (int ai = 0; ai < 3; ++ai) {
+    const int t = wave + 4 * ai;
+    if (t < ntaps_g) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int row = (i & 3) + 8 * (i >> 2) + 4 * hh;
+          wk[((long)(tap0 + t) * COW + (co0 + m * 32 + row)) * CIW + (ci0 + col)] = acc[ai][m][i] + lo[ai][m][i];
+        }
+    }
+  }
+}
+
 // dW[row_off[co] + chan_off[ci] + tap_off[t]] += scale * sum over workers (fixed order); the tables are the layer's
 // forward packing tables (convpack.forward_tables), so PixelShuffle row order, concatenation channel order,
 // zero-padded channels and Conv3d holders scatter to the right parameter element
@@ -608,12 +857,31 @@ extern "C" int64_t tdvc_conv_wgrad_work_floats(int cout, int cin, int ntaps, int
   return (int64_t)wgrad_workers(co_tiles, ci_tiles, groups, nblocks, ntaps) * co_tiles * WG_CO * (ci_tiles * WG_CI * ntaps + 1);   // + bias partials
 }
 
-extern "C" int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
-                                        int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
-                                        const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
-                                        float* work, int64_t work_floats, tdvc_wgrad_reduce_job* job, void* stream) {
+// the split form's LDS plan: the widest sub-tile (4 x 32, else 4 x 16 output pixels) whose three-plane dY and X tiles fit the 160 KB a launch
+// may ask for, with at most 7 X pieces per thread (the register budget of conv_wgrad_split_kernel); 0 = no plan
+static int wgrad_split_plan(int kh, int kw, int stride, int* tih, int* tiw, size_t* lds) {
+  for (int sw = 32; sw >= 16; sw >>= 1) {
+    *tih = (WS_TH - 1) * stride + kh; *tiw = (sw - 1) * stride + kw;
+    *lds = 3 * ((size_t)WS_TH * sw * PSG + (size_t)*tih * *tiw * PSX);
+    if (*lds <= 160 * 1024 && (*tih * *tiw * (WG_CI / 8) + 255) / 256 <= 7) return sw;
+  }
+  return 0;
+}
+
+// `split`: the dtype dispatch of tdvc_conv_wgrad_partials (fp16 / fp32 kernel), or conv_wgrad_split_kernel on fp32 maps
+static int wgrad_partials(bool split, const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
+                          int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
+                          const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
+                          float* work, int64_t work_floats, tdvc_wgrad_reduce_job* job, void* stream) {
   TDVC_CHECK(job, "tdvc_conv_wgrad_partials: null job");
   TDVC_CHECK(g && x && dw && work && tap_dy && tap_dx && row_off && chan_off && tap_off, "tdvc_conv_wgrad: null pointer");
+  if (split) {
+    TDVC_CHECK(g->dtype == TDVC_F32 && x->dtype == TDVC_F32, "tdvc_conv_wgrad_split: dY is %s, X is %s: both fmaps must be fp32",
+               g->dtype == TDVC_F32 ? "fp32" : "fp16", x->dtype == TDVC_F32 ? "fp32" : "fp16");
+    for (const tdvc_fmap* f : {g, x})                               // conv_f32's rule for its input: a piece is two 16-byte loads
+      TDVC_CHECK(fmap_ok32(*f) && (f->C % 8) == 0 && (f->sp % 4) == 0 && (f->sn % 4) == 0 && aligned16(f->p),
+                 "tdvc_conv_wgrad_split: fmaps must be fp32 with C %% 8 == 0 and 16-byte aligned pixels");
+  }
   // both maps fp16: the transposing-read kernel; both fp32: conv_wgrad_f32_kernel (same workspace, same second stage)
   TDVC_CHECK(g->dtype == x->dtype, "tdvc_conv_wgrad: dY is %s, X is %s: both fmaps must be fp16 or both fp32", g->dtype == TDVC_F32 ? "fp32" : "fp16",
              x->dtype == TDVC_F32 ? "fp32" : "fp16");
@@ -649,7 +917,22 @@ extern "C" int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, 
   p.stamps = (g_wg_stamp && (long)p.co_tiles * p.ci_tiles * workers * groups <= g_wg_stamp_cap) ? g_wg_stamp : nullptr;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(8 * ((workers + 7) / 8) * p.co_tiles * p.ci_tiles * groups));
-  if (f32) {                         // operands straight from global memory in MFMA order: no LDS plan, no per-thread tile pieces
+  if (split) {                       // sub-tiles of the 8 x 32 block: p.tih x p.tiw is the sub-tile's X extent
+    size_t lds;
+    const int sw = wgrad_split_plan(kh, kw, stride, &p.tih, &p.tiw, &lds);
+    TDVC_CHECK(sw, "tdvc_conv_wgrad_split: no LDS plan for a %dx%d window at stride %d (three planes of a 4 x 16 sub-tile need %zu bytes)", kh, kw,
+               stride, lds);
+    p.stamps = nullptr;
+    const int xl = (p.tih * p.tiw * (WG_CI / 8) + 255) / 256;
+    auto go = [&](auto kern) -> int {
+      hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (err != hipSuccess) { tdvc_set_error("tdvc_conv_wgrad_split: hipFuncSetAttribute failed: %s", hipGetErrorString(err)); return (int)err; }
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p);
+      return 0;
+    };
+    const int rc = sw == 16 ? go(&conv_wgrad_split_kernel<16, 7>) : (xl <= 4 ? go(&conv_wgrad_split_kernel<32, 4>) : go(&conv_wgrad_split_kernel<32, 7>));
+    if (rc) return rc;
+  } else if (f32) {                  // operands straight from global memory in MFMA order: no LDS plan, no per-thread tile pieces
     hipLaunchKernelGGL(conv_wgrad_f32_kernel<4>, grid, dim3(256), 0, st, p);
   } else {
     const size_t lds = (size_t)WG_TH * WG_TW * PSG + (size_t)p.tih * p.tiw * PSX;
@@ -672,7 +955,24 @@ extern "C" int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, 
   job->dw = dw; job->db = db; job->scale = scale;
   job->nworkers = workers; job->cow = p.co_tiles * WG_CO; job->ciw = p.ci_tiles * WG_CI; job->ntaps = ntaps; job->cout = cout; job->cin = cin;
   job->wblocks = wblocks; job->nblocks = wblocks + bblocks;
-  return tdvc_launch_status("tdvc_conv_wgrad");
+  return tdvc_launch_status(split ? "tdvc_conv_wgrad_split" : "tdvc_conv_wgrad");
+}
+
+extern "C" int tdvc_conv_wgrad_partials(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
+                                        int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
+                                        const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
+                                        float* work, int64_t work_floats, tdvc_wgrad_reduce_job* job, void* stream) {
+  return wgrad_partials(false, g, x, cout, kh, kw, stride, pad, ntaps, tap_dy, tap_dx, row_off, chan_off, tap_off, square_x, scale, dw, bias_index, db,
+                        work, work_floats, job, stream);
+}
+
+// conv_wgrad_split_kernel (six bf16 MFMA products per MAC) on fp32 maps: the signature, workspace and job of tdvc_conv_wgrad_partials
+extern "C" int tdvc_conv_wgrad_partials_split(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
+                                              int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
+                                              const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
+                                              float* work, int64_t work_floats, tdvc_wgrad_reduce_job* job, void* stream) {
+  return wgrad_partials(true, g, x, cout, kh, kw, stride, pad, ntaps, tap_dy, tap_dx, row_off, chan_off, tap_off, square_x, scale, dw, bias_index, db,
+                        work, work_floats, job, stream);
 }
 
 extern "C" int tdvc_wgrad_reduce_batch(const tdvc_wgrad_reduce_job* jobs, const int32_t* block_start, int njobs, int total_blocks, void* stream) {
@@ -681,17 +981,33 @@ extern "C" int tdvc_wgrad_reduce_batch(const tdvc_wgrad_reduce_job* jobs, const 
   return tdvc_launch_status("tdvc_wgrad_reduce_batch");
 }
 
+static int wgrad_bias(bool split, const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
+                      int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
+                      const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
+                      float* work, int64_t work_floats, void* stream) {
+  tdvc_wgrad_reduce_job j;
+  const int rc = wgrad_partials(split, g, x, cout, kh, kw, stride, pad, ntaps, tap_dy, tap_dx, row_off, chan_off, tap_off, square_x, scale, dw,
+                                bias_index, db, work, work_floats, &j, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)j.nblocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), j.work, j.nworkers, j.cow,
+                     j.ciw, j.ntaps, j.row_off, j.chan_off, j.tap_off, j.cout, j.cin, j.scale, j.dw, j.wblocks, j.bwork, j.bias_index, j.db);
+  return tdvc_launch_status(split ? "tdvc_conv_wgrad_split" : "tdvc_conv_wgrad");
+}
+
 extern "C" int tdvc_conv_wgrad_bias(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
                                     int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
                                     const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
                                     float* work, int64_t work_floats, void* stream) {
-  tdvc_wgrad_reduce_job j;
-  const int rc = tdvc_conv_wgrad_partials(g, x, cout, kh, kw, stride, pad, ntaps, tap_dy, tap_dx, row_off, chan_off, tap_off, square_x, scale, dw,
-                                          bias_index, db, work, work_floats, &j, stream);
-  if (rc) return rc;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)j.nblocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), j.work, j.nworkers, j.cow,
-                     j.ciw, j.ntaps, j.row_off, j.chan_off, j.tap_off, j.cout, j.cin, j.scale, j.dw, j.wblocks, j.bwork, j.bias_index, j.db);
-  return tdvc_launch_status("tdvc_conv_wgrad");
+  return wgrad_bias(false, g, x, cout, kh, kw, stride, pad, ntaps, tap_dy, tap_dx, row_off, chan_off, tap_off, square_x, scale, dw, bias_index, db, work,
+                    work_floats, stream);
+}
+
+extern "C" int tdvc_conv_wgrad_bias_split(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,
+                                          int ntaps, const int8_t* tap_dy, const int8_t* tap_dx, const int32_t* row_off, const int32_t* chan_off,
+                                          const int32_t* tap_off, int square_x, float scale, float* dw, const int32_t* bias_index, float* db,
+                                          float* work, int64_t work_floats, void* stream) {
+  return wgrad_bias(true, g, x, cout, kh, kw, stride, pad, ntaps, tap_dy, tap_dx, row_off, chan_off, tap_off, square_x, scale, dw, bias_index, db, work,
+                    work_floats, stream);
 }
 
 extern "C" int tdvc_conv_wgrad(const tdvc_fmap* g, const tdvc_fmap* x, int cout, int kh, int kw, int stride, int pad,

@@ -32,8 +32,6 @@ void tdvc_set_last_conv_kernel(const char* name);                               
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct SplitExtra {
   const float* x;          // fp32 activations (ConvParams::x is typed half_t*)
   const __bf16* w;         // the three-plane bf16 packing
@@ -42,13 +40,7 @@ struct SplitExtra {
   int total_px;
 };
 
-// v == h + m + l, each part the round-to-nearest-even bf16 of what the parts before it left (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)v;
-  const float r1 = v - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
+// split3(): common.h
 
 // MT cout tiles x NT pixel groups of 32 per wave, as conv_f32_kernel; per k-step MT * 3 weight fragments and NT activation fragments
 // feed 6 * MT * NT MFMAs

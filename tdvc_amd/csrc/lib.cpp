@@ -24,7 +24,7 @@ static_assert(sizeof(tdvc_ar_loop) == 272 && offsetof(tdvc_ar_loop, sym_dev) == 
 static_assert(sizeof(tdvc_lf_tail_desc) == 168 && offsetof(tdvc_lf_tail_desc, slope) == 160, "tdvc_lf_tail_desc layout");
 static_assert(sizeof(tdvc_lanes_enc) == 104 && offsetof(tdvc_lanes_enc, info) == 96, "tdvc_lanes_enc layout");
 
-extern "C" int tdvc_abi_version(void) { return 17; }   // 17: tdvc_conv2d_split, tdvc_pack_conv_weights_indexed_bf16x3 (csrc/conv_split.hip); 16: tdvc_dcn_columns / tdvc_dcn_col2im / tdvc_dcn_col2im_det take fp32 maps (all of one dtype), tdvc_dcn_col2im_tile, tdvc_add_flow_backward / tdvc_bcast_add_act_backward / tdvc_upsample2x_backward / tdvc_match_gather_backward take fp32 maps, tdvc_spynet_level_input_backward an fp32 dcat8; 15: tdvc_dcn_fused takes fp32 maps (x and om fp32, y fp32 or fp16, `w` the fp32 packing: csrc/dcn_f32.hip), tdvc_add_flow / tdvc_bcast_add_act / tdvc_upsample2x / tdvc_avgpool_k / tdvc_match_gather take fp32 maps, tdvc_spynet_level_input an fp32 cat8; 14: tdvc_lf_tail, tdvc_lf_tail_supported (tdvc_lf_tail_desc); 13: the context loop's arguments as descriptors (tdvc_ar_loop, tdvc_cdf_tables, tdvc_cdf_tables_dev, tdvc_lanes_enc): new parameter lists of tdvc_ar_wavefront_batch, tdvc_ar_decode_serial_batch, tdvc_ar_wavefront_lanes_batch, tdvc_ar_decode_lanes_step_batch, tdvc_ar_encode_lanes_batch, tdvc_rans_encode_lanes_dev_ref; 12: device encoder of lane-split streams (tdvc_ar_encode_lanes_*, tdvc_rans_encode_lanes_dev_ref); 11: tdvc_conv_desc::flow, tdvc_conv_flow_supported, tdvc_scale_act_res3, tdvc_avgpool2_pyramid; 10: a single image is B = y_hat->N = 1 of the tdvc_ar_*_batch entry points; removed: tdvc_ar_gather, tdvc_ar_quantize, tdvc_ar_indexes, tdvc_ar_lanes_init, tdvc_ar_decode_lanes_step, tdvc_ar_decode_serial, tdvc_ar_wavefront, tdvc_ar_wavefront_lanes; 9: batched context loop (tdvc_ar_*_batch), tdvc_ar_last_loop_launches; 8: per-image launch predicate, tdvc_frames_changed, out-of-place bcast_T; 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
+extern "C" int tdvc_abi_version(void) { return 18; }   // 18: tdvc_conv_wgrad_bias_split, tdvc_conv_wgrad_partials_split (conv_wgrad_split_kernel); 17: tdvc_conv2d_split, tdvc_pack_conv_weights_indexed_bf16x3 (csrc/conv_split.hip); 16: tdvc_dcn_columns / tdvc_dcn_col2im / tdvc_dcn_col2im_det take fp32 maps (all of one dtype), tdvc_dcn_col2im_tile, tdvc_add_flow_backward / tdvc_bcast_add_act_backward / tdvc_upsample2x_backward / tdvc_match_gather_backward take fp32 maps, tdvc_spynet_level_input_backward an fp32 dcat8; 15: tdvc_dcn_fused takes fp32 maps (x and om fp32, y fp32 or fp16, `w` the fp32 packing: csrc/dcn_f32.hip), tdvc_add_flow / tdvc_bcast_add_act / tdvc_upsample2x / tdvc_avgpool_k / tdvc_match_gather take fp32 maps, tdvc_spynet_level_input an fp32 cat8; 14: tdvc_lf_tail, tdvc_lf_tail_supported (tdvc_lf_tail_desc); 13: the context loop's arguments as descriptors (tdvc_ar_loop, tdvc_cdf_tables, tdvc_cdf_tables_dev, tdvc_lanes_enc): new parameter lists of tdvc_ar_wavefront_batch, tdvc_ar_decode_serial_batch, tdvc_ar_wavefront_lanes_batch, tdvc_ar_decode_lanes_step_batch, tdvc_ar_encode_lanes_batch, tdvc_rans_encode_lanes_dev_ref; 12: device encoder of lane-split streams (tdvc_ar_encode_lanes_*, tdvc_rans_encode_lanes_dev_ref); 11: tdvc_conv_desc::flow, tdvc_conv_flow_supported, tdvc_scale_act_res3, tdvc_avgpool2_pyramid; 10: a single image is B = y_hat->N = 1 of the tdvc_ar_*_batch entry points; removed: tdvc_ar_gather, tdvc_ar_quantize, tdvc_ar_indexes, tdvc_ar_lanes_init, tdvc_ar_decode_lanes_step, tdvc_ar_decode_serial, tdvc_ar_wavefront, tdvc_ar_wavefront_lanes; 9: batched context loop (tdvc_ar_*_batch), tdvc_ar_last_loop_launches; 8: per-image launch predicate, tdvc_frames_changed, out-of-place bcast_T; 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
 extern "C" const char* tdvc_last_error(void) { return g_err; }
 
 // ---- launch predicate (tdvc_set_predicate): a device flag the predicated kernels (conv_c8, conv_pair, conv_row, avgpool_k) read at

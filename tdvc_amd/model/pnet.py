@@ -32,7 +32,11 @@ def _under_f32_split(fn):
     The model's flag is an inference / coding switch: a .train() forward ignores it, with or without a recording tape"""
     @functools.wraps(fn)
     def run(self, *a, **kw):
-        with ops.f32_split((self.f32_split and not self.training) or ops.F32_SPLIT):
+        # `train_f32_split` is the training switch: a .train() forward that a tape records, and (through the tape) its backward sweep
+        train_split = self.train_f32_split and self.training and ops.TAPE is not None
+        if train_split:
+            ops.TAPE.f32_split_train = True
+        with ops.f32_split((self.f32_split and not self.training) or ops.F32_SPLIT), ops.f32_split_train(train_split or ops.F32_SPLIT_TRAIN):
             return fn(self, *a, **kw)
     return run
 
@@ -73,6 +77,11 @@ class VideoCompressor(nn.Module):
         # the 5-tuple return), and the tape differentiates all of it in fp32 (fp32 mirrors, conv_f32 dgrad, conv_wgrad_f32, the fp32
         # deformable-conv backward).  Set by TrainStep(model_fp32=True).  `model_fp32` alone keeps refusing .train() and the tape
         self.train_model_fp32 = False
+        # the training form of `f32_split`: with this flag a .train() forward under a recording tape, and that tape's backward sweep, run
+        # every conv of an fp32 map (forward, data gradient) on conv_split and every fp32 conv weight gradient on conv_wgrad_split_kernel
+        # (six bf16 MFMA products per MAC) instead of conv_f32 / conv_wgrad_f32.  It needs fp32 maps to act on:
+        # set by TrainStep(coder_fp32=True or model_fp32=True, f32_split=True).  `f32_split` alone keeps leaving training on conv_f32
+        self.train_f32_split = False
         # symbol order of the y streams encode() writes and decode() expects: "raster" (compressai's, what the reference's
         # decoder reads), "wavefront" (an extension: the decoder takes an anti-diagonal per step instead of a position) or "lanes"
         # (a second extension: the wavefront sequence split over `stream_lanes` = 64 or 128 rANS sub-streams, which the decoder's

@@ -582,9 +582,34 @@ class f32_split:
         return False
 
 
+F32_SPLIT_TRAIN = False   # inside `with f32_split_train(True)`: the TRAINING convs of fp32 maps (recorded, data- and weight-gradient) on the bf16 pipe
+
+
+class f32_split_train:
+    """`with ops.f32_split_train(True):` -- the training form of `f32_split`, a switch of its own (`f32_split` keeps leaving recorded convs
+    and the backward sweep on conv_f32).  Inside the block a conv() of an fp32 map that a tape records, a conv() issued by the backward
+    sweep and every `conv_dgrad` launch `tdvc_conv2d_split` with the form's `packed_split()` weights, and a `conv_wgrad` of fp32 maps
+    launches the split entry points (conv_wgrad_split_kernel, csrc/conv_backward.hip): the same six-product arithmetic for the forward,
+    the data gradient and the weight gradient.  fp16 maps and un-recorded convs outside a backward sweep are not affected; no geometry
+    falls back to the fp32 kernels.  Nests like `f32_split`."""
+
+    def __init__(self, enable: bool):
+        self.enable = bool(enable)
+
+    def __enter__(self):
+        global F32_SPLIT_TRAIN
+        self.prev, F32_SPLIT_TRAIN = F32_SPLIT_TRAIN, self.enable
+        return self
+
+    def __exit__(self, *exc):
+        global F32_SPLIT_TRAIN
+        F32_SPLIT_TRAIN = self.prev
+        return False
+
+
 def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None,
               res2: FM | None = None, gdn=GDN_NONE, aux: FM | None = None, square=False, out_dtype=None,
-              round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0):
+              round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0, _wsplit: bool = False):
     """the `tdvc_conv_desc` a conv() call would launch, without launching it (native loops re-launch fixed descriptors:
     `tdvc_ar_decode_serial_batch`).  -> (descriptor, result FM / tensor, Ho, Wo, layer form used, layer as recorded)
 
@@ -605,7 +630,8 @@ def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=
         Wo = (x.W + 2 * pc.pad - pc.kw) // pc.stride + 1
     # the layer's part of the descriptor (weights, bias, window, taps) is built once per layer and weight form and copied per call
     # (re-packing writes the same buffers in place; a re-allocated blob is caught by the pointer check)
-    wt = pc.packed_f32() if x.f32 else pc.w
+    # `_wsplit` (conv() under f32_split_train): the split twin at once, so that a training step packs one twin per form, not two
+    wt = pc.packed_split() if _wsplit else pc.packed_f32() if x.f32 else pc.w
     d = L.ConvDesc.from_buffer_copy(pc.tmpl.of(wt.dtype, wt.data_ptr(), _conv_template, pc, wt))
     d.x = x.desc()
     d.square_input, d.gdn = int(square), gdn
@@ -637,7 +663,7 @@ def conv_desc(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=
 def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, res: FM | None = None,
          res2: FM | None = None, gdn=GDN_NONE, aux: FM | None = None, square=False, out_dtype=None,
          round16=False, nchw_out: torch.Tensor | None = None, bcast_T=0, bcast_slope=0.0, chan_sum: list | None = None,
-         flow: FM | None = None) -> FM | torch.Tensor:
+         flow: FM | None = None, _dgrad: bool = False) -> FM | torch.Tensor:
     """`flow` (inference only): an fp32 flow map added to the stored output, x to even and y to odd channels -- in the conv's epilogue
     (tdvc_conv_desc::flow) when the kernel it dispatches to does that (tdvc_conv_flow_supported), else by `add_flow` behind it; the
     same bytes either way.
@@ -647,11 +673,15 @@ def conv(x: FM, pc: PackedConv, out: FM | None = None, act=ACT_NONE, slope=0.0, 
     `chan_sum` (inference only): a list; when the kernel this conv dispatches to can sum the values it stores per channel
     (tdvc_conv_desc::chan_sum), (partial [N][rows][cout] fp32, rows) is appended -- the input of `se_gate(..., partial=)`;
     left empty otherwise (the caller then sums with tdvc_channel_sum)."""
-    split = x.f32 and F32_SPLIT and TAPE is None       # ops.f32_split: inference convs of fp32 maps on the bf16 matrix pipe
+    # ops.f32_split: inference convs of fp32 maps on the bf16 matrix pipe; ops.f32_split_train: the recorded ones and the backward sweep's
+    tsplit = split = False
+    if x.f32:                                     # (one test per conv of an fp16 map, as before the training switch: the step is host-bound)
+        tsplit = F32_SPLIT_TRAIN and (TAPE is not None or _IN_BACKWARD or _dgrad)
+        split = tsplit or (F32_SPLIT and TAPE is None)
     entry = "tdvc_conv2d_split" if split else "tdvc_conv2d"
-    d, ret, Ho, Wo, pc, rec_pc = conv_desc(x, pc, out, act, slope, res, res2, gdn, aux, square, out_dtype, round16, nchw_out, bcast_T, bcast_slope)
-    if split:                                     # conv_desc() never selects the split form: the descriptor it built is conv_f32's, and
-        d.w = pc.packed_split().data_ptr()        # only this launch swaps the weights (the layer's form `pc`, as conv_desc chose it)
+    d, ret, Ho, Wo, pc, rec_pc = conv_desc(x, pc, out, act, slope, res, res2, gdn, aux, square, out_dtype, round16, nchw_out, bcast_T, bcast_slope, tsplit)
+    if split and not tsplit:                      # f32_split: conv_desc() built conv_f32's descriptor, and only this launch swaps the
+        d.w = pc.packed_split().data_ptr()        # weights (the layer's form `pc`, as conv_desc chose it)
     if chan_sum is not None and TAPE is None and FUSE_CHAN_SUM:
         rows = L.lib().tdvc_conv_chan_sum_rows(d)
         if rows > 0:
@@ -834,8 +864,8 @@ def conv_dgrad(pc: PackedConv, g: FM, dx: FM, accumulate=True, extra: FM | None 
     un-shuffled gradient (`pixel_unshuffle`), for a stride-2 layer the result is stored through PixelShuffle."""
     dpc = _dgrad_conv(pc, g.C, dx.C)
     if accumulate:
-        return conv(g, dpc, out=dx, res=dx, res2=extra)
-    return conv(g, dpc, out=dx, res=extra)          # `extra`: one more gradient of the same geometry added in the epilogue (Tape.add_identity)
+        return conv(g, dpc, out=dx, res=dx, res2=extra, _dgrad=True)
+    return conv(g, dpc, out=dx, res=extra, _dgrad=True)          # `extra`: one more gradient of the same geometry added in the epilogue (Tape.add_identity)
 
 
 class WgradBatch:
@@ -919,13 +949,16 @@ def conv_wgrad(pc: PackedConv, g: FM, x: FM, dw: torch.Tensor, scale=1.0, square
         assert db.is_cuda and db.dtype == torch.float32 and db.is_contiguous() and db.numel() >= pc.cout
         bidx = _bias_index(pc, db.device)
     args = (g, x, *static, int(square_x), scale, dw, bidx, db, work, nwork)
+    split = x.f32 and F32_SPLIT_TRAIN               # ops.f32_split_train: six bf16 MFMA products per MAC; every geometry, or an error
     if defer is not None and PROFILE is None:
         job = L.WgradReduceJob()
-        launch("tdvc_conv_wgrad_partials", *args, job)
+        launch("tdvc_conv_wgrad_partials_split" if split else "tdvc_conv_wgrad_partials", *args, job)
         defer.add(job, (work, dw, db, tb, bidx))             # the workspace and the tables live until the flush
         return
-    _profiled("conv_wgrad_f32" if x.f32 else "conv_wgrad", f"{o['kh']}x{o['kw']} s{o['stride']} {x.C}->{pc.cout} @{x.N}x{x.H}x{x.W}",
-              2.0 * x.N * Ho * Wo * pc.cout * x.C * len(taps), lambda: launch("tdvc_conv_wgrad_bias", *args, what="conv_wgrad"),
+    _profiled("conv_wgrad_split" if split else "conv_wgrad_f32" if x.f32 else "conv_wgrad",
+              f"{o['kh']}x{o['kw']} s{o['stride']} {x.C}->{pc.cout} @{x.N}x{x.H}x{x.W}",
+              2.0 * x.N * Ho * Wo * pc.cout * x.C * len(taps),
+              lambda: launch("tdvc_conv_wgrad_bias_split" if split else "tdvc_conv_wgrad_bias", *args, what="conv_wgrad_split" if split else "conv_wgrad"),
               flops_real=2.0 * x.N * Ho * Wo * pc.cout * pc.cin_real * len(taps),
               # geometry class (kh, kw, stride, cin, cout, shuffle, square_x, masked): the op-level test coverage guard
               geo=(o["kh"], o["kw"], o["stride"], pc.cin_real, pc.cout, bool(pc.shuffle), bool(square_x), "wgrad_taps" in o))

@@ -13,6 +13,7 @@ by rank and the gradients averaged over RCCL (`train.GradBuckets`).
   python -m tdvc_amd.tools.train --distortion ms-ssim --train-lambda 8     # rd_loss = lambda * (1 - MS-SSIM) + bpp (tools/train.py:133,139)
   python -m tdvc_amd.tools.train --coder-fp32                              # both coders optimised in fp32 (pnet.py:33,57)
   python -m tdvc_amd.tools.train --model-fp32                              # the whole model in fp32: the reference's `amp: False` (tools/train.py:152-159)
+  python -m tdvc_amd.tools.train --model-fp32 --f32-split                  # the same, its fp32 convs as six bf16 MFMA products (conv_split, conv_wgrad_split)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m tdvc_amd.tools.train --batch 4
 """
 from __future__ import annotations
@@ -63,12 +64,15 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--model-fp32", action="store_true",
                     help="train the whole model in fp32, the reference's `amp: False` setting (tools/train.py:152-159: no autocast, no GradScaler, "
                          "rd_loss.backward(), clip 2, Adam): TrainStep(model_fp32=True).  Implies --coder-fp32; no loss scaling")
+    ap.add_argument("--f32-split", action="store_true",
+                    help="with --coder-fp32 or --model-fp32: the step's convs of fp32 maps (forward, data and weight gradients) as six bf16 MFMA "
+                         "products per MAC instead of on the fp32 matrix pipe: TrainStep(f32_split=True).  fp32-grade, not bit-equal")
     return ap
 
 
 def step_kwargs(a) -> dict:
     """the TrainStep arguments a parsed command line selects"""
-    kw = dict(train_lambda=a.train_lambda, lr=a.lr, distortion=a.distortion, coder_fp32=a.coder_fp32, model_fp32=a.model_fp32)
+    kw = dict(train_lambda=a.train_lambda, lr=a.lr, distortion=a.distortion, coder_fp32=a.coder_fp32, model_fp32=a.model_fp32, f32_split=a.f32_split)
     if a.loss_scale is not None:
         kw["loss_scale"] = a.loss_scale              # with --model-fp32 any value but 1 is refused by TrainStep
     elif not a.model_fp32:
@@ -97,7 +101,7 @@ def main():
     net = net.to(dev)
     step = TrainStep(net, **step_kwargs(a))
     if rank == 0:
-        print(json.dumps({"distortion": a.distortion, "coder_fp32": step.coder_fp32, "model_fp32": step.model_fp32, "train_lambda": a.train_lambda, "batch": a.batch, "size": a.size, "world": world}), flush=True)
+        print(json.dumps({"distortion": a.distortion, "coder_fp32": step.coder_fp32, "model_fp32": step.model_fp32, "f32_split": step.f32_split, "train_lambda": a.train_lambda, "batch": a.batch, "size": a.size, "world": world}), flush=True)
 
     pool, cursor = [], 0
     t0 = time.time()

@@ -219,7 +219,7 @@ class TrainStep:
     def __init__(self, model, train_lambda: float = 2048.0, lr: float = 1e-4, loss_scale: float | None = None, clip: float = 2.0,
                  dynamic_scale: bool | None = None, growth_interval: int = 2000, graph: bool = False, graph_warmup: int = 2,
                  side_stream: bool = True, scale_update: str = "exact", freeze_gc: bool = True, distortion="mse", coder_fp32: bool = False,
-                 model_fp32: bool = False):
+                 model_fp32: bool = False, f32_split: bool = False):
         """distortion: what lambda multiplies in rd_loss.  "mse" (the reference's active line, tools/train.py:136-140); "ms-ssim":
         rd_loss = lambda * (1 - mean_n ms_ssim(recon, input, data_range=1.0)) + bpp_res + bpp_mv, the reference's commented line
         (:133,139), images of at least 176 pixels a side; or a callable fn(recon_fp32, target_fp32) -> (D, dD_drecon) with D a
@@ -233,6 +233,10 @@ class TrainStep:
         `model.train_model_fp32`; implies fp32 coders.  The loss scale is 1 and never changes (`loss_scale` / `dynamic_scale` left at their
         defaults -- None: 1024 and dynamic without this mode; any other value together with it raises ValueError); a step whose gradient
         norm is not finite is still skipped.  Not available with graph=True.
+        f32_split: with coder_fp32=True or model_fp32=True (ValueError without either: there is no fp32 map to split), the convs of fp32 maps
+        of the step -- forward, data gradients, weight gradients -- run as six bf16 MFMA products per MAC (conv_split, conv_wgrad_split)
+        instead of on the fp32 matrix pipe; written to `model.train_f32_split`.  fp32-grade gradients, not bit-equal to the fp32 kernels';
+        everything else of the step (side stream, buckets, loss scaling, clipping, Adam, ops.DETERMINISTIC) is untouched.
         freeze_gc: after the second step (model, packed weights, descriptor caches and pools exist by then; bench.py's three warm-up steps
         include the collection) everything alive
         moves to the garbage collector's permanent generation (gc.freeze): a step allocates ~50 k short-lived containers (tape
@@ -274,8 +278,12 @@ class TrainStep:
             # the fp32 weight twins are re-packed lazily, on first use after an optimizer step (an allocation-free launch, but one whose
             # place in the stream a captured graph would freeze together with the pre-step weights of the eager warm-up)
             raise ValueError("TrainStep: coder_fp32=True is not supported with graph=True (the fp32-coder step runs eagerly)")
+        self.f32_split = bool(f32_split)
+        if self.f32_split and not self.coder_fp32:
+            raise ValueError("TrainStep: f32_split=True needs coder_fp32=True or model_fp32=True (without fp32 maps there is nothing to split)")
         model.train_coder_fp32 = self.coder_fp32
         model.train_model_fp32 = self.model_fp32
+        model.train_f32_split = self.f32_split
         # at least two eager steps: the gradient buckets are re-laid after the first one (GradBuckets.reorder), and only the second builds
         # the device pointer tables of the coders on the final layout -- a host-to-device copy, which a capture does not allow
         self.use_graph, self.graph_warmup, self._eager_steps = bool(graph), max(int(graph_warmup), 2), 0

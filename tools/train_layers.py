@@ -1,5 +1,8 @@
 """diagnostic: per-launch table of the conv kernels (forward, data-gradient and weight-gradient launches; the DCN backward's two
-launches) of one training step at 4 x 256x256 (HIP events on the launch stream).  `--coder-fp32` / `--model-fp32`: that step mode."""
+launches) of one training step at 4 x 256x256 (HIP events on the launch stream).  `--coder-fp32` / `--model-fp32`: that step mode;
+`--f32-split` with either: its fp32 convs on conv_split / conv_wgrad_split; `--all`: every row instead of the 40 largest;
+`--no-side-stream`: TrainStep(side_stream=False).  The events are recorded on the launch stream, so the weight-gradient rows that a step
+moves to its side stream (all but the GDN pools' and the DCN column conv's) time an enqueue, not a kernel, unless this option is given."""
 import os
 import sys
 
@@ -21,10 +24,11 @@ for i in range(4):
     xs.append(g[3:4])
     rs.append(ref_list([g[0:1], g[1:2], g[2:3]]))
 x, refs = torch.cat(xs), torch.cat(rs)
+split, side = "--f32-split" in sys.argv, "--no-side-stream" not in sys.argv
 if "--model-fp32" in sys.argv:
-    step = TrainStep(m, model_fp32=True)
+    step = TrainStep(m, model_fp32=True, f32_split=split, side_stream=side)
 else:
-    step = TrainStep(m, loss_scale=128.0, coder_fp32="--coder-fp32" in sys.argv)
+    step = TrainStep(m, loss_scale=128.0, coder_fp32="--coder-fp32" in sys.argv, f32_split=split, side_stream=side)
 for _ in range(2):
     step(x, refs)
 torch.cuda.synchronize()
@@ -43,5 +47,5 @@ tot = {}
 for (k, sh), (n, ms, fl) in agg.items():
     tot[k] = tot.get(k, 0.0) + ms
 print({k: round(v, 2) for k, v in sorted(tot.items(), key=lambda kv: -kv[1])})
-for (k, sh), (n, ms, fl) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:40]:
+for (k, sh), (n, ms, fl) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:None if "--all" in sys.argv else 40]:
     print(f"{ms:7.3f} ms  n={n:3d}  {ms / n * 1e3:7.1f} us/launch  {fl / ms / 1e9:7.1f} TF  {k:18s} {sh}")
