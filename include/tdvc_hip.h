@@ -354,6 +354,44 @@ int tdvc_gc_forward(const tdvc_fmap* y, const tdvc_fmap* gp, const tdvc_fmap* no
 /* y_hat = round(y) (half-to-even, torch.round) or y + noise. */
 int tdvc_quantize(const tdvc_fmap* y, const tdvc_fmap* noise, const tdvc_fmap* y_hat, void* stream);
 
+/* ---------------------------------------------------------------- a coder's rate branch on a side stream (ABI 19)
+ * The rate branch of Cheng2020Anchor.forward -- h_a, tdvc_eb_forward, h_s, the context conv, entropy_parameters, tdvc_gc_forward --
+ * feeds only `bits`, which the frame reads once at its end, while the synthesis transform needs y_hat alone: two chains of small
+ * launches that do not depend on each other.  tdvc_rate_branch enqueues the whole branch on a SIDE stream, so that what the caller
+ * enqueues on `main_stream` behind the call (g_s) runs beside it, and tdvc_rate_join makes the main stream wait for it.
+ * tdvc_rate_chain: convs[0 .. nconvs) in launch order (1 <= nconvs <= TDVC_RATE_MAX_CONVS), tdvc_eb_forward's launch behind
+ * convs[eb_after - 1] (1 <= eb_after <= nconvs), tdvc_gc_forward's behind the last conv; z / eb_params / z_hat / eb_partial and
+ * y / gp / gc_partial are those calls' arguments (eval form: no noise), bits[0] the y bits and bits[1] the z bits.  `split` != 0:
+ * the convs go through tdvc_conv2d_split (their `w` the three-plane packing) instead of tdvc_conv2d.  `which`: the branch's slot,
+ * 0 <= which < TDVC_RATE_BRANCHES (one per coder of a frame); a slot whose branch has not been joined is refused.
+ * The call validates the chain, records an event on `main_stream`, makes the side stream wait for it, makes the nconvs + 2 calls
+ * there -- the entry points themselves, so every conv takes the kernel and the tile-walk direction it would take on the main stream
+ * in this position -- and records the slot's done event.  Everything the branch reads must have been enqueued on `main_stream`
+ * before the call; everything it touches must stay allocated, and untouched by later main-stream work that writes it, until the join
+ * has been enqueued.  A failing launch ends the branch: the status is returned, the done event is recorded all the same, and the
+ * slot is pending -- a join never waits for an event that was not recorded.
+ * The side stream: one per (device, main stream), created on first use (non-blocking, its events without timing) and kept for the life
+ * of the process.  No graph capture, no environment variable and no queue setting is involved.  Thread-safe. */
+#define TDVC_RATE_MAX_CONVS 16
+#define TDVC_RATE_BRANCHES 2
+typedef struct tdvc_rate_chain {
+  const tdvc_conv_desc* convs;
+  int32_t nconvs, eb_after;
+  tdvc_fmap z, z_hat;
+  const float* eb_params;
+  float* eb_partial;
+  int32_t eb_partial_cap;
+  int32_t gc_partial_cap;
+  float* gc_partial;
+  tdvc_fmap y, gp;
+  double* bits;
+  int32_t which, split;
+} tdvc_rate_chain;
+int tdvc_rate_branch(const tdvc_rate_chain* c, void* main_stream);
+/* `main_stream` waits for the done event of slot `which` of ITS side stream (on the current device) and the slot is free again.
+ * Nothing pending there -- joined already, never forked, no side stream, no device -- is a no-op: TDVC_OK, nothing enqueued. */
+int tdvc_rate_join(void* main_stream, int which);
+
 /* ---------------------------------------------------------------- range coder (host side)
  * compressai `ans` extension (rans64, 16-bit precision, 4-bit bypass) used by
  * Cheng2020Anchor.compress (main/model/pnet.py:46-49,70-73).  Pure host code, like the

@@ -84,6 +84,16 @@ class LanesEncDesc(C.Structure):
                 ("out", _P), ("out_stride", C.c_int64), ("out_cap", C.c_int64), ("info", _P)]
 
 
+RATE_MAX_CONVS, RATE_BRANCHES = 16, 2
+
+
+class RateChainDesc(C.Structure):
+    """tdvc_rate_chain (ABI 19); lib.cpp pins its layout"""
+    _fields_ = [("convs", C.POINTER(ConvDesc)), ("nconvs", C.c_int32), ("eb_after", C.c_int32), ("z", FMapDesc), ("z_hat", FMapDesc),
+                ("eb_params", _P), ("eb_partial", _P), ("eb_partial_cap", C.c_int32), ("gc_partial_cap", C.c_int32), ("gc_partial", _P),
+                ("y", FMapDesc), ("gp", FMapDesc), ("bits", _P), ("which", C.c_int32), ("split", C.c_int32)]
+
+
 _LOOP, _CDF, _CDFD, _ENC = C.POINTER(ArLoopDesc), C.POINTER(CdfTablesDesc), C.POINTER(CdfTablesDevDesc), C.POINTER(LanesEncDesc)
 _i, _f, _i64 = C.c_int, C.c_float, C.c_int64
 
@@ -200,6 +210,8 @@ SIGNATURES = {
     "tdvc_eb_forward": (_i, [_FM, _P, _FM, _FM, _P, _P, _i, _P]),
     "tdvc_gc_forward": (_i, [_FM, _FM, _FM, _P, _P, _i, _P]),
     "tdvc_quantize": (_i, [_FM, _FM, _FM, _P]),
+    "tdvc_rate_branch": (_i, [C.POINTER(RateChainDesc), _P]),
+    "tdvc_rate_join": (_i, [_P, _i]),
     "tdvc_rans_encode": (_i64, [_P, _P, _i64, _P, C.c_int32, _P, _P, _P, _i64]),
     "tdvc_rans_decode": (_i, [_P, _i64, _P, _i64, _P, C.c_int32, _P, _P, _P]),
     "tdvc_rans_encode_lanes": (_i64, [_P, _P, _i64, _i, _i, _P, C.c_int32, _P, _P, _P, _i64]),

@@ -4,7 +4,9 @@
 #include <stddef.h>
 #include <stdio.h>
 
+#include <map>
 #include <mutex>
+#include <utility>
 
 #include "../../include/tdvc_hip.h"
 
@@ -23,8 +25,9 @@ static_assert(sizeof(tdvc_cdf_tables_dev) == 40 && offsetof(tdvc_cdf_tables_dev,
 static_assert(sizeof(tdvc_ar_loop) == 272 && offsetof(tdvc_ar_loop, sym_dev) == 264, "tdvc_ar_loop layout");
 static_assert(sizeof(tdvc_lf_tail_desc) == 168 && offsetof(tdvc_lf_tail_desc, slope) == 160, "tdvc_lf_tail_desc layout");
 static_assert(sizeof(tdvc_lanes_enc) == 104 && offsetof(tdvc_lanes_enc, info) == 96, "tdvc_lanes_enc layout");
+static_assert(sizeof(tdvc_rate_chain) == 224 && offsetof(tdvc_rate_chain, bits) == 208, "tdvc_rate_chain layout");
 
-extern "C" int tdvc_abi_version(void) { return 18; }   // 18: tdvc_conv_wgrad_bias_split, tdvc_conv_wgrad_partials_split (conv_wgrad_split_kernel); 17: tdvc_conv2d_split, tdvc_pack_conv_weights_indexed_bf16x3 (csrc/conv_split.hip); 16: tdvc_dcn_columns / tdvc_dcn_col2im / tdvc_dcn_col2im_det take fp32 maps (all of one dtype), tdvc_dcn_col2im_tile, tdvc_add_flow_backward / tdvc_bcast_add_act_backward / tdvc_upsample2x_backward / tdvc_match_gather_backward take fp32 maps, tdvc_spynet_level_input_backward an fp32 dcat8; 15: tdvc_dcn_fused takes fp32 maps (x and om fp32, y fp32 or fp16, `w` the fp32 packing: csrc/dcn_f32.hip), tdvc_add_flow / tdvc_bcast_add_act / tdvc_upsample2x / tdvc_avgpool_k / tdvc_match_gather take fp32 maps, tdvc_spynet_level_input an fp32 cat8; 14: tdvc_lf_tail, tdvc_lf_tail_supported (tdvc_lf_tail_desc); 13: the context loop's arguments as descriptors (tdvc_ar_loop, tdvc_cdf_tables, tdvc_cdf_tables_dev, tdvc_lanes_enc): new parameter lists of tdvc_ar_wavefront_batch, tdvc_ar_decode_serial_batch, tdvc_ar_wavefront_lanes_batch, tdvc_ar_decode_lanes_step_batch, tdvc_ar_encode_lanes_batch, tdvc_rans_encode_lanes_dev_ref; 12: device encoder of lane-split streams (tdvc_ar_encode_lanes_*, tdvc_rans_encode_lanes_dev_ref); 11: tdvc_conv_desc::flow, tdvc_conv_flow_supported, tdvc_scale_act_res3, tdvc_avgpool2_pyramid; 10: a single image is B = y_hat->N = 1 of the tdvc_ar_*_batch entry points; removed: tdvc_ar_gather, tdvc_ar_quantize, tdvc_ar_indexes, tdvc_ar_lanes_init, tdvc_ar_decode_lanes_step, tdvc_ar_decode_serial, tdvc_ar_wavefront, tdvc_ar_wavefront_lanes; 9: batched context loop (tdvc_ar_*_batch), tdvc_ar_last_loop_launches; 8: per-image launch predicate, tdvc_frames_changed, out-of-place bcast_T; 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
+extern "C" int tdvc_abi_version(void) { return 19; }   // 19: tdvc_rate_branch, tdvc_rate_join (tdvc_rate_chain): a coder's rate branch on a side stream; 18: tdvc_conv_wgrad_bias_split, tdvc_conv_wgrad_partials_split (conv_wgrad_split_kernel); 17: tdvc_conv2d_split, tdvc_pack_conv_weights_indexed_bf16x3 (csrc/conv_split.hip); 16: tdvc_dcn_columns / tdvc_dcn_col2im / tdvc_dcn_col2im_det take fp32 maps (all of one dtype), tdvc_dcn_col2im_tile, tdvc_add_flow_backward / tdvc_bcast_add_act_backward / tdvc_upsample2x_backward / tdvc_match_gather_backward take fp32 maps, tdvc_spynet_level_input_backward an fp32 dcat8; 15: tdvc_dcn_fused takes fp32 maps (x and om fp32, y fp32 or fp16, `w` the fp32 packing: csrc/dcn_f32.hip), tdvc_add_flow / tdvc_bcast_add_act / tdvc_upsample2x / tdvc_avgpool_k / tdvc_match_gather take fp32 maps, tdvc_spynet_level_input an fp32 cat8; 14: tdvc_lf_tail, tdvc_lf_tail_supported (tdvc_lf_tail_desc); 13: the context loop's arguments as descriptors (tdvc_ar_loop, tdvc_cdf_tables, tdvc_cdf_tables_dev, tdvc_lanes_enc): new parameter lists of tdvc_ar_wavefront_batch, tdvc_ar_decode_serial_batch, tdvc_ar_wavefront_lanes_batch, tdvc_ar_decode_lanes_step_batch, tdvc_ar_encode_lanes_batch, tdvc_rans_encode_lanes_dev_ref; 12: device encoder of lane-split streams (tdvc_ar_encode_lanes_*, tdvc_rans_encode_lanes_dev_ref); 11: tdvc_conv_desc::flow, tdvc_conv_flow_supported, tdvc_scale_act_res3, tdvc_avgpool2_pyramid; 10: a single image is B = y_hat->N = 1 of the tdvc_ar_*_batch entry points; removed: tdvc_ar_gather, tdvc_ar_quantize, tdvc_ar_indexes, tdvc_ar_lanes_init, tdvc_ar_decode_lanes_step, tdvc_ar_decode_serial, tdvc_ar_wavefront, tdvc_ar_wavefront_lanes; 9: batched context loop (tdvc_ar_*_batch), tdvc_ar_last_loop_launches; 8: per-image launch predicate, tdvc_frames_changed, out-of-place bcast_T; 7: launch predicate, tdvc_frame_changed; 6: lane-split y streams (tdvc_*_lanes*); 5: tdvc_conv_select; 4: tdvc_conv_desc::chan_sum; 3: tdvc_prepare_device, SE-pool conv epilogue, deterministic col2im
 extern "C" const char* tdvc_last_error(void) { return g_err; }
 
 // ---- launch predicate (tdvc_set_predicate): a device flag the predicated kernels (conv_c8, conv_pair, conv_row, avgpool_k) read at
@@ -109,3 +112,103 @@ int tdvc_scratch_pages(const void** zeros, void** dump) {
 }
 
 extern "C" int tdvc_prepare_device(void) { return tdvc_scratch_pages(nullptr, nullptr); }
+
+// ---- a coder's rate branch on a side stream (tdvc_rate_branch / tdvc_rate_join).  One side stream per (device, main stream) with a fork
+// event and a done event per slot, created on first use and never destroyed; `pending` says which done events a join has to wait for.
+// All of it under one mutex: a call is ~20 enqueues, and two threads that share a main stream share its side stream.
+namespace {
+struct SideStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, done[TDVC_RATE_BRANCHES] = {};
+  bool pending[TDVC_RATE_BRANCHES] = {};
+};
+std::mutex g_side_mu;
+std::map<std::pair<int, void*>, SideStream> g_side;
+
+int hip_fail(const char* who, const char* what, hipError_t e) {
+  tdvc_set_error("%s: %s failed: %s", who, what, hipGetErrorString(e));
+  return (int)e;
+}
+
+// the side stream of (current device, main) with its events, created on first use; g_side_mu is held
+int side_stream(const char* who, void* main, SideStream** out) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_fail(who, "hipGetDevice", e);
+  SideStream& s = g_side[{dev, main}];
+  if (!s.stream) {
+    SideStream n;
+    e = hipStreamCreateWithFlags(&n.stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&n.fork, hipEventDisableTiming);
+    for (int i = 0; i < TDVC_RATE_BRANCHES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&n.done[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      for (hipEvent_t ev : n.done) if (ev) (void)hipEventDestroy(ev);
+      if (n.fork) (void)hipEventDestroy(n.fork);
+      if (n.stream) (void)hipStreamDestroy(n.stream);
+      return hip_fail(who, "creating the side stream", e);
+    }
+    s = n;
+  }
+  *out = &s;
+  return TDVC_OK;
+}
+
+int rate_chain_args(const tdvc_rate_chain* c) {
+  if (!c || !c->convs || !c->eb_params || !c->eb_partial || !c->gc_partial || !c->bits || !c->z.p || !c->z_hat.p || !c->y.p || !c->gp.p) {
+    tdvc_set_error("tdvc_rate_branch: null argument");
+    return TDVC_EINVAL;
+  }
+  if (c->nconvs < 1 || c->nconvs > TDVC_RATE_MAX_CONVS || c->eb_after < 1 || c->eb_after > c->nconvs) {
+    tdvc_set_error("tdvc_rate_branch: 1 <= eb_after <= nconvs <= %d expected, got eb_after %d, nconvs %d", TDVC_RATE_MAX_CONVS, c->eb_after, c->nconvs);
+    return TDVC_EINVAL;
+  }
+  if (c->which < 0 || c->which >= TDVC_RATE_BRANCHES) {
+    tdvc_set_error("tdvc_rate_branch: slot %d out of range (%d slots)", c->which, TDVC_RATE_BRANCHES);
+    return TDVC_EINVAL;
+  }
+  return TDVC_OK;
+}
+}  // namespace
+
+extern "C" int tdvc_rate_branch(const tdvc_rate_chain* c, void* main_stream) {
+  if (const int rc = rate_chain_args(c)) return rc;
+  std::lock_guard<std::mutex> lk(g_side_mu);
+  SideStream* s = nullptr;
+  if (const int rc = side_stream("tdvc_rate_branch", main_stream, &s)) return rc;
+  if (s->pending[c->which]) {
+    tdvc_set_error("tdvc_rate_branch: slot %d has a branch that was not joined (tdvc_rate_join)", c->which);
+    return TDVC_EINVAL;
+  }
+  hipError_t e = hipEventRecord(s->fork, reinterpret_cast<hipStream_t>(main_stream));
+  if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, s->fork, 0);
+  if (e != hipSuccess) return hip_fail("tdvc_rate_branch", "the fork", e);      // nothing was enqueued on the side stream: nothing is pending
+  void* side = s->stream;
+  int rc = TDVC_OK;
+  for (int k = 0; k < c->nconvs && rc == TDVC_OK; ++k) {
+    rc = c->split ? tdvc_conv2d_split(&c->convs[k], side) : tdvc_conv2d(&c->convs[k], side);
+    if (rc == TDVC_OK && k + 1 == c->eb_after)
+      rc = tdvc_eb_forward(&c->z, c->eb_params, nullptr, &c->z_hat, c->bits + 1, c->eb_partial, c->eb_partial_cap, side);
+  }
+  if (rc == TDVC_OK) rc = tdvc_gc_forward(&c->y, &c->gp, nullptr, c->bits, c->gc_partial, c->gc_partial_cap, side);
+  // whatever the launches said, the done event is recorded behind what did get enqueued: the join waits for exactly that
+  e = hipEventRecord(s->done[c->which], s->stream);
+  if (e != hipSuccess) return rc != TDVC_OK ? rc : hip_fail("tdvc_rate_branch", "recording the done event", e);
+  s->pending[c->which] = true;
+  return rc;
+}
+
+extern "C" int tdvc_rate_join(void* main_stream, int which) {
+  if (which < 0 || which >= TDVC_RATE_BRANCHES) {
+    tdvc_set_error("tdvc_rate_join: slot %d out of range (%d slots)", which, TDVC_RATE_BRANCHES);
+    return TDVC_EINVAL;
+  }
+  std::lock_guard<std::mutex> lk(g_side_mu);
+  if (g_side.empty()) return TDVC_OK;              // no branch was ever forked (also: no device)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return TDVC_OK;
+  const auto it = g_side.find({dev, main_stream});
+  if (it == g_side.end() || !it->second.pending[which]) return TDVC_OK;
+  it->second.pending[which] = false;               // a failed wait is not retried: the slot is free either way
+  const hipError_t e = hipStreamWaitEvent(reinterpret_cast<hipStream_t>(main_stream), it->second.done[which], 0);
+  return e == hipSuccess ? TDVC_OK : hip_fail("tdvc_rate_join", "hipStreamWaitEvent", e);
+}

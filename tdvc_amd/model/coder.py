@@ -446,6 +446,7 @@ class Cheng2020Anchor(nn.Module, PackCache):
             nn.Conv2d(M * 8 // 3, M * 6 // 3, 1))
         self.context_prediction = MaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1)
         self.gaussian_conditional = GaussianConditional()
+        self.rate_hold = []        # what a forked rate branch touches, referenced from the fork until its join is enqueued (_fork_rate_branch)
 
     # -- transforms ------------------------------------------------------------------------
     def run_g_a(self, x: FM):
@@ -524,8 +525,55 @@ class Cheng2020Anchor(nn.Module, PackCache):
         """`estmv.float()` / `input_residual.float()` of pnet.py:34,58: the fp32 island's input"""
         return x if x.f32 else ops.cast_f32(x)
 
-    def run(self, x: FM, training: bool, out: FM | None = None, res: FM | None = None, trace=None, noise=None, f32=False):
+    def _fork_rate_branch(self, y32: FM, y16: FM, adt, slot: int):
+        """`run`'s rate branch -- h_a, eb_forward, h_s, context conv, entropy_parameters, gc_forward: the same calls in the same order
+        -- as ONE native call that enqueues them on the launch stream's side stream (ops.rate_branch, slot `slot`), so that g_s, which
+        needs y_hat alone, runs beside it.  -> (y_hat, bits); `bits` is valid behind `ops.rate_join(slot)`.  Every buffer the branch
+        touches is allocated here, by the launch stream's allocator in front of the fork, and stays referenced in `self.rate_hold`
+        until VideoCompressor.forward has enqueued the join: the allocator cannot hand it out again under the side stream."""
+        dev, M, h, e = y32.t.device, self.M, self.h_a, self.entropy_parameters
+        B, hh, ww = y32.N, y32.H, y32.W
+        split = ops.F32_SPLIT and y16.f32           # what ops.conv() does with an fp32 map under ops.f32_split
+        descs, hold = [], self.rate_hold
+        assert not hold, "the coder's last rate branch was not joined"
+
+        def conv(x, pc, **kw):
+            d, ret, _, _, form, _ = ops.conv_desc(x, pc, **kw)
+            if split:
+                d.w = form.packed_split().data_ptr()
+            descs.append(d)
+            hold.append(ret.t)
+            return ret
+
+        bits = torch.zeros(2, dtype=torch.float64, device=dev)
+        y_hat = ops.quantize(y32, FM.empty(B, hh, ww, M, dtype=adt, device=dev))
+        t = conv(y16, pk_conv(self, "ha0", h[0]), **LR)
+        t = conv(t, pk_conv(self, "ha2", h[2]), **LR)
+        t = conv(t, pk_conv(self, "ha4", h[4]), **LR)
+        t = conv(t, pk_conv(self, "ha6", h[6]), **LR)
+        z = conv(t, pk_conv(self, "ha8", h[8]), out_dtype=torch.float32)
+        z_hat = FM.empty(z.N, z.H, z.W, z.C, dtype=adt, device=dev)
+        pcat = FM.empty(B, hh, ww, 4 * M, dtype=adt, device=dev)  # [h_s params | context]
+        h = self.h_s
+        t = conv(z_hat, pk_conv(self, "hs0", h[0]), **LR)
+        t = conv(t, pk_conv(self, "hs2", h[2][0], shuffle=True), **LR)
+        t = conv(t, pk_conv(self, "hs4", h[4]), **LR)
+        t = conv(t, pk_conv(self, "hs6", h[6][0], shuffle=True), **LR)
+        conv(t, pk_conv(self, "hs8", h[8]), out=pcat.ch(0, 2 * M))
+        conv(y_hat, self.ctx_conv(), out=pcat.ch(2 * M, 2 * M))
+        t = conv(pcat, pk_conv(self, "ep0", e[0]), **LR)
+        t = conv(t, pk_conv(self, "ep2", e[2]), **LR)
+        gp = conv(t, pk_conv(self, "ep4", e[4]), out_dtype=torch.float32)
+        eb = self.entropy_bottleneck.packed_params()
+        hold += [y32.t, y16.t, y_hat.t, z_hat.t, bits, eb]
+        hold += ops.rate_branch(descs, 5, z, eb, z_hat, y32, gp, bits, slot, split)     # raises: `hold` is filled, forward's `finally` joins
+        return y_hat, bits
+
+    def run(self, x: FM, training: bool, out: FM | None = None, res: FM | None = None, trace=None, noise=None, f32=False,
+            fork: int | None = None):
         """x: (B,H,W,64) fp16.  Returns (x_hat FM [+res], bits tensor (2,) float64 = [y, z]).
+        `fork` (inference without trace, tape or profile; VideoCompressor.forward decides): the rate branch goes to the side stream as
+        slot `fork` (`_fork_rate_branch`) and `bits` is valid behind `ops.rate_join(fork)`; the same launches, the same bytes.
         `f32`: run the coder as the reference's fp32 island (pnet.py:33-49: autocast off, `estmv.float()`): fp32
         activations and weights on the fp32 MFMA form of every conv.  With `training` under the tape the whole island is
         differentiated in fp32 as well (fp32 gradient mirrors, conv_f32 data gradients, conv_wgrad_f32 weight gradients); only its
@@ -536,6 +584,10 @@ class Cheng2020Anchor(nn.Module, PackCache):
             x = self._as_f32(x)
         adt = torch.float32 if f32 else torch.float16          # activation dtype inside the coder
         y32, y16 = self.run_g_a(x)
+        if fork is not None:
+            assert not training and trace is None and ops.TAPE is None and ops.PROFILE is None, "the rate fork is an inference form"
+            y_hat, bits = self._fork_rate_branch(y32, y16, adt, fork)
+            return self.run_g_s(y_hat, out=out, res=res, out_dtype=xdt), bits
         z = self.run_h_a(y16)
         B, h, w, M = y32.N, y32.H, y32.W, self.M
         bits = torch.zeros(2, dtype=torch.float64, device=dev)

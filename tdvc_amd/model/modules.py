@@ -182,6 +182,7 @@ PYRAMID_FUSED = True            # SPyNet's two image pyramids in one launch (ops
 FLOW_EPILOGUE = True            # OffsetGen: the flow added in the level-1 fusion conv's epilogue (ops.conv(..., flow=)) instead of add_flow
 RESID_FUSED = True              # the residual f_cur - pred as a second result of LoopFilter's last pass (ops.scale_act_res3)
 RGB_HEAD = True                 # FeatureFix.featdown on conv_head3 (a tile's loads in flight under the tile before) instead of conv_n16
+RATE_FORK = True                # the coders' rate branches on a side stream beside their synthesis transforms (ops.rate_branch); not in coding calls
 
 
 def glue_fusions_allowed(module: nn.Module, traced: bool = False) -> bool:

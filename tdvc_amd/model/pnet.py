@@ -10,6 +10,7 @@ matching and rate terms.  There is no PyTorch/CPU fallback: tensors must live on
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 
 import torch
@@ -20,6 +21,9 @@ from ..ops import FM
 from . import modules
 from .coder import STREAM_CODERS, MVCoder, ResCoder
 from .modules import FeaExtra, FeatureFix, LoopFilter, MCNet, OffsetGen
+
+
+MV_SLOT, RES_SLOT = 0, 1      # the two coders' slots on the side stream (ops.rate_branch / ops.rate_join)
 
 
 def _ref_views(refs8: FM, B: int):
@@ -141,7 +145,10 @@ class VideoCompressor(nn.Module):
         if H % 64 or W % 64:
             raise RuntimeError(f"input must be padded to a multiple of 64 (got {H}x{W}); see tools/predict.py:51-53")
         dev = input_image.device
-        with torch.cuda.device(dev), torch.no_grad(), ops.train_model_fp32(tm32):
+        # the coders' rate branches beside their synthesis transforms (modules.RATE_FORK): a plain inference forward only, under the
+        # condition of the other inference forms (whole-model fp32 runs the plain sequence of traced calls)
+        fork = modules.RATE_FORK and not is_compress and modules.glue_fusions_allowed(self, trace is not None or mf32)
+        with torch.cuda.device(dev), torch.no_grad(), ops.train_model_fp32(tm32), self._rate_branches_joined():
             x = input_image.float()
             refs = refer_frames.float().reshape(B * 4, 3, H, W)
             cur32 = ops.from_nchw(x, Cpad=4, dtype=torch.float32)
@@ -161,7 +168,7 @@ class VideoCompressor(nn.Module):
             estmv = self.motion_est.run(feats, cur32, ref32, traced=trace is not None or mf32)
 
             tr_mv = {} if trace is not None else None
-            mv_hat, mv_bits = self.mvCoder.run(estmv, training=training, trace=tr_mv, noise=noise.get("mv"), f32=f32)
+            mv_hat, mv_bits = self.mvCoder.run(estmv, training=training, trace=tr_mv, noise=noise.get("mv"), f32=f32, fork=MV_SLOT if fork else None)
             coded = {}
             if is_compress:                                      # pnet.py:45-49
                 self.mvCoder.update(force=True)
@@ -178,7 +185,8 @@ class VideoCompressor(nn.Module):
                 ops.scale_act_res(f_cur, resid, res=pred, res_sign=-1.0)
 
             tr_res = {} if trace is not None else None
-            recon_f, res_bits = self.resCoder.run(resid, training=training, res=pred, trace=tr_res, noise=noise.get("res"), f32=f32)
+            recon_f, res_bits = self.resCoder.run(resid, training=training, res=pred, trace=tr_res, noise=noise.get("res"), f32=f32,
+                                                  fork=RES_SLOT if fork else None)
             if is_compress:                                      # pnet.py:69-73
                 self.resCoder.update(force=True)
                 coded["res"] = self.resCoder.compress(resid, f32=f32)
@@ -189,6 +197,7 @@ class VideoCompressor(nn.Module):
             recon = self.loopfilter.run(recon_f, iframe8, training=training, trace=trace)
 
             npx = float(B * H * W)
+            self._join_rate_branches()                # the bits are read from here on
             bpp_mv = (mv_bits.sum() / npx).float().view(-1)
             bpp_res = (res_bits.sum() / npx).float().view(-1)
             if trace is not None:
@@ -197,6 +206,24 @@ class VideoCompressor(nn.Module):
         if training:
             return recon, bpp_res, bpp_mv, self.mvCoder.aux_loss(), self.resCoder.aux_loss()
         return recon, bpp_res, bpp_mv
+
+    def _join_rate_branches(self):
+        """the launch stream waits for the rate branches the coders forked (coder.py `_fork_rate_branch`), and the buffers they touch are
+        released to its allocator; nothing forked, or joined already: nothing happens"""
+        for slot, coder in ((MV_SLOT, self.mvCoder), (RES_SLOT, self.resCoder)):
+            if coder.rate_hold:
+                try:
+                    ops.rate_join(slot)
+                finally:
+                    coder.rate_hold.clear()
+
+    @contextlib.contextmanager
+    def _rate_branches_joined(self):
+        """whatever ends the block -- forward's return or an exception between a fork and the join -- leaves no branch pending"""
+        try:
+            yield
+        finally:
+            self._join_rate_branches()
 
     # ---- real encode / decode (SURVEY §8f rank 1; the reference only sketches it: tools/utils/encoder.py, decoder.py) ----
     def _model_fp32_checked(self) -> bool:

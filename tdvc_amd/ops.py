@@ -1343,6 +1343,30 @@ def gc_forward(y: FM, gp: FM, bits_out: torch.Tensor, noise: FM | None = None):
     _rec("gc_forward", y, gp, noise)
 
 
+def rate_branch(descs: list, eb_after: int, z: FM, eb_params: torch.Tensor, z_hat: FM, y: FM, gp: FM, bits: torch.Tensor, which: int,
+                split: bool = False) -> list:
+    """a coder's rate branch on the side stream of the launch stream (`tdvc_rate_branch`): the convs `descs` (conv_desc()'s descriptors)
+    in order, `eb_forward(z, eb_params, z_hat, bits[1:2])` behind descs[eb_after - 1] and `gc_forward(y, gp, bits[0:1])` behind the last,
+    as slot `which`.  -> the tensors the call allocated (the two reductions' partial buffers): the caller keeps them, and everything
+    else the branch touches, referenced until `rate_join(which)` has been enqueued -- the allocator of the launch stream owns them all
+    and knows nothing of the side stream"""
+    assert bits.dtype == torch.float64 and bits.numel() == 2 and bits.is_contiguous() and PROFILE is None and TAPE is None
+    dev = z.t.device
+    ecap, gcap = (z.N * z.H * z.W * z.C + 255) // 256, (y.N * y.H * y.W * y.C + 255) // 256
+    epart = torch.empty(ecap, dtype=torch.float32, device=dev)
+    gpart = torch.empty(gcap, dtype=torch.float32, device=dev)
+    convs = (L.ConvDesc * len(descs))(*descs)
+    chain = L.RateChainDesc(convs, len(descs), eb_after, z.desc(), z_hat.desc(), eb_params.data_ptr(), epart.data_ptr(), ecap, gcap,
+                            gpart.data_ptr(), y.desc(), gp.desc(), bits.data_ptr(), which, int(split))
+    launch("tdvc_rate_branch", chain)
+    return [epart, gpart]
+
+
+def rate_join(which: int) -> None:
+    """the launch stream waits for slot `which` of its side stream (`tdvc_rate_join`); nothing pending there: a no-op"""
+    L.check(L.lib().tdvc_rate_join(_stream(), which), "rate_join")
+
+
 def quantize(y: FM, out: FM, noise: FM | None = None) -> FM:
     launch("tdvc_quantize", y, noise, out)
     _rec("quantize", y, out, noise)
